@@ -12,6 +12,7 @@ are independent (reverb.py:148-180) so there is no data-path collective, only th
   python bench.py --gpus N --steps K --warmup W          # N > 1: launches N ranks itself, one per GPU
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W          # or under torchrun
+  python bench.py ... --dump-outputs DIR                 # + the last timed step's results as DIR/*.npy (seeded inputs)
 
 At N = 1 the same JSON line also carries
   roofline.traffic  HBM bytes per GEMM launch, from two nested `rocprofv3 --pmc` passes of this very command
@@ -74,7 +75,55 @@ def parse(argv=None):
     p.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive leg (N = 1 only)")
     p.add_argument("--no-variants", action="store_true", help="skip the parity_f32 / asr_fp8 / r268 sub-records (N = 1 only)")
     p.add_argument("--joint-hours", type=float, default=3.0, help="length of the joint_fp8 sub-record's recording (BASELINE configs[4]: 3 h)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write what the last timed step returned (the per-chunk attention_rescoring results of every rank) "
+                        "as DIR/<name>.npy, float64, at most 64 MB (a fixed sample of the chunks beyond that)")
     return p.parse_args(argv)
+
+
+# ------------------------------------------------------------------------------------------------ output dump
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(hyps, out_dir, limit=DUMP_LIMIT_BYTES):
+    """The per-chunk DecodeResults of one step as float64 arrays, one row per chunk, in chunk order:
+      chunk_index        which chunk of the step each row is (all of them unless the sample below applies)
+      token_count        number of tokens of the chunk's best hypothesis
+      tokens, times, ctc_frames, token_confidence   [rows, max tokens], padded with -1 (times / ctc_frames all -1 when absent)
+      score, confidence  per chunk
+    When the arrays would exceed `limit` bytes, a fixed sample of the chunks (seed 0, kept in chunk order) is written.
+    Returns {name: shape}."""
+    hyps = list(hyps)
+    n = len(hyps)
+    width = max([len(v or ()) for h in hyps for v in (h.tokens, h.times, getattr(h, "ctc_frames", None), h.tokens_confidence)],
+                default=0)
+    keep = np.arange(n)
+    per_row = 8 * (4 + 4 * width)
+    if n * per_row > limit:
+        k = max(1, limit // per_row)
+        keep = np.sort(np.random.default_rng(0).choice(n, size=k, replace=False))
+    rows = [hyps[i] for i in keep]
+
+    def padded(get):
+        a = np.full((len(rows), width), -1.0, np.float64)
+        for r, h in enumerate(rows):
+            v = get(h)
+            if v:
+                a[r, :len(v)] = v
+        return a
+
+    arrays = {"chunk_index": keep.astype(np.float64),
+              "token_count": np.array([len(h.tokens) for h in rows], np.float64),
+              "tokens": padded(lambda h: list(h.tokens)),
+              "times": padded(lambda h: h.times),
+              "ctc_frames": padded(lambda h: getattr(h, "ctc_frames", None)),
+              "token_confidence": padded(lambda h: h.tokens_confidence),
+              "score": np.array([h.score for h in rows], np.float64),
+              "confidence": np.array([h.confidence for h in rows], np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 # ------------------------------------------------------------------------------------------------ launcher
@@ -551,6 +600,8 @@ def main():
         eng.reset_timings()
         eng.set_profiling(not args.no_profile, gemm_only=True)      # timed region: HIP events around the GEMM launches only
     dt, (hyps, ntok) = timed(args.steps)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(hyps, args.dump_outputs)          # what the last timed step returned, outside the timed region
     g, g8, att, stages, pcie = None, None, None, None, None
     if not STUB:
         eng.set_profiling(False)

@@ -3,6 +3,7 @@
 import json
 import os
 
+import numpy as np
 import pytest
 
 from conftest import ROOT
@@ -56,6 +57,49 @@ def test_bench_gpus_2_launches_two_ranks_itself():
     assert d["config"]["results_gathered"] == 2 * 4 and d["config"]["parallelism"] == "chunk-shard x2"   # 72 s = 4 chunks per rank
     assert d["data"].startswith("stub") and d["roofline"] is None       # can never be mistaken for a measurement
     assert d["steps"] == 2 and d["warmup"] == 1 and d["scaling"] == "weak" and d["value"] > 0
+
+
+def test_bench_dump_outputs_writes_the_last_timed_step(tmp_path):
+    """`--dump-outputs DIR`: after the timed steps, the per-chunk results of the last one as DIR/<name>.npy (float64), one row per
+    chunk in chunk order; `--steps` timed steps, `ms_per_step` in the line.  RVB_BENCH_STUB: results are a pure function of the
+    chunk (3 + c % 5 tokens, score -c, times 0 .. k-1, token confidences 0.25) and each step sleeps 10 ms."""
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
+    env["RVB_BENCH_STUB"] = "1"
+    out = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--model", "tiny", "--hours", "0.02", "--dump-outputs", str(out)], env=env, capture_output=True, text=True,
+                       timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+    assert d["steps"] == 3 and d["ms_per_step"] >= 10.0
+    names = {"chunk_index", "token_count", "tokens", "times", "ctc_frames", "token_confidence", "score", "confidence"}
+    assert {p.stem for p in out.iterdir()} == names and all(p.suffix == ".npy" for p in out.iterdir())
+    a = {n: np.load(out / (n + ".npy")) for n in names}
+    assert all(v.dtype == np.float64 for v in a.values())
+    n = 4                                                     # 72 s = 4 chunks
+    k = 3 + np.arange(n) % 5
+    assert a["chunk_index"].tolist() == list(range(n)) and a["token_count"].tolist() == k.tolist()
+    assert a["tokens"].shape == (n, k.max()) and a["score"].tolist() == [-float(c) for c in range(n)]
+    for c in range(n):
+        assert a["tokens"][c].tolist() == list(range(1, 1 + k[c])) + [-1] * (k.max() - k[c])
+        assert a["times"][c].tolist() == list(range(k[c])) + [-1] * (k.max() - k[c])
+        assert a["token_confidence"][c].tolist() == [0.25] * k[c] + [-1] * (k.max() - k[c])
+    assert (a["ctc_frames"] == -1).all() and (a["confidence"] == 0.5).all()
+
+
+def test_dump_outputs_samples_a_fixed_set_of_chunks_beyond_the_limit(tmp_path):
+    import bench
+    from reverb_amd.search import DecodeResult
+    hyps = [DecodeResult(tuple(range(c % 7)), float(c), times=list(range(c % 7))) for c in range(1000)]
+    limit = 100 * 8 * (4 + 4 * 6)                             # room for 100 rows of width 6
+    shapes = bench.dump_outputs(hyps, str(tmp_path / "a"), limit=limit)
+    assert shapes["tokens"] == [100, 6] and sum(os.path.getsize(p) for p in (tmp_path / "a").iterdir()) < limit + 8 * 1024
+    idx = np.load(tmp_path / "a" / "chunk_index.npy")
+    assert (np.diff(idx) > 0).all() and np.load(tmp_path / "a" / "score.npy").tolist() == idx.tolist()
+    bench.dump_outputs(hyps, str(tmp_path / "b"), limit=limit)
+    assert np.load(tmp_path / "b" / "chunk_index.npy").tolist() == idx.tolist()       # the same sample every run
 
 
 def test_bench_gpus_more_than_visible_is_refused():
