@@ -173,6 +173,14 @@ TEST_SIGNATURES = {
                                       _f64p, _f64p]),
     "rvb_test_prefix_beam": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p,
                                        _f64p]),
+    "rvb_test_window_stats": (C.c_int, [_f32p, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_float, _f32p]),
+    "rvb_test_sinc_conv": (C.c_int, [C.c_int, _f32p, C.c_int64, _f32p, C.c_int, C.c_int, C.c_int, C.c_int64, _f32p]),
+    "rvb_test_pool_norm": (C.c_int, [C.c_int, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, C.c_float,
+                                     C.c_int, _f32p, C.c_int64, C.c_int64, C.c_int, _f32p, _f32p, C.c_float, C.c_float, _f32p]),
+    "rvb_test_conv1d5": (C.c_int, [C.c_int, _f32p, C.c_int64, _f32p, _f32p, _f32p, C.c_int64]),
+    "rvb_test_lstm_layer": (C.c_int, [C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p]),
+    "rvb_test_classifier": (C.c_int, [C.c_int, _f32p, C.c_int, _f32p, _f32p, _f32p, C.POINTER(C.c_uint8), C.c_int64, C.c_int, C.c_int]),
+    "rvb_test_tstp": (C.c_int, [C.c_int, _f32p, C.c_int, _i32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
 }
 
 

@@ -6,6 +6,8 @@
 // window hop (16 000 samples) is a multiple of the stride, the filter bank is evaluated ONCE on the raw
 // waveform (sinc_conv) and each window applies its own normalisation as an affine correction
 // (pool_norm, first block) -- 10x fewer FLOPs and no per-window copies of the audio.
+#include <cstring>
+
 #include "kernels.h"
 
 namespace rvb {
@@ -408,7 +410,9 @@ int pool_norm(hipStream_t s, int dtype, const PoolNormArgs& a) {
     const int vec = lab_env("RVD_POOLNORM_VEC") ? atoi(lab_env("RVD_POOLNORM_VEC")) : 1;      // lab: 0 = the scalar form (read per call: the A/B test flips it)
     const int ldi = first ? a.C : a.ld_in;
     const uintptr_t base = first ? (uintptr_t)a.craw : (uintptr_t)a.x;
-    if (vec && dtype == DT_BF16 && (ldi % 8) == 0 && (a.ld_out % 8) == 0 && a.ld_out >= 8 && (base % 16) == 0 && ((uintptr_t)a.out % 16) == 0 &&
+    // a thread reads all 8 channels of its group, pad channels included: the input rows must hold ld_out of them
+    if (vec && dtype == DT_BF16 && (ldi % 8) == 0 && (a.ld_out % 8) == 0 && a.ld_out >= 8 && ldi >= a.ld_out && (base % 16) == 0 &&
+        ((uintptr_t)a.out % 16) == 0 &&
         (!first || ((a.craw_frame0 * a.C) % 8 == 0 && ((int64_t)a.craw_frames_per_step * a.C) % 8 == 0)) &&
         (first || ((size_t)a.rows_in * a.ld_in) % 8 == 0)) {
       const int CG = a.ld_out / 8, nslots = 256 / CG;
@@ -683,6 +687,18 @@ __global__ __launch_bounds__(256, sizeof(T) == 2 ? 2 : 1) void lstm_kernel(const
       }
     }
     __syncthreads();
+  }
+}
+
+// The eight pre-activations one lane of lstm_kernel starts a step from -- gates i, f, g, o of hidden units u and u + 16 -- are
+// consecutive (one 16-byte load per window and step instead of eight 2-byte ones): gate q of unit 32 v + 16 hf + c -> column
+// 128 v + 8 c + 2 q + hf.
+void lstm_pack_inproj(const float* w_ih, const float* b_ih, const float* b_hh, int H, int in, int in_pad, float* wih, float* bias) {
+  for (int r = 0; r < 4 * H; ++r) {
+    const int q = r / H, u = r % H, v = u / 32, hf = (u % 32) / 16, cc = u % 16;
+    const int col = 128 * v + 8 * cc + 2 * q + hf;
+    std::memcpy(&wih[(size_t)col * in_pad], &w_ih[(size_t)r * in], (size_t)in * 4);
+    bias[col] = b_ih[r] + b_hh[r];
   }
 }
 

@@ -236,6 +236,9 @@ int conv1d5(hipStream_t s, int dtype, const void* A, int cin, const void* W, con
 // 4H columns in the kernel's read order: gate q (i, f, g, o) of hidden unit 32 v + 16 hf + c is column 128 v + 8 c + 2 q + hf
 // (diar_engine.hip permutes W_ih / the biases accordingly); whh T [2][4H][H]; out T [W*T, 2H].
 int lstm_recurrence(hipStream_t s, int dtype, const void* xproj, const void* whh, void* out, int W, int T);
+// host: one direction's PyTorch weight_ih [4H][in] (gates i, f, g, o) and b_ih + b_hh -> the rows of its projection operand
+// wih [4H][in_pad] (pad columns left as they are) and bias [4H] in the read order above
+void lstm_pack_inproj(const float* w_ih, const float* b_ih, const float* b_hh, int H, int in, int in_pad, float* wih, float* bias);
 
 // logp[r][:] = log_softmax(x[r].Wc^T + bc)   x T [M, ldx], Wc fp32 [C][in], C <= 16; cls[r] = argmax (nullable)
 int classifier_logsoftmax(hipStream_t s, int dtype, const void* x, int ldx, const float* w, const float* b,

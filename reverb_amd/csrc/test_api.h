@@ -85,6 +85,22 @@ int rvb_test_prefix_beam(const float* topk_val, const int32_t* topk_idx, int T, 
                          int32_t* n_hyps, int32_t* tokens /* [beam][T] */, int32_t* lens, int32_t* times,
                          int32_t* times_lens, double* scores);
 
+/* diarization kernels (diar.hip, resnet.hip tstp_pool) on host floats; see test_api.hip for the layouts */
+int rvb_test_window_stats(const float* wave, int64_t n, int64_t first, int nwin, int64_t step, int len, float eps, float* stats);
+int rvb_test_sinc_conv(int dtype, const float* wave, int64_t n_samples, const float* filt, int nf, int ksize, int stride,
+                       int64_t n_frames, float* out);
+int rvb_test_pool_norm(int dtype, int first_block, const float* x, int rows_in, int ld_in, int frames_in, int C, int ld_out,
+                       const float* gamma, const float* beta, float eps, int W, const float* craw, int64_t craw_rows,
+                       int64_t craw_frame0, int craw_frames_per_step, const float* stats, const float* fsum, float wn_gamma,
+                       float wn_beta, float* out);
+int rvb_test_conv1d5(int cin, const float* A, int64_t rows, const float* W, const float* bias, float* out, int64_t M);
+int rvb_test_lstm_layer(int dtype, const float* x, int W, int T, int in, const float* w_ih, const float* w_hh, const float* b_ih,
+                        const float* b_hh, float* out);
+int rvb_test_classifier(int dtype, const float* x, int ldx, const float* w, const float* b, float* logp, uint8_t* cls,
+                        int64_t M, int in, int C);
+int rvb_test_tstp(int dtype, const float* x, int B, const int32_t* item_b, const float* mask, int mask_len, int n_items, int F,
+                  int TT, int C, float* stats);
+
 /* GEMM kernel selection / micro-benchmark hooks (tests and tuning only) */
 int rvb_test_set_gemm_variant(int variant /* 0 auto, 1 gemm.hip 128x128, 2 gemm2.hip 256x256 LDS-DMA */);
 /* gemm2.hip tuning switches: flags bit 0 = 32x32x16 MFMAs, bit 1 = s_setprio for the later-dispatched waves;

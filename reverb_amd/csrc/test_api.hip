@@ -772,3 +772,177 @@ extern "C" int rvb_test_gemm_bench(int dtype, int M, int N, int K, int variant, 
   g_gemm_variant = saved;
   return r;
 }
+
+// ---------------------------------------------------------------------------------------------- diarization kernels (diar.hip, resnet.hip)
+// Each hook launches exactly the launcher the engine calls, on host floats (rounded to bf16 here when dtype == 1); the form a
+// launcher picks follows its lab switch (RVD_SINC_MFMA, RVD_POOLNORM_VEC) as in the engine.
+
+// window_stats: wave [n]; stats [nwin][2] = (mean, 1 / sqrt(var + eps)) of wave[(first + w) step .. + len)
+extern "C" int rvb_test_window_stats(const float* wave, int64_t n, int64_t first, int nwin, int64_t step, int len, float eps, float* stats) {
+  if (!wave || !stats || n < 1 || first < 0 || nwin < 1 || step < 1 || len < 1 || (first + nwin - 1) * step + len > n) {
+    set_error("rvb_test_window_stats: bad argument"); return E_ARG;
+  }
+  T_TRY(need_gpu());
+  Dev dw, ds;
+  T_TRY(up_T(dw, DT_F32, wave, (size_t)n));
+  T_TRY(ds.alloc((size_t)nwin * 2 * 4));
+  T_TRY(window_stats(nullptr, (const float*)dw.p, first, nwin, step, len, eps, (float*)ds.p));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  return down_T(ds, DT_F32, true, stats, (size_t)nwin * 2);
+}
+
+// sinc_conv: out [n_frames][nf] (dtype) = sum_k wave[t stride + k] filt[f][k]; the launcher refuses what neither form covers
+extern "C" int rvb_test_sinc_conv(int dtype, const float* wave, int64_t n_samples, const float* filt, int nf, int ksize, int stride,
+                                  int64_t n_frames, float* out) {
+  if (!wave || !filt || !out || nf < 1 || ksize < 1 || stride < 1 || n_frames < 1 || (n_frames - 1) * stride + ksize > n_samples ||
+      (dtype != DT_F32 && dtype != DT_BF16)) {
+    set_error("rvb_test_sinc_conv: bad argument"); return E_ARG;
+  }
+  T_TRY(need_gpu());
+  Dev dw, df, dout;
+  T_TRY(up_T(dw, DT_F32, wave, (size_t)n_samples));
+  T_TRY(up_T(df, DT_F32, filt, (size_t)nf * ksize));
+  T_TRY(dout.alloc((size_t)n_frames * nf * dt_size(dtype)));
+  T_TRY(sinc_conv(nullptr, dtype, (const float*)dw.p, (const float*)df.p, dout.p, n_frames, nf, ksize, stride));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  return down_T(dout, dtype, false, out, (size_t)n_frames * nf);
+}
+
+// pool_norm on the fields of PoolNormArgs.  Later block: x [W rows_in][ld_in].  First block: craw [craw_rows][C], stats [W][2],
+// fsum [C], wn_gamma / wn_beta.  out [W (frames_in / 3)][ld_out], pad columns included.
+extern "C" int rvb_test_pool_norm(int dtype, int first_block, const float* x, int rows_in, int ld_in, int frames_in, int C, int ld_out,
+                                  const float* gamma, const float* beta, float eps, int W, const float* craw, int64_t craw_rows,
+                                  int64_t craw_frame0, int craw_frames_per_step, const float* stats, const float* fsum, float wn_gamma,
+                                  float wn_beta, float* out) {
+  const int TP = frames_in / 3;
+  bool ok = gamma && beta && out && W >= 1 && TP >= 1 && C >= 1 && ld_out >= C && (dtype == DT_F32 || dtype == DT_BF16);
+  if (first_block) ok = ok && craw && stats && fsum && craw_frame0 >= 0 && craw_frames_per_step >= 0 &&
+                        craw_frame0 + (int64_t)(W - 1) * craw_frames_per_step + 3 * TP <= craw_rows;
+  else ok = ok && x && rows_in >= frames_in && ld_in >= C;
+  if (!ok) { set_error("rvb_test_pool_norm: bad argument"); return E_ARG; }
+  T_TRY(need_gpu());
+  Dev dx, dcr, dst, dfs, dg, db, dout;
+  PoolNormArgs a{};
+  if (first_block) {
+    T_TRY(up_T(dcr, dtype, craw, (size_t)craw_rows * C));
+    T_TRY(up_T(dst, DT_F32, stats, (size_t)W * 2));
+    T_TRY(up_T(dfs, DT_F32, fsum, (size_t)C));
+    a.craw = dcr.p; a.craw_frame0 = craw_frame0; a.craw_frames_per_step = craw_frames_per_step;
+    a.stats = (const float*)dst.p; a.fsum = (const float*)dfs.p; a.wn_gamma = wn_gamma; a.wn_beta = wn_beta;
+  } else {
+    T_TRY(up_T(dx, dtype, x, (size_t)W * rows_in * ld_in));
+    a.x = dx.p; a.rows_in = rows_in; a.ld_in = ld_in;
+  }
+  T_TRY(up_T(dg, DT_F32, gamma, (size_t)C));
+  T_TRY(up_T(db, DT_F32, beta, (size_t)C));
+  const size_t no = (size_t)W * TP * ld_out;
+  T_TRY(dout.alloc(no * dt_size(dtype)));
+  RVB_HIP_CHECK(hipMemset(dout.p, 0x7f, no * dt_size(dtype)));      // unwritten pad columns show up as 3.4e38 / 3.3e38
+  a.frames_in = frames_in; a.C = C; a.ld_out = ld_out; a.gamma = (const float*)dg.p; a.beta = (const float*)db.p; a.eps = eps;
+  a.out = dout.p; a.W = W;
+  T_TRY(pool_norm(nullptr, dtype, a));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  return down_T(dout, dtype, false, out, no);
+}
+
+// conv1d5 (bf16): A [rows][cin] with rows >= M + 4, W [60][cin_real][5] as torch stores Conv1d weights (cin_real = 80 for cin 80,
+// 60 for cin 64), bias [60]; out [M][64] (filters 60 .. 63 are the zero pads).  The weights are packed as pack_conv1d packs them
+// (diar_engine.hip: [64][5][cin]); the device input has M + 8 rows as the engine's, rows M + 4 .. M + 7 hold 1e30 (nobody reads them).
+extern "C" int rvb_test_conv1d5(int cin, const float* A, int64_t rows, const float* W, const float* bias, float* out, int64_t M) {
+  if (!A || !W || !bias || !out || (cin != 80 && cin != 64) || M < 1 || rows < M + 4) { set_error("rvb_test_conv1d5: bad argument"); return E_ARG; }
+  T_TRY(need_gpu());
+  const int cr = cin == 80 ? 80 : 60, NO = 60, NP = 64, K = 5;
+  std::vector<float> pw((size_t)NP * K * cin, 0.f), pb(NP, 0.f);
+  for (int o = 0; o < NO; ++o) {
+    pb[o] = bias[o];
+    for (int c = 0; c < cr; ++c)
+      for (int k = 0; k < K; ++k) pw[((size_t)o * K + k) * cin + c] = W[((size_t)o * cr + c) * K + k];
+  }
+  std::vector<bf16_t> ab((size_t)(M + 8) * cin, f32_to_bf16(1e30f));
+  for (size_t i = 0; i < (size_t)(M + 4) * cin; ++i) ab[i] = f32_to_bf16(A[i]);
+  Dev da, dw, db, dout;
+  T_TRY(up_raw(da, ab.data(), ab.size() * 2));
+  T_TRY(up_T(dw, DT_BF16, pw.data(), pw.size()));
+  T_TRY(up_T(db, DT_F32, pb.data(), pb.size()));
+  T_TRY(dout.alloc((size_t)M * NP * 2));
+  T_TRY(conv1d5(nullptr, DT_BF16, da.p, cin, dw.p, (const float*)db.p, dout.p, M));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  return down_T(dout, DT_BF16, false, out, (size_t)M * NP);
+}
+
+// One bidirectional LSTM layer (hidden 128) as segment_impl runs it: x [W T][in] . w_ih^T + b_ih + b_hh on the GEMM into the
+// recurrence kernel's column order (lstm_pack_inproj), then lstm_recurrence.  w_ih [2][4H][in], w_hh [2][4H][H], b_ih / b_hh [2][4H]
+// (PyTorch layout, forward then reverse); out [W T][2H] = (forward h | reverse h).
+extern "C" int rvb_test_lstm_layer(int dtype, const float* x, int W, int T, int in, const float* w_ih, const float* w_hh, const float* b_ih,
+                                   const float* b_hh, float* out) {
+  constexpr int H = 128;
+  if (!x || !w_ih || !w_hh || !b_ih || !b_hh || !out || W < 1 || T < 1 || in < 8 || (in % 8) || (int64_t)W * T > 0x7fffffff / (8 * H) ||
+      (dtype != DT_F32 && dtype != DT_BF16)) {
+    set_error("rvb_test_lstm_layer: bad argument"); return E_ARG;
+  }
+  T_TRY(need_gpu());
+  std::vector<float> wih((size_t)8 * H * in, 0.f), bias((size_t)8 * H, 0.f);
+  for (int d = 0; d < 2; ++d)
+    lstm_pack_inproj(w_ih + (size_t)d * 4 * H * in, b_ih + (size_t)d * 4 * H, b_hh + (size_t)d * 4 * H, H, in, in,
+                     &wih[(size_t)d * 4 * H * in], &bias[(size_t)d * 4 * H]);
+  const size_t R = (size_t)W * T;
+  Dev dx, dwi, db, dwh, dxp, dout;
+  T_TRY(up_T(dx, dtype, x, R * in));
+  T_TRY(up_T(dwi, dtype, wih.data(), wih.size()));
+  T_TRY(up_T(db, DT_F32, bias.data(), bias.size()));
+  T_TRY(up_T(dwh, dtype, w_hh, (size_t)8 * H * H));
+  T_TRY(dxp.alloc(R * 8 * H * dt_size(dtype)));
+  T_TRY(dout.alloc(R * 2 * H * dt_size(dtype)));
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A = dx.p; g.W = dwi.p; g.bias = (const float*)db.p; g.C = dxp.p;
+  g.M = (int)R; g.N = 8 * H; g.K = in; g.lda = in; g.ldw = in; g.ldc = 8 * H; g.alpha = 1.f; g.act = ACT_NONE;
+  T_TRY(gemm(nullptr, dtype, g));
+  T_TRY(lstm_recurrence(nullptr, dtype, dxp.p, dwh.p, dout.p, W, T));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  return down_T(dout, dtype, false, out, R * 2 * H);
+}
+
+// classifier_logsoftmax: x [M][ldx] (dtype), w [C][in], b [C] fp32; logp [M][C]; cls [M] (nullable)
+extern "C" int rvb_test_classifier(int dtype, const float* x, int ldx, const float* w, const float* b, float* logp, uint8_t* cls,
+                                   int64_t M, int in, int C) {
+  if (!x || !w || !b || !logp || M < 1 || C < 1 || in < 1 || ldx < in || (dtype != DT_F32 && dtype != DT_BF16)) {
+    set_error("rvb_test_classifier: bad argument"); return E_ARG;
+  }
+  T_TRY(need_gpu());
+  Dev dx, dw, db, dl, dc;
+  T_TRY(up_T(dx, dtype, x, (size_t)M * ldx));
+  T_TRY(up_T(dw, DT_F32, w, (size_t)C * in));
+  T_TRY(up_T(db, DT_F32, b, (size_t)C));
+  T_TRY(dl.alloc((size_t)M * C * 4));
+  if (cls) T_TRY(dc.alloc((size_t)M));
+  T_TRY(classifier_logsoftmax(nullptr, dtype, dx.p, ldx, (const float*)dw.p, (const float*)db.p, (float*)dl.p, (uint8_t*)dc.p, M, in, C));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  if (cls) RVB_HIP_CHECK(hipMemcpy(cls, dc.p, (size_t)M, hipMemcpyDeviceToHost));
+  return down_T(dl, DT_F32, true, logp, (size_t)M * C);
+}
+
+// tstp_pool: x [B][F][TT][C] (unbordered), item_b [n_items] in [0, B), mask [n_items][mask_len]; stats [n_items][2 C F] = (mean | std)
+// with feature index c F + f.  Builds the bordered [B][F + 2][TT + 2][C] plane the kernel reads, its border at 1e3 (never read).
+extern "C" int rvb_test_tstp(int dtype, const float* x, int B, const int32_t* item_b, const float* mask, int mask_len, int n_items, int F,
+                             int TT, int C, float* stats) {
+  bool ok = x && item_b && mask && stats && B >= 1 && mask_len >= 1 && n_items >= 1 && F >= 1 && TT >= 1 && C >= 1 &&
+            (dtype == DT_F32 || dtype == DT_BF16);
+  for (int i = 0; ok && i < n_items; ++i) ok = item_b[i] >= 0 && item_b[i] < B;
+  if (!ok) { set_error("rvb_test_tstp: bad argument"); return E_ARG; }
+  T_TRY(need_gpu());
+  const size_t np = (size_t)B * (F + 2) * (TT + 2) * C;
+  std::vector<float> xb(np, 1e3f);
+  for (int b = 0; b < B; ++b)
+    for (int f = 0; f < F; ++f)
+      for (int t = 0; t < TT; ++t)
+        memcpy(&xb[(((size_t)b * (F + 2) + f + 1) * (TT + 2) + t + 1) * C], &x[(((size_t)b * F + f) * TT + t) * C], (size_t)C * 4);
+  Dev dx, di, dm, ds;
+  T_TRY(up_T(dx, dtype, xb.data(), np));
+  T_TRY(up_raw(di, item_b, (size_t)n_items * 4));
+  T_TRY(up_T(dm, DT_F32, mask, (size_t)n_items * mask_len));
+  T_TRY(ds.alloc((size_t)n_items * 2 * C * F * dt_size(dtype)));
+  T_TRY(tstp_pool(nullptr, dtype, dx.p, (const int*)di.p, (const float*)dm.p, mask_len, n_items, F, TT, C, ds.p));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  return down_T(ds, dtype, false, stats, (size_t)n_items * 2 * C * F);
+}

@@ -105,6 +105,25 @@ def test_fails_loudly_without_gpu(lib):
     assert rc != 0 and b"no CPU fallback" in lib.rvb_last_error()
 
 
+def test_diarization_kernel_hooks_refuse_out_of_range_shapes_before_any_device_work(lib):
+    """The hooks of tests/test_diar_kernels_gpu.py check that the host buffers cover what the kernel will read (E_ARG = -1)
+    before they look for a device, so these hold with and without a GPU."""
+    f = _lib.fptr
+    z = np.zeros(4096, np.float32)
+    ib = np.array([0, 3], np.int32)
+    assert lib.rvb_test_window_stats(f(z), 4096, 1, 2, 2048, 2048, 1e-5, f(z)) == -1          # window 2 ends past the wave
+    assert lib.rvb_test_sinc_conv(0, f(z), 4096, f(z), 1, 251, 10, 400, f(z)) == -1           # 400 frames need 4 241 samples
+    assert lib.rvb_test_pool_norm(1, 1, None, 0, 0, 30, 8, 8, f(z), f(z), 1e-5, 2, f(z), 20, 0, 5, f(z), f(z), 1.0, 0.0,
+                                  f(z)) == -1                                                 # window 1 reads craw rows 5 .. 34
+    assert lib.rvb_test_pool_norm(0, 0, f(z), 9, 8, 9, 16, 16, f(z), f(z), 1e-5, 2, None, 0, 0, 0, None, None, 1.0, 0.0,
+                                  f(z)) == -1                                                 # 16 channels in rows of 8
+    assert lib.rvb_test_conv1d5(80, f(z), 10, f(z), f(z), f(z), 7) == -1                        # M + 4 rows needed
+    assert lib.rvb_test_conv1d5(72, f(z), 20, f(z), f(z), f(z), 7) == -1                        # 80 or 64 input channels
+    assert lib.rvb_test_lstm_layer(0, f(z), 1, 1, 60, f(z), f(z), f(z), f(z), f(z)) == -1     # in % 8
+    assert lib.rvb_test_classifier(0, f(z), 8, f(z), f(z), f(z), None, 4, 16, 2) == -1        # ldx < in
+    assert lib.rvb_test_tstp(0, f(z), 3, _lib.iptr(ib), f(z), 10, 2, 1, 4, 8, f(z)) == -1     # item 1 in window 3 of 3
+
+
 def test_bad_arguments_are_reported_not_crashed(lib):
     cfg = _lib.ModelCfg()
     h = ctypes.c_void_p()

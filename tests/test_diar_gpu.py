@@ -179,6 +179,68 @@ def test_short_audio_single_padded_window(case):
     eng.close()
 
 
+# ------------------------------------------------------------------------------------ segmentation at many windows
+@pytest.fixture(scope="module")
+def long_case(case):
+    """52.3 s: 44 windows, the last one zero-padded.  At this count the LSTM runs three 16-window blocks per direction (the
+    last one partial) and conv1d5 hands workgroups a second 256-frame tile (44 x 5 325 rows = 916 tiles for layer 2), which
+    the 6-window case never reaches."""
+    pcm = SD.synth_conversation(52.3, seed=23)
+    x = windows_of(pcm, case["cfg"])
+    taps = {}
+    with torch.no_grad():
+        logp = R.pyannet(R.to_torch_sd(case["seg_sd"]), x, taps)
+    return dict(pcm=pcm, x=x, logp=logp.numpy(), taps={k: v.numpy() for k, v in taps.items()})
+
+
+def test_segmentation_f32_matches_oracle_at_44_windows(case, long_case):
+    from reverb_amd.diar_engine import DiarEngine
+    eng = DiarEngine(case["cfg"], case["seg_sd"], dtype="f32")
+    W = eng.upload(long_case["pcm"])
+    assert W == long_case["x"].shape[0] == 44
+    logp = eng.segment()
+    sinc = eng.tap("sincnet", W)
+    lstm = eng.tap("lstm", W)
+    # the bounds of test_segmentation_f32_matches_oracle
+    assert np.abs(sinc - long_case["taps"]["sincnet"]).max() < 2e-3
+    assert np.abs(lstm - long_case["taps"]["lstm"]).max() < 2e-3
+    assert np.abs(logp - long_case["logp"]).max() < 1e-2
+    agree = (logp.argmax(-1) == long_case["logp"].argmax(-1)).mean()
+    assert agree > 0.995, agree
+    eng.close()
+
+
+def test_segmentation_bf16_close_to_oracle_at_44_windows(case, long_case):
+    from reverb_amd.diar_engine import DiarEngine
+    eng = DiarEngine(case["cfg"], case["seg_sd"], dtype="bf16")
+    W = eng.upload(long_case["pcm"])
+    logp = eng.segment()
+    sinc = eng.tap("sincnet", W)
+    ref = long_case["taps"]["sincnet"]
+    # the bounds of test_segmentation_bf16_close_to_oracle
+    assert np.abs(sinc - ref).mean() < 0.02 * np.abs(ref).mean() + 1e-3
+    p, q = np.exp(logp), np.exp(long_case["logp"])
+    assert np.abs(p - q).mean() < 0.02
+    agree = (logp.argmax(-1) == long_case["logp"].argmax(-1)).mean()
+    assert agree > 0.93, agree
+    eng.close()
+
+
+@pytest.mark.parametrize("dtype", ["f32", "bf16"])
+def test_segmentation_batch_splits_are_bit_identical_at_44_windows(case, long_case, dtype):
+    """Batches of 16 / 17 / 33 windows (LSTM blocks split differently, conv1d5 with fewer tiles per workgroup) and the window range
+    13 .. 31 alone give the bits of the one-call run: every kernel computes a window's rows the same way whatever else is in the
+    call."""
+    from reverb_amd.diar_engine import DiarEngine
+    eng = DiarEngine(case["cfg"], case["seg_sd"], dtype=dtype)
+    eng.upload(long_case["pcm"])
+    a = eng.segment()
+    for batch in (16, 17, 33):
+        assert np.array_equal(eng.segment(batch=batch), a), batch
+    assert np.array_equal(eng.segment(first=13, n=19), a[13:32])
+    eng.close()
+
+
 # ------------------------------------------------------------------------------------ embedding network
 @pytest.fixture(scope="module")
 def emb_case(case):
