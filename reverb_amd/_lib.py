@@ -181,6 +181,10 @@ TEST_SIGNATURES = {
     "rvb_test_lstm_layer": (C.c_int, [C.c_int, _f32p, C.c_int, C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p]),
     "rvb_test_classifier": (C.c_int, [C.c_int, _f32p, C.c_int, _f32p, _f32p, _f32p, C.POINTER(C.c_uint8), C.c_int64, C.c_int, C.c_int]),
     "rvb_test_tstp": (C.c_int, [C.c_int, _f32p, C.c_int, _i32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p]),
+    "rvb_test_conv2d": (C.c_int, [C.c_int, C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                  C.c_int, C.c_int, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p]),
+    "rvb_test_emb_stem": (C.c_int, [C.c_int, _f32p, C.c_int64, _i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p,
+                                    _f32p, _f32p]),
 }
 
 

@@ -360,6 +360,8 @@ bool conv_stream_applicable(int dtype, const ConvArgs& p) {
          (int64_t)(p.Fi + 2) * (p.Ti + 2) * p.Cin * 2 < ((int64_t)1 << 31) && (int64_t)p.B * cdiv(p.Fo, CS_OF) * 64 < ((int64_t)1 << 31);
 }
 
+int conv_stream_split(const ConvArgs& p) { return std::max(1, std::min(stream_mode(), cdiv(p.To, CS_OT))); }
+
 int conv_stream(hipStream_t s, const ConvArgs& p) {
   if (p.B <= 0) return OK;
   const int ts = stream_mode();

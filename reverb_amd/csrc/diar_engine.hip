@@ -398,30 +398,22 @@ int pack_conv_bn(rvd_engine* e, ConvW& c, const std::string& conv, const std::st
   RVD_TRY(need(e, bn + ".running_var", cout, &v));
   const int CK = 64 / (int)dt_size(e->dtype);
   if (cin % CK) { set_error("embedding conv " + conv + ": input channels must be a multiple of " + std::to_string(CK)); return E_UNSUPPORTED; }
-  const int taps = k * k, nch = cin / CK;
-  std::vector<float> pw((size_t)taps * cin * cout), pb(cout);
+  const int taps = k * k;
+  std::vector<float> pw((size_t)taps * cin * cout), pb(cout), sc(cout);
   for (int o = 0; o < cout; ++o) {
-    const float sc = g->data[o] / std::sqrt(v->data[o] + 1e-5f);
-    pb[o] = b->data[o] - m->data[o] * sc;
-    for (int ci = 0; ci < cin; ++ci)
-      for (int t = 0; t < taps; ++t)
-        pw[(((size_t)t * nch + ci / CK) * cout + o) * CK + ci % CK] = w->data[((size_t)o * cin + ci) * taps + t] * sc;
+    sc[o] = g->data[o] / std::sqrt(v->data[o] + 1e-5f);
+    pb[o] = b->data[o] - m->data[o] * sc[o];
   }
+  conv_pack_direct(w->data.data(), sc.data(), cout, cin, taps, CK, pw.data());
   c.cin = cin; c.cout = cout; c.taps = taps; c.stride = stride;
   RVD_TRY(pack_T(e, c.w, pw.data(), pw.size()));
   // implicit-GEMM kernel (conv_gemm.hip) for the 128- and 256-channel stride-1 convolutions: second weight layout
   // [cout][tap][cin].  Validated on hardware in round 2 (tests/test_diar_gpu.py: both kernels against the oracle and
   // against each other; 806 / 1150 TFLOP/s vs 555-598 for the direct kernel); RVD_CONV_IGEMM=0 selects the direct kernel.
   // Round 4: the stride-2 convolutions that open stages 3 and 4 go there too (RVD_CONV_IGEMM=1: stride 1 only, as in round 2).
-  const char* ig = lab_env("RVD_CONV_IGEMM");
-  const int ig_mode = ig ? atoi(ig) : 2;
-  if (ig_mode != 0 && e->dtype == DT_BF16 && k == 3 && (stride == 1 || (stride == 2 && ig_mode >= 2)) && cin % 64 == 0 && cout % 128 == 0) {
+  if (conv_igemm_packed(e->dtype, k, stride, cin, cout)) {
     std::vector<float> pg((size_t)cout * taps * cin);
-    for (int o = 0; o < cout; ++o) {
-      const float sc = g->data[o] / std::sqrt(v->data[o] + 1e-5f);
-      for (int t = 0; t < taps; ++t)
-        for (int ci = 0; ci < cin; ++ci) pg[((size_t)o * taps + t) * cin + ci] = w->data[((size_t)o * cin + ci) * taps + t] * sc;
-    }
+    conv_pack_igemm(w->data.data(), sc.data(), cout, cin, taps, (size_t)taps * cin, pg.data());
     RVD_TRY(pack_T(e, c.w_ig, pg.data(), pg.size()));
     if (e->emb_fp8 && cin % 128 == 0) {          // e4m3 copy, one scale per output channel (as engine.hip's pack_linear)
       std::vector<uint8_t> q(pg.size());
@@ -462,15 +454,13 @@ int pack_fused_shortcut(rvd_engine* e, ResBlock& B, const std::string& p) {
   RVD_TRY(need(e, p + ".shortcut.1.bias", cout, &bs));
   RVD_TRY(need(e, p + ".shortcut.1.running_mean", cout, &ms));
   RVD_TRY(need(e, p + ".shortcut.1.running_var", cout, &vs));
-  const size_t ld = (size_t)9 * cin + c2;
-  std::vector<float> pg((size_t)cout * ld), pb(cout);
+  std::vector<float> pg((size_t)cout * (9 * (size_t)cin + c2)), pb(cout), sc(cout), ss(cout);
   for (int o = 0; o < cout; ++o) {
-    const float sc = g->data[o] / std::sqrt(v->data[o] + 1e-5f), ss = gs->data[o] / std::sqrt(vs->data[o] + 1e-5f);
-    pb[o] = (b->data[o] - m->data[o] * sc) + (bs->data[o] - ms->data[o] * ss);
-    for (int t = 0; t < 9; ++t)
-      for (int ci = 0; ci < cin; ++ci) pg[(size_t)o * ld + (size_t)t * cin + ci] = w->data[((size_t)o * cin + ci) * 9 + t] * sc;
-    for (int ci = 0; ci < c2; ++ci) pg[(size_t)o * ld + (size_t)9 * cin + ci] = ws->data[(size_t)o * c2 + ci] * ss;
+    sc[o] = g->data[o] / std::sqrt(v->data[o] + 1e-5f);
+    ss[o] = gs->data[o] / std::sqrt(vs->data[o] + 1e-5f);
+    pb[o] = (b->data[o] - m->data[o] * sc[o]) + (bs->data[o] - ms->data[o] * ss[o]);
   }
+  conv_pack_fused_shortcut(w->data.data(), sc.data(), ws->data.data(), ss.data(), cout, cin, c2, pg.data());
   RVD_TRY(pack_T(e, B.c2.w_ig_sc, pg.data(), pg.size()));
   return up_f32(e, B.c2.b_sc, pb.data(), pb.size());
 }

@@ -283,6 +283,20 @@ struct ConvArgs {
   unsigned* sat8;         // += values of the fp8 output clipped at 448
 };
 int conv2d(hipStream_t s, int dtype, const ConvArgs& a);
+// the tail of conv2d(): resnet.hip's direct kernel whatever the lab switches say (test hooks); conv2d_direct_nt = its channel tile
+int conv2d_direct(hipStream_t s, int dtype, const ConvArgs& a);
+int conv2d_direct_nt(const ConvArgs& a);
+// host: Conv2d weight w [cout][cin][taps] as torch stores it, row o times scale[o] (BatchNorm folded; null = 1) ->
+//   conv_pack_direct: conv2d's layout [taps][cin/ck][cout][ck] (ck = 64 bytes of input channels);
+//   conv_pack_igemm: conv_gemm.hip's rows [cout][ld], tap t / channel ci at column t cin + ci (columns past 9 cin left as they are);
+//   conv_pack_fused_shortcut: the rows of the fused projection shortcut [cout][9 cin + cin2] = the 3x3 weights, then w2 [cout][cin2]
+//   times scale2[o]
+void conv_pack_direct(const float* w, const float* scale, int cout, int cin, int taps, int ck, float* out);
+void conv_pack_igemm(const float* w, const float* scale, int cout, int cin, int taps, size_t ld, float* out);
+void conv_pack_fused_shortcut(const float* w, const float* scale, const float* w2, const float* scale2, int cout, int cin, int cin2,
+                              float* out);
+// whether the engine packs conv_gemm.hip's layout for a convolution of this shape (lab switch RVD_CONV_IGEMM)
+bool conv_igemm_packed(int dtype, int k, int stride, int cin, int cout);
 // conv_block.hip: a whole stride-1 BasicBlock of 32 channels in one kernel (bf16): out = relu(conv_b(relu(conv_a(in) + ba)) + bb + in),
 // BN folded; the intermediate tensor lives in LDS, the residual comes out of the input patch.  Same tensor layouts as conv2d.
 struct ConvBlockArgs {
@@ -332,6 +346,7 @@ bool conv_row64_applicable(int dtype, const ConvArgs& a);
 int conv_row64(hipStream_t s, const ConvArgs& a);
 bool conv_stream_applicable(int dtype, const ConvArgs& a);
 int conv_stream(hipStream_t s, const ConvArgs& a);
+int conv_stream_split(const ConvArgs& a);      // workgroups per row of tiles conv_stream() launches with (RVD_CONV_STREAM, capped)
 int conv_igemm(hipStream_t s, const ConvArgs& a);
 
 // weighted mean/std over time of the trunk output x T [B][F+2][TT+2][C] for each item (item_b = batch row,

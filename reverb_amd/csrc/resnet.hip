@@ -371,18 +371,33 @@ static int launch_conv(hipStream_t st, const ConvArgs& p) {
   return p.stride == 2 ? launch_conv_st<T, NT, 2, 9>(st, p) : launch_conv_st<T, NT, 1, 9>(st, p);
 }
 
-int conv2d(hipStream_t s, int dtype, const ConvArgs& p) {
+static bool conv2d_shape_ok(int dtype, const ConvArgs& p) {
   const int ck = dtype == DT_BF16 ? 32 : 16;
   if ((p.taps != 9 && p.taps != 1) || (p.stride != 1 && p.stride != 2) || p.Cin % ck || p.Cout % 32 ||
       p.Fo != (p.Fi - 1) / p.stride + 1 || p.To != (p.Ti - 1) / p.stride + 1) {
     set_error("conv2d: unsupported shape (3x3 pad 1 or 1x1, stride 1|2, channels multiples of 32)");
-    return E_UNSUPPORTED;
+    return false;
   }
+  return true;
+}
+
+int conv2d(hipStream_t s, int dtype, const ConvArgs& p) {
+  if (!conv2d_shape_ok(dtype, p)) return E_UNSUPPORTED;
   if (p.B <= 0) return OK;
   if (conv_igemm_applicable(dtype, p)) return conv_igemm(s, p);     // only when the engine packed w_ig (RVD_CONV_IGEMM=1)
+  if (p.in2) { set_error("conv2d: the fused projection shortcut (in2) runs on the implicit GEMM only"); return E_UNSUPPORTED; }
   if (conv_row64_applicable(dtype, p)) return conv_row64(s, p);
   if (conv_stream_applicable(dtype, p)) return conv_stream(s, p);
-  const int nt = p.Cout % 128 == 0 ? 128 : (p.Cout % 64 == 0 ? 64 : 32);
+  return conv2d_direct(s, dtype, p);
+}
+
+int conv2d_direct_nt(const ConvArgs& p) { return p.Cout % 128 == 0 ? 128 : (p.Cout % 64 == 0 ? 64 : 32); }
+
+int conv2d_direct(hipStream_t s, int dtype, const ConvArgs& p) {
+  if (!conv2d_shape_ok(dtype, p)) return E_UNSUPPORTED;
+  if (p.in2) { set_error("conv2d_direct: no fused projection shortcut (in2) on the direct kernel"); return E_UNSUPPORTED; }
+  if (p.B <= 0) return OK;
+  const int nt = conv2d_direct_nt(p);
   if (dtype == DT_BF16) {
     if (nt == 128) return launch_conv<bf16_t, 128>(s, p);
     if (nt == 64) return launch_conv<bf16_t, 64>(s, p);
@@ -391,6 +406,41 @@ int conv2d(hipStream_t s, int dtype, const ConvArgs& p) {
   if (nt == 128) return launch_conv<float, 128>(s, p);
   if (nt == 64) return launch_conv<float, 64>(s, p);
   return launch_conv<float, 32>(s, p);
+}
+
+// ------------------------------------------------------------------------------------ weight packing (host; engine and test hooks)
+void conv_pack_direct(const float* w, const float* scale, int cout, int cin, int taps, int ck, float* out) {
+  const int nch = cin / ck;
+  for (int o = 0; o < cout; ++o) {
+    const float sc = scale ? scale[o] : 1.f;
+    for (int ci = 0; ci < cin; ++ci)
+      for (int t = 0; t < taps; ++t)
+        out[(((size_t)t * nch + ci / ck) * cout + o) * ck + ci % ck] = w[((size_t)o * cin + ci) * taps + t] * sc;
+  }
+}
+
+void conv_pack_igemm(const float* w, const float* scale, int cout, int cin, int taps, size_t ld, float* out) {
+  for (int o = 0; o < cout; ++o) {
+    const float sc = scale ? scale[o] : 1.f;
+    for (int t = 0; t < taps; ++t)
+      for (int ci = 0; ci < cin; ++ci) out[(size_t)o * ld + (size_t)t * cin + ci] = w[((size_t)o * cin + ci) * taps + t] * sc;
+  }
+}
+
+void conv_pack_fused_shortcut(const float* w, const float* scale, const float* w2, const float* scale2, int cout, int cin, int cin2,
+                              float* out) {
+  const size_t ld = (size_t)9 * cin + cin2;
+  conv_pack_igemm(w, scale, cout, cin, 9, ld, out);
+  for (int o = 0; o < cout; ++o) {
+    const float ss = scale2 ? scale2[o] : 1.f;
+    for (int ci = 0; ci < cin2; ++ci) out[(size_t)o * ld + (size_t)9 * cin + ci] = w2[(size_t)o * cin2 + ci] * ss;
+  }
+}
+
+bool conv_igemm_packed(int dtype, int k, int stride, int cin, int cout) {
+  const char* ig = lab_env("RVD_CONV_IGEMM");
+  const int ig_mode = ig ? atoi(ig) : 2;
+  return ig_mode != 0 && dtype == DT_BF16 && k == 3 && (stride == 1 || (stride == 2 && ig_mode >= 2)) && cin % 64 == 0 && cout % 128 == 0;
 }
 
 // ------------------------------------------------------------------------------------ masked statistics pooling (TSTP)

@@ -100,6 +100,15 @@ int rvb_test_classifier(int dtype, const float* x, int ldx, const float* w, cons
                         int64_t M, int in, int C);
 int rvb_test_tstp(int dtype, const float* x, int B, const int32_t* item_b, const float* mask, int mask_len, int n_items, int F,
                   int TT, int C, float* stats);
+/* embedding trunk (resnet.hip, conv_gemm.hip, conv_row64.hip, conv_stream.hip) on host floats; see test_api.hip for the layouts.
+ * conv2d: one convolution through a named path (0 = conv2d's dispatch, 1 = direct, 2 = implicit GEMM, 3 = row64, 4 = stream),
+ * optionally with the fused projection shortcut (x2 / w2); ran[2] = {kernel that ran, its tile}.  emb_stem: emb_window_mean over
+ * all windows, then emb_conv1 on the listed ones. */
+int rvb_test_conv2d(int dtype, int path, const float* x, const float* w, const float* bias, const float* res, float* out, int B, int Fi,
+                    int Ti, int Cin, int Cout, int stride, int taps, int relu, const float* x2, const float* w2, int Fi2, int Ti2, int Cin2,
+                    int stride2, int32_t* ran);
+int rvb_test_emb_stem(int dtype, const float* fb, int64_t n_rows, const int64_t* win, int B, int n_windows, int frames_per_step, int nfr,
+                      int F, int C, const float* w, const float* bias, float* mean, float* out);
 
 /* GEMM kernel selection / micro-benchmark hooks (tests and tuning only) */
 int rvb_test_set_gemm_variant(int variant /* 0 auto, 1 gemm.hip 128x128, 2 gemm2.hip 256x256 LDS-DMA */);

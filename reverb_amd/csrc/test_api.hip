@@ -946,3 +946,147 @@ extern "C" int rvb_test_tstp(int dtype, const float* x, int B, const int32_t* it
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(ds, dtype, false, stats, (size_t)n_items * 2 * C * F);
 }
+
+// ---------------------------------------------------------------------------------------------- embedding trunk (resnet.hip, conv_*.hip)
+namespace {
+// unbordered NHWC [B][F][T][C] host floats -> bordered [B][F + 2][T + 2][C] in dtype (zero border) + `slack` zero bytes behind it
+int up_bordered(Dev& d, int dtype, const float* src, int B, int F, int T, int C, size_t slack) {
+  const size_t n = (size_t)B * (F + 2) * (T + 2) * C, es = dt_size(dtype);
+  T_TRY(d.alloc(n * es + slack));
+  RVB_HIP_CHECK(hipMemset(d.p, 0, n * es + slack));
+  std::vector<float> p(n, 0.f);
+  for (int b = 0; b < B; ++b)
+    for (int f = 0; f < F; ++f)
+      for (int t = 0; t < T; ++t)
+        memcpy(&p[(((size_t)b * (F + 2) + f + 1) * (T + 2) + t + 1) * C], &src[(((size_t)b * F + f) * T + t) * C], (size_t)C * 4);
+  if (dtype == DT_F32) { RVB_HIP_CHECK(hipMemcpy(d.p, p.data(), n * 4, hipMemcpyHostToDevice)); return OK; }
+  std::vector<bf16_t> h(n);
+  for (size_t i = 0; i < n; ++i) h[i] = f32_to_bf16(p[i]);
+  RVB_HIP_CHECK(hipMemcpy(d.p, h.data(), n * 2, hipMemcpyHostToDevice));
+  return OK;
+}
+// bordered device plane (+ slack bytes) -> unbordered host floats; E_STATE if anything outside the interior is not zero
+int down_bordered(const Dev& d, int dtype, float* dst, int B, int F, int T, int C, size_t slack, const char* who) {
+  const size_t n = (size_t)B * (F + 2) * (T + 2) * C, es = dt_size(dtype);
+  std::vector<unsigned char> raw(n * es + slack);
+  RVB_HIP_CHECK(hipMemcpy(raw.data(), d.p, raw.size(), hipMemcpyDeviceToHost));
+  for (size_t i = n * es; i < raw.size(); ++i)
+    if (raw[i]) { set_error(std::string(who) + ": the kernel wrote past the end of its output plane"); return E_STATE; }
+  for (int b = 0; b < B; ++b)
+    for (int f = 0; f < F + 2; ++f)
+      for (int t = 0; t < T + 2; ++t) {
+        const size_t at = (((size_t)b * (F + 2) + f) * (T + 2) + t) * C;
+        const bool border = f == 0 || f == F + 1 || t == 0 || t == T + 1;
+        for (int c = 0; c < C; ++c) {
+          float v;
+          if (dtype == DT_F32) memcpy(&v, &raw[(at + c) * 4], 4);
+          else { bf16_t h; memcpy(&h, &raw[(at + c) * 2], 2); v = bf16_to_f32(h); }
+          if (border) {
+            bool zero = true;
+            for (size_t k = 0; k < es; ++k) zero = zero && raw[(at + c) * es + k] == 0;
+            if (!zero) { set_error(std::string(who) + ": the kernel wrote into the zero border"); return E_STATE; }
+          } else {
+            dst[(((size_t)b * F + f - 1) * T + t - 1) * C + c] = v;
+          }
+        }
+      }
+  return OK;
+}
+constexpr size_t kSlack = 64 * 1024;      // zeros behind every device tensor of the conv hooks (kernels that read a row ahead stay inside)
+}  // namespace
+
+// One convolution of the trunk through a named path, on host floats.  x [B][Fi][Ti][Cin] (unbordered NHWC), w [Cout][Cin][k][k] as torch
+// stores it (BatchNorm folded; k = 3 for taps 9, 1 for taps 1), bias [Cout], res [B][Fo][To][Cout] or null; out [B][Fo][To][Cout],
+// Fo = (Fi - 1) / stride + 1 (the same for To).  Fused projection shortcut (x2 non-null): x2 [B][Fi2][Ti2][Cin2], w2 [Cout][Cin2],
+// stride2, with Fo = (Fi2 - 1) / stride2 + 1 (To alike); bias is then the sum of both biases and res must be null (pack_fused_shortcut).
+// path: 0 = conv2d()'s own dispatch, with w_ig present when the engine would pack it for this shape (conv_igemm_packed);
+// 1 = resnet.hip's direct kernel; 2 = conv_gemm.hip's implicit GEMM; 3 = conv_row64.hip; 4 = conv_stream.hip.  A path that does not
+// apply to the shape (lab switches included) is refused with E_STATE before anything runs.  ran[2] = {kernel that ran, 1 .. 4 as
+// `path`; its tile: output channels per workgroup (direct), pixels per tile (implicit GEMM: 256 | 512 wide), 0 (row64), workgroups
+// per row of tiles (stream)}.  The output plane is zero-filled first; E_STATE if the kernel wrote into its border or past its end.
+extern "C" int rvb_test_conv2d(int dtype, int path, const float* x, const float* w, const float* bias, const float* res, float* out,
+                               int B, int Fi, int Ti, int Cin, int Cout, int stride, int taps, int relu, const float* x2,
+                               const float* w2, int Fi2, int Ti2, int Cin2, int stride2, int32_t* ran) {
+  const int ck = dtype == DT_BF16 ? 32 : 16;
+  bool ok = x && w && bias && out && ran && (dtype == DT_F32 || dtype == DT_BF16) && path >= 0 && path <= 4 && B >= 1 && Fi >= 1 &&
+            Ti >= 1 && Cin >= 1 && Cout >= 1 && Cin % ck == 0 && Cout % 32 == 0 && (stride == 1 || stride == 2) && (taps == 9 || taps == 1);
+  const int Fo = ok ? (Fi - 1) / stride + 1 : 0, To = ok ? (Ti - 1) / stride + 1 : 0;
+  ok = ok && (int64_t)(Fi + 2) * (Ti + 2) * Cin < ((int64_t)1 << 30) && (int64_t)(Fo + 2) * (To + 2) * Cout < ((int64_t)1 << 30) &&
+       (int64_t)B * (Fi + 2) * (Ti + 2) * Cin < ((int64_t)1 << 31) && (int64_t)B * (Fo + 2) * (To + 2) * Cout < ((int64_t)1 << 31);
+  if (x2)
+    ok = ok && w2 && !res && (stride2 == 1 || stride2 == 2) && Fi2 >= 1 && Ti2 >= 1 && Cin2 >= 1 && Cin2 % ck == 0 &&
+         Fo == (Fi2 - 1) / stride2 + 1 && To == (Ti2 - 1) / stride2 + 1 && (int64_t)B * (Fi2 + 2) * (Ti2 + 2) * Cin2 < ((int64_t)1 << 31);
+  if (!ok) { set_error("rvb_test_conv2d: bad argument"); return E_ARG; }
+  // which kernel runs: decided on the shape alone (the host pointers stand in for the device tensors they will become)
+  const int k = taps == 9 ? 3 : 1;
+  const bool pack_ig = path == 2 || (path == 0 && conv_igemm_packed(dtype, k, stride, Cin, Cout));
+  ConvArgs a{};
+  a.in = x; a.w = w; a.bias = bias; a.res = res; a.out = out;
+  a.B = B; a.Fi = Fi; a.Ti = Ti; a.Cin = Cin; a.Fo = Fo; a.To = To; a.Cout = Cout; a.stride = stride; a.taps = taps; a.relu = relu;
+  a.w_ig = pack_ig ? w : nullptr;
+  if (x2) { a.in2 = x2; a.Cin2 = Cin2; a.Fi2 = Fi2; a.Ti2 = Ti2; a.stride2 = stride2; }
+  int kind = 0;
+  if (path == 0) kind = conv_igemm_applicable(dtype, a) ? 2 : x2 ? 0 : conv_row64_applicable(dtype, a) ? 3 : conv_stream_applicable(dtype, a) ? 4 : 1;
+  else if (path == 1) kind = x2 ? 0 : 1;
+  else if (path == 2) kind = conv_igemm_applicable(dtype, a) ? 2 : 0;
+  else if (path == 3) kind = !x2 && conv_row64_applicable(dtype, a) ? 3 : 0;
+  else kind = !x2 && conv_stream_applicable(dtype, a) ? 4 : 0;
+  if (kind == 0) { set_error("rvb_test_conv2d: the path does not apply to this shape (or is switched off)"); return E_STATE; }
+  T_TRY(need_gpu());
+  Dev dx, dw, dwg, db, dr, dout, dx2;
+  T_TRY(up_bordered(dx, dtype, x, B, Fi, Ti, Cin, kSlack));
+  if (res) T_TRY(up_bordered(dr, dtype, res, B, Fo, To, Cout, kSlack));
+  if (x2) T_TRY(up_bordered(dx2, dtype, x2, B, Fi2, Ti2, Cin2, kSlack));
+  std::vector<float> pw((size_t)taps * Cin * Cout);
+  conv_pack_direct(w, nullptr, Cout, Cin, taps, ck, pw.data());
+  T_TRY(up_T(dw, dtype, pw.data(), pw.size()));
+  if (kind == 2) {
+    std::vector<float> pg((size_t)Cout * ((size_t)taps * Cin + (x2 ? Cin2 : 0)));
+    if (x2) conv_pack_fused_shortcut(w, nullptr, w2, nullptr, Cout, Cin, Cin2, pg.data());
+    else conv_pack_igemm(w, nullptr, Cout, Cin, taps, (size_t)taps * Cin, pg.data());
+    T_TRY(up_T(dwg, DT_BF16, pg.data(), pg.size()));
+  }
+  T_TRY(up_raw(db, bias, (size_t)Cout * 4));
+  const size_t no = (size_t)B * (Fo + 2) * (To + 2) * Cout * dt_size(dtype);
+  T_TRY(dout.alloc(no + kSlack));
+  RVB_HIP_CHECK(hipMemset(dout.p, 0, no + kSlack));
+  a.in = dx.p; a.w = dw.p; a.bias = (const float*)db.p; a.res = dr.p; a.out = dout.p; a.w_ig = kind == 2 ? dwg.p : nullptr;
+  a.in2 = dx2.p;
+  ran[0] = kind;
+  ran[1] = kind == 1 ? conv2d_direct_nt(a) : kind == 2 ? (conv_igemm_wide(a) ? 512 : 256) : kind == 4 ? conv_stream_split(a) : 0;
+  if (path == 0) T_TRY(conv2d(nullptr, dtype, a));
+  else if (kind == 1) T_TRY(conv2d_direct(nullptr, dtype, a));
+  else if (kind == 2) T_TRY(conv_igemm(nullptr, a));
+  else if (kind == 3) T_TRY(conv_row64(nullptr, a));
+  else T_TRY(conv_stream(nullptr, a));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  return down_bordered(dout, dtype, out, B, Fo, To, Cout, kSlack, "rvb_test_conv2d");
+}
+
+// The stem of the trunk as run_trunk runs it: emb_window_mean over ALL n_windows windows of the fbank rows fb [n_rows][80] (window w
+// = rows w frames_per_step .. + nfr), then emb_conv1 on the windows win [B] (any order, repeats allowed) with w [C][1][3][3] (BatchNorm
+// folded), bias [C].  mean [n_windows][80] (fp32); out [B][F][nfr][C] (unbordered; the bordered plane's border must stay zero).
+extern "C" int rvb_test_emb_stem(int dtype, const float* fb, int64_t n_rows, const int64_t* win, int B, int n_windows, int frames_per_step,
+                                 int nfr, int F, int C, const float* w, const float* bias, float* mean, float* out) {
+  bool ok = fb && win && w && bias && mean && out && (dtype == DT_F32 || dtype == DT_BF16) && B >= 1 && n_windows >= 1 &&
+            frames_per_step >= 1 && nfr >= 1 && F >= 1 && F <= 80 && (C == 8 || C == 16 || C == 32) &&
+            (int64_t)(n_windows - 1) * frames_per_step + nfr <= n_rows && (int64_t)B * (F + 2) * (nfr + 2) * C < ((int64_t)1 << 31);
+  for (int b = 0; ok && b < B; ++b) ok = win[b] >= 0 && win[b] < n_windows && win[b] * frames_per_step + nfr <= n_rows;
+  if (!ok) { set_error("rvb_test_emb_stem: bad argument"); return E_ARG; }
+  T_TRY(need_gpu());
+  Dev dfb, dwin, dmean, dw, db, dout;
+  T_TRY(up_raw(dfb, fb, (size_t)n_rows * 80 * 4));
+  T_TRY(up_raw(dwin, win, (size_t)B * 8));
+  T_TRY(dmean.alloc((size_t)n_windows * 80 * 4));
+  T_TRY(up_raw(dw, w, (size_t)C * 9 * 4));
+  T_TRY(up_raw(db, bias, (size_t)C * 4));
+  const size_t no = (size_t)B * (F + 2) * (nfr + 2) * C * dt_size(dtype);
+  T_TRY(dout.alloc(no + kSlack));
+  RVB_HIP_CHECK(hipMemset(dout.p, 0, no + kSlack));
+  T_TRY(emb_window_mean(nullptr, (const float*)dfb.p, nullptr, n_windows, frames_per_step, nfr, (float*)dmean.p));
+  T_TRY(emb_conv1(nullptr, dtype, (const float*)dfb.p, (const int64_t*)dwin.p, (const float*)dmean.p, (const float*)dw.p, (const float*)db.p,
+                  dout.p, B, F, nfr, frames_per_step, C));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  RVB_HIP_CHECK(hipMemcpy(mean, dmean.p, (size_t)n_windows * 80 * 4, hipMemcpyDeviceToHost));
+  return down_bordered(dout, dtype, out, B, F, nfr, C, kSlack, "rvb_test_emb_stem");
+}

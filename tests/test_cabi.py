@@ -124,6 +124,35 @@ def test_diarization_kernel_hooks_refuse_out_of_range_shapes_before_any_device_w
     assert lib.rvb_test_tstp(0, f(z), 3, _lib.iptr(ib), f(z), 10, 2, 1, 4, 8, f(z)) == -1     # item 1 in window 3 of 3
 
 
+def test_trunk_kernel_hooks_refuse_out_of_range_shapes_before_any_device_work(lib):
+    """The hooks of tests/test_emb_conv_kernels_gpu.py check their arguments (E_ARG = -1) and whether the named kernel applies to the
+    shape (E_STATE = -3) before they look for a device, so these hold with and without a GPU."""
+    f = _lib.fptr
+    z = np.zeros(1 << 20, np.float32)
+    ran = np.zeros(2, np.int32)
+
+    def conv(dtype, path, B, Fi, Ti, cin, cout, stride, x2=False, Fi2=0, Ti2=0, cin2=0, stride2=2):
+        return lib.rvb_test_conv2d(dtype, path, f(z), f(z), f(z), None, f(z), B, Fi, Ti, cin, cout, stride, 9, 1,
+                                   f(z) if x2 else None, f(z) if x2 else None, Fi2, Ti2, cin2, stride2, _lib.iptr(ran))
+    assert conv(1, 5, 1, 4, 8, 64, 64, 1) == -1                          # no path 5
+    assert conv(1, 3, 1, 8, 16, 64, 64, 2) == -3                         # row64 runs stride 1 only
+    assert conv(0, 2, 1, 4, 8, 128, 128, 1) == -3                        # the implicit GEMM is bf16 only
+    assert conv(1, 4, 1, 4, 8, 128, 128, 1) == -3                        # the stream is 32 / 64 channels only
+    assert conv(1, 1, 1, 4, 8, 48, 64, 1) == -1                          # 48 channels: not a whole 64-byte chunk in bf16
+    assert conv(0, 1, 1, 4, 8, 24, 64, 1) == -1                          # ... nor 24 in fp32
+    assert conv(1, 1, 1, 4, 8, 64, 48, 1) == -1                          # output channels in 32s
+    assert conv(1, 2, 1, 20, 250, 128, 128, 1, True, 38, 499, 64) == -1  # x2 of 38 rows gives 19 at stride 2, not 20
+    assert conv(1, 2, 1, 20, 250, 128, 128, 1, True, 40, 502, 64) == -1  # ... and 502 columns 251, not 250
+    assert conv(1, 1, 1, 20, 250, 128, 128, 1, True, 40, 499, 64) == -3  # the direct kernel has no fused shortcut
+    win = np.array([0, 3], np.int64)
+    assert lib.rvb_test_emb_stem(0, f(z), 3 * 100 + 997, win.ctypes.data_as(_lib._i64p), 2, 4, 100, 998, 80, 32, f(z), f(z), f(z),
+                                 f(z)) == -1                              # window 3 ends one row past the fbank
+    assert lib.rvb_test_emb_stem(0, f(z), 3 * 100 + 998, win.ctypes.data_as(_lib._i64p), 2, 3, 100, 998, 80, 32, f(z), f(z), f(z),
+                                 f(z)) == -1                              # window 3 of 3
+    assert lib.rvb_test_emb_stem(0, f(z), 3 * 100 + 998, win.ctypes.data_as(_lib._i64p), 2, 4, 100, 998, 80, 24, f(z), f(z), f(z),
+                                 f(z)) == -1                              # 24 stem channels
+
+
 def test_bad_arguments_are_reported_not_crashed(lib):
     cfg = _lib.ModelCfg()
     h = ctypes.c_void_p()
