@@ -13,8 +13,12 @@ are independent (reverb.py:148-180) so there is no data-path collective, only th
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W          # or under torchrun
   python bench.py ... --dump-outputs DIR                 # + the last timed step's results as DIR/*.npy (seeded inputs)
+  python bench.py ... --full                             # + everything below, measured after the headline steps
 
-At N = 1 the same JSON line also carries
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` and prints the line: `value`, `ms_per_step` and the GEMM
+`roofline` from the HIP events around the timed steps' GEMM launches (`traffic` and `cpu_baseline` null).  Whatever takes runs
+of its own is measured only with `--full`, after the timed steps: the per-stage table (one extra step with every stage
+bracketed), the long form in a file, `xgmi_allgather` on the collective path (N > 1 or RVB_FORCE_DIST), and at N = 1
   roofline.traffic  HBM bytes per GEMM launch, from two nested `rocprofv3 --pmc` passes of this very command
                     (FETCH_SIZE, WRITE_SIZE; corrected as MI355X_MICROARCH.md prescribes), `--traffic off` skips them
   pcie_inclusive    the same step with the 115 MB/h PCM upload from host memory inside it (never `value`)
@@ -62,18 +66,25 @@ def parse(argv=None):
     p.add_argument("--beam", type=int, default=10)
     p.add_argument("--ctc-weight", type=float, default=0.1)
     p.add_argument("--reverse-weight", type=float, default=0.0)
-    p.add_argument("--cpu-baseline-chunks", type=int, default=8, help="0 disables the CPU baseline leg (BASELINE.md section 3: >= 8 chunks)")
-    p.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
+    p.add_argument("--full", action="store_true",
+                   help="after the headline steps also measure what takes runs of its own: the per-stage table, the xGMI "
+                        "all-gather (collective path), and at N = 1 the PCIe-inclusive leg, the CPU baseline, the GEMMs' HBM "
+                        "traffic, the diarization / joint_fp8 sub-records and the ASR variants (the options below trim that set)")
+    p.add_argument("--cpu-baseline-chunks", type=int, default=8,
+                   help="--full: 0 disables the CPU baseline leg (BASELINE.md section 3: >= 8 chunks)")
+    p.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events (--full: no per-stage table)")
     p.add_argument("--traffic", default="auto", choices=["auto", "off"],
-                   help="auto: at N = 1 measure the GEMMs' HBM traffic with two nested rocprofv3 --pmc passes")
+                   help="auto: with --full at N = 1 measure the GEMMs' HBM traffic with two nested rocprofv3 --pmc passes")
     p.add_argument("--gather", default="results", choices=["results", "posteriors"],
                    help="what the ranks exchange per step: the decoded results (1.3 KB per chunk, the product path) or ALSO the "
                         "top-beam CTC posteriors (int32 id + fp32 log-prob x beam per encoder frame, 41 KB per chunk) -- the "
-                        "alternative exchange of SURVEY 8(e), inside the timed region; either way a device-to-device "
+                        "alternative exchange of SURVEY 8(e), inside the timed region; either way, with --full, a device-to-device "
                         "all-gather of that posterior payload is timed once outside it (`xgmi_allgather` in the line)")
-    p.add_argument("--no-diarization", action="store_true", help="skip the diarization sub-record (N = 1 only)")
-    p.add_argument("--no-pcie", action="store_true", help="skip the PCIe-inclusive leg (N = 1 only)")
-    p.add_argument("--no-variants", action="store_true", help="skip the parity_f32 / asr_fp8 / r268 sub-records (N = 1 only)")
+    p.add_argument("--no-diarization", action="store_true",
+                   help="--full: skip the diarization and joint_fp8 sub-records (N = 1 only)")
+    p.add_argument("--no-pcie", action="store_true", help="--full: skip the PCIe-inclusive leg (N = 1 only)")
+    p.add_argument("--no-variants", action="store_true",
+                   help="--full: skip the parity_f32 / asr_fp8 / r268 / two_streams sub-records (N = 1 only)")
     p.add_argument("--joint-hours", type=float, default=3.0, help="length of the joint_fp8 sub-record's recording (BASELINE configs[4]: 3 h)")
     p.add_argument("--dump-outputs", metavar="DIR", default=None,
                    help="write what the last timed step returned (the per-chunk attention_rescoring results of every rank) "
@@ -262,12 +273,13 @@ def pmc_traffic(sub, match, what, last=None):
 
 
 def measure_traffic(args, per_step):
-    """HBM bytes per GEMM launch of this workload: this same command (headline leg only) under the two PMC passes, one warm-up
-    step and one timed step; the last `per_step` GEMM dispatches -- the timed step's -- are what counts."""
+    """HBM bytes per GEMM launch of this workload: this same command as a plain run (no --full: headline leg only) under the
+    two PMC passes, one warm-up step and one timed step; the last `per_step` GEMM dispatches -- the timed step's -- are what
+    counts."""
     sub = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", "1", "--warmup", "1", "--model", args.model,
            "--dtype", args.dtype, "--hours", str(args.hours), "--chunks-per-launch", str(args.chunks_per_launch),
            "--beam", str(args.beam), "--ctc-weight", str(args.ctc_weight), "--reverse-weight", str(args.reverse_weight),
-           "--cpu-baseline-chunks", "0", "--no-profile", "--traffic", "off", "--no-diarization", "--no-pcie", "--no-variants"]
+           "--no-profile"]
     return pmc_traffic(sub, ("gemm",), "the last step of this command", last=per_step)
 
 
@@ -608,14 +620,14 @@ def main():
         g = eng.timing("gemm")
         g8 = eng.timing("gemm_fp8")
         att = eng.timing("attention")
-        if not args.no_profile:       # the per-stage table comes from ONE extra, untimed step with every stage bracketed
+        if args.full and not args.no_profile:       # the per-stage table comes from ONE extra, untimed step with every stage bracketed
             eng.reset_timings()
             eng.set_profiling(True)
             step()
             eng.set_profiling(False)
             stages = {k: eng.timing(k) for k in ("fbank", "subsample", "gemm", "gemm_fp8", "attention", "rownorm", "glu_dwconv",
                                                  "ctc_topk", "embed", "lse_gather", "search_host")}
-        if world == 1 and not args.no_pcie:
+        if args.full and world == 1 and not args.no_pcie:
             # the same steps from PCM in (page-locked) HOST memory: SURVEY.md 8d's end-to-end definition.  Every step's
             # samples cross PCIe inside the timed region (K uploads for K steps); since round 4 they are double-buffered
             # (rvb_upload_pcm_async): step i+1's samples travel on a copy stream underneath step i's encoder -- the steady state
@@ -629,7 +641,7 @@ def main():
                     "overlap": "double-buffered: upload of step i+1 on a copy stream under step i (rvb_upload_pcm_async)"}
 
     xgmi = None
-    if comm is not None:
+    if args.full and comm is not None:
         # SURVEY 8(e)'s bandwidth datapoint, outside the timed region: the posterior exchange of one hour per rank as ONE
         # all-gather between device buffers (every rank calls it; rank 0 reports)
         enc_frames = ((chunk - 3) // 2 - 3) // 2 + 1 if chunk >= 7 else 0
@@ -699,7 +711,7 @@ def main():
             "pcie_inclusive": pcie,
             "xgmi_allgather": xgmi,
         }
-        if not STUB and world == 1 and args.cpu_baseline_chunks > 0:
+        if args.full and not STUB and world == 1 and args.cpu_baseline_chunks > 0:
             nb = min(args.cpu_baseline_chunks, n_chunks)
             _, feats = eng.fbank(return_feats=True)
             x = np.zeros((nb, chunk, 80), np.float32)
@@ -717,7 +729,7 @@ def main():
         eng.close()
     if use_dist:
         dist.destroy_process_group()
-    if rank == 0 and not STUB and world == 1:
+    if args.full and rank == 0 and not STUB and world == 1:
         # the engine is closed and the GPU idle: nested measurements of the same workload
         if args.traffic == "auto" and out["roofline"] is not None and args.dtype != "fp8":
             per_step = out["roofline"]["launches"] // max(args.steps, 1)
@@ -766,7 +778,7 @@ def main():
     if rank == 0:
         import ctypes
         ctypes.CDLL(None).fflush(None)      # RCCL's version banner sits in the C stdout buffer: get it out first,
-        long_path = write_long_form(out)
+        long_path = write_long_form(out) if args.full else None
         sys.stderr.write("bench.py long form: " + json.dumps(out) + "\n")
         sys.stderr.flush()
         print(json.dumps(compact(out, long_path)), flush=True)  # so that the (compact) JSON line is the LAST line of stdout

@@ -102,6 +102,55 @@ def test_dump_outputs_samples_a_fixed_set_of_chunks_beyond_the_limit(tmp_path):
     assert np.load(tmp_path / "b" / "chunk_index.npy").tolist() == idx.tolist()       # the same sample every run
 
 
+def _run_bench(args, long_path, stub):
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR",
+                                                             "RVB_BENCH_STUB", "RVB_FORCE_DIST")}
+    env["RVB_BENCH_LONG"] = str(long_path)
+    if stub:
+        env["RVB_BENCH_STUB"] = "1"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--model", "tiny", "--hours", "0.02"] + args, env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    return json.loads([l for l in r.stdout.splitlines() if l.strip()][-1])
+
+
+SUB_RECORDS = ("pcie_inclusive", "xgmi_allgather", "two_streams", "parity_f32", "asr_fp8", "r268", "diarization", "joint_fp8")
+
+
+def test_bench_full_is_off_by_default_and_a_plain_run_writes_no_long_form(tmp_path):
+    """A plain run does what the headline needs and no more: the line carries no sub-record, no CPU baseline and no long form;
+    `--full` adds the long form (RVB_BENCH_LONG) whose headline is the line's.  RVB_BENCH_STUB: the stub engine has no legs
+    beyond the headline, so this checks the switch itself."""
+    import bench
+    assert bench.parse([]).full is False and bench.parse(["--full"]).full is True
+    d = _run_bench([], tmp_path / "plain.json", stub=True)
+    assert not (tmp_path / "plain.json").exists() and "long_form" not in d
+    assert d["cpu_baseline"] is None and not set(SUB_RECORDS) & set(d)
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["value"] > 0
+    d = _run_bench(["--full"], tmp_path / "full.json", stub=True)
+    assert d["long_form"] and json.load(open(tmp_path / "full.json"))["value"] == d["value"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_and_full_runs_on_the_device(tmp_path):
+    """The real engine, tiny model, 4 chunks: a plain run reports the GEMM roofline of its timed steps and nothing that takes a
+    run of its own (no PMC traffic, no per-stage table, no PCIe leg, no CPU baseline); `--full` adds them (the PMC passes, the
+    diarization / joint and the ASR variants trimmed off here: the driver's --full run carries those)."""
+    d = _run_bench([], tmp_path / "plain.json", stub=False)
+    assert d["data"] == "synthetic" and d["n_gpus"] == 1 and d["value"] > 0 and d["ms_per_step"] > 0
+    r = d["roofline"]
+    assert r["bound"] == "mfma" and r["traffic"] is None and 0 < r["frac"] < 1 and r["launches"] > 0
+    assert d["cpu_baseline"] is None and not set(SUB_RECORDS) & set(d) and not (tmp_path / "plain.json").exists()
+    d = _run_bench(["--full", "--no-diarization", "--no-variants", "--traffic", "off", "--cpu-baseline-chunks", "1"],
+                   tmp_path / "full.json", stub=False)
+    assert d["pcie_inclusive"]["value"] > 0 and d["cpu_baseline"]["value"] > 0 and d["roofline"]["traffic"] is None
+    L = json.load(open(tmp_path / "full.json"))
+    assert L["value"] == d["value"] and L["stage_ms_per_step"]["gemm"] > 0
+    assert L["pcie_inclusive"]["uploads_in_timed_region"] == 2 and "1 chunks" in L["cpu_baseline"]["sample"]
+
+
 def test_bench_gpus_more_than_visible_is_refused():
     import subprocess
     import sys
