@@ -124,6 +124,19 @@ SIGNATURES = {
     "rvb_wer_counts": (C.c_int, [_i32p, C.c_int64, _i32p, C.c_int64, _i64p]),
 }
 
+class AttnTestArgs(C.Structure):
+    """rvb_test_attn_args of csrc/test_api.h (rvb_test_attention_ex): one attention() call on host floats."""
+    _fields_ = ([(n, C.c_int32) for n in ("dtype", "heads", "dk", "nseq")] +
+                [f for b in ("q", "k", "v", "out") for f in ((b, _f32p), (b[0] + "_rows", C.c_int32), (b[0] + "_stride", C.c_int32),
+                                                             (b[0] + "_col", C.c_int32), ("pad_" + b, C.c_int32))] +
+                [("p", _f32p), ("p_rows", C.c_int32), ("p_stride", C.c_int32), ("p_col", C.c_int32), ("p_off", C.c_int32),
+                 ("bias_u", _f32p), ("bias_v", _f32p)] +
+                [(n, _i32p) for n in ("q_start", "q_len", "kv_start", "kv_len", "q_pos0", "kv_index", "work")] +
+                [(n, C.c_int32) for n in ("n_index", "n_work", "max_q", "q_block", "causal", "chunk", "left", "plain_order", "fold",
+                                          "k_prefolded", "fold_kv_cap", "lab")] +
+                [("ran", C.c_int32 * 8)])
+
+
 # librvb_test.so (csrc/test_api.h): raw kernel / host-search hooks for tests/ and scripts/ -- not in the product library
 TEST_SIGNATURES = {
     "rvb_test_gemm": (C.c_int, [C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float,
@@ -148,6 +161,8 @@ TEST_SIGNATURES = {
                                      C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_int, C.c_int]),
     "rvb_test_attention_trie": (C.c_int, [C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p,
                                           _i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int]),
+    "rvb_test_attention_ex": (C.c_int, [C.POINTER(AttnTestArgs)]),
+    "rvb_test_attention_pos_bias": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_float, _f32p]),
     "rvb_test_logsoftmax_topk": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _f32p, _i32p, _f32p]),
     "rvb_test_lse_gather": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, _f32p]),
     "rvb_test_gemm_glu": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int]),

@@ -420,9 +420,19 @@ __global__ __launch_bounds__(64 * NW, OCC) void attn_kernel(AttnArgs a) {
   }
 }
 
+// the instantiation launch_attn chose last on this thread (librvb_test.so's rvb_test_attention_ex reports it: a test that meant to
+// reach one form and reached another must fail); set before the launch checks, so a refused launch names its form too
+static thread_local AttnForm t_last_form = {0, 0, 0, 0, 0, 0, 0, 0};
+AttnForm attention_last_form(bool reset) {
+  const AttnForm f = t_last_form;
+  if (reset) t_last_form = AttnForm{0, 0, 0, 0, 0, 0, 0, 0};
+  return f;
+}
+
 template <typename T, int DKP, bool HAS_POS, int NW, int FOLD = 0, int PADK = 32, int OCC = 1, int MF = 1>
 static int launch_attn(hipStream_t s, const AttnArgs& a) {
   using L = AttnLds<T, DKP, HAS_POS, FOLD, PADK>;
+  t_last_form = AttnForm{(int)sizeof(T), DKP, HAS_POS ? 1 : 0, NW, FOLD, PADK, OCC, MF};
   static bool attr_set = false;
   auto kern = attn_kernel<T, DKP, HAS_POS, NW, FOLD, PADK, OCC, MF>;
   if (!attr_set) {
@@ -446,22 +456,19 @@ static int dispatch_attn(hipStream_t s, const AttnArgs& a) {
   if constexpr (sizeof(T) == 2) {      // the folded positional term: bf16, dk <= 64, 128-query workgroups (the encoder's form)
     if (pos && a.pos_bias != nullptr && a.fold_kv_cap > 0 && dk <= 64 && dk > 32 && (a.q_block == 0 || a.q_block == 128))
     {
-      static const int occ = lab_env("RVB_ATTN_OCC") ? atoi(lab_env("RVB_ATTN_OCC")) : 2;      // workgroups per CU asked for (lab A/B)
-      if (a.k_prefolded && occ == 3) return launch_attn<T, 64, true, 8, 2, 32, 6>(s, a);
+      if (a.k_prefolded && (a.lab & ATTN_LAB_OCC3)) return launch_attn<T, 64, true, 8, 2, 32, 6>(s, a);      // three workgroups per CU asked for (lab A/B, RVB_ATTN_OCC=3)
       // Two 16-query fragments per wave, 256 queries per workgroup, held to 128 VGPRs = two workgroups per CU (round 6; lab switch
       // RVB_ATTN_MF=0 = one fragment per wave): 8.13 -> 7.25 ms per hour of audio.  Measured beside it and dropped
       // (profiles/r06_call11_*, r06_call13_*): the same with 4 waves / 128 queries (149 VGPRs: 10.2 ms), with 8 waves at the
       // allocator's own 133 VGPRs (one workgroup per CU: 9.2 ms), with 16 waves / 512 queries (8.17 ms), and softmax + P.V fragment by
       // fragment in one basic block (8.55 ms: hipcc does not interleave the two chains and the V fragments are read twice).
-      static const int mfv = lab_env("RVB_ATTN_MF") ? atoi(lab_env("RVB_ATTN_MF")) : 1;
-      if (a.k_prefolded && a.work == nullptr && a.kv_index == nullptr && a.q_block == 0 && a.max_q > 128 && mfv != 0) return launch_attn<T, 64, true, 8, 2, 32, 4, 2>(s, a);
+      if (a.k_prefolded && a.work == nullptr && a.kv_index == nullptr && a.q_block == 0 && a.max_q > 128 && !(a.lab & ATTN_LAB_MF1)) return launch_attn<T, 64, true, 8, 2, 32, 4, 2>(s, a);
       return a.k_prefolded ? launch_attn<T, 64, true, 8, 2>(s, a) : launch_attn<T, 64, true, 8, 1>(s, a);
     }
     // A/B switch for the encoder's form (dk 33..64, 128-query workgroups, positional keys): RVB_ATTN_PADK=16 = the 144-byte row
     // pitch of rounds 1-3 (2-way bank conflicts on every S-phase fragment read: 10.41 vs 9.99 ms per hour, SQ_LDS_BANK_CONFLICT
     // 2.1e8 vs 0 on a quarter hour, profiles/r04_call7_attention_padk_pmc.txt); every other form uses the 32-byte pad
-    static const int padk = lab_env("RVB_ATTN_PADK") ? atoi(lab_env("RVB_ATTN_PADK")) : 32;
-    if (pos && padk == 16 && dk <= 64 && dk > 32 && (a.q_block == 0 || a.q_block == 128)) return launch_attn<T, 64, true, 8, 0, 16>(s, a);
+    if (pos && (a.lab & ATTN_LAB_PADK16) && dk <= 64 && dk > 32 && (a.q_block == 0 || a.q_block == 128)) return launch_attn<T, 64, true, 8, 0, 16>(s, a);
   }
 #define RVB_ATTN_CASE(D)                                                           \
   if (dk <= D) {                                                                   \
@@ -505,9 +512,7 @@ int attention_pos_bias(hipStream_t s, const void* P, int rows, int p_stride, con
 
 int attention(hipStream_t s, int dtype, const AttnArgs& a0) {
   if (a0.nseq <= 0 || a0.max_q <= 0) return OK;
-  static const int plain = lab_env("RVB_ATTN_PLAIN") ? atoi(lab_env("RVB_ATTN_PLAIN")) : 0;      // tuning: A/B of the block order
-  AttnArgs a = a0;
-  if (plain) a.plain_order = 1;
+  const AttnArgs& a = a0;
   const int ve = dtype == DT_BF16 ? 8 : 4;
   if (a.dk % ve || a.q_stride % ve || a.k_stride % ve || a.v_stride % ve || (a.p && a.p_stride % ve)) {
     set_error("attention: dk and row strides must be multiples of the 16-byte vector width");

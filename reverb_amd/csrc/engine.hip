@@ -230,6 +230,9 @@ static int make_fbank_tables(rvb_engine* e) {
 static int out_frames(int T0) { const int T1 = (T0 - 3) / 2 + 1; return (T1 - 3) / 2 + 1; }
 
 // ------------------------------------------------------------------------------------ gemm wrapper
+// every attention launch of the engine carries the lab build's RVB_ATTN_* switches (AttnArgs::lab; the product build: none)
+static const AttnArgs& with_lab(AttnArgs& a) { attention_lab_switches(a); return a; }
+
 // saturation counters of the fp8 activations: one row of 8 per block (+ a guard row: the last block's norm_final names "the next
 // block"); zeroed whenever scales are (re)calibrated or installed
 static int reset_f8sat(rvb_engine* e) {
@@ -615,7 +618,7 @@ static int encoder_layer(rvb_engine* e, EncLayer& L, int lidx, int M, int B, int
       keys = st.cache_len + M;
     }
     Scope sc(e, "attention", 6.0 * B * (double)T * keys * d);
-    RVB_TRY(attention(e->stream, e->dtype, a));
+    RVB_TRY(attention(e->stream, e->dtype, with_lab(a)));
   }
   RVB_TRY(run_gemm(e, e->ao.p, d, L.att_out, x, d, M, true, 1.f, ACT_NONE, x, d));
   // convolution module: x += Conv(LN(x))                   encoder_layer.py:218-229, convolution.py:89-144
@@ -1287,7 +1290,7 @@ static int decoder_forward(rvb_engine* e, Decoder& D, const TrieBatch& t, std::v
     a.nseq = nhyp; a.heads = heads; a.dk = dk; a.max_q = 16; a.causal = 1; a.sqrt_dk = std::sqrt((float)dk);
     {
       Scope sc(e, "attention");
-      RVB_TRY(attention(e->stream, e->dtype, a));
+      RVB_TRY(attention(e->stream, e->dtype, with_lab(a)));
     }
     RVB_TRY(run_gemm(e, e->dao.p, d, L.self_out, x, d, R, true, 1.f, ACT_NONE, x, d));
     // cross attention over the chunk's encoder frames (memory K/V computed once, not per hypothesis:
@@ -1304,7 +1307,7 @@ static int decoder_forward(rvb_engine* e, Decoder& D, const TrieBatch& t, std::v
     a.nseq = e->B; a.heads = heads; a.dk = dk; a.max_q = t.max_chunk_rows; a.causal = 0; a.sqrt_dk = std::sqrt((float)dk);
     {
       Scope sc(e, "attention");
-      RVB_TRY(attention(e->stream, e->dtype, a));
+      RVB_TRY(attention(e->stream, e->dtype, with_lab(a)));
     }
     RVB_TRY(run_gemm(e, e->dao.p, d, L.src_out, x, d, R, true, 1.f, ACT_NONE, x, d));
     // feed forward (ReLU) with the language-specific mix     decoder_layer.py:121-127 / :313-333
@@ -1528,7 +1531,7 @@ static int attention_decode_impl(rvb_engine* e, int N, float length_penalty) {
       a.q_start = e->d_hq_start.as<int>(); a.q_len = e->d_hq_len.as<int>();
       a.kv_start = e->d_seq_start.as<int>(); a.kv_len = e->d_seq_len.as<int>();
       a.nseq = R; a.heads = heads; a.dk = dk; a.max_q = 1; a.causal = 0; a.sqrt_dk = std::sqrt((float)dk);
-      { Scope sc(e, "attention"); RVB_TRY(attention(e->stream, e->dtype, a)); }
+      { Scope sc(e, "attention"); RVB_TRY(attention(e->stream, e->dtype, with_lab(a))); }
       RVB_TRY(run_gemm(e, e->dao.p, d, Ly.self_out, x, d, R, true, 1.f, ACT_NONE, x, d));
       RVB_TRY(run_norm(e, x, Ly.n2, e->dxn.p, false, R, d));
       RVB_TRY(run_gemm(e, e->dxn.p, d, Ly.src_q, e->dq.p, d, R, false));
@@ -1537,7 +1540,7 @@ static int attention_decode_impl(rvb_engine* e, int N, float length_penalty) {
       a.q_start = e->d_hkv_start.as<int>(); a.q_len = e->d_hkv_len.as<int>();
       a.kv_start = e->d_aux_i32.as<int>(); a.kv_len = e->d_aux_i32.as<int>() + B;
       a.nseq = B; a.max_q = N;
-      { Scope sc(e, "attention"); RVB_TRY(attention(e->stream, e->dtype, a)); }
+      { Scope sc(e, "attention"); RVB_TRY(attention(e->stream, e->dtype, with_lab(a))); }
       RVB_TRY(run_gemm(e, e->dao.p, d, Ly.src_out, x, d, R, true, 1.f, ACT_NONE, x, d));
       RVB_TRY(run_norm(e, x, Ly.n3, e->dxn.p, false, R, d));
       const void* ffin = e->dxn.p;
@@ -1821,7 +1824,7 @@ static int joint_decode_impl(rvb_engine* e, int beam, double ctc_weight, double 
       a.q_start = e->d_hq_start.as<int>(); a.q_len = e->d_hq_len.as<int>();
       a.kv_start = e->d_hpath_start.as<int>(); a.kv_len = e->d_hpath_len.as<int>(); a.kv_index = e->d_path.as<int>();
       a.nseq = R; a.heads = heads; a.dk = dk; a.max_q = 1; a.causal = 0; a.sqrt_dk = std::sqrt((float)dk);
-      { Scope sc(e, "attention"); RVB_TRY(attention(e->stream, e->dtype, a)); }
+      { Scope sc(e, "attention"); RVB_TRY(attention(e->stream, e->dtype, with_lab(a))); }
       RVB_TRY(run_gemm(e, e->dao.p, d, Ly.self_out, x, d, R, true, 1.f, ACT_NONE, x, d));
       RVB_TRY(run_norm(e, x, Ly.n2, e->dxn.p, false, R, d));
       RVB_TRY(run_gemm(e, e->dxn.p, d, Ly.src_q, e->dq.p, d, R, false));
@@ -1831,7 +1834,7 @@ static int joint_decode_impl(rvb_engine* e, int beam, double ctc_weight, double 
       a.q_start = e->d_hkv_start.as<int>(); a.q_len = e->d_hkv_len.as<int>();
       a.kv_start = e->d_aux_i32.as<int>(); a.kv_len = e->d_aux_i32.as<int>() + nx;
       a.nseq = nx; a.heads = heads; a.dk = dk; a.max_q = max_xq; a.causal = 0; a.sqrt_dk = std::sqrt((float)dk);
-      { Scope sc(e, "attention"); RVB_TRY(attention(e->stream, e->dtype, a)); }
+      { Scope sc(e, "attention"); RVB_TRY(attention(e->stream, e->dtype, with_lab(a))); }
       RVB_TRY(run_gemm(e, e->dao.p, d, Ly.src_out, x, d, R, true, 1.f, ACT_NONE, x, d));
       RVB_TRY(run_norm(e, x, Ly.n3, e->dxn.p, false, R, d));
       const void* ffin = e->dxn.p;
@@ -1930,6 +1933,15 @@ const char* lab_env(const char* name) { return getenv(name); }      // librvb_te
 #else
 const char* lab_env(const char*) { return nullptr; }                // librvb.so: defaults only
 #endif
+void attention_lab_switches(AttnArgs& a) {
+  static const int sw[2] = {
+      (lab_env("RVB_ATTN_OCC") && atoi(lab_env("RVB_ATTN_OCC")) == 3 ? ATTN_LAB_OCC3 : 0) |
+          (lab_env("RVB_ATTN_MF") && atoi(lab_env("RVB_ATTN_MF")) == 0 ? ATTN_LAB_MF1 : 0) |
+          (lab_env("RVB_ATTN_PADK") && atoi(lab_env("RVB_ATTN_PADK")) == 16 ? ATTN_LAB_PADK16 : 0),
+      lab_env("RVB_ATTN_PLAIN") ? atoi(lab_env("RVB_ATTN_PLAIN")) : 0};
+  a.lab |= sw[0];
+  if (sw[1]) a.plain_order = 1;
+}
 }  // namespace rvb
 extern "C" {
 

@@ -189,7 +189,18 @@ struct AttnArgs {
   int pos_bias_stride;
   int fold_kv_cap;       // with pos_bias: keys whose constants the kernel keeps in LDS (a multiple of 64, >= every sequence's kv_len; <= 16384); 0 = do not fold
   int k_prefolded;       // with pos_bias: `k` already holds K' = k + p (written by the qkv GEMM, GemmArgs::rowadd): nothing to add while staging
+  int lab;               // tuning switches (ATTN_LAB_*), 0 = the product's forms; attention.hip reads no environment of its own
 };
+// AttnArgs::lab: the measured-and-dropped alternatives of the bf16 encoder form (docs/tuning-log.md)
+enum { ATTN_LAB_OCC3 = 1,      // RVB_ATTN_OCC=3: prefolded form squeezed to three workgroups per CU (80 VGPRs + scratch)
+       ATTN_LAB_MF1 = 2,       // RVB_ATTN_MF=0: one 16-query fragment per wave where the prefolded form would take two
+       ATTN_LAB_PADK16 = 4 };  // RVB_ATTN_PADK=16: the 144-byte K / P row pitch of the two-product form
+// fills AttnArgs::lab and plain_order from RVB_ATTN_OCC / _MF / _PADK / _PLAIN, read once per process through lab_env() (engine.hip:
+// the product library reads nothing and leaves the defaults)
+void attention_lab_switches(AttnArgs& a);
+// the kernel instantiation the last attention() of this thread chose ({0} = none since the last reset); tests only
+struct AttnForm { int elem_size, dkp, has_pos, nw, fold, padk, occ, mf; };
+AttnForm attention_last_form(bool reset);
 // builds that table for positional keys P [rows, p_stride] (bf16): out fp32 [heads][rows]
 int attention_pos_bias(hipStream_t s, const void* P, int rows, int p_stride, const float* bias_u, const float* bias_v, int heads, int dk,
                        float scale, float* out);

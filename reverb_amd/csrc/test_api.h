@@ -47,6 +47,32 @@ int rvb_test_attention(int dtype, const float* q, const float* k, const float* v
 int rvb_test_attention_trie(int dtype, const float* q, const float* k, const float* v, float* out, int rows, int heads, int dk,
                             const int32_t* q_start, const int32_t* q_len, const int32_t* q_pos0, const int32_t* kv_start,
                             const int32_t* kv_len, const int32_t* kv_index, int n_index, int nseq, int q_block);
+/* attention() with everything AttnArgs carries, on host floats, so that a test can build any call the engine builds.
+ * q / k / v / out are (buffer [rows][stride], column offset of head 0): buffers given by the same host pointer are uploaded once, so
+ * q, k, v may share the fused qkv buffer (stride 3d, columns 0 / d / 2d) or k, v one of stride 2d.  `out` goes up as the caller filled
+ * it and comes back whole: columns the kernel does not own keep their sentinel.  The kernel reads positional row p_off + j for key j;
+ * fold = 1 builds the per-key table with attention_pos_bias from row p_off on (p_rows - p_off entries per head) and passes
+ * fold_kv_cap / k_prefolded as given (prefolded: `k` holds k + p already).  max_q 0 = the longest q_len.  lab = ATTN_LAB_* bits
+ * (1 = three workgroups per CU, 2 = one fragment per wave, 4 = 16-byte K row pad).  ran[8] = the instantiation that was chosen:
+ * {element size, DKP, HAS_POS, NW, FOLD, PADK, OCC, MF}, zeros when none was launched.  Every index, stride and kv_index entry is
+ * checked against the buffer sizes before any device work (E_ARG). */
+typedef struct rvb_test_attn_args {
+  int32_t dtype, heads, dk, nseq;
+  const float* q; int32_t q_rows, q_stride, q_col, pad0;
+  const float* k; int32_t k_rows, k_stride, k_col, pad1;
+  const float* v; int32_t v_rows, v_stride, v_col, pad2;
+  float* out; int32_t o_rows, o_stride, o_col, pad3;
+  const float* p; int32_t p_rows, p_stride, p_col, p_off;
+  const float* bias_u; const float* bias_v;
+  const int32_t* q_start; const int32_t* q_len; const int32_t* kv_start; const int32_t* kv_len;
+  const int32_t* q_pos0; const int32_t* kv_index; const int32_t* work;
+  int32_t n_index, n_work, max_q, q_block, causal, chunk, left, plain_order, fold, k_prefolded, fold_kv_cap, lab;
+  int32_t ran[8];
+} rvb_test_attn_args;
+int rvb_test_attention_ex(rvb_test_attn_args* a);
+/* attention_pos_bias on its own: the fp32 table out[heads][p_rows - p_off] of positional rows p_off.. of p [p_rows][p_stride] */
+int rvb_test_attention_pos_bias(const float* p, int p_rows, int p_stride, int p_col, int p_off, const float* bias_u, const float* bias_v,
+                                int heads, int dk, float scale, float* out);
 int rvb_test_logsoftmax_topk(const float* logits, int M, int V, int k, float blank_penalty, int blank_id,
                              float* topk_val, int32_t* topk_idx, float* logp);
 int rvb_test_lse_gather(const float* logits, int R, int V, const int32_t* target, float* out);

@@ -365,6 +365,7 @@ int rvb_test_attention(int dtype, const float* q, const float* k, const float* v
     a.fold_kv_cap = (mk + 63) / 64 * 64;
     a.k_prefolded = prefolded ? 1 : 0;
   }
+  attention_lab_switches(a);      // RVB_ATTN_* of the lab build, as the engine passes them
   T_TRY(attention(nullptr, dtype, a));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(dout, dtype, false, out, (size_t)q_rows * d);
@@ -405,9 +406,132 @@ int rvb_test_attention_trie(int dtype, const float* q, const float* k, const flo
     T_TRY(up_raw(wk, work.data(), work.size() * 4));
     a.work = (const int*)wk.p; a.n_work = (int)work.size() / 2;
   }
+  attention_lab_switches(a);      // RVB_ATTN_* of the lab build, as the engine passes them
   T_TRY(attention(nullptr, dtype, a));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(dout, dtype, false, out, (size_t)rows * d);
+}
+
+// attention() as the engine calls it: strided / fused operand buffers, positional rows from an offset, fold, index list, work list,
+// block size, masks, lab switches; reports the instantiation launch_attn chose.  All checks come before any device work.
+static int attn_ex_check(const rvb_test_attn_args& t) {
+  auto bad = [](const char* m) { set_error(std::string("rvb_test_attention_ex: ") + m); return E_ARG; };
+  if (t.dtype != DT_F32 && t.dtype != DT_BF16) return bad("dtype");
+  if (t.heads <= 0 || t.dk <= 0 || t.nseq <= 0 || t.heads > 64 || t.dk > 4096) return bad("heads / dk / nseq");
+  if (!t.q || !t.k || !t.v || !t.out || !t.q_start || !t.q_len || !t.kv_start || !t.kv_len) return bad("null operand");
+  const int d = t.heads * t.dk, ve = t.dtype == DT_BF16 ? 8 : 4;
+  auto cols = [&](int rows, int stride, int col, int align) { return rows >= 0 && stride > 0 && col >= 0 && col % align == 0 && (int64_t)col + d <= stride; };
+  if (!cols(t.q_rows, t.q_stride, t.q_col, ve) || !cols(t.k_rows, t.k_stride, t.k_col, ve) || !cols(t.v_rows, t.v_stride, t.v_col, ve))
+    return bad("q / k / v: head columns outside the row, or not on a 16-byte boundary");
+  if (!cols(t.o_rows, t.o_stride, t.o_col, 4)) return bad("out: head columns outside the row, or not on a 4-element boundary");
+  // buffers named by one host pointer are one device buffer: they must agree on its shape
+  if ((t.q == t.k && (t.q_rows != t.k_rows || t.q_stride != t.k_stride)) || (t.q == t.v && (t.q_rows != t.v_rows || t.q_stride != t.v_stride)) ||
+      (t.k == t.v && (t.k_rows != t.v_rows || t.k_stride != t.v_stride)))
+    return bad("operands that share a buffer disagree on its rows / stride");
+  if ((t.bias_u == nullptr) != (t.bias_v == nullptr)) return bad("bias_u / bias_v come together");
+  if (t.n_index < 0 || (t.kv_index == nullptr) != (t.n_index == 0)) return bad("kv_index / n_index");
+  if (t.n_work < 0 || (t.work == nullptr) != (t.n_work == 0)) return bad("work / n_work");
+  if (t.chunk < 0 || t.max_q < 0 || t.fold_kv_cap < 0 || t.p_off < 0) return bad("negative chunk / max_q / fold_kv_cap / p_off");
+  const int kv_rows = t.k_rows < t.v_rows ? t.k_rows : t.v_rows;
+  int max_kv = 0;
+  for (int i = 0; i < t.nseq; ++i) {
+    if (t.q_start[i] < 0 || t.q_len[i] < 0 || (int64_t)t.q_start[i] + t.q_len[i] > t.q_rows || (int64_t)t.q_start[i] + t.q_len[i] > t.o_rows)
+      return bad("a sequence's queries lie outside q / out");
+    if (t.kv_start[i] < 0 || t.kv_len[i] < 0 || (int64_t)t.kv_start[i] + t.kv_len[i] > (t.kv_index ? t.n_index : kv_rows))
+      return bad("a sequence's keys lie outside k / v (or the index list)");
+    if (t.q_pos0 && t.q_pos0[i] < 0) return bad("negative q_pos0");
+    max_kv = t.kv_len[i] > max_kv ? t.kv_len[i] : max_kv;
+  }
+  for (int i = 0; i < t.n_index; ++i)
+    if (t.kv_index[i] < 0 || t.kv_index[i] >= kv_rows) return bad("kv_index entry outside k / v");
+  for (int i = 0; i < t.n_work; ++i)
+    if (t.work[2 * i] < 0 || t.work[2 * i] >= t.nseq || t.work[2 * i + 1] < 0) return bad("work list entry");
+  if (t.p) {
+    if (t.p_rows <= 0 || t.p_stride <= 0 || t.p_col < 0 || t.p_col % ve || (int64_t)t.p_col + d > t.p_stride || t.p_off >= t.p_rows)
+      return bad("p: head columns outside the row, not on a 16-byte boundary, or p_off past the last row");
+    if (!t.bias_u) return bad("positional keys need bias_u / bias_v");
+    // prefolded keys: the kernel reads no positional row, only the table (clamped at its last entry)
+    if (!(t.fold && t.k_prefolded) && (int64_t)t.p_off + max_kv > t.p_rows) return bad("positional rows p_off .. p_off + kv_len lie outside p");
+  }
+  if (t.fold && (!t.p || t.dtype != DT_BF16)) return bad("fold needs bf16 positional keys");
+  if (t.fold && t.fold_kv_cap < max_kv) return bad("fold_kv_cap must cover every sequence's kv_len");
+  if (t.k_prefolded && !t.fold) return bad("k_prefolded without fold");
+  return OK;
+}
+
+int rvb_test_attention_ex(rvb_test_attn_args* tp) {
+  if (!tp) { set_error("rvb_test_attention_ex: null"); return E_ARG; }
+  rvb_test_attn_args& t = *tp;
+  for (int i = 0; i < 8; ++i) t.ran[i] = 0;
+  T_TRY(attn_ex_check(t));
+  T_TRY(need_gpu());
+  const int dtype = t.dtype, d = t.heads * t.dk;
+  const size_t es = dt_size(dtype);
+  Dev dq, dkk, dv, dp, du, dvv, dout, dc, qs, ql, ks, kl, qp, ki, wk;
+  T_TRY(up_T(dq, dtype, t.q, (size_t)t.q_rows * t.q_stride));
+  if (t.k != t.q) T_TRY(up_T(dkk, dtype, t.k, (size_t)t.k_rows * t.k_stride));
+  if (t.v != t.q && t.v != t.k) T_TRY(up_T(dv, dtype, t.v, (size_t)t.v_rows * t.v_stride));
+  const char* bq = (const char*)dq.p;
+  const char* bk = t.k == t.q ? bq : (const char*)dkk.p;
+  const char* bv = t.v == t.q ? bq : t.v == t.k ? bk : (const char*)dv.p;
+  T_TRY(up_T(dout, dtype, t.out, (size_t)t.o_rows * t.o_stride));
+  if (t.p) T_TRY(up_T(dp, dtype, t.p, (size_t)t.p_rows * t.p_stride));
+  T_TRY(up_raw(du, t.bias_u, (size_t)d * 4));
+  T_TRY(up_raw(dvv, t.bias_v, (size_t)d * 4));
+  T_TRY(up_raw(qs, t.q_start, (size_t)t.nseq * 4)); T_TRY(up_raw(ql, t.q_len, (size_t)t.nseq * 4));
+  T_TRY(up_raw(ks, t.kv_start, (size_t)t.nseq * 4)); T_TRY(up_raw(kl, t.kv_len, (size_t)t.nseq * 4));
+  T_TRY(up_raw(qp, t.q_pos0, (size_t)t.nseq * 4));
+  T_TRY(up_raw(ki, t.kv_index, (size_t)t.n_index * 4));
+  T_TRY(up_raw(wk, t.work, (size_t)t.n_work * 8));
+  AttnArgs a;
+  memset(&a, 0, sizeof(a));
+  a.q = bq + (size_t)t.q_col * es; a.k = bk + (size_t)t.k_col * es; a.v = bv + (size_t)t.v_col * es;
+  a.out = (char*)dout.p + (size_t)t.o_col * es;
+  a.q_stride = t.q_stride; a.k_stride = t.k_stride; a.v_stride = t.v_stride; a.o_stride = t.o_stride;
+  if (t.p) { a.p = (const char*)dp.p + ((size_t)t.p_off * t.p_stride + t.p_col) * es; a.p_stride = t.p_stride; }
+  a.bias_u = (const float*)du.p; a.bias_v = (const float*)dvv.p;
+  a.q_start = (const int*)qs.p; a.q_len = (const int*)ql.p; a.kv_start = (const int*)ks.p; a.kv_len = (const int*)kl.p;
+  a.q_pos0 = (const int*)qp.p; a.kv_index = (const int*)ki.p; a.work = (const int*)wk.p; a.n_work = t.n_work;
+  a.nseq = t.nseq; a.heads = t.heads; a.dk = t.dk; a.causal = t.causal ? 1 : 0; a.chunk = t.chunk; a.left = t.left;
+  a.sqrt_dk = sqrtf((float)t.dk); a.q_block = t.q_block; a.plain_order = t.plain_order ? 1 : 0; a.lab = t.lab;
+  a.max_q = t.max_q;
+  if (a.max_q == 0)
+    for (int i = 0; i < t.nseq; ++i) a.max_q = t.q_len[i] > a.max_q ? t.q_len[i] : a.max_q;
+  if (t.fold) {
+    const int rows = t.p_rows - t.p_off;
+    T_TRY(dc.alloc((size_t)t.heads * rows * 4));
+    T_TRY(attention_pos_bias(nullptr, a.p, rows, t.p_stride, a.bias_u, a.bias_v, t.heads, t.dk, 1.44269504f / sqrtf((float)t.dk), (float*)dc.p));
+    a.pos_bias = (const float*)dc.p; a.pos_bias_stride = rows; a.fold_kv_cap = t.fold_kv_cap; a.k_prefolded = t.k_prefolded ? 1 : 0;
+  }
+  (void)attention_last_form(true);
+  const int rc = attention(nullptr, dtype, a);
+  const AttnForm f = attention_last_form(true);
+  const int ran[8] = {f.elem_size, f.dkp, f.has_pos, f.nw, f.fold, f.padk, f.occ, f.mf};
+  for (int i = 0; i < 8; ++i) t.ran[i] = ran[i];
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  T_TRY(down_T(dout, dtype, false, t.out, (size_t)t.o_rows * t.o_stride));      // also after a refusal: the sentinel must be intact
+  return rc;
+}
+
+int rvb_test_attention_pos_bias(const float* p, int p_rows, int p_stride, int p_col, int p_off, const float* bias_u, const float* bias_v,
+                                int heads, int dk, float scale, float* out) {
+  if (!p || !bias_u || !bias_v || !out || heads <= 0 || dk <= 0 || p_rows <= 0 || p_stride <= 0 || p_col < 0 || p_off < 0 || p_off >= p_rows ||
+      (int64_t)p_col + (int64_t)heads * dk > p_stride) {
+    set_error("rvb_test_attention_pos_bias: head columns outside the row, or p_off past the last row");
+    return E_ARG;
+  }
+  T_TRY(need_gpu());
+  Dev dp, du, dvv, dc;
+  const int rows = p_rows - p_off;
+  T_TRY(up_T(dp, DT_BF16, p, (size_t)p_rows * p_stride));
+  T_TRY(up_raw(du, bias_u, (size_t)heads * dk * 4));
+  T_TRY(up_raw(dvv, bias_v, (size_t)heads * dk * 4));
+  T_TRY(dc.alloc((size_t)heads * rows * 4));
+  T_TRY(attention_pos_bias(nullptr, (const bf16_t*)dp.p + (size_t)p_off * p_stride + p_col, rows, p_stride, (const float*)du.p, (const float*)dvv.p,
+                           heads, dk, scale, (float*)dc.p));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  RVB_HIP_CHECK(hipMemcpy(out, dc.p, (size_t)heads * rows * 4, hipMemcpyDeviceToHost));
+  return OK;
 }
 
 int rvb_test_logsoftmax_topk(const float* logits, int M, int V, int k, float blank_penalty, int blank_id,

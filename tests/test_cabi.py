@@ -153,6 +153,64 @@ def test_trunk_kernel_hooks_refuse_out_of_range_shapes_before_any_device_work(li
                                  f(z)) == -1                              # 24 stem channels
 
 
+def test_attention_hook_refuses_out_of_range_arguments_before_any_device_work(lib):
+    """rvb_test_attention_ex (tests/test_attention_kernels_gpu.py) checks every index, stride, offset and kv_index entry against the host
+    buffer sizes (E_ARG = -1) before it looks for a device, so these hold with and without a GPU; `out` keeps its sentinel."""
+    f, ip = _lib.fptr, _lib.iptr
+    heads, dk, rows = 2, 64, 40
+    d = heads * dk
+    z = np.zeros((rows, 3 * d), np.float32)
+    pz = np.zeros((rows, d), np.float32)
+    bias = np.zeros(d, np.float32)
+    base_i = dict(q_start=[0, 20], q_len=[20, 20], kv_start=[0, 20], kv_len=[20, 20])
+
+    def call(ints=None, with_p=False, **kw):
+        a = _lib.AttnTestArgs()
+        out = np.full((rows, d), -77.0, np.float32)
+        keep = [out]
+        a.dtype, a.heads, a.dk, a.nseq = 1, heads, dk, 2
+        for n, col in (("q", 0), ("k", d), ("v", 2 * d)):
+            setattr(a, n, f(z)); setattr(a, n + "_rows", rows); setattr(a, n + "_stride", 3 * d); setattr(a, n + "_col", col)
+        a.out, a.o_rows, a.o_stride, a.o_col = f(out), rows, d, 0
+        if with_p:
+            a.p, a.p_rows, a.p_stride, a.bias_u, a.bias_v = f(pz), rows, d, f(bias), f(bias)
+        for n, val in dict(base_i, **(ints or {})).items():
+            arr = np.ascontiguousarray(val, np.int32)
+            keep.append(arr)
+            setattr(a, n, ip(arr))
+        for n, val in kw.items():
+            if isinstance(val, (list, np.ndarray)):
+                arr = np.ascontiguousarray(val, np.int32)
+                keep.append(arr)
+                val = ip(arr)
+            setattr(a, n, val)
+        rc = lib.rvb_test_attention_ex(ctypes.byref(a))
+        assert np.all(out == -77.0) and not any(a.ran)
+        return rc
+    assert call(dict(q_len=[20, 21])) == -1                                   # queries past the last row of q / out
+    assert call(dict(kv_len=[20, 21])) == -1                                  # keys past the last row of k / v
+    assert call(dict(q_start=[-1, 20])) == -1
+    assert call(v_col=2 * d + 8) == -1                                        # the last head's columns past the row
+    assert call(k_col=d + 4) == -1                                            # not on a 16-byte boundary (bf16: 8 elements)
+    assert call(o_col=2) == -1
+    assert call(k_rows=rows - 1) == -1                                        # q and k name one buffer but disagree on its rows
+    assert call(kv_index=[0, 1, 2], n_index=3) == -1                          # index list shorter than kv_start + kv_len
+    assert call(kv_index=list(range(39)) + [40], n_index=40) == -1            # an entry past the last row
+    assert call(kv_index=[-1] + list(range(39)), n_index=40) == -1
+    assert call(work=[2, 0], n_work=1) == -1                                  # work item of a sequence that does not exist
+    assert call(q_pos0=[0, -1]) == -1
+    assert call(with_p=True, p_off=21) == -1                                  # positional rows 21 .. 41 of 40
+    assert call(with_p=True, p_col=8) == -1
+    assert call(with_p=True, bias_v=None) == -1                               # one bias without the other
+    assert call(with_p=True, fold=1, fold_kv_cap=0) == -1                     # the fold's LDS table must cover every kv_len
+    assert call(fold=1, fold_kv_cap=64) == -1                                 # fold without positional keys
+    assert call(with_p=True, k_prefolded=1) == -1                             # prefolded keys without the fold
+    assert call(dtype=2) == -1
+    assert lib.rvb_test_attention_ex(None) == -1
+    assert lib.rvb_test_attention_pos_bias(f(pz), rows, d, 8, 0, f(bias), f(bias), heads, dk, 1.0, f(pz)) == -1      # columns past the row
+    assert lib.rvb_test_attention_pos_bias(f(pz), rows, d, 0, rows, f(bias), f(bias), heads, dk, 1.0, f(pz)) == -1   # no row left
+
+
 def test_bad_arguments_are_reported_not_crashed(lib):
     cfg = _lib.ModelCfg()
     h = ctypes.c_void_p()
