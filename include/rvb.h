@@ -204,6 +204,27 @@ int rvb_get_ctc_topk(rvb_engine* e, float* vals, int32_t* idx /* [B,T,beam] each
  * token's first emission. */
 int rvb_ctc_greedy(rvb_engine* e, int32_t* tokens, int32_t* ntok, int32_t* frames);
 
+/* Forced alignment of a KNOWN transcript: force_align (asr/wenet/utils/ctc_utils.py:105-161) as bin/alignment.py:233-242 calls it
+ * on `model.ctc.log_softmax(encoder_out)` -- CTC Viterbi of the given token ids over the log-probs (no blank penalty) of the chunks
+ * of the last rvb_encode / rvb_stream_finish, on the device (csrc/ctc_viterbi.hip; fp32 adds and comparisons only, so the labels equal
+ * the reference's for the same log-prob bits, ties included).
+ * n_seq sequences; sequence i aligns tokens [sum tok_lens[..i), +tok_lens[i]) against the VALID encoder frames
+ * (rvb_get_encoder_lens) of the chunks first_chunk[i] .. first_chunk[i] + n_chunks[i] - 1, concatenated: n_chunks = 1 is the
+ * reference's utterance-by-utterance use, one sequence over every chunk aligns the transcript of a whole recording.  Frames are
+ * numbered within the sequence.  Outputs (each nullable): labels [sum of the sequences' frames], concatenated: the token id or
+ * the blank id per frame; per token (concatenated like `tokens`): begin / end = first / last frame of the token's run, peak = the
+ * frame of that run with the largest log-prob of the token (first on ties), confidence = exp of that log-prob; score [n_seq] = the
+ * fp32 path score.  Refused by name (RVB_E_ARG) where the reference's output is undefined: an empty transcript, ids outside
+ * [0, vocab) or equal to the blank, a transcript the frames cannot emit (fewer frames than tokens + adjacent repeats, or no path
+ * with a finite score).  Caps per sequence (RVB_E_UNSUPPORTED, before any device work; rvb_ctc_align_limits): */
+#define RVB_CTC_ALIGN_MAX_TOKENS 16383      /* 32 767 lattice states (the reference's int16 back-pointers break there, silently) */
+#define RVB_CTC_ALIGN_MAX_FRAMES 1048576    /* 11.6 h at 40 ms; back-pointers take 2 bits per frame and state of device memory
+                                               (RVB_E_NOMEM if they do not fit) */
+int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,
+                  const int32_t* n_chunks, int32_t* labels, int32_t* begin, int32_t* end, int32_t* peak, float* confidence,
+                  float* score);
+int rvb_ctc_align_limits(int32_t* max_tokens, int32_t* max_frames);
+
 /* ctc_prefix_beam_search (search.py:124-248), float64 host arithmetic, one host thread per chunk.
  * Results are kept in the engine; read them with rvb_get_nbest. */
 int rvb_ctc_prefix_beam(rvb_engine* e, int beam);
@@ -311,7 +332,8 @@ int rvb_comm_destroy(rvb_engine* e);
 
 /* Stage timing (HIP events on the engine stream).  level 1: every kernel family is bracketed;
  * names: "fbank","subsample","gemm","attention","rownorm","glu_dwconv","ctc_topk","embed",
- * "lse_gather","search_host".  level 2: only the GEMM launches (the dominant kernel; half the
+ * "lse_gather","search_host","ctc_align_lp" (rvb_ctc_align: CTC head + log-softmax),"ctc_viterbi" (its
+ * forward pass + back-trace).  level 2: only the GEMM launches (the dominant kernel; half the
  * events, ~1 % less perturbation of the step).  level 0: off.
  * flops: algorithmic FLOPs launched (gemm/attention only). */
 int rvb_set_profiling(rvb_engine* e, int level);

@@ -89,6 +89,8 @@ SIGNATURES = {
     "rvb_get_ctc_logprobs": (C.c_int, [_eng, C.c_int, _f32p]),
     "rvb_get_ctc_topk": (C.c_int, [_eng, _f32p, _i32p]),
     "rvb_ctc_greedy": (C.c_int, [_eng, _i32p, _i32p, _i32p]),
+    "rvb_ctc_align": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _f32p, _f32p]),
+    "rvb_ctc_align_limits": (C.c_int, [_i32p, _i32p]),
     "rvb_ctc_prefix_beam": (C.c_int, [_eng, C.c_int]),
     "rvb_get_nbest_count": (C.c_int, [_eng, C.c_int, _i32p, _i32p]),
     "rvb_get_nbest": (C.c_int, [_eng, C.c_int, _i32p, _i32p, _i32p, _i32p, _f64p]),
@@ -165,6 +167,7 @@ TEST_SIGNATURES = {
     "rvb_test_attention_pos_bias": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_float, _f32p]),
     "rvb_test_logsoftmax_topk": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _f32p, _i32p, _f32p]),
     "rvb_test_lse_gather": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, _f32p]),
+    "rvb_test_ctc_viterbi": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _f32p]),
     "rvb_test_gemm_glu": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int]),
     "rvb_test_gemm_rowadd": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rvb_test_mp3_decode": (C.c_int64, [C.c_char_p, C.c_int64, C.c_int, _f32p, C.c_int64, _i64p, _i64p, C.c_int]),

@@ -1,0 +1,57 @@
+"""Forced alignment of a known transcript: the job of the reference's `asr/wenet/bin/alignment.py` (:221-242: encoder, CTC
+log-softmax, force_align, one `<key> [labels]` line per utterance) for one audio file and its transcript, written as
+`<result_dir>/<audio>.<ctm|ali|json>`.  Praat .lab / TextGrid output (--gen_praat there) is not written."""
+from __future__ import annotations
+
+import argparse
+import json
+import logging
+import os
+from pathlib import Path
+
+
+def get_args(argv=None):
+    p = argparse.ArgumentParser(description="align a transcript with your model")
+    p.add_argument("--model", default=None, help="reverb model name or a directory with config.yaml and a .pt file")
+    p.add_argument("--config", default=None, help="config file")
+    p.add_argument("--checkpoint", default=None, help="checkpoint model")
+    p.add_argument("--audio_file", required=True, help="audio the transcript belongs to")
+    p.add_argument("--transcript_file", required=True, help="text file with the transcript of the whole audio")
+    p.add_argument("--result_dir", required=True, help="directory of the result file")
+    p.add_argument("--format", default="ctm", choices=["ctm", "ali", "json"], help="word CTM, the reference's label line, or per-token JSON")
+    p.add_argument("--gpu", type=int, default=-1, help="gpu id for this rank, -1 means device 0")
+    p.add_argument("--chunk_size", type=int, default=2051, help="Chunk size")
+    p.add_argument("--verbatimicity", type=float, default=1.0, help="the level of verbatimicity to run the model")
+    p.add_argument("--timings_adjustment", type=float, default=230, help="time shift applied to all timings (ms)")
+    p.add_argument("--log_level", default="INFO", help="log level")
+    p.add_argument("--dtype", default="bf16", choices=["bf16", "f32"], help="device compute mode")
+    p.add_argument("--max_chunks", type=int, default=64, help="chunks per device batch: at least the chunks of the file")
+    return p.parse_args(argv)
+
+
+def main(argv=None):
+    args = get_args(argv)
+    logging.basicConfig(level=getattr(logging, str(args.log_level).upper(), logging.INFO),
+                        format="%(asctime)s %(levelname)s %(message)s")
+    from reverb_amd.reverb import ReverbASR, load_model
+    if (args.model is not None) == (args.checkpoint is not None and args.config is not None):
+        raise RuntimeError("One of either --model or (--checkpoint and --config) must be set.")
+    if args.model:
+        reverb = load_model(args.model, gpu=args.gpu, dtype=args.dtype, max_chunks=args.max_chunks)
+    else:
+        reverb = ReverbASR(args.config, args.checkpoint, gpu=args.gpu, dtype=args.dtype, max_chunks=args.max_chunks)
+    with open(args.transcript_file, encoding="utf-8") as f:
+        transcript = " ".join(f.read().split())
+    out = reverb.align(args.audio_file, transcript=transcript, format=args.format, verbatimicity=args.verbatimicity,
+                       chunk_size=args.chunk_size, timings_adjustment=args.timings_adjustment)
+    if args.format == "json":
+        out = json.dumps(out, ensure_ascii=False, indent=1)
+    os.makedirs(args.result_dir, exist_ok=True)
+    path = os.path.join(args.result_dir, Path(args.audio_file).with_suffix("." + args.format).name)
+    with open(path, "w", encoding="utf-8") as f:
+        f.write(out)
+    logging.info("wrote %s", path)
+
+
+if __name__ == "__main__":
+    main()

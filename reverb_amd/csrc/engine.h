@@ -138,6 +138,26 @@ struct TrieBatch {
   std::vector<int32_t> work;                       // self-attention blocks: {hypothesis, first owned query}
 };
 
+// ---- forced alignment (ctc_viterbi.hip): the host side of a batch of lattices, shared by rvb_ctc_align and the lab hook.
+// plan() validates and lays out (no device work), begin() allocates and uploads, advance() runs the forward kernel over the frames
+// whose rows lie in the slab just computed (slabs in row order), finish() back-traces and returns states and scores.
+struct CtcAligner {
+  std::vector<VitSeq> seq;
+  std::vector<int32_t> h_tokens, h_rows;
+  int max_S = 0, blank = 0;
+  size_t alpha_floats = 0, bp_bytes = 0;
+  int64_t total_frames = 0;
+  DevBuf d_tokens, d_rows, d_seqs, d_alpha, d_bp, d_states, d_score;
+  // seq_rows[i][f]: the (increasing) log-prob row of frame f of sequence i
+  int plan(const char* who, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const std::vector<std::vector<int32_t>>& seq_rows,
+           int V, int blank_id);
+  int begin(hipStream_t s);
+  bool touches(int r0, int nrows) const;
+  int advance(hipStream_t s, const float* lp, int ld, int r0, int nrows);
+  int finish(hipStream_t s, int32_t* states /* [total_frames] */, float* score /* [n_seq] */);
+  void release();
+};
+
 }  // namespace rvb
 
 struct rvb_engine {
@@ -225,6 +245,10 @@ struct rvb_engine {
     std::vector<rvb::DevBuf> cnn, cnn2; // causal conv module, per layer T [K-1][2d]: pointwise-conv1 outputs of the last frames
   } stream_st;
   rvb::DevBuf d_stream_i32;         // {kv_start = 0, kv_len = cache + chunk}
+
+  // ---- forced alignment (rvb_ctc_align) ----
+  rvb::CtcAligner aligner;
+  rvb::DevBuf align_lp, align_tv, align_ti, align_row, align_col, align_out;   // fp32 [LOGIT_SLAB][V] log-softmax slab; gather scratch
 
   // ---- RCCL communicator of the C-ABI collectives (comm.hip; optional) ----
   void* comm = nullptr;

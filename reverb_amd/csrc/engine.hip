@@ -2001,6 +2001,8 @@ void rvb_destroy(rvb_engine* e) {
                     &e->conv2.w, &e->conv2.b, &e->embed_out.w, &e->embed_out.b, &e->ctc.w, &e->ctc.b,
                     &e->enc_after.g, &e->enc_after.b};
   for (DevBuf* b : bufs) b->release();
+  e->aligner.release();
+  for (DevBuf* b : {&e->align_lp, &e->align_tv, &e->align_ti, &e->align_row, &e->align_col, &e->align_out}) b->release();
   e->atopv.release(); e->atopi.release(); e->d_stream_i32.release(); e->d_amax.release(); e->d_f8sat.release();
   e->wave_f32.release(); e->wave_in.release(); e->rs_kernel.release();
   e->jlogp.release(); e->jpair_row.release(); e->jpair_tok.release(); e->jpair_out.release();
@@ -2302,6 +2304,130 @@ int rvb_ctc_greedy(rvb_engine* e, int32_t* tokens, int32_t* ntok, int32_t* frame
     ntok[b] = (int32_t)tk.size();
     for (size_t i = 0; i < tk.size(); ++i) { tokens[(size_t)b * T + i] = tk[i]; if (frames) frames[(size_t)b * T + i] = fr[i]; }
     for (size_t i = tk.size(); i < (size_t)T; ++i) { tokens[(size_t)b * T + i] = -1; if (frames) frames[(size_t)b * T + i] = -1; }
+  }
+  return OK;
+}
+
+// Forced alignment (ctc_utils.py:105-161 / bin/alignment.py:233-242).  The log-probs exist one LOGIT_SLAB of rows at a time, exactly as
+// rvb_encode produces them (run_gemm on the CTC head + logsoftmax_topk with its lp output, no blank penalty); the Viterbi kernel
+// consumes a slab before the next one overwrites it and carries alpha in HBM.  Token confidences need lp[t][label[t]] along the path,
+// which is known only after the back-trace: a second sweep of the slabs gathers those T values.
+static int align_slab(rvb_engine* e, int r0, int rows) {
+  const int d = e->cfg.d_model, V = e->cfg.vocab, Vld = (V + 3) & ~3;
+  Scope sc(e, "ctc_align_lp");
+  RVB_TRY(run_gemm(e, (const char*)e->enc_out.p + (size_t)r0 * d * dt_size(e->dtype), d, e->ctc, e->logits.p, Vld, rows, true));
+  return logsoftmax_topk(e->stream, e->logits.as<float>(), rows, V, Vld, 1, 0.f, e->cfg.blank_id, e->align_tv.as<float>(),
+                         e->align_ti.as<int>(), e->align_lp.as<float>());
+}
+
+int rvb_ctc_align_limits(int32_t* max_tokens, int32_t* max_frames) {
+  if (max_tokens) *max_tokens = CTC_ALIGN_MAX_TOKENS;
+  if (max_frames) *max_frames = CTC_ALIGN_MAX_FRAMES;
+  return OK;
+}
+
+int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,
+                  const int32_t* n_chunks, int32_t* labels, int32_t* begin, int32_t* end, int32_t* peak, float* confidence, float* score) {
+  static_assert(CTC_ALIGN_MAX_TOKENS == RVB_CTC_ALIGN_MAX_TOKENS && CTC_ALIGN_MAX_FRAMES == RVB_CTC_ALIGN_MAX_FRAMES, "caps of rvb.h");
+  if (!e) { set_error("rvb_ctc_align: null engine"); return E_ARG; }
+  if (!tokens || !tok_lens || !first_chunk || !n_chunks || n_seq <= 0) { set_error("rvb_ctc_align: null argument or n_seq <= 0"); return E_ARG; }
+  if (e->B <= 0) { set_error("rvb_ctc_align before rvb_encode"); return E_STATE; }
+  const int T = e->T2, V = e->cfg.vocab, blank = e->cfg.blank_id, M = e->B * T;
+  std::vector<std::vector<int32_t>> seq_rows(n_seq);
+  for (int i = 0; i < n_seq; ++i) {
+    if (first_chunk[i] < 0 || n_chunks[i] < 1 || (int64_t)first_chunk[i] + n_chunks[i] > e->B) {
+      set_error("rvb_ctc_align: sequence " + std::to_string(i) + ": chunk range outside the encoded batch of " + std::to_string(e->B) + " chunks");
+      return E_ARG;
+    }
+    for (int c = first_chunk[i]; c < first_chunk[i] + n_chunks[i]; ++c)
+      for (int t = 0; t < e->enc_lens[c]; ++t) seq_rows[i].push_back(c * T + t);
+  }
+  CtcAligner& al = e->aligner;
+  RVB_TRY(al.plan("rvb_ctc_align", tokens, tok_lens, n_seq, seq_rows, V, blank));
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(wait_slices(e, -1));
+  const int Vld = (V + 3) & ~3, slab = std::min(LOGIT_SLAB, M);
+  RVB_TRY(e->logits.ensure((size_t)LOGIT_SLAB * Vld * 4));
+  RVB_TRY(e->align_lp.ensure((size_t)slab * V * 4));
+  RVB_TRY(e->align_tv.ensure((size_t)slab * 4));
+  RVB_TRY(e->align_ti.ensure((size_t)slab * 4));
+  // the slabs rvb_encode computed its log-probs in (per slice of the batch, LOGIT_SLAB rows at a time): the same GEMM launches, so
+  // the same bits as the top-k the searches saw
+  std::vector<std::pair<int, int>> slabs;
+  auto add_range = [&](int row0, int m) { for (int r0 = 0; r0 < m; r0 += LOGIT_SLAB) slabs.push_back({row0 + r0, std::min(LOGIT_SLAB, m - r0)}); };
+  if (e->slices.empty()) add_range(0, M);
+  for (const auto& sl : e->slices) add_range(sl.c0 * T, sl.nb * T);
+  RVB_TRY(al.begin(e->stream));
+  for (const auto& [r0, rows] : slabs) {
+    if (!al.touches(r0, rows)) continue;
+    RVB_TRY(align_slab(e, r0, rows));
+    Scope sc(e, "ctc_viterbi");
+    RVB_TRY(al.advance(e->stream, e->align_lp.as<float>(), V, r0, rows));
+  }
+  std::vector<int32_t> states((size_t)al.total_frames);
+  std::vector<float> sc_host(n_seq);
+  {
+    Scope sc(e, "ctc_viterbi");
+    RVB_TRY(al.finish(e->stream, states.data(), sc_host.data()));
+  }
+  if (score) memcpy(score, sc_host.data(), (size_t)n_seq * 4);
+  std::vector<int32_t> lab(states.size());
+  for (int i = 0; i < n_seq; ++i) {
+    const VitSeq& q = al.seq[i];
+    for (int t = 0; t < q.T; ++t) {
+      const int st = states[q.frame_off + t];
+      lab[q.frame_off + t] = (st & 1) ? tokens[q.tok_off + (st >> 1)] : blank;
+    }
+  }
+  if (labels) memcpy(labels, lab.data(), lab.size() * 4);
+  if (!begin && !end && !peak && !confidence) return OK;
+  std::vector<float> emit;
+  if (peak || confidence) {
+    // lp[t][label[t]] of every frame: the slabs once more, one gather_pairs per slab
+    emit.resize(lab.size());
+    std::vector<int32_t> grow, gcol, gidx;
+    std::vector<float> gout;
+    for (const auto& [r0, rows] : slabs) {
+      grow.clear(); gcol.clear(); gidx.clear();
+      for (int i = 0; i < n_seq; ++i) {
+        const VitSeq& q = al.seq[i];
+        const int32_t* rw = al.h_rows.data() + q.frame_off;
+        for (int f = (int)(std::lower_bound(rw, rw + q.T, r0) - rw); f < q.T && rw[f] < r0 + rows; ++f) {
+          grow.push_back(rw[f] - r0); gcol.push_back(lab[q.frame_off + f]); gidx.push_back(q.frame_off + f);
+        }
+      }
+      if (grow.empty()) continue;
+      RVB_TRY(align_slab(e, r0, rows));
+      RVB_TRY(upload_i32(e, e->align_row, grow.data(), grow.size()));
+      RVB_TRY(upload_i32(e, e->align_col, gcol.data(), gcol.size()));
+      RVB_TRY(e->align_out.ensure(grow.size() * 4));
+      RVB_TRY(gather_pairs(e->stream, e->align_lp.as<float>(), (size_t)V, e->align_row.as<int>(), e->align_col.as<int>(), (int)grow.size(),
+                           e->align_out.as<float>()));
+      gout.resize(grow.size());
+      RVB_HIP_CHECK(hipMemcpyAsync(gout.data(), e->align_out.p, grow.size() * 4, hipMemcpyDeviceToHost, e->stream));
+      RVB_HIP_CHECK(hipStreamSynchronize(e->stream));     // also: grow / gcol may be rewritten
+      for (size_t k = 0; k < gidx.size(); ++k) emit[gidx[k]] = gout[k];
+    }
+  }
+  for (int i = 0; i < n_seq; ++i) {
+    const VitSeq& q = al.seq[i];
+    for (int t = 0; t < q.T;) {
+      const int st = states[q.frame_off + t];
+      int t1 = t;
+      while (t1 + 1 < q.T && states[q.frame_off + t1 + 1] == st) ++t1;
+      if (st & 1) {
+        const int k = q.tok_off + (st >> 1);
+        if (begin) begin[k] = t;
+        if (end) end[k] = t1;
+        if (peak || confidence) {
+          int pk = t;
+          for (int u = t + 1; u <= t1; ++u) if (emit[q.frame_off + u] > emit[q.frame_off + pk]) pk = u;
+          if (peak) peak[k] = pk;
+          if (confidence) confidence[k] = std::exp(emit[q.frame_off + pk]);
+        }
+      }
+      t = t1 + 1;
+    }
   }
   return OK;
 }

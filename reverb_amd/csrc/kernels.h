@@ -163,6 +163,29 @@ int amax_abs(hipStream_t s, int dtype, const void* x, size_t n, float* slot);
 // fp32 -> T conversion copy (weight packing), n elements
 int convert_f32(hipStream_t s, int dtype, const float* src, void* dst, size_t n);
 
+// ---------------------------------------------------------------- ctc_viterbi.hip
+// CTC forced alignment (force_align, asr/wenet/utils/ctc_utils.py:105-161): Viterbi of a known token sequence over per-frame
+// log-probs, one workgroup per lattice, states in registers.  Caps (refused with E_UNSUPPORTED before any device work):
+enum { CTC_ALIGN_MAX_TOKENS = 16383,             // per lattice: 2 L + 1 = 32 767 states = 1024 threads x 32 states
+       CTC_ALIGN_MAX_STATES = 2 * CTC_ALIGN_MAX_TOKENS + 1,
+       CTC_ALIGN_MAX_FRAMES = 1 << 20 };         // per lattice (11.6 h of audio at 40 ms per frame)
+struct VitSeq {            // one lattice of a batch, as the kernels read it
+  int L, S, T;             // tokens, states 2 L + 1, frames
+  int tok_off;             // its tokens: tokens[tok_off .. tok_off + L)
+  int frame_off;           // its frames in rows[] / states[]
+  int f0, f1;              // frames this launch advances (f0 == 0: initialise alpha; else continue from alpha in HBM)
+  int pad_;
+  long long alpha_off;     // floats into alpha
+  long long bp_off;        // bytes into bp
+  long long bp_stride;     // bytes per frame: 2 bits per state, states padded to a multiple of 32
+};
+// advances every lattice over its frames [f0, f1): frame f reads row rows[frame_off + f] - r0 of lp ([.., ld] fp32 log-probs);
+// bp receives the back-pointers (0 / 1 / 2 states down), alpha the last frame's scores.  max_S selects the instantiation.
+int ctc_viterbi_forward(hipStream_t s, const VitSeq* seqs, int n_seq, int max_S, const float* lp, int ld, int r0, const int* rows,
+                        const int* tokens, int blank, float* alpha, uint8_t* bp);
+// states[frame_off + t] = state of frame t on the best path, score[i] = its fp32 score (-inf: no path)
+int ctc_viterbi_backtrace(hipStream_t s, const VitSeq* seqs, int n_seq, const float* alpha, const uint8_t* bp, int* states, float* score);
+
 // ---------------------------------------------------------------- attention.hip
 struct AttnArgs {
   const void* q; const void* k; const void* v;   // T, row-major, head h at column offset h*dk

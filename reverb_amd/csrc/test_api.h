@@ -105,6 +105,12 @@ int rvb_test_build_trie(const int32_t* tokens, const int32_t* lens, const int32_
 /* host only: the worker pool of the CTC search / trie building (engine.h HostPool) runs `rounds` jobs on up to n_threads threads;
  * fails unless every work item of every job was executed exactly once */
 int rvb_test_host_pool(int n_threads, int items, int rounds);
+/* ctc_viterbi.hip: forced alignment of tokens[L] over host log-probs lp [T][V] with the kernels rvb_ctc_align runs, advancing
+ * slab_rows frames per launch (alpha carried in HBM between launches).  labels_out[T] = z[state] per frame, score_out = the fp32
+ * path score.  Refuses (before any device work, by name): L = 0, ids outside [0, V) or equal to blank, a transcript T frames cannot
+ * emit, sizes above the caps of include/rvb.h. */
+int rvb_test_ctc_viterbi(const float* lp, int T, int V, const int32_t* tokens, int L, int blank, int slab_rows, int32_t* labels_out,
+                         float* score_out);
 int rvb_test_fbank(const int16_t* pcm, int64_t n_samples, float* feats /* [frames,80] */);
 /* native prefix beam search on host arrays: top-k log-probs/indices [T,beam] of one utterance */
 int rvb_test_prefix_beam(const float* topk_val, const int32_t* topk_idx, int T, int beam, int blank,

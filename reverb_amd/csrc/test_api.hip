@@ -2,11 +2,13 @@
 // uploads fp32 host data (rounded to the compute dtype with the same RNE conversion the engine
 // uses), launches exactly the kernel the engine launches, and downloads the result as fp32.
 #include "mp3.h"
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "test_api.h"
+#include "engine.h"
 #include "kernels.h"
 #include "search.h"
 
@@ -548,6 +550,32 @@ int rvb_test_logsoftmax_topk(const float* logits, int M, int V, int k, float bla
   RVB_HIP_CHECK(hipMemcpy(topk_val, dv.p, (size_t)M * k * 4, hipMemcpyDeviceToHost));
   RVB_HIP_CHECK(hipMemcpy(topk_idx, di.p, (size_t)M * k * 4, hipMemcpyDeviceToHost));
   if (logp) RVB_HIP_CHECK(hipMemcpy(logp, dp.p, (size_t)M * V * 4, hipMemcpyDeviceToHost));
+  return OK;
+}
+
+int rvb_test_ctc_viterbi(const float* lp, int T, int V, const int32_t* tokens, int L, int blank, int slab_rows, int32_t* labels_out,
+                         float* score_out) {
+  if (!lp || !tokens || !labels_out || !score_out) { set_error("rvb_test_ctc_viterbi: null argument"); return E_ARG; }
+  if (T < 1 || slab_rows < 1) { set_error("rvb_test_ctc_viterbi: need T >= 1 and slab_rows >= 1"); return E_ARG; }
+  CtcAligner al;
+  std::vector<std::vector<int32_t>> rows(1);
+  if (T <= CTC_ALIGN_MAX_FRAMES) { rows[0].resize(T); for (int t = 0; t < T; ++t) rows[0][t] = t; }
+  else rows[0].resize((size_t)T);           // over the cap: plan() refuses on the count alone
+  T_TRY(al.plan("rvb_test_ctc_viterbi", tokens, &L, 1, rows, V, blank));
+  T_TRY(need_gpu());
+  Dev dlp;
+  int r = up_raw(dlp, lp, (size_t)T * V * 4);
+  if (r == OK) r = al.begin(nullptr);
+  for (int r0 = 0; r == OK && r0 < T; r0 += slab_rows) {
+    const int n = std::min(slab_rows, T - r0);
+    r = al.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, n);
+  }
+  std::vector<int32_t> states((size_t)T);
+  if (r == OK) r = al.finish(nullptr, states.data(), score_out);
+  if (r != OK) (void)hipDeviceSynchronize();
+  al.release();
+  if (r != OK) return r;
+  for (int t = 0; t < T; ++t) labels_out[t] = (states[t] & 1) ? tokens[states[t] >> 1] : blank;
   return OK;
 }
 

@@ -13,7 +13,8 @@ by the reference-generated known answer C2 of SURVEY.md Appendix C (tests/test_h
 """
 from __future__ import annotations
 
-from typing import Any, Dict, List, Optional, Sequence
+from dataclasses import dataclass, field
+from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 SPACE_MARK = "▁"
 GAP_MS = 100
@@ -118,3 +119,67 @@ def hyps_to_txt(path):
     """Plain words (cli/utils.py:16-21)."""
     for w in path:
         yield w["word"]
+
+
+# ---------------------------------------------------------------- forced alignment of a known transcript (Engine.align)
+@dataclass
+class AlignResult:
+    """One aligned sequence (rvb_ctc_align): frames are numbered within the sequence = the valid encoder frames of its chunks,
+    concatenated; `chunk_lens` (valid frames per chunk) and `first_chunk` map a frame back to (chunk, t)."""
+    tokens: List[int]
+    labels: List[int]                 # per frame: token id or blank id (the reference's force_align output)
+    begin: List[int]                  # per token: first / last frame of its run
+    end: List[int]
+    peak: List[int]                   # per token: the frame of its run where its log-prob is largest
+    confidence: List[float]           # per token: exp of that log-prob
+    score: float                      # fp32 Viterbi path score
+    first_chunk: int = 0
+    chunk_lens: List[int] = field(default_factory=list)
+
+    def chunk_frame(self, frame: int) -> Tuple[int, int]:
+        """sequence frame -> (chunk index in the encoded batch, frame inside that chunk)"""
+        if frame < 0:
+            raise ValueError("negative frame")
+        for i, n in enumerate(self.chunk_lens):
+            if frame < n:
+                return self.first_chunk + i, frame
+            frame -= n
+        raise ValueError("frame past the end of the sequence")
+
+
+@dataclass
+class DecodeLike:
+    """What get_output reads of a DecodeResult."""
+    tokens: List[int]
+    times: List[int]
+    tokens_confidence: List[float]
+    ctc_frames: Optional[List[int]] = None
+
+
+def split_by_chunk(res: AlignResult):
+    """The aligned tokens as one (tokens, times, tokens_confidence) triple per chunk of the sequence, a token going to the chunk
+    its `begin` frame lies in, times = begin frames relative to that chunk: what `get_output` takes from a DecodeResult per chunk
+    (the first frame of a token's run is also what ctc_greedy_search stamps a token with)."""
+    parts = [([], [], []) for _ in res.chunk_lens]
+    for tok, b, conf in zip(res.tokens, res.begin, res.confidence):
+        c, t = res.chunk_frame(b)
+        part = parts[c - res.first_chunk]
+        part[0].append(int(tok)); part[1].append(int(t)); part[2].append(float(conf))
+    return parts
+
+
+def align_to_ali(audio_name: str, res: AlignResult) -> str:
+    """The reference's result line: `<key> [label, label, ...]` (asr/wenet/bin/alignment.py:242)."""
+    return "{} {}".format(audio_name, [int(x) for x in res.labels])
+
+
+def align_to_json(res: AlignResult, tokenizer, chunk_size: int, input_frame_ms: int, output_frame_ms: int) -> Dict[str, Any]:
+    """Per token: piece, id, start_ms = chunk shift + begin * frame, end_ms = chunk shift + (end + 1) * frame (both inside the chunk the
+    frame lies in), confidence; plus the sequence score."""
+    def ms(frame: int, extra: int) -> int:
+        c, t = res.chunk_frame(frame)
+        return c * chunk_size * input_frame_ms + (t + extra) * output_frame_ms
+
+    toks = [{"piece": piece_of(int(tok), tokenizer), "id": int(tok), "start_ms": ms(b, 0), "end_ms": ms(e, 1), "confidence": float(conf)}
+            for tok, b, e, conf in zip(res.tokens, res.begin, res.end, res.confidence)]
+    return {"score": float(res.score), "tokens": toks}

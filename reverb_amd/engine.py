@@ -395,6 +395,37 @@ class Engine:
             res.append(r)
         return res
 
+    def align(self, token_seqs, chunk_ranges=None):
+        """Forced alignment (rvb_ctc_align; reference: force_align, utils/ctc_utils.py:105-161) of known token sequences against the
+        chunks of the last encode(): sequence i covers the chunks chunk_ranges[i] = (first, count), default one sequence per chunk
+        in order (utterance by utterance); ONE sequence with (0, batch) aligns the transcript of the whole batch.  -> List[AlignResult]."""
+        from .ctc_align import AlignResult
+        seqs = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in token_seqs]
+        if chunk_ranges is None:
+            chunk_ranges = [(i, 1) for i in range(len(seqs))]
+        if len(chunk_ranges) != len(seqs) or not seqs:
+            raise RvbError("align: one chunk range per token sequence, at least one sequence")
+        lens = self.encoder_lens()
+        first = np.array([r[0] for r in chunk_ranges], np.int32)
+        count = np.array([r[1] for r in chunk_ranges], np.int32)
+        tok = np.ascontiguousarray(np.concatenate(seqs) if sum(map(len, seqs)) else np.zeros(1, np.int32), np.int32)
+        tl = np.array([len(t) for t in seqs], np.int32)
+        frames = [int(lens[f:f + c].sum()) if 0 <= f and c >= 1 and f + c <= self.batch else 0 for f, c in zip(first, count)]
+        labels = np.empty(max(sum(frames), 1), np.int32)
+        nt = max(int(tl.sum()), 1)
+        begin, end, peak = (np.empty(nt, np.int32) for _ in range(3))
+        conf, score = np.empty(nt, np.float32), np.empty(len(seqs), np.float32)
+        check(self.lib.rvb_ctc_align(self.handle, iptr(tok), iptr(tl), len(seqs), iptr(first), iptr(count), iptr(labels), iptr(begin),
+                                     iptr(end), iptr(peak), fptr(conf), fptr(score)), "rvb_ctc_align")
+        out, t0, f0 = [], 0, 0
+        for i, t in enumerate(seqs):
+            n = len(t)
+            out.append(AlignResult(t.tolist(), labels[f0:f0 + frames[i]].tolist(), begin[t0:t0 + n].tolist(), end[t0:t0 + n].tolist(),
+                                   peak[t0:t0 + n].tolist(), conf[t0:t0 + n].tolist(), float(score[i]), int(first[i]),
+                                   lens[first[i]:first[i] + count[i]].tolist()))
+            t0 += n; f0 += frames[i]
+        return out
+
     def _nbest(self, chunk: int):
         nh, ml = C.c_int32(0), C.c_int32(0)
         check(self.lib.rvb_get_nbest_count(self.handle, chunk, C.byref(nh), C.byref(ml)))

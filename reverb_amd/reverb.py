@@ -18,7 +18,7 @@ from functools import partial
 from itertools import chain
 from math import ceil
 from pathlib import Path
-from typing import Generator, List, Tuple
+from typing import Generator, List, Optional, Tuple
 
 import numpy as np
 
@@ -264,6 +264,46 @@ class ReverbASR:
         hyps = self.decode_resident(n_frames, modes, chunk_size, beam_size, ctc_weight, reverse_weight, blank_penalty, length_penalty)
         return [get_output(format, self.tokenizer, Path(audio_file).name, hyps[mode], timings_adjustment, chunk_size,
                            self.input_frame_length, self.output_frame_length) for mode in modes]
+
+    def align(self, audio_file, transcript: Optional[str] = None, tokens=None, format: str = "ctm", verbatimicity: float = 1.0,
+              chunk_size: int = 2051, timings_adjustment: float = 230):
+        """Forced alignment of a KNOWN transcript (the reference's bin/alignment.py -> force_align, utils/ctc_utils.py:105-161): exactly
+        one of `transcript` (text, tokenised with the model's tokenizer) or `tokens` (ids).  The whole file is encoded as
+        transcribe_modes does and the transcript aligned as ONE sequence over all chunks.  format: "ctm" / "txt" (through get_output,
+        a token going to the chunk its first frame lies in), "ali" (the reference's `<audio> [labels]` line), "json" (dict: per-token
+        times + score)."""
+        from .ctc_align import DecodeLike, align_to_ali, align_to_json, split_by_chunk
+        if (transcript is None) == (tokens is None):
+            raise ValueError("align: give exactly one of transcript= (text) or tokens= (ids)")
+        if format not in ("ctm", "txt", "ali", "json"):
+            raise ValueError("Invalid output format.")
+        fc = self.test_conf["fbank_conf"]
+        if (fc["num_mel_bins"], fc["frame_length"], fc["frame_shift"]) != (80, 25, 10):
+            raise NotImplementedError("the device fbank is built for 80 bins / 25 ms / 10 ms")
+        if chunk_size < 7:
+            raise ValueError("chunk_size must be at least 7 frames (Conv2dSubsampling4 needs 7 input frames, subsampling.py:201-226)")
+        ids = list(self.tokenizer.tokenize(transcript)[1]) if tokens is None else [int(t) for t in tokens]
+        eng = self._engine_for_chunk(chunk_size)
+        eng.upload_pcm(*self._load_pcm(audio_file, 16000))
+        eng.set_cat_embs([verbatimicity, 1.0 - verbatimicity])
+        eng.apply_decoding_chunk(-1, -1)
+        n_frames = eng.fbank()
+        n_chunks = -(-n_frames // chunk_size)
+        if n_chunks > eng.cfg.max_chunks:
+            raise ValueError(f"align: the file has {n_chunks} chunks of {chunk_size} frames, the engine batches {eng.cfg.max_chunks}: "
+                             "one lattice spans one encoded batch -- load the model with max_chunks >= the file's chunks")
+        lens = np.full(n_chunks, chunk_size, np.int32)
+        lens[-1] = n_frames - (n_chunks - 1) * chunk_size
+        eng.encode(None, lens, 1, 0.0, first_chunk=0, T0=chunk_size)
+        res = eng.align([ids], [(0, n_chunks)])[0]
+        name = Path(audio_file).name
+        if format == "ali":
+            return align_to_ali(name, res)
+        if format == "json":
+            return align_to_json(res, self.tokenizer, chunk_size, self.input_frame_length, self.output_frame_length)
+        hyps = [DecodeLike(t, fr, cf) for t, fr, cf in split_by_chunk(res)]
+        return get_output(format, self.tokenizer, name, hyps, timings_adjustment, chunk_size, self.input_frame_length,
+                          self.output_frame_length)
 
     def _engine_for_chunk(self, chunk_size: int) -> Engine:
         """The reference accepts any --chunk_size (cli/reverb.py:188, recognize_wav.py:66-70).  The engine sizes its

@@ -2,11 +2,16 @@
 
 At inference the reference only maps ids to pieces through `tk.units.txt`
 (asr/wenet/text/rev_bpe_tokenizer.py:10-82, char_tokenizer.py:71-76,
-utils/file_utils.py:61-68); the sentencepiece model is needed only for text -> ids, which the
-recognize_wav path never calls, so it is loaded lazily and only if asked for."""
+utils/file_utils.py:61-68); the sentencepiece model is needed only for text -> ids (forced alignment of a transcript given as
+text), so it is loaded lazily and only if asked for.  A model directory without a sentencepiece
+file (the synthetic models) segments text against the unit table instead: longest match per word."""
 from __future__ import annotations
 
+import logging
+import os
 from typing import Dict, List, Tuple
+
+SPACE_MARK = "\u2581"
 
 
 def read_symbol_table(path: str) -> Dict[str, int]:
@@ -58,7 +63,34 @@ class RevBpeTokenizer:
         tokens = self.ids2tokens(ids)
         return self.tokens2text(tokens), tokens
 
+    def _table_tokens(self, line: str) -> List[str]:
+        """Text -> pieces with the unit table alone: every whitespace word is cut by longest match, its first piece preferring the
+        word-initial form; what no piece covers becomes one <unk>."""
+        out: List[str] = []
+        for word in line.split():
+            if word in self._symbol_table:
+                out.append(word)
+                continue
+            pos = 0
+            while pos < len(word):
+                for n in range(len(word), pos, -1):
+                    cands = ([SPACE_MARK + word[pos:n]] if pos == 0 else []) + [word[pos:n]]
+                    hit = next((c for c in cands if c in self._symbol_table), None)
+                    if hit is not None:
+                        out.append(hit)
+                        pos = n
+                        break
+                else:
+                    out.append(self.unk)
+                    break
+        return out
+
     def text2tokens(self, line: str) -> List[str]:
+        if not self._model or not os.path.isfile(self._model):
+            if self.bpe_model is None:
+                logging.warning("no sentencepiece model at %r: segmenting text by longest match against the unit table", self._model)
+                self.bpe_model = False
+            return self._table_tokens(line.strip())
         if self.bpe_model is None:
             import sentencepiece as spm
             self.bpe_model = spm.SentencePieceProcessor()

@@ -1,0 +1,60 @@
+"""Forced alignment of the benched hour: synthetic weights, transcript = the engine's own greedy tokens of the whole recording,
+ONE lattice over all chunks.  Prints one JSON line: wall time of Engine.align per repetition (host clock around a call that ends in a
+device synchronise) and the "ctc_align_lp" / "ctc_viterbi" device times of rvb_get_timing (HIP events; a profiled run of its own).
+
+    python scripts/align_bench.py [--model r640] [--dtype bf16] [--seconds 3600] [--reps 5] [--warmup 2]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def main():
+    p = argparse.ArgumentParser()
+    p.add_argument("--model", default="r640")
+    p.add_argument("--dtype", default="bf16")
+    p.add_argument("--seconds", type=float, default=3600.0)
+    p.add_argument("--reps", type=int, default=5)
+    p.add_argument("--warmup", type=int, default=2)
+    a = p.parse_args()
+    from reverb_amd import synth
+    from reverb_amd.engine import Engine
+    chunk = 2051
+    cfg, sd = synth.calibrated_state_dict(a.model, 0)
+    pcm = synth.synth_audio(a.seconds, seed=1234)
+    n_chunks = -(-int((len(pcm) - 400) // 160 + 1) // chunk)
+    eng = Engine(cfg, sd, dtype=a.dtype, device=0, max_chunks=n_chunks, chunk_frames=chunk)
+    eng.upload_pcm(pcm)
+    n = eng.fbank()
+    lens = np.full(n_chunks, chunk, np.int32)
+    lens[-1] = n - (n_chunks - 1) * chunk
+    eng.encode(None, lens, 1, 0.0, T0=chunk)
+    tokens = [t for g in eng.greedy() for t in g.tokens]
+    T = int(eng.encoder_lens().sum())
+    for _ in range(a.warmup):
+        res = eng.align([tokens], [(0, n_chunks)])[0]
+    wall = []
+    for _ in range(a.reps):
+        t0 = time.perf_counter()
+        res = eng.align([tokens], [(0, n_chunks)])[0]
+        wall.append((time.perf_counter() - t0) * 1e3)
+    eng.set_profiling(True)
+    eng.reset_timings()
+    for _ in range(a.reps):
+        eng.align([tokens], [(0, n_chunks)])
+    lp, vit = eng.timing("ctc_align_lp"), eng.timing("ctc_viterbi")
+    print(json.dumps({"model": a.model, "dtype": a.dtype, "frames": T, "tokens": len(tokens), "states": 2 * len(tokens) + 1,
+                      "align_wall_ms": [round(w, 2) for w in wall], "align_wall_ms_median": round(float(np.median(wall)), 2),
+                      "ctc_align_lp_ms": round(lp["ms"] / a.reps, 3), "ctc_viterbi_ms": round(vit["ms"] / a.reps, 3),
+                      "viterbi_us_per_frame": round(vit["ms"] / a.reps * 1e3 / T, 3), "score": res.score}))
+    eng.close()
+
+
+if __name__ == "__main__":
+    main()
