@@ -229,6 +229,18 @@ int rvb_ctc_align_limits(int32_t* max_tokens, int32_t* max_frames);
  * Results are kept in the engine; read them with rvb_get_nbest. */
 int rvb_ctc_prefix_beam(rvb_engine* e, int beam);
 int rvb_get_nbest_count(rvb_engine* e, int chunk, int32_t* n_hyps, int32_t* max_len);
+/* Hot-word context biasing of ctc_prefix_beam_search: the ContextGraph of asr/wenet/utils/context_graph.py:103-265 (an Aho-Corasick
+ * automaton over token ids) applied as search.py:169-233 does.  n_phrases phrases, concatenated in `tokens`, lens[i] ids each; every
+ * matched token of a phrase earns context_score, a broken match gives its bonus back, a completed one keeps it.  The graph never
+ * changes which tokens a frame offers (still the top-`beam` of its log-probs): it reorders the host beam, which is pruned by
+ * score + context score; the scores rvb_get_nbest reports include the context score each hypothesis ends with.
+ * n_phrases == 0 clears the graph.  Empty phrases are allowed and ignored.  RVB_E_ARG, with the phrase and position named: a token
+ * id outside [0, vocab) or equal to the blank id, a negative length.  The engine copies what it needs; the graph stays until it is
+ * replaced or cleared and applies to every later rvb_ctc_prefix_beam -- after rvb_encode and after rvb_stream_finish alike -- and
+ * through its n-best and scores to rvb_attention_rescore (ctc_weight * biased score, search.py:436-444).  rvb_ctc_greedy,
+ * rvb_attention_decode and rvb_joint_decode ignore it, as the reference's modes do.  Without a graph the search executes exactly the
+ * float64 operations it always did. */
+int rvb_set_context_graph(rvb_engine* e, const int32_t* tokens, const int32_t* lens, int n_phrases, double context_score);
 /* tokens/times: [n_hyps][max_len] padded with -1; lens/times_lens/scores: [n_hyps] */
 int rvb_get_nbest(rvb_engine* e, int chunk, int32_t* tokens, int32_t* lens, int32_t* times, int32_t* times_lens,
                   double* scores);

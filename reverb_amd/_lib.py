@@ -92,6 +92,7 @@ SIGNATURES = {
     "rvb_ctc_align": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _f32p, _f32p]),
     "rvb_ctc_align_limits": (C.c_int, [_i32p, _i32p]),
     "rvb_ctc_prefix_beam": (C.c_int, [_eng, C.c_int]),
+    "rvb_set_context_graph": (C.c_int, [_eng, _i32p, _i32p, C.c_int, C.c_double]),
     "rvb_get_nbest_count": (C.c_int, [_eng, C.c_int, _i32p, _i32p]),
     "rvb_get_nbest": (C.c_int, [_eng, C.c_int, _i32p, _i32p, _i32p, _i32p, _f64p]),
     "rvb_prepare_rescoring": (C.c_int, [_eng, C.c_int]),
@@ -191,6 +192,10 @@ TEST_SIGNATURES = {
                                       _f64p, _f64p]),
     "rvb_test_prefix_beam": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p,
                                        _f64p]),
+    "rvb_test_prefix_beam_context": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, C.c_int, C.c_double,
+                                               _i32p, _i32p, _i32p, _i32p, _i32p, _f64p, _f64p]),
+    "rvb_test_context_walk": (C.c_int, [_i32p, _i32p, C.c_int, C.c_double, C.c_int, C.c_int, _i32p, C.c_int, _i32p, _f64p, _i32p,
+                                        _f64p]),
     "rvb_test_window_stats": (C.c_int, [_f32p, C.c_int64, C.c_int64, C.c_int, C.c_int64, C.c_int, C.c_float, _f32p]),
     "rvb_test_sinc_conv": (C.c_int, [C.c_int, _f32p, C.c_int64, _f32p, C.c_int, C.c_int, C.c_int, C.c_int64, _f32p]),
     "rvb_test_pool_norm": (C.c_int, [C.c_int, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, C.c_float,

@@ -40,6 +40,8 @@ def get_args(argv=None):
     p.add_argument("--log_level", default="INFO", help="log level")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f32"], help="device compute mode")
     p.add_argument("--max_chunks", type=int, default=64, help="chunks per device batch")
+    p.add_argument("--context_list_path", default=None, help="hot words to bias ctc_prefix_beam_search / attention_rescoring towards, one per line")
+    p.add_argument("--context_graph_score", type=float, default=6.0, help="bonus per matched hot-word token")
     return p.parse_args(argv)
 
 
@@ -53,11 +55,13 @@ def main(argv=None):
     if model_set == pair_set:
         raise RuntimeError("One of either --model or (--checkpoint and --config) must be set.")
     if args.model:
-        reverb = load_model(args.model, gpu=args.gpu, dtype=args.dtype, max_chunks=args.max_chunks)
+        reverb = load_model(args.model, gpu=args.gpu, dtype=args.dtype, max_chunks=args.max_chunks,
+                            context_path=args.context_list_path, context_score=args.context_graph_score)
     else:
         reverb = ReverbASR(args.config, args.checkpoint, cmvn_path=args.cmvn_path,
                            tokenizer_symbols=args.tokenizer_symbols, bpe_path=args.bpe_path, gpu=args.gpu,
-                           overwrite_cmvn=args.overwrite_cmvn, dtype=args.dtype, max_chunks=args.max_chunks)
+                           overwrite_cmvn=args.overwrite_cmvn, dtype=args.dtype, max_chunks=args.max_chunks,
+                           context_path=args.context_list_path, context_score=args.context_graph_score)
     outputs = reverb.transcribe_modes(
         args.audio_file, args.modes, format="ctm", verbatimicity=args.verbatimicity, chunk_size=args.chunk_size,
         batch_size=args.batch_size, beam_size=args.beam_size, decoding_chunk_size=args.decoding_chunk_size,

@@ -36,11 +36,15 @@ def run(audio, asr, pipe, out_dir, mode="attention_rescoring", device=None, worl
     chunk = asr.engine.cfg.chunk_frames
     kw = dict(beam_size=10, ctc_weight=0.1, reverse_weight=0.0)
     kw.update(decode_kw)
+    graph = getattr(asr, "context_graph", None)      # hot words of load_model(context_path=...): biases the CTC prefix beam
+    if graph is not None:
+        asr.engine.set_context_graph(graph)
     if world > 1:
         from reverb_amd.dist import decode_sharded, diarize_sharded
         if rate != 16000:
             raise NotImplementedError("sharded decoding slices 16 kHz PCM; resample the file first")
-        hyps = decode_sharded(asr.engine, wave[0], [mode], chunk, kw["beam_size"], kw["ctc_weight"], kw["reverse_weight"], device)[mode]
+        hyps = decode_sharded(asr.engine, wave[0], [mode], chunk, kw["beam_size"], kw["ctc_weight"], kw["reverse_weight"], device,
+                              **({"context_graph": graph} if graph is not None else {}))[mode]
 
     def asr_local():
         ta = time.perf_counter()
@@ -112,6 +116,8 @@ def main(argv=None):
     p.add_argument("--mode", default="attention_rescoring")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f32", "fp8"], help="fp8: the ASR encoder's feed-forward GEMMs and stages 3-4 of the embedding ResNet34 on e4m3 operands")
     p.add_argument("--sequential", action="store_true", help="do not overlap ASR and diarization")
+    p.add_argument("--context_list_path", default=None, help="hot words to bias the CTC prefix beam towards, one per line")
+    p.add_argument("--context_graph_score", type=float, default=6.0, help="bonus per matched hot-word token")
     args = p.parse_args(argv)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -124,7 +130,8 @@ def main(argv=None):
         dist.init_process_group("nccl", device_id=device)
     from reverb_amd.diarization import Pipeline
     from reverb_amd.reverb import load_model
-    asr = load_model(args.asr_model, gpu=local, dtype=args.dtype, max_chunks=256)
+    asr = load_model(args.asr_model, gpu=local, dtype=args.dtype, max_chunks=256, context_path=args.context_list_path,
+                     context_score=args.context_graph_score)
     pipe = Pipeline.from_pretrained(args.pipeline_model, dtype=args.dtype).to(f"cuda:{local}")
     for audio in args.audios:
         _, ann, stm, t = run(audio, asr, pipe, args.out_dir, args.mode, device, world, rank, overlap=not args.sequential)

@@ -3,6 +3,7 @@
 #include <condition_variable>
 #include <functional>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -217,6 +218,7 @@ struct rvb_engine {
   int xattn_max_rows = 0;          // most decoder rows of any chunk (cross-attention query sequence length)
   const int* cur_lens = nullptr;   // device pointer: valid encoder frames of the slice being encoded
   std::vector<rvb::PrefixResult> nbest;
+  std::shared_ptr<const rvb::ContextGraph> context_graph;   // rvb_set_context_graph: biases every later rvb_ctc_prefix_beam (null: none)
   std::vector<rvb::RescoreResult> rescored;
   std::vector<rvb::TrieBatch> trie_l;   // per chunk, local numbering: built by the prefix-beam workers for the rescoring decoder
   rvb::HostPool pool;                   // host workers of the CTC search and the trie building

@@ -1084,10 +1084,11 @@ static int prefix_beam_impl(rvb_engine* e, int beam) {
     const unsigned nthr = std::max(1u, std::min<unsigned>(hw, (unsigned)(nb + 1) / 2));
     std::atomic<int> next_chunk(c0);
     const int sos = e->cfg.sos_id, eos = e->cfg.eos_id;
+    const ContextGraph* graph = e->context_graph.get();   // read-only, shared by the workers
     auto work = [&, c0, nb]() {
       for (int b = next_chunk.fetch_add(1); b < c0 + nb; b = next_chunk.fetch_add(1)) {
         prefix_beam_search(e->h_topv + (size_t)b * T * K, e->h_topi + (size_t)b * T * K, e->enc_lens[b], K,
-                           beam, e->cfg.blank_id, &e->nbest[b]);
+                           beam, e->cfg.blank_id, &e->nbest[b], graph);
         // the chunk's prefix trie for the left-to-right rescoring decoder, while the worker has the n-best list hot: for
         // every slice but the last this happens underneath the encoder of the next slice (rescore_impl only stitches)
         if (prebuild) build_chunk_trie(e, b, false, sos, eos, &e->trie_l[b]);
@@ -2435,6 +2436,19 @@ int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens,
 int rvb_ctc_prefix_beam(rvb_engine* e, int beam) {
   if (!e) { set_error("null engine"); return E_ARG; }
   return prefix_beam_impl(e, beam);
+}
+int rvb_set_context_graph(rvb_engine* e, const int32_t* tokens, const int32_t* lens, int n_phrases, double context_score) {
+  if (!e) { set_error("rvb_set_context_graph: null engine"); return E_ARG; }
+  if (n_phrases == 0) { e->context_graph.reset(); return OK; }
+  const std::string bad = ContextGraph::check(tokens, lens, n_phrases, e->cfg.vocab, e->cfg.blank_id);
+  if (!bad.empty()) { set_error(("rvb_set_context_graph: " + bad).c_str()); return E_ARG; }
+  if (!std::isfinite(context_score)) { set_error("rvb_set_context_graph: context_score is not finite"); return E_ARG; }
+  try {
+    e->context_graph = std::make_shared<const ContextGraph>(tokens, lens, n_phrases, context_score);
+  } catch (const std::bad_alloc&) {
+    set_error("rvb_set_context_graph: out of host memory"); return E_NOMEM;
+  }
+  return OK;
 }
 int rvb_get_nbest_count(rvb_engine* e, int chunk, int32_t* n_hyps, int32_t* max_len) {
   if (!e || chunk < 0 || chunk >= (int)e->nbest.size()) { set_error("rvb_get_nbest_count: bad chunk / no search results"); return E_STATE; }

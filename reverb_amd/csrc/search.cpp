@@ -13,7 +13,14 @@
 // (top-k tokens outer, current beam inner), the insertion order of new prefixes, the stable descending
 // sort and every float64 operation are kept identical -- including the `vs_ns` typo at search.py:178
 // that leaves the Viterbi non-blank score of a repeated token un-updated.
+//
+//   ContextGraph        <- asr/wenet/utils/context_graph.py:103-265; with one, prefix_beam_search carries the context state and
+//                          score of every hypothesis as search.py:94-103, :169-218 and :226-236 do: a candidate takes its context
+//                          from the FIRST (token, beam entry) pair that touches it in the frame, the pruning sorts by
+//                          score + context score, and after the last frame the context score is REPLACED by finalize's.
 #include "search.h"
+
+#include <deque>
 
 #include <algorithm>
 #include <cmath>
@@ -46,13 +53,135 @@ struct Hyp {
   int id;        // trie node of the prefix, -1 while it is a candidate that has no node yet
   int par, tok;  // ... in which case it is `par` extended by `tok`
   PS ps;
-  double score_cache;  // ps.score(), computed once per frame (pure function of ps)
+  double score_cache;  // ps.score(), computed once per frame (pure function of ps); what the pruning sorts by after it
+  // context biasing (unused without a graph): state in the graph, accumulated bonus, the per-frame `has_context` latch
+  int ctx_state = 0;
+  double ctx_score = 0.0;
+  bool has_ctx = false;
 };
 struct Kid { int tok, hj; };
 }  // namespace
 
-void prefix_beam_search(const float* tv, const int* ti, int T, int kstride, int beam, int blank,
-                        PrefixResult* out) {
+// ================================================================================================
+// ContextGraph
+// ================================================================================================
+std::string ContextGraph::check(const int32_t* tokens, const int32_t* lens, int n_phrases, int vocab, int blank) {
+  if (n_phrases < 0) return "negative number of phrases";
+  if (n_phrases > 0 && !lens) return "null phrase lengths";
+  size_t off = 0;
+  for (int p = 0; p < n_phrases; ++p) {
+    if (lens[p] < 0) return "phrase " + std::to_string(p) + " has negative length " + std::to_string(lens[p]);
+    if (lens[p] > 0 && !tokens) return "null phrase tokens";
+    for (int i = 0; i < lens[p]; ++i) {
+      const int32_t t = tokens[off + i];
+      const std::string where = "phrase " + std::to_string(p) + " position " + std::to_string(i) + ": token id " + std::to_string(t);
+      if (t < 0 || t >= vocab) return where + " outside [0, " + std::to_string(vocab) + ")";
+      if (t == blank) return where + " is the blank";
+    }
+    off += (size_t)lens[p];
+  }
+  return "";
+}
+
+ContextGraph::ContextGraph(const int32_t* tokens, const int32_t* lens, int n_phrases, double context_score)
+    : context_score_(context_score) {
+  nodes_.emplace_back();                                   // root: token -1, every score 0, its own fail arc
+  std::vector<std::vector<std::pair<int, int>>> kids(1);   // per node (token, child) in insertion order
+  size_t off = 0;
+  for (int p = 0; p < n_phrases; ++p) {                    // build_graph :158-173
+    int node = 0;
+    for (int i = 0; i < lens[p]; ++i) {
+      const int tok = tokens[off + i];
+      int c = -1;
+      for (const auto& k : kids[node]) if (k.first == tok) { c = k.second; break; }
+      if (c < 0) {
+        Node n;
+        n.token = tok;
+        n.is_end = i == lens[p] - 1;
+        n.token_score = context_score;
+        n.node_score = nodes_[node].node_score + context_score;
+        n.output_score = n.is_end ? n.node_score : 0.0;
+        c = (int)nodes_.size();
+        nodes_.push_back(n);
+        kids.emplace_back();
+        kids[node].push_back({tok, c});
+      }
+      node = c;
+    }
+    off += (size_t)lens[p];
+  }
+  for (size_t n = 0; n < nodes_.size(); ++n) {             // lookup table of next(): sorted by token within a node
+    nodes_[n].kid0 = (int)sorted_.size();
+    nodes_[n].nkid = (int)kids[n].size();
+    sorted_.insert(sorted_.end(), kids[n].begin(), kids[n].end());
+    std::sort(sorted_.begin() + nodes_[n].kid0, sorted_.end());
+  }
+  std::deque<int> queue;                                   // _fill_fail_output :176-210
+  for (const auto& k : kids[0]) { nodes_[k.second].fail = 0; queue.push_back(k.second); }
+  while (!queue.empty()) {
+    const int cur = queue.front();
+    queue.pop_front();
+    for (const auto& k : kids[cur]) {
+      const int tok = k.first, node = k.second;
+      int fail = nodes_[cur].fail;
+      int c = next(fail, tok);
+      if (c >= 0) {
+        fail = c;
+      } else {
+        fail = nodes_[fail].fail;
+        while (next(fail, tok) < 0) {
+          fail = nodes_[fail].fail;
+          if (nodes_[fail].token == -1) break;
+        }
+        c = next(fail, tok);
+        if (c >= 0) fail = c;
+      }
+      nodes_[node].fail = fail;
+      int output = fail;
+      while (!nodes_[output].is_end) {
+        output = nodes_[output].fail;
+        if (nodes_[output].token == -1) { output = -1; break; }
+      }
+      nodes_[node].output = output;
+      if (output >= 0) nodes_[node].output_score += nodes_[output].output_score;
+      queue.push_back(node);
+    }
+  }
+}
+
+int ContextGraph::next(int state, int token) const {
+  const Node& n = nodes_[state];
+  const auto b = sorted_.begin() + n.kid0, e = b + n.nkid;
+  const auto it = std::lower_bound(b, e, std::make_pair(token, -1));
+  return it != e && it->first == token ? it->second : -1;
+}
+
+double ContextGraph::forward_one_step(int state, int token, int* next_state) const {
+  int node = next(state, token);
+  double score;
+  if (node >= 0) {
+    score = nodes_[node].token_score;
+  } else {
+    // follow the fail arcs until one of them has the token or the root is reached (:235-245)
+    node = nodes_[state].fail;
+    while (next(node, token) < 0) {
+      node = nodes_[node].fail;
+      if (nodes_[node].token == -1) break;
+    }
+    const int c = next(node, token);
+    if (c >= 0) node = c;
+    score = nodes_[node].node_score - nodes_[state].node_score;
+  }
+  *next_state = node;
+  return score + nodes_[node].output_score;
+}
+
+// ================================================================================================
+// prefix beam search; CTX = with a context graph.  Without one, nothing of the biasing is executed.
+// ================================================================================================
+template <bool CTX>
+static void prefix_beam_search_impl(const float* tv, const int* ti, int T, int kstride, int beam, int blank,
+                                    PrefixResult* out, const ContextGraph* graph) {
   // trie of the prefixes that have been in the beam: node 0 = empty prefix; the children of a node
   // form a singly linked sibling list (short: only survivors get nodes)
   std::vector<int> parent(1, -1), last(1, -1), first_child(1, -1), next_sib(1, -1);
@@ -99,21 +228,32 @@ void prefix_beam_search(const float* tv, const int* ti, int T, int kstride, int 
       for (int hi = 0; hi < nc; ++hi)
         if (cur[hi].id == pj) { kids[hi].push_back({last[cur[hj].id], hj}); break; }
     }
-    auto self_of = [&](int hi) -> PS& {               // next_hyps[prefix]
+    auto self_of = [&](int hi) -> Hyp& {              // next_hyps[prefix]
       if (self_slot[hi] < 0) {
         self_slot[hi] = (int)nxt.size();
         nxt.emplace_back();
         nxt.back().id = cur[hi].id;
       }
-      return nxt[self_slot[hi]].ps;
+      return nxt[self_slot[hi]];
     };
-    auto child_of = [&](int hi, int u) -> PS& {       // next_hyps[prefix + (u,)]
+    auto child_of = [&](int hi, int u) -> Hyp& {      // next_hyps[prefix + (u,)]
       for (const Kid& k : kids[hi])
         if (k.tok == u) return self_of(k.hj);
       nxt.emplace_back();
       Hyp& h = nxt.back();
       h.id = -1; h.par = cur[hi].id; h.tok = u;
-      return h.ps;
+      return h;
+    };
+    // `if context_graph and not next_score.has_context:` copy_context (prefix unchanged) / update_context (prefix + u)
+    auto copy_ctx = [&](Hyp& n, const Hyp& from) {
+      if (n.has_ctx) return;
+      n.ctx_state = from.ctx_state; n.ctx_score = from.ctx_score; n.has_ctx = true;
+    };
+    auto update_ctx = [&](Hyp& n, const Hyp& from, int u) {
+      if (n.has_ctx) return;
+      int state;
+      const double sc = graph->forward_one_step(from.ctx_state, u, &state);
+      n.ctx_score = from.ctx_score + sc; n.ctx_state = state; n.has_ctx = true;
     };
 
     for (int kk = 0; kk < beam; ++kk) {
@@ -123,12 +263,15 @@ void prefix_beam_search(const float* tv, const int* ti, int T, int kstride, int 
         const PS& ps = cur[hi].ps;
         const double sc = cur[hi].score_cache;
         if (u == blank) {
-          PS& n = self_of(hi);
+          Hyp& hn = self_of(hi);
+          PS& n = hn.ps;
           n.s = log_add2(n.s, sc + prob);
           n.v_s = ps.viterbi() + prob;
           n.times_s = ps.times();
+          if (CTX) copy_ctx(hn, cur[hi]);
         } else if (u == last[cur[hi].id]) {
-          PS& n1 = self_of(hi);
+          Hyp& h1 = self_of(hi);
+          PS& n1 = h1.ps;
           n1.ns = log_add2(n1.ns, ps.ns + prob);
           if (n1.v_ns < ps.v_ns + prob) {
             // reference assigns a misspelled attribute here (`vs_ns`): v_ns stays as it was
@@ -138,15 +281,19 @@ void prefix_beam_search(const float* tv, const int* ti, int T, int kstride, int 
               n1.times_ns = ps.times_ns >= 0 ? t_push(tn_parent[ps.times_ns], t) : -1;
             }
           }
-          PS& n2 = child_of(hi, u);
+          if (CTX) copy_ctx(h1, cur[hi]);
+          Hyp& h2 = child_of(hi, u);
+          PS& n2 = h2.ps;
           n2.ns = log_add2(n2.ns, ps.s + prob);
           if (n2.v_ns < ps.v_s + prob) {
             n2.v_ns = ps.v_s + prob;
             n2.cur_token_prob = prob;
             n2.times_ns = t_push(ps.times_s, t);
           }
+          if (CTX) update_ctx(h2, cur[hi], u);
         } else {
-          PS& n = child_of(hi, u);
+          Hyp& hn = child_of(hi, u);
+          PS& n = hn.ps;
           n.ns = log_add2(n.ns, sc + prob);
           const double vit = ps.viterbi() + prob;
           if (n.v_ns < vit) {
@@ -154,14 +301,18 @@ void prefix_beam_search(const float* tv, const int* ti, int T, int kstride, int 
             n.cur_token_prob = prob;
             n.times_ns = t_push(ps.times(), t);
           }
+          if (CTX) update_ctx(hn, cur[hi], u);
         }
       }
     }
-    // sorted(..., reverse=True)[:beam] of the reference: descending score, equal scores keep their
-    // insertion order (= index in nxt).
+    // sorted(..., reverse=True)[:beam] of the reference: descending score (total_score() = score() + context_score with a
+    // graph), equal scores keep their insertion order (= index in nxt).
     const int nn = (int)nxt.size();
     order.resize(nn);
-    for (int i = 0; i < nn; ++i) { nxt[i].score_cache = nxt[i].ps.score(); order[i] = i; }
+    for (int i = 0; i < nn; ++i) {
+      nxt[i].score_cache = CTX ? nxt[i].ps.score() + nxt[i].ctx_score : nxt[i].ps.score();
+      order[i] = i;
+    }
     const int keep = std::min<int>(beam, nn);
     std::partial_sort(order.begin(), order.begin() + keep, order.end(), [&](int a, int b) {
       const double sa = nxt[a].score_cache, sb = nxt[b].score_cache;
@@ -175,18 +326,31 @@ void prefix_beam_search(const float* tv, const int* ti, int T, int kstride, int 
     }
   }
 
-  out->nbest.clear(); out->scores.clear(); out->times.clear();
+  out->nbest.clear(); out->scores.clear(); out->times.clear(); out->context_scores.clear();
   for (auto& h : cur) {
     std::vector<int> toks;
     for (int id = h.id; id > 0; id = parent[id]) toks.push_back(last[id]);
     std::reverse(toks.begin(), toks.end());
     out->nbest.push_back(std::move(toks));
-    out->scores.push_back(h.ps.score());
+    if (CTX) {
+      // :228-236 -- finalize's score REPLACES the accumulated one (it is not added), the list is not sorted again
+      h.ctx_score = graph->finalize(h.ctx_state, &h.ctx_state);
+      out->scores.push_back(h.ps.score() + h.ctx_score);
+      out->context_scores.push_back(h.ctx_score);
+    } else {
+      out->scores.push_back(h.ps.score());
+    }
     std::vector<int> tm;
     for (int n = h.ps.times(); n >= 0; n = tn_parent[n]) tm.push_back(tn_val[n]);
     std::reverse(tm.begin(), tm.end());
     out->times.push_back(std::move(tm));
   }
+}
+
+void prefix_beam_search(const float* tv, const int* ti, int T, int kstride, int beam, int blank,
+                        PrefixResult* out, const ContextGraph* graph) {
+  if (graph) prefix_beam_search_impl<true>(tv, ti, T, kstride, beam, blank, out, graph);
+  else prefix_beam_search_impl<false>(tv, ti, T, kstride, beam, blank, out, nullptr);
 }
 
 void greedy_collapse(const int* top1, int T_valid, int stride, int blank, std::vector<int>* tokens,

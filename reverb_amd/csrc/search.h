@@ -1,19 +1,55 @@
 // Host-side CTC search (see search.cpp).
 #pragma once
 #include <stdint.h>
+#include <string>
+#include <utility>
 #include <vector>
 
 namespace rvb {
 
 struct PrefixResult {
   std::vector<std::vector<int>> nbest;   // best first
-  std::vector<double> scores;            // log_add(s, ns) of each prefix
+  std::vector<double> scores;            // log_add(s, ns) of each prefix (+ its context score when a graph was given)
   std::vector<std::vector<int>> times;   // Viterbi peak frame per token
+  std::vector<double> context_scores;    // with a graph: the context score each hypothesis ends with (after finalize)
 };
 
-// tv/ti: per-frame top-`beam` log-probs / token ids in torch.topk order, row stride `kstride`.
+// Hot-word biasing graph (asr/wenet/utils/context_graph.py:103-265): an Aho-Corasick automaton over token ids.  A trie of the
+// phrases with, per node, the bonus of its token, the bonus accumulated from the root, and the sum of the accumulated bonuses of
+// every phrase that ends here or at a node reachable over output arcs; fail / output arcs filled breadth-first, children in
+// insertion order (the order of the reference's dicts, which its BFS follows).  All arithmetic float64 in the reference's order.
+// Quirks kept: `is_end` is decided when a node is CREATED, so a phrase that is a prefix of an earlier one (or a duplicate) marks
+// nothing; finalize returns -node_score whether or not the state ends a phrase.  Immutable once built: any number of threads may
+// walk one graph.
+class ContextGraph {
+ public:
+  // phrases concatenated in `tokens`, lens[i] ids each; an empty phrase adds no node
+  ContextGraph(const int32_t* tokens, const int32_t* lens, int n_phrases, double context_score);
+  // "" if every id lies in [0, vocab) and is not `blank` and no length is negative, else the complaint (phrase and position named)
+  static std::string check(const int32_t* tokens, const int32_t* lens, int n_phrases, int vocab, int blank);
+  int num_nodes() const { return (int)nodes_.size() - 1; }     // the reference does not count the root (state 0)
+  double context_score() const { return context_score_; }
+  // score of consuming `token` in `state` (own bonus or the fail path's difference, plus the matched phrases) and the next state
+  double forward_one_step(int state, int token, int* next_state) const;
+  double finalize(int state, int* next_state) const { *next_state = 0; return -nodes_[state].node_score; }
+
+ private:
+  struct Node {
+    int token = -1, fail = 0, output = -1;
+    double token_score = 0.0, node_score = 0.0, output_score = 0.0;
+    bool is_end = false;
+    int kid0 = 0, nkid = 0;                 // its children in sorted_, by token
+  };
+  int next(int state, int token) const;     // child of `state` over `token`, -1 if none
+  double context_score_;
+  std::vector<Node> nodes_;
+  std::vector<std::pair<int, int>> sorted_; // (token, child) of every node, grouped by node, each group sorted by token
+};
+
+// tv/ti: per-frame top-`beam` log-probs / token ids in torch.topk order, row stride `kstride`.  graph (nullable): context biasing
+// as search.py:169-233 applies it; without one the float64 operations are exactly those of the unbiased search.
 void prefix_beam_search(const float* tv, const int* ti, int T, int kstride, int beam, int blank,
-                        PrefixResult* out);
+                        PrefixResult* out, const ContextGraph* graph = nullptr);
 
 // top1: best token per frame (stride between frames), T_valid frames.
 void greedy_collapse(const int* top1, int T_valid, int stride, int blank, std::vector<int>* tokens,

@@ -116,6 +116,18 @@ int rvb_test_fbank(const int16_t* pcm, int64_t n_samples, float* feats /* [frame
 int rvb_test_prefix_beam(const float* topk_val, const int32_t* topk_idx, int T, int beam, int blank,
                          int32_t* n_hyps, int32_t* tokens /* [beam][T] */, int32_t* lens, int32_t* times,
                          int32_t* times_lens, double* scores);
+/* the same search with a hot-word context graph (search.cpp ContextGraph; host only).  The phrases go through the checks of
+ * rvb_set_context_graph against `vocab` and `blank` first (RVB_E_ARG by name).  n_phrases < 0: no graph at all; 0: a graph of the
+ * root alone.  scores = score + context score; context_scores (nullable) = the context score each hypothesis ends with. */
+int rvb_test_prefix_beam_context(const float* topk_val, const int32_t* topk_idx, int T, int beam, int blank, int vocab,
+                                 const int32_t* phrase_tokens, const int32_t* phrase_lens, int n_phrases, double context_score,
+                                 int32_t* n_hyps, int32_t* tokens /* [beam][T] */, int32_t* lens, int32_t* times, int32_t* times_lens,
+                                 double* scores, double* context_scores);
+/* the graph alone: from the root, forward_one_step over stream[n_steps]; per step the score and the node id reached, and what
+ * finalize returns from that node.  num_nodes (nullable) = nodes below the root. */
+int rvb_test_context_walk(const int32_t* phrase_tokens, const int32_t* phrase_lens, int n_phrases, double context_score, int vocab,
+                          int blank, const int32_t* stream, int n_steps, int32_t* num_nodes, double* step_scores, int32_t* step_nodes,
+                          double* final_scores);
 
 /* diarization kernels (diar.hip, resnet.hip tstp_pool) on host floats; see test_api.hip for the layouts */
 int rvb_test_window_stats(const float* wave, int64_t n, int64_t first, int nwin, int64_t step, int len, float eps, float* stats);

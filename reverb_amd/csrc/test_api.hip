@@ -814,6 +814,54 @@ int rvb_test_prefix_beam(const float* topk_val, const int32_t* topk_idx, int T, 
   return OK;
 }
 
+int rvb_test_prefix_beam_context(const float* topk_val, const int32_t* topk_idx, int T, int beam, int blank, int vocab,
+                                 const int32_t* phrase_tokens, const int32_t* phrase_lens, int n_phrases, double context_score,
+                                 int32_t* n_hyps, int32_t* tokens, int32_t* lens, int32_t* times, int32_t* times_lens, double* scores,
+                                 double* context_scores) {
+  if (!topk_val || !topk_idx || !n_hyps || T < 0 || beam < 1) { set_error("rvb_test_prefix_beam_context: bad argument"); return E_ARG; }
+  const int np = n_phrases < 0 ? 0 : n_phrases;
+  const std::string bad = ContextGraph::check(phrase_tokens, phrase_lens, np, vocab, blank);
+  if (!bad.empty()) { set_error("rvb_test_prefix_beam_context: " + bad); return E_ARG; }
+  PrefixResult pr;
+  if (n_phrases < 0) {
+    prefix_beam_search(topk_val, topk_idx, T, beam, beam, blank, &pr);
+  } else {
+    const ContextGraph graph(phrase_tokens, phrase_lens, np, context_score);
+    prefix_beam_search(topk_val, topk_idx, T, beam, beam, blank, &pr, &graph);
+  }
+  *n_hyps = (int32_t)pr.nbest.size();
+  const int ml = T > 0 ? T : 1;
+  for (size_t i = 0; i < pr.nbest.size(); ++i) {
+    if (lens) lens[i] = (int32_t)pr.nbest[i].size();
+    if (times_lens) times_lens[i] = (int32_t)pr.times[i].size();
+    if (scores) scores[i] = pr.scores[i];
+    if (context_scores) context_scores[i] = n_phrases < 0 ? 0.0 : pr.context_scores[i];
+    for (int j = 0; j < ml; ++j) {
+      if (tokens) tokens[i * ml + j] = j < (int)pr.nbest[i].size() ? pr.nbest[i][j] : -1;
+      if (times) times[i * ml + j] = j < (int)pr.times[i].size() ? pr.times[i][j] : -1;
+    }
+  }
+  return OK;
+}
+
+int rvb_test_context_walk(const int32_t* phrase_tokens, const int32_t* phrase_lens, int n_phrases, double context_score, int vocab,
+                          int blank, const int32_t* stream, int n_steps, int32_t* num_nodes, double* step_scores, int32_t* step_nodes,
+                          double* final_scores) {
+  if (n_steps < 0 || (n_steps > 0 && !stream)) { set_error("rvb_test_context_walk: bad argument"); return E_ARG; }
+  const std::string bad = ContextGraph::check(phrase_tokens, phrase_lens, n_phrases, vocab, blank);
+  if (!bad.empty()) { set_error("rvb_test_context_walk: " + bad); return E_ARG; }
+  const ContextGraph graph(phrase_tokens, phrase_lens, n_phrases, context_score);
+  if (num_nodes) *num_nodes = graph.num_nodes();
+  int state = 0, root;
+  for (int i = 0; i < n_steps; ++i) {
+    const double sc = graph.forward_one_step(state, stream[i], &state);
+    if (step_scores) step_scores[i] = sc;
+    if (step_nodes) step_nodes[i] = state;
+    if (final_scores) final_scores[i] = graph.finalize(state, &root);
+  }
+  return OK;
+}
+
 }  // extern "C"
 
 // ------------------------------------------------------------------------------------------------

@@ -662,10 +662,17 @@ def _recover_sharded(engine, pcm, modes, chunk_size, beam_size, ctc_weight, reve
     return out
 
 
+_KEEP_GRAPH = object()      # decode_sharded(context_graph=...) default: leave the engine's graph alone
+
+
 def decode_sharded(engine, pcm: np.ndarray, modes, chunk_size: int, beam_size: int, ctc_weight: float,
-                   reverse_weight: float, device, blank_penalty: float = 0.0, timeout: float = None):
+                   reverse_weight: float, device, blank_penalty: float = 0.0, timeout: float = None, context_graph=_KEEP_GRAPH):
     """Decode one long recording with every rank of the default process group taking a contiguous
     chunk range; returns {mode: results of ALL chunks} on every rank.
+
+    `context_graph`: hot-word biasing of the CTC prefix beam (reverb_amd.context_graph.ContextGraph, token-id lists, or None for
+    none), set on THIS rank's engine before it decodes its range -- every rank passes the same one, so a re-decoded range of a
+    lost rank is biased alike.  Left out, the engine keeps whatever graph it has.
 
     `timeout` (seconds; None = wait for ever, as round 3 did): how long the result gather may take before a peer is presumed
     dead.  The RCCL collective then returns RVB_E_TIMEOUT instead of hanging (rvb_comm_set_timeout), a gloo / torch
@@ -675,6 +682,8 @@ def decode_sharded(engine, pcm: np.ndarray, modes, chunk_size: int, beam_size: i
     global _EPOCH
     _EPOCH += 1
     decode_sharded.last_recovery = None
+    if context_graph is not _KEEP_GRAPH:
+        engine.set_context_graph(context_graph)
     world, rank = dist.get_world_size(), dist.get_rank()
     n_chunks = -(-num_frames(len(pcm)) // chunk_size)
     ranges = ranges_over_alive(n_chunks, world)

@@ -144,6 +144,20 @@ class Engine:
         check(self.lib.rvb_finalize(self.handle, fptr(cat), len(cat) if n else 0), "rvb_finalize")
         self._cat = cat
 
+    def set_context_graph(self, graph=None, context_score: Optional[float] = None):
+        """Hot-word biasing of every later ctc_prefix_beam_search (and, through its n-best, attention_rescoring): `graph` is a
+        reverb_amd.context_graph.ContextGraph or a list of token-id lists (then `context_score`, default 6.0, is the bonus per
+        matched token); None clears it.  The graph stays on the engine until replaced (rvb_set_context_graph)."""
+        if graph is None:
+            check(self.lib.rvb_set_context_graph(self.handle, None, None, 0, 0.0), "rvb_set_context_graph")
+            return
+        if not hasattr(graph, "context_list"):
+            from .context_graph import ContextGraph
+            graph = ContextGraph.from_token_ids(graph, 6.0 if context_score is None else context_score)
+        toks, lens = graph.flat()
+        score = float(graph.context_score if context_score is None else context_score)
+        check(self.lib.rvb_set_context_graph(self.handle, iptr(toks), iptr(lens), len(lens), score), "rvb_set_context_graph")
+
     # -------------------------------------------------------------------------------- front end
     def pinned_pcm(self, n_samples: int) -> np.ndarray:
         """int16 array of page-locked host memory (rvb_host_alloc) for the audio reader to fill: upload_pcm from it runs

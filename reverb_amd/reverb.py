@@ -64,8 +64,8 @@ class RvbASRModel:
                length_penalty: float = 0.0, infos=None, cat_embs=None, cv=None, cv_lengths=None):
         assert speech.shape[0] == speech_lengths.shape[0]
         assert decoding_chunk_size != 0
-        if context_graph is not None:
-            raise NotImplementedError("context biasing is out of scope")
+        # search.py:124-248: the graph biases ctc_prefix_beam_search and what attention_rescoring rescores; None decodes unbiased
+        self.engine.set_context_graph(context_graph)
         if blank_id != self.engine.cfg.blank_id:
             raise ValueError("blank_id differs from the model's ctc_blank_id")
         feats = speech.detach().cpu().numpy() if hasattr(speech, "detach") else np.asarray(speech)
@@ -80,7 +80,7 @@ class RvbASRModel:
                 if cat.shape[0] != feats.shape[0]:
                     raise ValueError(f"cat_embs has {cat.shape[0]} rows for a batch of {feats.shape[0]}")
                 kw = dict(decoding_chunk_size=decoding_chunk_size, num_decoding_left_chunks=num_decoding_left_chunks, ctc_weight=ctc_weight,
-                          simulate_streaming=simulate_streaming, reverse_weight=reverse_weight, blank_id=blank_id,
+                          simulate_streaming=simulate_streaming, reverse_weight=reverse_weight, context_graph=context_graph, blank_id=blank_id,
                           blank_penalty=blank_penalty, length_penalty=length_penalty)
                 rows, groups = {}, []
                 for b in range(cat.shape[0]):
@@ -124,7 +124,7 @@ class RvbASRModel:
 class ReverbASR:
     def __init__(self, config, checkpoint, cmvn_path: str | None = None, tokenizer_symbols: str | None = None,
                  bpe_path: str | None = None, gpu: int = -1, overwrite_cmvn: bool = False, dtype: str = "bf16",
-                 max_chunks: int = 64):
+                 max_chunks: int = 64, context_path: str | None = None, context_score: float = 6.0):
         import yaml
         torch = _torch()
         self.jit = False
@@ -142,6 +142,13 @@ class ReverbASR:
         self.tokenizer = RevBpeTokenizer(tc["bpe_path"], tc["symbol_table_path"], tc.get("non_lang_syms_path"),
                                          split_with_space=tc.get("split_with_space", False), full_config=tc)
         self.blank_id = self._blank_id()
+        # cli/model.py:51-56: a list file of hot words, one phrase per line; cut with the model's own tokenizer
+        self.context_graph = None
+        if context_path is not None:
+            from .context_graph import ContextGraph
+            char = self.configs.get("tokenizer", "rev_bpe") == "char"
+            self.context_graph = ContextGraph(context_path, self.tokenizer.symbol_table, None if char else tc["bpe_path"] or "",
+                                              context_score)
         self.configs["output_dim"] = len(self.tokenizer.symbol_table)
 
         # weights: the checkpoint as torch.load reads it (utils/checkpoint.py:29-46, strict=False)
@@ -248,13 +255,15 @@ class ReverbASR:
         eng = self._engine_for_chunk(chunk_size)
         eng.upload_pcm(*self._load_pcm(audio_file, 16000))
         eng.set_cat_embs([verbatimicity, 1.0 - verbatimicity])
+        eng.set_context_graph(self.context_graph)
         if simulate_streaming and decoding_chunk_size > 0:
             # the reference's loop (cli/reverb.py:220-253) with the encoder run chunk by chunk inside model.decode
             _, feats = eng.fbank(return_feats=True)
             hyps = {m: [] for m in modes}
             for x, lens in self.feats_batcher(_torch().from_numpy(feats).unsqueeze(0), chunk_size, batch_size):
                 part = self.model.decode(modes, x, lens, beam_size, decoding_chunk_size, num_decoding_left_chunks, ctc_weight,
-                                         True, reverse_weight, blank_id=self.blank_id, blank_penalty=blank_penalty, length_penalty=length_penalty)
+                                         True, reverse_weight, context_graph=self.context_graph, blank_id=self.blank_id,
+                                         blank_penalty=blank_penalty, length_penalty=length_penalty)
                 for m in modes:
                     hyps[m].extend(part[m])
             return [get_output(format, self.tokenizer, Path(audio_file).name, hyps[mode], timings_adjustment, chunk_size,
@@ -386,8 +395,10 @@ def get_output(format: str, tokenizer, audio_name: str, hyps: List[DecodeResult]
     return sep.join(lines)
 
 
-def load_model(model: str, gpu: int = -1, dtype: str = "bf16", max_chunks: int = 64):
-    """Loads a reverb model from a directory (config.yaml + *.pt) or by name (cli/reverb.py:330-363)."""
+def load_model(model: str, gpu: int = -1, dtype: str = "bf16", max_chunks: int = 64, context_path: str | None = None,
+               context_score: float = 6.0):
+    """Loads a reverb model from a directory (config.yaml + *.pt) or by name (cli/reverb.py:330-363).  context_path: a list of hot
+    words, one phrase per line, that ctc_prefix_beam_search / attention_rescoring are biased towards (context_score per token)."""
     if Path(model).exists():
         model_dir = Path(model)
         config_path = model_dir / "config.yaml"
@@ -405,7 +416,8 @@ def load_model(model: str, gpu: int = -1, dtype: str = "bf16", max_chunks: int =
                          f"{','.join(get_available_models())}")
     config_path, checkpoint_path = config_path.resolve(), checkpoint_path.resolve()
     logging.info(f"Loading the model with {config_path = } and {checkpoint_path = }")
-    return ReverbASR(str(config_path), str(checkpoint_path), gpu=gpu, dtype=dtype, max_chunks=max_chunks)
+    return ReverbASR(str(config_path), str(checkpoint_path), gpu=gpu, dtype=dtype, max_chunks=max_chunks, context_path=context_path,
+                     context_score=context_score)
 
 
 def get_available_models():

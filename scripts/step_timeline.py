@@ -1,7 +1,10 @@
 """Where the wall time of one bench step goes on the HOST side: the calls of Engine.decode_resident one by one, each bracketed
 with perf_counter (ctypes calls block only where librvb waits for the device).  Run after a warm-up step; prints milliseconds.
 
-    python scripts/step_timeline.py [--model r640] [--hours 1.0] [--dtype bf16] [--steps 3]
+    python scripts/step_timeline.py [--model r640] [--hours 1.0] [--dtype bf16] [--steps 3] [--context_phrases 100]
+
+--context_phrases N: afterwards the same steps again with a hot-word graph (rvb_set_context_graph) of N phrases, 2 and 3 tokens long,
+drawn from the run's own greedy tokens, so that they do match; the stage to compare is "prefix beam" / search_host of the same run.
 """
 import argparse
 import os
@@ -19,6 +22,8 @@ def main():
     p.add_argument("--hours", type=float, default=1.0)
     p.add_argument("--dtype", default="bf16")
     p.add_argument("--steps", type=int, default=3)
+    p.add_argument("--context_phrases", type=int, default=0)
+    p.add_argument("--context_score", type=float, default=6.0)
     a = p.parse_args()
     import torch
     from reverb_amd import synth
@@ -50,21 +55,39 @@ def main():
             rec.append(np.diff(t) * 1e3)
         return res
 
-    step(None)
-    rec = []
-    t0 = time.perf_counter()
-    for _ in range(a.steps):
-        step(rec)
-    wall = (time.perf_counter() - t0) / a.steps * 1e3
-    m = np.mean(rec, axis=0)
     names = ["fbank (sync)", "encode (enqueue 2 slices)", "prefix beam (waits for slices, host search)",
              "rescore (trie, decoder, D2H)", "fetch results", "final sync"]
-    for n, v in zip(names, m):
-        print(f"{n:48s} {v:8.2f} ms")
-    print(f"{'step':48s} {wall:8.2f} ms")
-    for k in ("search_host", "rescore_trie_host", "rescore_decoder_wall", "rescore_scores_host"):
-        t = eng.timing(k)
-        print(f"  {k:46s} {t['ms'] / max(t['launches'], 1):8.2f} ms per call ({t['launches']} calls)")
+
+    def measure(title):
+        step(None)
+        eng.reset_timings()
+        rec = []
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            step(rec)
+        wall = (time.perf_counter() - t0) / a.steps * 1e3
+        m = np.mean(rec, axis=0)
+        print(title)
+        for n, v in zip(names, m):
+            print(f"{n:48s} {v:8.2f} ms")
+        print(f"{'step':48s} {wall:8.2f} ms")
+        for k in ("search_host", "rescore_trie_host", "rescore_decoder_wall", "rescore_scores_host"):
+            t = eng.timing(k)
+            print(f"  {k:46s} {t['ms'] / max(t['launches'], 1):8.2f} ms per call ({t['launches']} calls)")
+
+    measure("-- no context graph")
+    if a.context_phrases > 0:
+        greedy = [list(r.tokens) for r in eng.greedy()]
+        phrases, seen = [], set()
+        for width in (2, 3):
+            for toks in greedy:
+                for i in range(0, max(len(toks) - width + 1, 0), 7):
+                    ph = tuple(toks[i:i + width])
+                    if ph not in seen and len(phrases) < (a.context_phrases // 2 if width == 2 else a.context_phrases):
+                        seen.add(ph); phrases.append(list(ph))
+        eng.set_context_graph(phrases, a.context_score)
+        measure(f"-- context graph: {len(phrases)} phrases from the greedy tokens, score {a.context_score}")
+        eng.set_context_graph(None)
     eng.close()
 
 
