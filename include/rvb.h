@@ -225,6 +225,21 @@ int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens,
                   float* score);
 int rvb_ctc_align_limits(int32_t* max_tokens, int32_t* max_frames);
 
+/* Full-sum CTC score of a KNOWN transcript: log p(tokens | frames) summed over every alignment, the quantity the reference calls
+ * the CTC loss (CTC.forward, asr/wenet/transformer/ctc.py:65-104 = torch.nn.CTCLoss(reduction='sum') over
+ * log_softmax(ctc_lo(encoder_out)), reported by bin/get_loss.py): loglik = -loss.  Valid after rvb_encode / rvb_stream_finish; the
+ * sequences, chunk ranges, refusals (by the same names) and caps are those of rvb_ctc_align, and n_seq > 1 scores several transcripts
+ * (or several chunk ranges) in one launch, which is how candidate transcripts are compared.  loglik [n_seq] is fp64: normalised fp32
+ * forward variables plus per-frame offsets summed in fp64 (csrc/ctc_forward_backward.hip).  The reference's zero_infinity=True turns
+ * a transcript that the frames cannot emit into loss 0; this call does NOT: it refuses (RVB_E_ARG) exactly as rvb_ctc_align does.
+ * Per-token outputs (each nullable, concatenated like `tokens`), from the posteriors gamma[t][token] of a backward sweep:
+ * occupancy = sum over frames of the posterior (the expected number of frames of the token), mean_frame = the posterior-weighted
+ * mean frame, peak_post = the largest posterior, peak_frame = its frame (first on ties).  With all four null only the forward sweep
+ * runs and nothing is stored per frame; otherwise the forward sweep keeps its rows, 4 bytes per frame and state (states = 2 tokens + 1
+ * padded to a multiple of 32) of device memory: RVB_E_NOMEM naming the byte count if they do not fit. */
+int rvb_ctc_score(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,
+                  const int32_t* n_chunks, double* loglik, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame);
+
 /* ctc_prefix_beam_search (search.py:124-248), float64 host arithmetic, one host thread per chunk.
  * Results are kept in the engine; read them with rvb_get_nbest. */
 int rvb_ctc_prefix_beam(rvb_engine* e, int beam);
@@ -345,7 +360,7 @@ int rvb_comm_destroy(rvb_engine* e);
 /* Stage timing (HIP events on the engine stream).  level 1: every kernel family is bracketed;
  * names: "fbank","subsample","gemm","attention","rownorm","glu_dwconv","ctc_topk","embed",
  * "lse_gather","search_host","ctc_align_lp" (rvb_ctc_align: CTC head + log-softmax),"ctc_viterbi" (its
- * forward pass + back-trace).  level 2: only the GEMM launches (the dominant kernel; half the
+ * forward pass + back-trace),"ctc_forward" / "ctc_backward" (rvb_ctc_score: the two sweeps).  level 2: only the GEMM launches (the dominant kernel; half the
  * events, ~1 % less perturbation of the step).  level 0: off.
  * flops: algorithmic FLOPs launched (gemm/attention only). */
 int rvb_set_profiling(rvb_engine* e, int level);

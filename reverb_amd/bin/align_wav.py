@@ -1,6 +1,7 @@
 """Forced alignment of a known transcript: the job of the reference's `asr/wenet/bin/alignment.py` (:221-242: encoder, CTC
 log-softmax, force_align, one `<key> [labels]` line per utterance) for one audio file and its transcript, written as
-`<result_dir>/<audio>.<ctm|ali|json>`.  Praat .lab / TextGrid output (--gen_praat there) is not written."""
+`<result_dir>/<audio>.<ctm|ali|json>`.  --score also writes `<result_dir>/<audio>.score.json`: the full-sum CTC log-likelihood of
+the transcript (the reference's bin/get_loss.py reports its negative as loss_ctc).  Praat .lab / TextGrid output (--gen_praat there) is not written."""
 from __future__ import annotations
 
 import argparse
@@ -26,6 +27,9 @@ def get_args(argv=None):
     p.add_argument("--log_level", default="INFO", help="log level")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f32"], help="device compute mode")
     p.add_argument("--max_chunks", type=int, default=64, help="chunks per device batch: at least the chunks of the file")
+    p.add_argument("--score", action="store_true", help="also write <audio>.score.json: full-sum CTC log-likelihood of the transcript")
+    p.add_argument("--posteriors", action="store_true",
+                   help="per-token occupancy, mean_time and peak_posterior in --format json and in the --score file")
     return p.parse_args(argv)
 
 
@@ -43,7 +47,8 @@ def main(argv=None):
     with open(args.transcript_file, encoding="utf-8") as f:
         transcript = " ".join(f.read().split())
     out = reverb.align(args.audio_file, transcript=transcript, format=args.format, verbatimicity=args.verbatimicity,
-                       chunk_size=args.chunk_size, timings_adjustment=args.timings_adjustment)
+                       chunk_size=args.chunk_size, timings_adjustment=args.timings_adjustment,
+                       posteriors=args.posteriors and args.format == "json")
     if args.format == "json":
         out = json.dumps(out, ensure_ascii=False, indent=1)
     os.makedirs(args.result_dir, exist_ok=True)
@@ -51,6 +56,13 @@ def main(argv=None):
     with open(path, "w", encoding="utf-8") as f:
         f.write(out)
     logging.info("wrote %s", path)
+    if args.score:
+        sc = reverb.score(args.audio_file, transcript=transcript, verbatimicity=args.verbatimicity, chunk_size=args.chunk_size,
+                          posteriors=args.posteriors)
+        path = os.path.join(args.result_dir, Path(args.audio_file).with_suffix(".score.json").name)
+        with open(path, "w", encoding="utf-8") as f:
+            f.write(json.dumps(sc, ensure_ascii=False, indent=1))
+        logging.info("wrote %s", path)
 
 
 if __name__ == "__main__":

@@ -159,6 +159,24 @@ struct CtcAligner {
   void release();
 };
 
+// ---- full-sum scoring (ctc_forward_backward.hip): the host side shared by rvb_ctc_score and the lab hook.  The lattices are the
+// aligner's: plan() is CtcAligner::plan (same checks, refusals and layout).  begin() allocates (with posteriors: the alpha rows, or
+// E_NOMEM naming their size), advance() runs the forward kernel over a slab (slabs in row order), finish_forward() returns loglik;
+// advance_backward() takes the same slabs in descending order, finish_backward() returns the per-token reductions.
+struct CtcScorer {
+  CtcAligner lat;
+  bool post = false;
+  DevBuf d_csum, d_loglik, d_llhat, d_coff, d_arows, d_beta, d_z, d_acc;
+  int plan(const char* who, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const std::vector<std::vector<int32_t>>& seq_rows,
+           int V, int blank_id);
+  int begin(hipStream_t s, bool posteriors);
+  int advance(hipStream_t s, const float* lp, int ld, int r0, int nrows);
+  int finish_forward(hipStream_t s, double* loglik /* [n_seq] */);
+  int advance_backward(hipStream_t s, const float* lp, int ld, int r0, int nrows);
+  int finish_backward(hipStream_t s, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame /* per token, nullable */);
+  void release();
+};
+
 }  // namespace rvb
 
 struct rvb_engine {
@@ -250,6 +268,7 @@ struct rvb_engine {
 
   // ---- forced alignment (rvb_ctc_align) ----
   rvb::CtcAligner aligner;
+  rvb::CtcScorer scorer;           // rvb_ctc_score
   rvb::DevBuf align_lp, align_tv, align_ti, align_row, align_col, align_out;   // fp32 [LOGIT_SLAB][V] log-softmax slab; gather scratch
 
   // ---- RCCL communicator of the C-ABI collectives (comm.hip; optional) ----

@@ -2003,6 +2003,7 @@ void rvb_destroy(rvb_engine* e) {
                     &e->enc_after.g, &e->enc_after.b};
   for (DevBuf* b : bufs) b->release();
   e->aligner.release();
+  e->scorer.release();
   for (DevBuf* b : {&e->align_lp, &e->align_tv, &e->align_ti, &e->align_row, &e->align_col, &e->align_out}) b->release();
   e->atopv.release(); e->atopi.release(); e->d_stream_i32.release(); e->d_amax.release(); e->d_f8sat.release();
   e->wave_f32.release(); e->wave_in.release(); e->rs_kernel.release();
@@ -2321,6 +2322,37 @@ static int align_slab(rvb_engine* e, int r0, int rows) {
                          e->align_ti.as<int>(), e->align_lp.as<float>());
 }
 
+// the log-prob rows of each sequence: the valid encoder frames of its chunks, in order
+static int align_seq_rows(rvb_engine* e, const char* who, const int32_t* first_chunk, const int32_t* n_chunks, int n_seq,
+                          std::vector<std::vector<int32_t>>* seq_rows) {
+  seq_rows->assign(n_seq, {});
+  for (int i = 0; i < n_seq; ++i) {
+    if (first_chunk[i] < 0 || n_chunks[i] < 1 || (int64_t)first_chunk[i] + n_chunks[i] > e->B) {
+      set_error(std::string(who) + ": sequence " + std::to_string(i) + ": chunk range outside the encoded batch of " + std::to_string(e->B) + " chunks");
+      return E_ARG;
+    }
+    for (int c = first_chunk[i]; c < first_chunk[i] + n_chunks[i]; ++c)
+      for (int t = 0; t < e->enc_lens[c]; ++t) (*seq_rows)[i].push_back(c * e->T2 + t);
+  }
+  return OK;
+}
+static int align_workspace(rvb_engine* e) {
+  const int V = e->cfg.vocab, Vld = (V + 3) & ~3, slab = std::min(LOGIT_SLAB, e->B * e->T2);
+  RVB_TRY(e->logits.ensure((size_t)LOGIT_SLAB * Vld * 4));
+  RVB_TRY(e->align_lp.ensure((size_t)slab * V * 4));
+  RVB_TRY(e->align_tv.ensure((size_t)slab * 4));
+  return e->align_ti.ensure((size_t)slab * 4);
+}
+// the slabs rvb_encode computed its log-probs in (per slice of the batch, LOGIT_SLAB rows at a time): the same GEMM launches, so
+// the same bits as the top-k the searches saw
+static std::vector<std::pair<int, int>> align_slabs(const rvb_engine* e) {
+  std::vector<std::pair<int, int>> slabs;
+  auto add_range = [&](int row0, int m) { for (int r0 = 0; r0 < m; r0 += LOGIT_SLAB) slabs.push_back({row0 + r0, std::min(LOGIT_SLAB, m - r0)}); };
+  if (e->slices.empty()) add_range(0, e->B * e->T2);
+  for (const auto& sl : e->slices) add_range(sl.c0 * e->T2, sl.nb * e->T2);
+  return slabs;
+}
+
 int rvb_ctc_align_limits(int32_t* max_tokens, int32_t* max_frames) {
   if (max_tokens) *max_tokens = CTC_ALIGN_MAX_TOKENS;
   if (max_frames) *max_frames = CTC_ALIGN_MAX_FRAMES;
@@ -2334,30 +2366,14 @@ int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens,
   if (!tokens || !tok_lens || !first_chunk || !n_chunks || n_seq <= 0) { set_error("rvb_ctc_align: null argument or n_seq <= 0"); return E_ARG; }
   if (e->B <= 0) { set_error("rvb_ctc_align before rvb_encode"); return E_STATE; }
   const int T = e->T2, V = e->cfg.vocab, blank = e->cfg.blank_id, M = e->B * T;
-  std::vector<std::vector<int32_t>> seq_rows(n_seq);
-  for (int i = 0; i < n_seq; ++i) {
-    if (first_chunk[i] < 0 || n_chunks[i] < 1 || (int64_t)first_chunk[i] + n_chunks[i] > e->B) {
-      set_error("rvb_ctc_align: sequence " + std::to_string(i) + ": chunk range outside the encoded batch of " + std::to_string(e->B) + " chunks");
-      return E_ARG;
-    }
-    for (int c = first_chunk[i]; c < first_chunk[i] + n_chunks[i]; ++c)
-      for (int t = 0; t < e->enc_lens[c]; ++t) seq_rows[i].push_back(c * T + t);
-  }
+  std::vector<std::vector<int32_t>> seq_rows;
+  RVB_TRY(align_seq_rows(e, "rvb_ctc_align", first_chunk, n_chunks, n_seq, &seq_rows));
   CtcAligner& al = e->aligner;
   RVB_TRY(al.plan("rvb_ctc_align", tokens, tok_lens, n_seq, seq_rows, V, blank));
   RVB_HIP_CHECK(hipSetDevice(e->device));
   RVB_TRY(wait_slices(e, -1));
-  const int Vld = (V + 3) & ~3, slab = std::min(LOGIT_SLAB, M);
-  RVB_TRY(e->logits.ensure((size_t)LOGIT_SLAB * Vld * 4));
-  RVB_TRY(e->align_lp.ensure((size_t)slab * V * 4));
-  RVB_TRY(e->align_tv.ensure((size_t)slab * 4));
-  RVB_TRY(e->align_ti.ensure((size_t)slab * 4));
-  // the slabs rvb_encode computed its log-probs in (per slice of the batch, LOGIT_SLAB rows at a time): the same GEMM launches, so
-  // the same bits as the top-k the searches saw
-  std::vector<std::pair<int, int>> slabs;
-  auto add_range = [&](int row0, int m) { for (int r0 = 0; r0 < m; r0 += LOGIT_SLAB) slabs.push_back({row0 + r0, std::min(LOGIT_SLAB, m - r0)}); };
-  if (e->slices.empty()) add_range(0, M);
-  for (const auto& sl : e->slices) add_range(sl.c0 * T, sl.nb * T);
+  RVB_TRY(align_workspace(e));
+  const std::vector<std::pair<int, int>> slabs = align_slabs(e);
   RVB_TRY(al.begin(e->stream));
   for (const auto& [r0, rows] : slabs) {
     if (!al.touches(r0, rows)) continue;
@@ -2431,6 +2447,45 @@ int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens,
     }
   }
   return OK;
+}
+
+// Full-sum score (CTC.forward, transformer/ctc.py:65-104) over the same slabs: a forward sweep, and for per-token outputs the slabs
+// once more in descending order for the backward sweep (the CTC head is recomputed, as for the alignment's confidences).
+int rvb_ctc_score(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,
+                  const int32_t* n_chunks, double* loglik, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame) {
+  if (!e) { set_error("rvb_ctc_score: null engine"); return E_ARG; }
+  if (!tokens || !tok_lens || !first_chunk || !n_chunks || !loglik || n_seq <= 0) { set_error("rvb_ctc_score: null argument or n_seq <= 0"); return E_ARG; }
+  if (e->B <= 0) { set_error("rvb_ctc_score before rvb_encode"); return E_STATE; }
+  const int V = e->cfg.vocab;
+  std::vector<std::vector<int32_t>> seq_rows;
+  RVB_TRY(align_seq_rows(e, "rvb_ctc_score", first_chunk, n_chunks, n_seq, &seq_rows));
+  CtcScorer& sc = e->scorer;
+  RVB_TRY(sc.plan("rvb_ctc_score", tokens, tok_lens, n_seq, seq_rows, V, e->cfg.blank_id));
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(wait_slices(e, -1));
+  RVB_TRY(align_workspace(e));
+  const std::vector<std::pair<int, int>> slabs = align_slabs(e);
+  const bool post = occupancy || mean_frame || peak_post || peak_frame;
+  RVB_TRY(sc.begin(e->stream, post));
+  for (const auto& [r0, rows] : slabs) {
+    if (!sc.lat.touches(r0, rows)) continue;
+    RVB_TRY(align_slab(e, r0, rows));
+    Scope t(e, "ctc_forward");
+    RVB_TRY(sc.advance(e->stream, e->align_lp.as<float>(), V, r0, rows));
+  }
+  {
+    Scope t(e, "ctc_forward");
+    RVB_TRY(sc.finish_forward(e->stream, loglik));
+  }
+  if (!post) return OK;
+  for (auto it = slabs.rbegin(); it != slabs.rend(); ++it) {
+    if (!sc.lat.touches(it->first, it->second)) continue;
+    RVB_TRY(align_slab(e, it->first, it->second));
+    Scope t(e, "ctc_backward");
+    RVB_TRY(sc.advance_backward(e->stream, e->align_lp.as<float>(), V, it->first, it->second));
+  }
+  Scope t(e, "ctc_backward");
+  return sc.finish_backward(e->stream, occupancy, mean_frame, peak_post, peak_frame);
 }
 
 int rvb_ctc_prefix_beam(rvb_engine* e, int beam) {

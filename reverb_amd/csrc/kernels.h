@@ -186,6 +186,22 @@ int ctc_viterbi_forward(hipStream_t s, const VitSeq* seqs, int n_seq, int max_S,
 // states[frame_off + t] = state of frame t on the best path, score[i] = its fp32 score (-inf: no path)
 int ctc_viterbi_backtrace(hipStream_t s, const VitSeq* seqs, int n_seq, const float* alpha, const uint8_t* bp, int* states, float* score);
 
+// ---------------------------------------------------------------- ctc_forward_backward.hip
+// CTC full-sum score of a known token sequence (CTC.forward, asr/wenet/transformer/ctc.py:65-104) and per-token posteriors, on the
+// lattices, caps and slab-by-slab feed of ctc_viterbi.hip.  The alpha rows of a lattice start 4 * bp_off floats into arows and take
+// 4 * bp_stride floats (S padded to 32) per frame.
+// forward: advances the normalised alpha of every lattice over its frames [f0, f1); csum[i] carries the fp64 sum of the per-frame
+// offsets; coff (per frame, nullable) and arows (nullable) receive what the backward sweep needs.
+int ctc_fb_forward(hipStream_t s, const VitSeq* seqs, int n_seq, int max_S, const float* lp, int ld, int r0, const int* rows,
+                   const int* tokens, int blank, float* alpha, double* csum, float* coff, float* arows);
+// loglik[i] (fp64; -inf: no path) and llhat[i] = its part above the summed offsets, from alpha after the last frame
+int ctc_fb_loglik(hipStream_t s, const VitSeq* seqs, int n_seq, const float* alpha, const double* csum, double* loglik, float* llhat);
+// backward: frames [f0, f1) in descending order (f1 == T starts the sweep); per token (index tok_off + k) occupancy, the sum of
+// t * posterior, the peak posterior and its frame accumulate across launches.
+int ctc_fb_backward(hipStream_t s, const VitSeq* seqs, int n_seq, int max_S, const float* lp, int ld, int r0, const int* rows,
+                    const int* tokens, int blank, float* beta, const float* coff, const float* arows, const float* llhat, float* zcarry,
+                    float* occ, float* tsum, float* peak, int* peak_frame);
+
 // ---------------------------------------------------------------- attention.hip
 struct AttnArgs {
   const void* q; const void* k; const void* v;   // T, row-major, head h at column offset h*dk

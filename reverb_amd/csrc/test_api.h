@@ -111,6 +111,18 @@ int rvb_test_host_pool(int n_threads, int items, int rounds);
  * emit, sizes above the caps of include/rvb.h. */
 int rvb_test_ctc_viterbi(const float* lp, int T, int V, const int32_t* tokens, int L, int blank, int slab_rows, int32_t* labels_out,
                          float* score_out);
+/* ctc_forward_backward.hip: full-sum score of tokens[L] over host log-probs lp [T][V] with the kernels rvb_ctc_score runs, advancing
+ * slab_rows frames per launch in both sweeps (forward ascending, backward descending from the last frame).  loglik_out is fp64; the
+ * four per-token outputs [L] are nullable, and with all four null only the forward sweep runs.  Refuses what rvb_test_ctc_viterbi
+ * refuses, in the same words.  RVB_CTC_SCORE_FAKE_NOMEM_ABOVE=<bytes> (lab switch) makes alpha rows above that size fail as an
+ * allocation would: RVB_E_NOMEM naming the byte count, with nothing allocated. */
+int rvb_test_ctc_score(const float* lp, int T, int V, const int32_t* tokens, int L, int blank, int slab_rows, double* loglik_out,
+                       float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame);
+/* the same for n_seq lattices in ONE launch per slab: lp is the lattices' frames concatenated ([sum T][V]), tokens their tokens
+ * concatenated; outputs are concatenated alike.  A slab of slab_rows rows may end inside a lattice or span several. */
+int rvb_test_ctc_score_batch(const float* lp, const int32_t* T, int V, const int32_t* tokens, const int32_t* L, int n_seq, int blank,
+                             int slab_rows, double* loglik_out, float* occupancy, float* mean_frame, float* peak_post,
+                             int32_t* peak_frame);
 int rvb_test_fbank(const int16_t* pcm, int64_t n_samples, float* feats /* [frames,80] */);
 /* native prefix beam search on host arrays: top-k log-probs/indices [T,beam] of one utterance */
 int rvb_test_prefix_beam(const float* topk_val, const int32_t* topk_idx, int T, int beam, int blank,

@@ -579,6 +579,58 @@ int rvb_test_ctc_viterbi(const float* lp, int T, int V, const int32_t* tokens, i
   return OK;
 }
 
+static int ctc_score_lab(const char* who, const float* lp, const int32_t* T, int V, const int32_t* tokens, const int32_t* L, int n_seq,
+                         int blank, int slab_rows, double* loglik_out, float* occupancy, float* mean_frame, float* peak_post,
+                         int32_t* peak_frame) {
+  const std::string w(who);
+  if (!lp || !T || !tokens || !L || !loglik_out || n_seq < 1) { set_error(w + ": null argument"); return E_ARG; }
+  if (slab_rows < 1) { set_error(w + ": need T >= 1 and slab_rows >= 1"); return E_ARG; }
+  CtcScorer sc;
+  std::vector<std::vector<int32_t>> rows(n_seq);
+  int64_t total = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    if (T[i] < 1) { set_error(w + ": need T >= 1 and slab_rows >= 1"); return E_ARG; }
+    rows[i].resize((size_t)T[i]);             // over the cap: plan() refuses on the count alone
+    if (T[i] <= CTC_ALIGN_MAX_FRAMES) for (int t = 0; t < T[i]; ++t) rows[i][t] = (int32_t)(total + t);
+    total += T[i];
+  }
+  T_TRY(sc.plan(who, tokens, L, n_seq, rows, V, blank));
+  T_TRY(need_gpu());
+  const bool post = occupancy || mean_frame || peak_post || peak_frame;
+  const int M = (int)total;
+  Dev dlp;
+  int r = up_raw(dlp, lp, (size_t)M * V * 4);
+  if (r == OK) r = sc.begin(nullptr, post);
+  for (int r0 = 0; r == OK && r0 < M; r0 += slab_rows)
+    r = sc.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, std::min(slab_rows, M - r0));
+  if (r == OK) r = sc.finish_forward(nullptr, loglik_out);
+  if (r == OK && post) {
+    // descending slabs that END at the last row, so that with the forward slabs (which START at row 0) the boundaries of the two
+    // sweeps fall on different frames
+    for (int r1 = M; r == OK && r1 > 0; r1 -= slab_rows) {
+      const int rb = std::max(0, r1 - slab_rows);
+      r = sc.advance_backward(nullptr, (const float*)dlp.p + (size_t)rb * V, V, rb, r1 - rb);
+    }
+    if (r == OK) r = sc.finish_backward(nullptr, occupancy, mean_frame, peak_post, peak_frame);
+  }
+  if (r != OK) (void)hipDeviceSynchronize();
+  sc.release();
+  return r;
+}
+
+int rvb_test_ctc_score(const float* lp, int T, int V, const int32_t* tokens, int L, int blank, int slab_rows, double* loglik_out,
+                       float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame) {
+  return ctc_score_lab("rvb_test_ctc_score", lp, &T, V, tokens, &L, 1, blank, slab_rows, loglik_out, occupancy, mean_frame, peak_post,
+                       peak_frame);
+}
+
+int rvb_test_ctc_score_batch(const float* lp, const int32_t* T, int V, const int32_t* tokens, const int32_t* L, int n_seq, int blank,
+                             int slab_rows, double* loglik_out, float* occupancy, float* mean_frame, float* peak_post,
+                             int32_t* peak_frame) {
+  return ctc_score_lab("rvb_test_ctc_score_batch", lp, T, V, tokens, L, n_seq, blank, slab_rows, loglik_out, occupancy, mean_frame,
+                       peak_post, peak_frame);
+}
+
 int rvb_test_lse_gather(const float* logits, int R, int V, const int32_t* target, float* out) {
   T_TRY(need_gpu());
   Dev dl, dt, dout;

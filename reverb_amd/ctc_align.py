@@ -183,3 +183,16 @@ def align_to_json(res: AlignResult, tokenizer, chunk_size: int, input_frame_ms: 
     toks = [{"piece": piece_of(int(tok), tokenizer), "id": int(tok), "start_ms": ms(b, 0), "end_ms": ms(e, 1), "confidence": float(conf)}
             for tok, b, e, conf in zip(res.tokens, res.begin, res.end, res.confidence)]
     return {"score": float(res.score), "tokens": toks}
+
+
+def posteriors_to_json(res: AlignResult, post: Dict[str, Any], chunk_size: int, input_frame_ms: int, output_frame_ms: int) -> List[Dict[str, Any]]:
+    """Per token, from Engine.score(..., posteriors=True) of the same sequence: occupancy (expected frames), mean_time (ms; the
+    posterior-weighted mean frame through the frame -> ms conversion of align_to_json, the fraction of a frame kept) and
+    peak_posterior."""
+    def ms(frame: float) -> float:
+        whole = min(max(int(frame), 0), sum(res.chunk_lens) - 1)
+        c, t = res.chunk_frame(whole)
+        return c * chunk_size * input_frame_ms + (t + frame - whole) * output_frame_ms
+
+    return [{"occupancy": float(o), "mean_time": float(ms(float(m))), "peak_posterior": float(p)}
+            for o, m, p in zip(post["occupancy"], post["mean_frame"], post["peak_posterior"])]

@@ -440,6 +440,41 @@ class Engine:
             t0 += n; f0 += frames[i]
         return out
 
+    def score(self, token_seqs, chunk_ranges=None, posteriors=False):
+        """Full-sum CTC score (rvb_ctc_score; reference: CTC.forward, transformer/ctc.py:65-104 = -CTCLoss(reduction='sum')) of known
+        token sequences against the chunks of the last encode(); sequences and chunk_ranges as in align(), and several sequences
+        over the SAME chunks compare candidate transcripts in one launch.  -> List[dict]: loglik (fp64), n_tokens, n_frames and, with
+        posteriors=True, per token occupancy (expected frames), mean_frame, peak_posterior, peak_frame (frames within the sequence)."""
+        seqs = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in token_seqs]
+        if chunk_ranges is None:
+            chunk_ranges = [(i, 1) for i in range(len(seqs))]
+        if len(chunk_ranges) != len(seqs) or not seqs:
+            raise RvbError("score: one chunk range per token sequence, at least one sequence")
+        lens = self.encoder_lens()
+        first = np.array([r[0] for r in chunk_ranges], np.int32)
+        count = np.array([r[1] for r in chunk_ranges], np.int32)
+        tok = np.ascontiguousarray(np.concatenate(seqs) if sum(map(len, seqs)) else np.zeros(1, np.int32), np.int32)
+        tl = np.array([len(t) for t in seqs], np.int32)
+        frames = [int(lens[f:f + c].sum()) if 0 <= f and c >= 1 and f + c <= self.batch else 0 for f, c in zip(first, count)]
+        nt = max(int(tl.sum()), 1)
+        loglik = np.empty(len(seqs), np.float64)
+        occ, mean, peak = (np.empty(nt, np.float32) for _ in range(3))
+        pkf = np.empty(nt, np.int32)
+        none_f, none_i = C.POINTER(C.c_float)(), C.POINTER(C.c_int32)()
+        check(self.lib.rvb_ctc_score(self.handle, iptr(tok), iptr(tl), len(seqs), iptr(first), iptr(count), dptr(loglik),
+                                     fptr(occ) if posteriors else none_f, fptr(mean) if posteriors else none_f,
+                                     fptr(peak) if posteriors else none_f, iptr(pkf) if posteriors else none_i), "rvb_ctc_score")
+        out, t0 = [], 0
+        for i, t in enumerate(seqs):
+            n = len(t)
+            r = {"loglik": float(loglik[i]), "n_tokens": n, "n_frames": frames[i]}
+            if posteriors:
+                r.update(occupancy=occ[t0:t0 + n].tolist(), mean_frame=mean[t0:t0 + n].tolist(), peak_posterior=peak[t0:t0 + n].tolist(),
+                         peak_frame=pkf[t0:t0 + n].tolist())
+            out.append(r)
+            t0 += n
+        return out
+
     def _nbest(self, chunk: int):
         nh, ml = C.c_int32(0), C.c_int32(0)
         check(self.lib.rvb_get_nbest_count(self.handle, chunk, C.byref(nh), C.byref(ml)))

@@ -275,13 +275,14 @@ class ReverbASR:
                            self.input_frame_length, self.output_frame_length) for mode in modes]
 
     def align(self, audio_file, transcript: Optional[str] = None, tokens=None, format: str = "ctm", verbatimicity: float = 1.0,
-              chunk_size: int = 2051, timings_adjustment: float = 230):
+              chunk_size: int = 2051, timings_adjustment: float = 230, posteriors: bool = False):
         """Forced alignment of a KNOWN transcript (the reference's bin/alignment.py -> force_align, utils/ctc_utils.py:105-161): exactly
         one of `transcript` (text, tokenised with the model's tokenizer) or `tokens` (ids).  The whole file is encoded as
         transcribe_modes does and the transcript aligned as ONE sequence over all chunks.  format: "ctm" / "txt" (through get_output,
         a token going to the chunk its first frame lies in), "ali" (the reference's `<audio> [labels]` line), "json" (dict: per-token
-        times + score)."""
-        from .ctc_align import DecodeLike, align_to_ali, align_to_json, split_by_chunk
+        times + score; with posteriors=True each token also carries occupancy, mean_time and peak_posterior of the full-sum
+        posteriors, see score())."""
+        from .ctc_align import DecodeLike, align_to_ali, align_to_json, posteriors_to_json, split_by_chunk
         if (transcript is None) == (tokens is None):
             raise ValueError("align: give exactly one of transcript= (text) or tokens= (ids)")
         if format not in ("ctm", "txt", "ali", "json"):
@@ -291,6 +292,25 @@ class ReverbASR:
             raise NotImplementedError("the device fbank is built for 80 bins / 25 ms / 10 ms")
         if chunk_size < 7:
             raise ValueError("chunk_size must be at least 7 frames (Conv2dSubsampling4 needs 7 input frames, subsampling.py:201-226)")
+        eng, ids, n_chunks = self._encode_for_align("align", audio_file, transcript, tokens, verbatimicity, chunk_size)
+        res = eng.align([ids], [(0, n_chunks)])[0]
+        name = Path(audio_file).name
+        if format == "ali":
+            return align_to_ali(name, res)
+        if format == "json":
+            out = align_to_json(res, self.tokenizer, chunk_size, self.input_frame_length, self.output_frame_length)
+            if posteriors:
+                post = eng.score([ids], [(0, n_chunks)], posteriors=True)[0]
+                for tok, extra in zip(out["tokens"], posteriors_to_json(res, post, chunk_size, self.input_frame_length,
+                                                                        self.output_frame_length)):
+                    tok.update(extra)
+            return out
+        hyps = [DecodeLike(t, fr, cf) for t, fr, cf in split_by_chunk(res)]
+        return get_output(format, self.tokenizer, name, hyps, timings_adjustment, chunk_size, self.input_frame_length,
+                          self.output_frame_length)
+
+    def _encode_for_align(self, who: str, audio_file, transcript, tokens, verbatimicity: float, chunk_size: int):
+        """Tokenise and encode the whole file as ONE batch, as align() and score() need it -> (engine, ids, n_chunks)."""
         ids = list(self.tokenizer.tokenize(transcript)[1]) if tokens is None else [int(t) for t in tokens]
         eng = self._engine_for_chunk(chunk_size)
         eng.upload_pcm(*self._load_pcm(audio_file, 16000))
@@ -299,20 +319,39 @@ class ReverbASR:
         n_frames = eng.fbank()
         n_chunks = -(-n_frames // chunk_size)
         if n_chunks > eng.cfg.max_chunks:
-            raise ValueError(f"align: the file has {n_chunks} chunks of {chunk_size} frames, the engine batches {eng.cfg.max_chunks}: "
+            raise ValueError(f"{who}: the file has {n_chunks} chunks of {chunk_size} frames, the engine batches {eng.cfg.max_chunks}: "
                              "one lattice spans one encoded batch -- load the model with max_chunks >= the file's chunks")
         lens = np.full(n_chunks, chunk_size, np.int32)
         lens[-1] = n_frames - (n_chunks - 1) * chunk_size
         eng.encode(None, lens, 1, 0.0, first_chunk=0, T0=chunk_size)
+        return eng, ids, n_chunks
+
+    def score(self, audio_file, transcript: Optional[str] = None, tokens=None, verbatimicity: float = 1.0, chunk_size: int = 2051,
+              posteriors: bool = False):
+        """How likely a KNOWN transcript is under the model: the full-sum CTC log-likelihood, the negative of what the reference
+        calls loss_ctc (CTC.forward, transformer/ctc.py:65-104; bin/get_loss.py), of the transcript as ONE sequence over the whole
+        file, tokenised and encoded exactly as align() does.  -> dict: loglik, n_tokens, n_frames, loglik_per_token, viterbi_score
+        (the best single path, from the align call: loglik >= viterbi_score) and, with posteriors=True, per token occupancy
+        (expected frames), mean_time (ms, the frame -> ms conversion of align's json) and peak_posterior.  A transcript the frames
+        cannot emit is refused, as by align(); the reference's zero_infinity would report loss 0."""
+        from .ctc_align import posteriors_to_json
+        if (transcript is None) == (tokens is None):
+            raise ValueError("score: give exactly one of transcript= (text) or tokens= (ids)")
+        fc = self.test_conf["fbank_conf"]
+        if (fc["num_mel_bins"], fc["frame_length"], fc["frame_shift"]) != (80, 25, 10):
+            raise NotImplementedError("the device fbank is built for 80 bins / 25 ms / 10 ms")
+        if chunk_size < 7:
+            raise ValueError("chunk_size must be at least 7 frames (Conv2dSubsampling4 needs 7 input frames, subsampling.py:201-226)")
+        eng, ids, n_chunks = self._encode_for_align("score", audio_file, transcript, tokens, verbatimicity, chunk_size)
         res = eng.align([ids], [(0, n_chunks)])[0]
-        name = Path(audio_file).name
-        if format == "ali":
-            return align_to_ali(name, res)
-        if format == "json":
-            return align_to_json(res, self.tokenizer, chunk_size, self.input_frame_length, self.output_frame_length)
-        hyps = [DecodeLike(t, fr, cf) for t, fr, cf in split_by_chunk(res)]
-        return get_output(format, self.tokenizer, name, hyps, timings_adjustment, chunk_size, self.input_frame_length,
-                          self.output_frame_length)
+        sc = eng.score([ids], [(0, n_chunks)], posteriors=posteriors)[0]
+        out = {"loglik": sc["loglik"], "n_tokens": sc["n_tokens"], "n_frames": sc["n_frames"],
+               "loglik_per_token": sc["loglik"] / sc["n_tokens"], "viterbi_score": float(res.score)}
+        if posteriors:
+            per = posteriors_to_json(res, sc, chunk_size, self.input_frame_length, self.output_frame_length)
+            for key in ("occupancy", "mean_time", "peak_posterior"):
+                out[key] = [p[key] for p in per]
+        return out
 
     def _engine_for_chunk(self, chunk_size: int) -> Engine:
         """The reference accepts any --chunk_size (cli/reverb.py:188, recognize_wav.py:66-70).  The engine sizes its

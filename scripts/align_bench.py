@@ -2,7 +2,7 @@
 ONE lattice over all chunks.  Prints one JSON line: wall time of Engine.align per repetition (host clock around a call that ends in a
 device synchronise) and the "ctc_align_lp" / "ctc_viterbi" device times of rvb_get_timing (HIP events; a profiled run of its own).
 
-    python scripts/align_bench.py [--model r640] [--dtype bf16] [--seconds 3600] [--reps 5] [--warmup 2]
+    python scripts/align_bench.py [--model r640] [--dtype bf16] [--seconds 3600] [--reps 5] [--warmup 2] [--score]
 """
 import argparse
 import json
@@ -22,6 +22,7 @@ def main():
     p.add_argument("--seconds", type=float, default=3600.0)
     p.add_argument("--reps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
+    p.add_argument("--score", action="store_true", help="also time Engine.score of the same lattice: ctc_forward / ctc_backward")
     a = p.parse_args()
     from reverb_amd import synth
     from reverb_amd.engine import Engine
@@ -49,10 +50,30 @@ def main():
     for _ in range(a.reps):
         eng.align([tokens], [(0, n_chunks)])
     lp, vit = eng.timing("ctc_align_lp"), eng.timing("ctc_viterbi")
+    extra = {}
+    if a.score:
+        # full-sum score of the same lattice: forward only (wall), then with posteriors under the profiler
+        for _ in range(a.warmup):
+            sc = eng.score([tokens], [(0, n_chunks)], posteriors=True)[0]
+        eng.set_profiling(False)
+        swall = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            eng.score([tokens], [(0, n_chunks)])
+            swall.append((time.perf_counter() - t0) * 1e3)
+        eng.set_profiling(True)
+        eng.reset_timings()
+        for _ in range(a.reps):
+            sc = eng.score([tokens], [(0, n_chunks)], posteriors=True)[0]
+        fw, bw = eng.timing("ctc_forward"), eng.timing("ctc_backward")
+        extra = {"score_forward_wall_ms_median": round(float(np.median(swall)), 2), "ctc_forward_ms": round(fw["ms"] / a.reps, 3),
+                 "ctc_backward_ms": round(bw["ms"] / a.reps, 3), "forward_us_per_frame": round(fw["ms"] / a.reps * 1e3 / T, 3),
+                 "backward_us_per_frame": round(bw["ms"] / a.reps * 1e3 / T, 3), "loglik": sc["loglik"],
+                 "alpha_rows_bytes": 4 * T * ((2 * len(tokens) + 1 + 31) // 32 * 32)}
     print(json.dumps({"model": a.model, "dtype": a.dtype, "frames": T, "tokens": len(tokens), "states": 2 * len(tokens) + 1,
                       "align_wall_ms": [round(w, 2) for w in wall], "align_wall_ms_median": round(float(np.median(wall)), 2),
                       "ctc_align_lp_ms": round(lp["ms"] / a.reps, 3), "ctc_viterbi_ms": round(vit["ms"] / a.reps, 3),
-                      "viterbi_us_per_frame": round(vit["ms"] / a.reps * 1e3 / T, 3), "score": res.score}))
+                      "viterbi_us_per_frame": round(vit["ms"] / a.reps * 1e3 / T, 3), "score": res.score, **extra}))
     eng.close()
 
 
