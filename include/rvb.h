@@ -268,6 +268,26 @@ int rvb_get_nbest(rvb_engine* e, int chunk, int32_t* tokens, int32_t* lens, int3
  * so that the device computes them while the host searches the last slice.  rvb_attention_rescore does it itself otherwise. */
 int rvb_prepare_rescoring(rvb_engine* e, int right_to_left);
 int rvb_attention_rescore(rvb_engine* e, double ctc_weight, double reverse_weight);
+/* Attention-decoder loss and accuracy of KNOWN transcripts: the teacher-forced pass of ASRModel._calc_att_loss (asr_model.py:248-286)
+ * on the chunks of the last rvb_encode / rvb_stream_finish.  n_seq sequences, concatenated in `tokens` (tok_lens[i] ids each);
+ * sequence i is scored against the memory of chunk chunk_of[i] -- ONE chunk: its frames are the only memory the decoder path has.
+ * Decoder inputs are [sos] + y, targets y + [eos]; the right-to-left decoder (run only when reverse_weight > 0) sees the reversed y
+ * (reverse_pad_list + add_sos_eos).  The sequences form the prefix trie of rvb_attention_rescore, so candidates of one chunk share the
+ * decoder rows of their common prefix and each one reads the bits it would read alone; the memory keys / values of
+ * rvb_prepare_rescoring are reused.  Per sequence: loss_l / loss_r = the label-smoothed KL of LabelSmoothingLoss
+ * (label_smoothing_loss.py:68-96, smoothing = lsm_weight) SUMMED over the L + 1 positions, in fp64, divided by nothing (loss_r
+ * nullable; zeros when reverse_weight = 0); n_correct = positions of the left decoder whose arg-max equals the target, the <eos>
+ * position included (th_accuracy, utils/common.py:268-287; ties to the lowest index); n_positions = L + 1.  The caller forms
+ * loss_att = (1 - reverse_weight) loss_l + reverse_weight loss_r, normalised as its configuration says.  Flat per-position outputs,
+ * concatenated in sequence order with L + 1 entries each, every one nullable: logp_l, logp_r (in the right decoder's own order:
+ * position j is its j-th target) = log p(target), top1_l = the left decoder's arg-max.
+ * Refused by name: before rvb_encode, a model without decoder, reverse_weight > 0 without a right-to-left decoder (RVB_E_STATE);
+ * an empty sequence, an id outside [0, vocab), chunk_of outside the batch, lsm_weight outside [0, 1) (RVB_E_ARG); L + 1 beyond the
+ * positional table (RVB_E_UNSUPPORTED).  The n-best lists, the rescoring results and what a later rvb_attention_rescore returns are
+ * left as they are. */
+int rvb_attention_score(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* chunk_of,
+                        double reverse_weight, double lsm_weight, double* loss_l, double* loss_r, int32_t* n_correct,
+                        int32_t* n_positions, float* logp_l, float* logp_r, int32_t* top1_l);
 /* `attention` mode (asr/wenet/transformer/search.py:251-360): autoregressive beam search with the left decoder on
  * the chunks of the last rvb_encode; per-hypothesis K/V caches on the device, beam bookkeeping on the host in float32
  * as the reference does.  Runs until every beam ended with <eos> or for encoder-frames steps. */
@@ -359,7 +379,7 @@ int rvb_comm_destroy(rvb_engine* e);
 
 /* Stage timing (HIP events on the engine stream).  level 1: every kernel family is bracketed;
  * names: "fbank","subsample","gemm","attention","rownorm","glu_dwconv","ctc_topk","embed",
- * "lse_gather","search_host","ctc_align_lp" (rvb_ctc_align: CTC head + log-softmax),"ctc_viterbi" (its
+ * "lse_gather" (the row kernel after the decoders' output layer: rescoring and rvb_attention_score),"search_host","ctc_align_lp" (rvb_ctc_align: CTC head + log-softmax),"ctc_viterbi" (its
  * forward pass + back-trace),"ctc_forward" / "ctc_backward" (rvb_ctc_score: the two sweeps).  level 2: only the GEMM launches (the dominant kernel; half the
  * events, ~1 % less perturbation of the step).  level 0: off.
  * flops: algorithmic FLOPs launched (gemm/attention only). */

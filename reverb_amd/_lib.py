@@ -98,6 +98,8 @@ SIGNATURES = {
     "rvb_get_nbest": (C.c_int, [_eng, C.c_int, _i32p, _i32p, _i32p, _i32p, _f64p]),
     "rvb_prepare_rescoring": (C.c_int, [_eng, C.c_int]),
     "rvb_attention_rescore": (C.c_int, [_eng, C.c_double, C.c_double]),
+    "rvb_attention_score": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, C.c_double, C.c_double, _f64p, _f64p, _i32p, _i32p, _f32p, _f32p,
+                                      _i32p]),
     "rvb_attention_decode": (C.c_int, [_eng, C.c_int, C.c_float]),
     "rvb_get_attention_result": (C.c_int, [_eng, C.c_int, _i32p, _i32p, _f32p]),
     "rvb_get_rescored": (C.c_int, [_eng, C.c_int, _i32p, _f32p, _f64p, _f64p]),
@@ -185,6 +187,7 @@ TEST_SIGNATURES = {
     "rvb_test_rownorm_fp8": (C.c_int, [_f32p, _f32p, _f32p, C.c_float, C.c_int, C.c_int, C.c_int, C.c_float, _f32p, _f32p, _f32p,
                                        C.c_float, C.c_float, _f32p, _f32p]),
     "rvb_test_lse_gather_multi": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, _i32p, C.c_int, _f32p]),
+    "rvb_test_row_xent": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f32p, _f32p, _f64p, _i32p]),
     "rvb_test_host_pool": (C.c_int, [C.c_int, C.c_int, C.c_int]),
     "rvb_test_build_trie": (C.c_int, [_i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
                                       _i32p, _i32p, _i32p, _i32p, _i32p]),

@@ -1,7 +1,8 @@
 """Forced alignment of a known transcript: the job of the reference's `asr/wenet/bin/alignment.py` (:221-242: encoder, CTC
 log-softmax, force_align, one `<key> [labels]` line per utterance) for one audio file and its transcript, written as
 `<result_dir>/<audio>.<ctm|ali|json>`.  --score also writes `<result_dir>/<audio>.score.json`: the full-sum CTC log-likelihood of
-the transcript (the reference's bin/get_loss.py reports its negative as loss_ctc).  Praat .lab / TextGrid output (--gen_praat there) is not written."""
+the transcript (the reference's bin/get_loss.py reports its negative as loss_ctc); with --attention that file also carries the
+attention decoders' loss_att and acc_att and the combined loss.  Praat .lab / TextGrid output (--gen_praat there) is not written."""
 from __future__ import annotations
 
 import argparse
@@ -30,6 +31,9 @@ def get_args(argv=None):
     p.add_argument("--score", action="store_true", help="also write <audio>.score.json: full-sum CTC log-likelihood of the transcript")
     p.add_argument("--posteriors", action="store_true",
                    help="per-token occupancy, mean_time and peak_posterior in --format json and in the --score file")
+    p.add_argument("--attention", action="store_true",
+                   help="with --score: also loss_ctc, loss_att, acc_att, loss and att_logp of the attention decoders (audio of one chunk)")
+    p.add_argument("--reverse_weight", type=float, default=None, help="weight of the right-to-left decoder in loss_att (default: the config's)")
     return p.parse_args(argv)
 
 
@@ -58,7 +62,7 @@ def main(argv=None):
     logging.info("wrote %s", path)
     if args.score:
         sc = reverb.score(args.audio_file, transcript=transcript, verbatimicity=args.verbatimicity, chunk_size=args.chunk_size,
-                          posteriors=args.posteriors)
+                          posteriors=args.posteriors, attention=args.attention, reverse_weight=args.reverse_weight)
         path = os.path.join(args.result_dir, Path(args.audio_file).with_suffix(".score.json").name)
         with open(path, "w", encoding="utf-8") as f:
             f.write(json.dumps(sc, ensure_ascii=False, indent=1))

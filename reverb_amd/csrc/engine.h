@@ -254,6 +254,7 @@ struct rvb_engine {
   rvb::DevBuf d_hq_start, d_hq_len, d_hkv_start, d_hkv_len;
   rvb::DevBuf d_hq_pos0, d_hpath_start, d_hpath_len, d_path, d_work, d_tgt_ptr;    // rescoring over the hypothesis trie
   int64_t rescore_rows = 0, rescore_pairs = 0;      // decoder rows computed / (hypothesis, position) pairs served, last call
+  rvb::DevBuf d_xlse, d_xsum, d_xtop;               // rvb_attention_score: lse fp32, sum of logits fp64, arg-max int32 per trie row
 
   // ---- streaming encoder (forward_chunk with caches, encoder.py:231-402) ----
   struct StreamState {

@@ -1243,7 +1243,10 @@ static int decoder_memory_kv(rvb_engine* e, Decoder& D, int M) {
   return OK;
 }
 
-static int decoder_forward(rvb_engine* e, Decoder& D, const TrieBatch& t, std::vector<float>* logp) {
+// xent (rvb_attention_score): the slabs go through row_xent instead of lse_gather_multi, which also returns lse, the sum of the
+// logits and the arg-max of every trie row; null (rescoring): the launches are exactly the ones they always were
+struct XentRows { std::vector<float> lse; std::vector<double> sum_x; std::vector<int32_t> top1; };
+static int decoder_forward(rvb_engine* e, Decoder& D, const TrieBatch& t, std::vector<float>* logp, XentRows* xent = nullptr) {
   const rvb_model_cfg& c = e->cfg;
   const int d = c.d_model, heads = c.dec_heads, dk = d / heads, ff = c.dec_ffn_dim, V = c.vocab;
   const int M = e->B * e->T2, R = t.R, nhyp = (int)t.hq_start.size();
@@ -1270,6 +1273,9 @@ static int decoder_forward(rvb_engine* e, Decoder& D, const TrieBatch& t, std::v
   RVB_TRY(e->dh.ensure((size_t)R * ff * es));
   if (!D.kv_ready) RVB_TRY(decoder_memory_kv(e, D, M));
   RVB_TRY(e->d_logp.ensure((size_t)t.P * 4));
+  if (xent) {
+    RVB_TRY(e->d_xlse.ensure((size_t)R * 4)); RVB_TRY(e->d_xsum.ensure((size_t)R * 8)); RVB_TRY(e->d_xtop.ensure((size_t)R * 4));
+  }
   float* x = e->dx.as<float>();
   {
     Scope sc(e, "embed");
@@ -1327,11 +1333,21 @@ static int decoder_forward(rvb_engine* e, Decoder& D, const TrieBatch& t, std::v
     const int rows = std::min(LOGIT_SLAB, R - r0);
     RVB_TRY(run_gemm(e, (const char*)e->dxn.p + (size_t)r0 * d * es, d, D.out, e->logits.p, Vld, rows, true));
     Scope sc(e, "lse_gather");
-    RVB_TRY(lse_gather_multi(e->stream, e->logits.as<float>(), rows, V, Vld, e->d_tgt_ptr.as<int>() + r0, e->d_tgt.as<int>(),
-                             e->d_logp.as<float>()));
+    if (xent)
+      RVB_TRY(row_xent(e->stream, e->logits.as<float>(), rows, V, Vld, e->d_tgt_ptr.as<int>() + r0, e->d_tgt.as<int>(),
+                       e->d_logp.as<float>(), e->d_xlse.as<float>() + r0, e->d_xsum.as<double>() + r0, e->d_xtop.as<int>() + r0));
+    else
+      RVB_TRY(lse_gather_multi(e->stream, e->logits.as<float>(), rows, V, Vld, e->d_tgt_ptr.as<int>() + r0, e->d_tgt.as<int>(),
+                               e->d_logp.as<float>()));
   }
   logp->resize(t.P);
   RVB_HIP_CHECK(hipMemcpyAsync(logp->data(), e->d_logp.p, (size_t)t.P * 4, hipMemcpyDeviceToHost, e->stream));
+  if (xent) {
+    xent->lse.resize(R); xent->sum_x.resize(R); xent->top1.resize(R);
+    RVB_HIP_CHECK(hipMemcpyAsync(xent->lse.data(), e->d_xlse.p, (size_t)R * 4, hipMemcpyDeviceToHost, e->stream));
+    RVB_HIP_CHECK(hipMemcpyAsync(xent->sum_x.data(), e->d_xsum.p, (size_t)R * 8, hipMemcpyDeviceToHost, e->stream));
+    RVB_HIP_CHECK(hipMemcpyAsync(xent->top1.data(), e->d_xtop.p, (size_t)R * 4, hipMemcpyDeviceToHost, e->stream));
+  }
   RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
   return OK;
 }
@@ -2005,6 +2021,7 @@ void rvb_destroy(rvb_engine* e) {
   e->aligner.release();
   e->scorer.release();
   for (DevBuf* b : {&e->align_lp, &e->align_tv, &e->align_ti, &e->align_row, &e->align_col, &e->align_out}) b->release();
+  e->d_xlse.release(); e->d_xsum.release(); e->d_xtop.release();
   e->atopv.release(); e->atopi.release(); e->d_stream_i32.release(); e->d_amax.release(); e->d_f8sat.release();
   e->wave_f32.release(); e->wave_in.release(); e->rs_kernel.release();
   e->jlogp.release(); e->jpair_row.release(); e->jpair_tok.release(); e->jpair_out.release();
@@ -2548,6 +2565,97 @@ int rvb_prepare_rescoring(rvb_engine* e, int right_to_left) {
 int rvb_attention_rescore(rvb_engine* e, double ctc_weight, double reverse_weight) {
   if (!e) { set_error("null engine"); return E_ARG; }
   return rescore_impl(e, ctc_weight, reverse_weight);
+}
+// Teacher-forced decoder pass over GIVEN sequences (ASRModel._calc_att_loss, asr_model.py:248-286): the rescoring decoder on a trie
+// built from the caller's sequences, row_xent in place of lse_gather_multi, and the label-smoothed KL of label_smoothing_loss.py:68-96
+// composed per position in fp64 from its closed form: with u = smoothing / (V - 1), c = 1 - smoothing and sum_v log p(v) =
+// sum_x - V lse,   kl = c ln c + (V - 1) u ln u - c logp_t - u (sum_x - V lse - logp_t)      (0 ln 0 = 0)
+int rvb_attention_score(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* chunk_of,
+                        double reverse_weight, double lsm_weight, double* loss_l, double* loss_r, int32_t* n_correct,
+                        int32_t* n_positions, float* logp_l, float* logp_r, int32_t* top1_l) {
+  const std::string w("rvb_attention_score");
+  if (!e) { set_error(w + ": null engine"); return E_ARG; }
+  if (!tokens || !tok_lens || !chunk_of || !loss_l || n_seq <= 0) { set_error(w + ": null argument or n_seq <= 0"); return E_ARG; }
+  if (e->B <= 0) { set_error(w + " before rvb_encode"); return E_STATE; }
+  if (!e->dec_l.present) { set_error(w + ": model has no attention decoder"); return E_STATE; }
+  const bool use_r = reverse_weight > 0.0;
+  if (use_r && !e->dec_r.present) { set_error(w + ": reverse_weight > 0 but model has no right-to-left decoder"); return E_STATE; }
+  const int B = e->B, T2 = e->T2, V = e->cfg.vocab, eos = e->cfg.eos_id, sos = e->cfg.sos_id;
+  if (!(lsm_weight >= 0.0 && lsm_weight < 1.0) || !(reverse_weight >= 0.0 && reverse_weight <= 1.0) || V < 2) {
+    set_error(w + ": need 0 <= lsm_weight < 1, 0 <= reverse_weight <= 1 and a vocabulary of at least 2"); return E_ARG;
+  }
+  std::vector<int64_t> tok_off(n_seq), pos_off(n_seq);
+  int64_t nt = 0, np = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    const int L = tok_lens[i];
+    const std::string at = w + ": sequence " + std::to_string(i) + ": ";
+    if (L <= 0) { set_error(at + "empty transcript (L = 0): nothing to score"); return E_ARG; }
+    if (chunk_of[i] < 0 || chunk_of[i] >= B) {
+      set_error(at + "chunk " + std::to_string(chunk_of[i]) + " outside the encoded batch of " + std::to_string(B) + " chunks"); return E_ARG;
+    }
+    for (int k = 0; k < L; ++k) {
+      const int y = tokens[nt + k];
+      if (y < 0 || y >= V) { set_error(at + "token id " + std::to_string(y) + " outside [0, " + std::to_string(V) + ")"); return E_ARG; }
+    }
+    if (L + 1 > e->pe_rows) {
+      set_error(at + std::to_string(L) + " tokens + <eos> are longer than the positional table of " + std::to_string(e->pe_rows) + " rows");
+      return E_UNSUPPORTED;
+    }
+    tok_off[i] = nt; pos_off[i] = np;
+    nt += L; np += L + 1;
+  }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(wait_slices(e, -1));
+  // the sequences in chunk order (build_trie_range walks chunk by chunk); candidates of one chunk share the rows of common prefixes
+  std::vector<int> order(n_seq);
+  for (int i = 0; i < n_seq; ++i) order[i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return chunk_of[a] < chunk_of[b]; });
+  std::vector<HypRef> hyps(n_seq);
+  int P = 0;
+  for (int k = 0; k < n_seq; ++k) { const int i = order[k]; hyps[k] = {chunk_of[i], i, tok_lens[i], P}; P += tok_lens[i] + 1; }
+  std::vector<int32_t> ckv(2 * (size_t)B);
+  for (int b = 0; b < B; ++b) { ckv[b] = b * T2; ckv[B + b] = e->enc_lens[b]; }
+  RVB_TRY(upload_i32(e, e->d_aux_i32, ckv.data(), ckv.size()));
+  const double c = 1.0 - lsm_weight, u = lsm_weight / (double)(V - 1);
+  const double k0 = (c > 0.0 ? c * std::log(c) : 0.0) + (u > 0.0 ? (double)(V - 1) * u * std::log(u) : 0.0);
+  for (int side = 0; side < (use_r ? 2 : 1); ++side) {
+    TrieBatch t;
+    if (side == 0)
+      build_trie_range(hyps.data(), hyps.data() + n_seq, 0, B, sos, eos,
+                       [&](const HypRef& h, int j) { return tokens[tok_off[h.idx] + j]; }, &t);
+    else       // reverse_pad_list + add_sos_eos: the reversed tokens, then <eos>
+      build_trie_range(hyps.data(), hyps.data() + n_seq, 0, B, sos, eos,
+                       [&](const HypRef& h, int j) { return tokens[tok_off[h.idx] + h.len - 1 - j]; }, &t);
+    std::vector<float> slot;
+    XentRows xr;
+    RVB_TRY(decoder_forward(e, side == 0 ? e->dec_l : e->dec_r, t, &slot, &xr));
+    for (int k = 0; k < n_seq; ++k) {
+      const HypRef& h = hyps[k];
+      double loss = 0.0;
+      int correct = 0;
+      for (int j = 0; j <= h.len; ++j) {
+        const int sl = t.pair_slot[h.row0 + j], row = t.path[t.hkv_start[k] + j];
+        const double lp = (double)slot[sl];
+        loss += k0 - c * lp - u * (xr.sum_x[row] - (double)V * (double)xr.lse[row] - lp);
+        correct += xr.top1[row] == t.tgt[sl];
+        if (side == 0) {
+          if (logp_l) logp_l[pos_off[h.idx] + j] = slot[sl];
+          if (top1_l) top1_l[pos_off[h.idx] + j] = xr.top1[row];
+        } else if (logp_r) {
+          logp_r[pos_off[h.idx] + j] = slot[sl];
+        }
+      }
+      if (side == 0) {
+        loss_l[h.idx] = loss;
+        if (n_correct) n_correct[h.idx] = correct;
+        if (n_positions) n_positions[h.idx] = h.len + 1;
+      } else if (loss_r) {
+        loss_r[h.idx] = loss;
+      }
+    }
+  }
+  if (!use_r && loss_r) for (int i = 0; i < n_seq; ++i) loss_r[i] = 0.0;
+  return OK;
 }
 int rvb_attention_decode(rvb_engine* e, int beam, float length_penalty) {
   if (!e) { set_error("rvb_attention_decode: null engine"); return E_ARG; }

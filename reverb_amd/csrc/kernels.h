@@ -150,6 +150,11 @@ int lse_gather(hipStream_t s, const float* logits, int R, int V, int ld, const i
                int blank_id = -1);
 // CSR form for rows with several targets: out[p] = logits[r][target[p]] - lse(r) for p in [ptr[r], ptr[r+1])
 int lse_gather_multi(hipStream_t s, const float* logits, int R, int V, int ld, const int* ptr, const int* target, float* out);
+// the same CSR form with the row statistics of the label-smoothed cross entropy and of the accuracy: logp[p] as lse_gather_multi
+// (the same bits), and per row lse[r], sum_x[r] = sum of the V logits (fp32 lane partials merged in fp64) and top1[r] = arg-max,
+// ties to the lowest index.  A row without targets still writes its three statistics.
+int row_xent(hipStream_t s, const float* logits, int R, int V, int ld, const int* ptr, const int* target, float* logp, float* lse,
+             double* sum_x, int* top1);
 
 // out[i] = table[row[i]][col[i]], fp32 table with ld entries per row
 int gather_pairs(hipStream_t s, const float* table, size_t ld, const int* row, const int* col, int n, float* out);

@@ -3,6 +3,7 @@
 //   logsoftmax_topk   asr/wenet/transformer/ctc.py:106-114, asr_model.py:318-329 (blank penalty),
 //                     search.py:111,155 (torch.topk per frame)
 //   lse_gather        asr_model.py:969 + search.py:417-437 (only the needed log-probs)
+//   row_xent          label_smoothing_loss.py:68-96 + utils/common.py:268-287 (log-probs, lse, sum of logits, arg-max per row)
 // One wave64 per row, 16-byte loads, four vectors per lane in flight.
 //   pass A : online max / sum-exp per lane (merged across the wave at the end) and the maximum of
 //            each lane's slice; the k-th largest of the 64 lane maxima is a lower bound t of the
@@ -214,6 +215,70 @@ int lse_gather_multi(hipStream_t s, const float* logits, int R, int V, int ld, c
   if (R <= 0) return OK;
   hipLaunchKernelGGL(row_lse_kernel<false>, dim3(cdiv(R, 4)), dim3(256), 0, s, logits, R, V, ld, -1, 0.f, -1,
                      (float*)nullptr, const_cast<int*>(ptr), (float*)nullptr, target, out);
+  RVB_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
+// Row statistics of the label-smoothed cross entropy (label_smoothing_loss.py:68-96) and of th_accuracy (utils/common.py:268-287)
+// over the CSR rows of lse_gather_multi, in ONE pass over the row: the online max / sum-exp of row_lse_kernel (the same RowStat calls
+// in the same order, so lse and logp carry the same bits), the sum of the logits (four fp32 partial sums per lane, one per vector of
+// the batch; merged in fp64 within the lane and across the wave) and the arg-max (value descending, ties to the lowest index, which
+// is what torch.argmax returns on the CPU).  The host composes the loss in fp64 from logp, lse and sum_x (engine.hip).
+__global__ __launch_bounds__(256) void row_xent_kernel(const float* __restrict__ logits, int M, int V, int ld,
+                                                       const int* __restrict__ ptr, const int* __restrict__ target,
+                                                       float* __restrict__ logp, float* __restrict__ lse_out,
+                                                       double* __restrict__ sum_out, int* __restrict__ top1_out) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int row = blockIdx.x * 4 + w;
+  if (row >= M) return;
+  RowReader rd;
+  rd.x = logits + (size_t)row * ld; rd.V = V; rd.blank = -1; rd.pen = 0.f;
+  const bool vec = ((ld & 3) == 0) && (((size_t)logits & 15) == 0);
+  rd.nvec = vec ? (V >> 2) : 0;
+  const int tail0 = rd.nvec * 4;
+
+  RowStat st;
+  float ps[UNR + 1] = {0.f, 0.f, 0.f, 0.f, 0.f};     // per vector of the batch; the last one: the scalar path
+  float bv = -INFINITY; int bi = 0x7fffffff;
+  for (int v0 = 0; v0 < rd.nvec; v0 += 64 * UNR) {
+    float e[4 * UNR];
+    rd.load(v0, lane, e);
+    st.add_batch(e, 4 * UNR);
+#pragma unroll
+    for (int u = 0; u < UNR; ++u) {
+      if (v0 + u * 64 + lane < rd.nvec) {              // slots past the row hold -inf: neither summed nor candidates
+        ps[u] += (e[4 * u] + e[4 * u + 1]) + (e[4 * u + 2] + e[4 * u + 3]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const int i = rd.idx(v0, lane, 4 * u + c);
+          if (better(e[4 * u + c], i, bv, bi)) { bv = e[4 * u + c]; bi = i; }
+        }
+      }
+    }
+  }
+  for (int i = tail0 + lane; i < V; i += 64) {
+    float one[4 * UNR];
+    one[0] = rd.tail(i);
+    st.add_batch(one, 1);
+    ps[UNR] += one[0];
+    if (better(one[0], i, bv, bi)) { bv = one[0]; bi = i; }
+  }
+  const float lse = st.wave_lse();
+  double sum = 0.0;
+#pragma unroll
+  for (int u = 0; u <= UNR; ++u) sum += (double)ps[u];
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+  wave_argbest(bv, bi);
+  if (lane == 0) { lse_out[row] = lse; sum_out[row] = sum; top1_out[row] = bi < V ? bi : 0; }   // a row of NaNs has no maximum
+  for (int p = ptr[row] + lane; p < ptr[row + 1]; p += 64) logp[p] = rd.tail(target[p]) - lse;
+}
+
+int row_xent(hipStream_t s, const float* logits, int R, int V, int ld, const int* ptr, const int* target, float* logp, float* lse,
+             double* sum_x, int* top1) {
+  if (R <= 0) return OK;
+  if (V < 1 || ld < V) { set_error("row_xent: need 1 <= V <= ld"); return E_ARG; }
+  hipLaunchKernelGGL(row_xent_kernel, dim3(cdiv(R, 4)), dim3(256), 0, s, logits, R, V, ld, ptr, target, logp, lse, sum_x, top1);
   RVB_HIP_CHECK(hipGetLastError());
   return OK;
 }

@@ -98,6 +98,11 @@ int rvb_test_rownorm_fp8(const float* x, const float* gamma, const float* beta, 
                          float* out, const float* gamma2, const float* beta2, float eps2, float scale2, float* out1_f32, float* out2);
 int rvb_test_lse_gather_multi(const float* logits, int R, int V, const int32_t* ptr /* [R+1] */, const int32_t* target,
                               int P, float* out /* [P] */);
+/* softmax_topk.hip row_xent on host logits [R][ld] (the first V entries of a row count): logp [ptr[R]] as rvb_test_lse_gather_multi,
+ * and per row lse, sum_x (fp64) and top1.  Arguments are checked (RVB_E_ARG: ptr not ascending from 0, a target outside [0, V),
+ * ld < V) before any device work. */
+int rvb_test_row_xent(const float* logits, int R, int V, int ld, const int32_t* ptr /* [R+1] */, const int32_t* target,
+                      float* logp /* [ptr[R]] */, float* lse /* [R] */, double* sum_x /* [R] */, int32_t* top1 /* [R] */);
 /* host only: the trie of distinct hypothesis prefixes attention rescoring computes decoder rows for (engine.hip build_trie) */
 int rvb_test_build_trie(const int32_t* tokens, const int32_t* lens, const int32_t* chunk_of, int n_hyps, int n_chunks, int sos, int eos,
                         int reversed, int32_t* n_rows, int32_t* tok, int32_t* pos, int32_t* path, int32_t* hq_start, int32_t* hq_len,

@@ -656,6 +656,31 @@ int rvb_test_lse_gather_multi(const float* logits, int R, int V, const int32_t* 
   return OK;
 }
 
+int rvb_test_row_xent(const float* logits, int R, int V, int ld, const int32_t* ptr, const int32_t* target, float* logp, float* lse,
+                      double* sum_x, int32_t* top1) {
+  if (!logits || !ptr || !lse || !sum_x || !top1 || R < 1 || V < 1 || ld < V) { set_error("rvb_test_row_xent: null argument, R < 1 or not 1 <= V <= ld"); return E_ARG; }
+  if (ptr[0] != 0) { set_error("rvb_test_row_xent: ptr[0] must be 0"); return E_ARG; }
+  for (int r = 0; r < R; ++r) if (ptr[r + 1] < ptr[r]) { set_error("rvb_test_row_xent: ptr decreases"); return E_ARG; }
+  const int P = ptr[R];
+  if (P > 0 && (!target || !logp)) { set_error("rvb_test_row_xent: targets without target / logp arrays"); return E_ARG; }
+  for (int p = 0; p < P; ++p) if (target[p] < 0 || target[p] >= V) { set_error("rvb_test_row_xent: target outside [0, V)"); return E_ARG; }
+  T_TRY(need_gpu());
+  Dev dl, dp, dt, dlogp, dlse, dsum, dtop;
+  T_TRY(up_raw(dl, logits, (size_t)R * ld * 4));
+  T_TRY(up_raw(dp, ptr, (size_t)(R + 1) * 4));
+  if (P > 0) { T_TRY(up_raw(dt, target, (size_t)P * 4)); } else { T_TRY(dt.alloc(4)); }
+  T_TRY(dlogp.alloc((size_t)(P > 0 ? P : 1) * 4));
+  T_TRY(dlse.alloc((size_t)R * 4)); T_TRY(dsum.alloc((size_t)R * 8)); T_TRY(dtop.alloc((size_t)R * 4));
+  T_TRY(row_xent(nullptr, (const float*)dl.p, R, V, ld, (const int*)dp.p, (const int*)dt.p, (float*)dlogp.p, (float*)dlse.p,
+                 (double*)dsum.p, (int*)dtop.p));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  if (P > 0) RVB_HIP_CHECK(hipMemcpy(logp, dlogp.p, (size_t)P * 4, hipMemcpyDeviceToHost));
+  RVB_HIP_CHECK(hipMemcpy(lse, dlse.p, (size_t)R * 4, hipMemcpyDeviceToHost));
+  RVB_HIP_CHECK(hipMemcpy(sum_x, dsum.p, (size_t)R * 8, hipMemcpyDeviceToHost));
+  RVB_HIP_CHECK(hipMemcpy(top1, dtop.p, (size_t)R * 4, hipMemcpyDeviceToHost));
+  return OK;
+}
+
 // fp8 GEMM of gemm2.hip on host floats: A is quantised per tensor (a_scale), W per output channel, exactly as the engine
 // does; a_deq / w_deq (nullable) receive the values the quantised operands stand for, so that the caller's fp64 reference
 // isolates the kernel from the quantisation.  out_kind 0 bf16, 1 fp32, 2 fp8 (values are returned de-quantised).

@@ -440,11 +440,18 @@ class Engine:
             t0 += n; f0 += frames[i]
         return out
 
-    def score(self, token_seqs, chunk_ranges=None, posteriors=False):
+    def score(self, token_seqs, chunk_ranges=None, posteriors=False, attention=False, reverse_weight=None, lsm_weight=None,
+              ctc_weight=None):
         """Full-sum CTC score (rvb_ctc_score; reference: CTC.forward, transformer/ctc.py:65-104 = -CTCLoss(reduction='sum')) of known
         token sequences against the chunks of the last encode(); sequences and chunk_ranges as in align(), and several sequences
         over the SAME chunks compare candidate transcripts in one launch.  -> List[dict]: loglik (fp64), n_tokens, n_frames and, with
-        posteriors=True, per token occupancy (expected frames), mean_frame, peak_posterior, peak_frame (frames within the sequence)."""
+        posteriors=True, per token occupancy (expected frames), mean_frame, peak_posterior, peak_frame (frames within the sequence).
+        attention=True adds what the reference's bin/get_loss.py reports for the transcript (ASRModel.forward, asr_model.py:105-151,
+        with a batch of one): loss_ctc (= -loglik), loss_att (the decoders' label-smoothed KL, (1 - reverse_weight) left +
+        reverse_weight right, divided by L + 1 when the config's length_normalized_loss is true, else by the batch size 1), acc_att
+        (th_accuracy of the left decoder over the L + 1 positions), loss = ctc_weight loss_ctc + (1 - ctc_weight) loss_att, att_logp
+        (left decoder, log p of each target, <eos> last).  lsm_weight, ctc_weight and reverse_weight
+        default to the config's model_conf.  The decoder's memory is ONE chunk: a sequence over several chunks is refused."""
         seqs = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in token_seqs]
         if chunk_ranges is None:
             chunk_ranges = [(i, 1) for i in range(len(seqs))]
@@ -473,6 +480,62 @@ class Engine:
                          peak_frame=pkf[t0:t0 + n].tolist())
             out.append(r)
             t0 += n
+        if attention:
+            self._attention_score(seqs, first, count, out, reverse_weight, lsm_weight, ctc_weight)
+        return out
+
+    def _attention_score(self, seqs, first, count, out, reverse_weight, lsm_weight, ctc_weight):
+        """rvb_attention_score of the sequences of score(); fills the attention keys into the dicts of `out`."""
+        mc = self.configs.get("model_conf", {})
+        rw = float(mc.get("reverse_weight", 0.0) if reverse_weight is None else reverse_weight)
+        lsm = float(mc.get("lsm_weight", 0.0) if lsm_weight is None else lsm_weight)
+        cw = float(mc.get("ctc_weight", 0.5) if ctc_weight is None else ctc_weight)
+        if np.any(count != 1):
+            raise RvbError("score(attention=True) failed (-5): RVB_E_UNSUPPORTED: a sequence spans several chunks; the attention "
+                           "decoder's memory is one chunk (score each chunk's transcript against its own chunk)")
+        tok = np.ascontiguousarray(np.concatenate(seqs) if sum(map(len, seqs)) else np.zeros(1, np.int32), np.int32)
+        tl = np.array([len(t) for t in seqs], np.int32)
+        n, npos = len(seqs), int(tl.sum()) + len(seqs)
+        loss_l, loss_r = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        ncor, nposn = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        logp = np.zeros(npos, np.float32)
+        check(self.lib.rvb_attention_score(self.handle, iptr(tok), iptr(tl), n, iptr(np.ascontiguousarray(first, np.int32)), rw, lsm,
+                                           dptr(loss_l), dptr(loss_r), iptr(ncor), iptr(nposn), fptr(logp), None, None),
+              "rvb_attention_score")
+        norm_len = bool(mc.get("length_normalized_loss", False))
+        p0 = 0
+        for i, r in enumerate(out):
+            k = int(nposn[i])
+            att = ((1.0 - rw) * float(loss_l[i]) + rw * float(loss_r[i])) / (k if norm_len else 1)
+            r["loss_ctc"] = -r["loglik"]
+            r["loss_att"] = att
+            r["acc_att"] = int(ncor[i]) / k
+            r["loss"] = cw * r["loss_ctc"] + (1.0 - cw) * att
+            r["att_logp"] = logp[p0:p0 + k].tolist()
+            p0 += k
+
+    def attention_score(self, token_seqs, chunk_of, reverse_weight: float = 0.0, lsm_weight: float = 0.0):
+        """rvb_attention_score as it is: per sequence the un-normalised loss sums of both decoders, the correct / total positions and
+        the per-position log-probs (right decoder in its own order) and arg-max.  -> List[dict]."""
+        seqs = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in token_seqs]
+        if not seqs or len(chunk_of) != len(seqs):
+            raise RvbError("attention_score: one chunk per token sequence, at least one sequence")
+        tok = np.ascontiguousarray(np.concatenate(seqs) if sum(map(len, seqs)) else np.zeros(1, np.int32), np.int32)
+        tl = np.array([len(t) for t in seqs], np.int32)
+        ch = np.ascontiguousarray(chunk_of, np.int32)
+        n, npos = len(seqs), max(int(np.maximum(tl, 0).sum()) + len(seqs), 1)
+        loss_l, loss_r = np.zeros(n, np.float64), np.zeros(n, np.float64)
+        ncor, nposn = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        lp_l, lp_r, top = np.zeros(npos, np.float32), np.zeros(npos, np.float32), np.zeros(npos, np.int32)
+        check(self.lib.rvb_attention_score(self.handle, iptr(tok), iptr(tl), n, iptr(ch), float(reverse_weight), float(lsm_weight),
+                                           dptr(loss_l), dptr(loss_r), iptr(ncor), iptr(nposn), fptr(lp_l), fptr(lp_r), iptr(top)),
+              "rvb_attention_score")
+        out, p0 = [], 0
+        for i in range(n):
+            k = int(nposn[i])
+            out.append({"loss_l": float(loss_l[i]), "loss_r": float(loss_r[i]), "n_correct": int(ncor[i]), "n_positions": k,
+                        "logp_l": lp_l[p0:p0 + k].copy(), "logp_r": lp_r[p0:p0 + k].copy(), "top1_l": top[p0:p0 + k].copy()})
+            p0 += k
         return out
 
     def _nbest(self, chunk: int):

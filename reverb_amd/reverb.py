@@ -327,13 +327,17 @@ class ReverbASR:
         return eng, ids, n_chunks
 
     def score(self, audio_file, transcript: Optional[str] = None, tokens=None, verbatimicity: float = 1.0, chunk_size: int = 2051,
-              posteriors: bool = False):
+              posteriors: bool = False, attention: bool = False, reverse_weight: Optional[float] = None):
         """How likely a KNOWN transcript is under the model: the full-sum CTC log-likelihood, the negative of what the reference
         calls loss_ctc (CTC.forward, transformer/ctc.py:65-104; bin/get_loss.py), of the transcript as ONE sequence over the whole
         file, tokenised and encoded exactly as align() does.  -> dict: loglik, n_tokens, n_frames, loglik_per_token, viterbi_score
         (the best single path, from the align call: loglik >= viterbi_score) and, with posteriors=True, per token occupancy
         (expected frames), mean_time (ms, the frame -> ms conversion of align's json) and peak_posterior.  A transcript the frames
-        cannot emit is refused, as by align(); the reference's zero_infinity would report loss 0."""
+        cannot emit is refused, as by align(); the reference's zero_infinity would report loss 0.
+        attention=True adds the other half of the reference's bin/get_loss.py: loss_ctc (= -loglik), loss_att and acc_att of the
+        attention decoders (ASRModel._calc_att_loss, asr_model.py:248-286; reverse_weight defaults to the config's), loss =
+        ctc_weight loss_ctc + (1 - ctc_weight) loss_att and att_logp (left decoder, per target, <eos> last) -- see Engine.score.  The
+        decoder attends to ONE chunk's frames: audio that encodes to more than one chunk raises ValueError."""
         from .ctc_align import posteriors_to_json
         if (transcript is None) == (tokens is None):
             raise ValueError("score: give exactly one of transcript= (text) or tokens= (ids)")
@@ -351,6 +355,13 @@ class ReverbASR:
             per = posteriors_to_json(res, sc, chunk_size, self.input_frame_length, self.output_frame_length)
             for key in ("occupancy", "mean_time", "peak_posterior"):
                 out[key] = [p[key] for p in per]
+        if attention:
+            if n_chunks != 1:
+                raise ValueError(f"score(attention=True): the audio encodes to {n_chunks} chunks of {chunk_size} frames; the attention "
+                                 "decoder's memory is one chunk -- score shorter audio or raise chunk_size")
+            att = eng.score([ids], [(0, 1)], attention=True, reverse_weight=reverse_weight)[0]
+            for key in ("loss_ctc", "loss_att", "acc_att", "loss", "att_logp"):
+                out[key] = att[key]
         return out
 
     def _engine_for_chunk(self, chunk_size: int) -> Engine:

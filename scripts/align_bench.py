@@ -2,7 +2,10 @@
 ONE lattice over all chunks.  Prints one JSON line: wall time of Engine.align per repetition (host clock around a call that ends in a
 device synchronise) and the "ctc_align_lp" / "ctc_viterbi" device times of rvb_get_timing (HIP events; a profiled run of its own).
 
-    python scripts/align_bench.py [--model r640] [--dtype bf16] [--seconds 3600] [--reps 5] [--warmup 2] [--score]
+    python scripts/align_bench.py [--model r640] [--dtype bf16] [--seconds 3600] [--reps 5] [--warmup 2] [--score [--attention]]
+
+--score --attention also times Engine.attention_score: every chunk's own greedy tokens against that chunk, all chunks in one call,
+both decoders (reverse_weight 0.3): the wall time per call and the "lse_gather" device time, which is the row_xent kernel there.
 """
 import argparse
 import json
@@ -23,6 +26,7 @@ def main():
     p.add_argument("--reps", type=int, default=5)
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--score", action="store_true", help="also time Engine.score of the same lattice: ctc_forward / ctc_backward")
+    p.add_argument("--attention", action="store_true", help="with --score: also time Engine.attention_score, one sequence per chunk")
     a = p.parse_args()
     from reverb_amd import synth
     from reverb_amd.engine import Engine
@@ -70,6 +74,27 @@ def main():
                  "ctc_backward_ms": round(bw["ms"] / a.reps, 3), "forward_us_per_frame": round(fw["ms"] / a.reps * 1e3 / T, 3),
                  "backward_us_per_frame": round(bw["ms"] / a.reps * 1e3 / T, 3), "loglik": sc["loglik"],
                  "alpha_rows_bytes": 4 * T * ((2 * len(tokens) + 1 + 31) // 32 * 32)}
+    if a.score and a.attention:
+        per_chunk = [g.tokens for g in eng.greedy()]
+        keep = [b for b, t in enumerate(per_chunk) if t]
+        seqs = [per_chunk[b] for b in keep]
+        eng.set_profiling(False)
+        for _ in range(a.warmup):
+            att = eng.attention_score(seqs, keep, reverse_weight=0.3, lsm_weight=0.1)
+        awall = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            eng.attention_score(seqs, keep, reverse_weight=0.3, lsm_weight=0.1)
+            awall.append((time.perf_counter() - t0) * 1e3)
+        eng.set_profiling(True)
+        eng.reset_timings()
+        for _ in range(a.reps):
+            eng.attention_score(seqs, keep, reverse_weight=0.3, lsm_weight=0.1)
+        rx = eng.timing("lse_gather")
+        npos = sum(r["n_positions"] for r in att)
+        extra.update({"attention_score_wall_ms_median": round(float(np.median(awall)), 2), "attention_positions": npos,
+                      "row_xent_ms": round(rx["ms"] / a.reps, 3), "row_xent_launches": rx["launches"] // a.reps,
+                      "acc_att": sum(r["n_correct"] for r in att) / npos})
     print(json.dumps({"model": a.model, "dtype": a.dtype, "frames": T, "tokens": len(tokens), "states": 2 * len(tokens) + 1,
                       "align_wall_ms": [round(w, 2) for w in wall], "align_wall_ms_median": round(float(np.median(wall)), 2),
                       "ctc_align_lp_ms": round(lp["ms"] / a.reps, 3), "ctc_viterbi_ms": round(vit["ms"] / a.reps, 3),
