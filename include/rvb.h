@@ -225,6 +225,24 @@ int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens,
                   float* score);
 int rvb_ctc_align_limits(int32_t* max_tokens, int32_t* max_frames);
 
+/* rvb_ctc_align for a transcript with GAPS: RVB_CTC_WILDCARD in `tokens` is a position that stands for "some audio that was not
+ * transcribed" (the <star> token of torchaudio's aligner).  It is an ordinary CTC label with an id of its own: it stays, is entered
+ * from the blank before it or from the token two states below, two adjacent wildcards need a blank between them like any repeated
+ * token, it takes AT LEAST ONE frame, and it counts as a token towards the caps and towards frames >= tokens + adjacent repeats.
+ * Its emission at frame t is w[t] + wildcard_bias in fp32, w[t] = the largest log-prob of the frame over all vocab columns, the
+ * blank included: a wildcard frame costs what the model's own greedy path costs there, so a wildcard absorbs speech and silence
+ * alike and never beats a token the model agrees with (it ties; ties go to the first maximum in the order stay, one below, two
+ * below).  wildcard_bias <= 0 (RVB_E_ARG if positive or not finite) is a penalty per wildcard frame in nats: the wildcard is used
+ * only where the transcript misfits by more than that.  A leading / trailing wildcard gives a free start / end.
+ * Arguments, outputs, caps and refusals are those of rvb_ctc_align; `labels` holds RVB_CTC_WILDCARD on a wildcard's frames, its
+ * peak is the frame of its run with the largest w (first on ties) and its confidence exp of that w (without the bias).  With no
+ * wildcard among the tokens every output is bit-identical to rvb_ctc_align's, which itself still refuses the id as outside
+ * [0, vocab).  rvb_ctc_score has no wildcards: a full-sum score of a transcript with gaps is not defined here. */
+#define RVB_CTC_WILDCARD (-2)
+int rvb_ctc_align_wild(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,
+                       const int32_t* n_chunks, float wildcard_bias, int32_t* labels, int32_t* begin, int32_t* end, int32_t* peak,
+                       float* confidence, float* score);
+
 /* Full-sum CTC score of a KNOWN transcript: log p(tokens | frames) summed over every alignment, the quantity the reference calls
  * the CTC loss (CTC.forward, asr/wenet/transformer/ctc.py:65-104 = torch.nn.CTCLoss(reduction='sum') over
  * log_softmax(ctc_lo(encoder_out)), reported by bin/get_loss.py): loglik = -loss.  Valid after rvb_encode / rvb_stream_finish; the

@@ -90,6 +90,7 @@ SIGNATURES = {
     "rvb_get_ctc_topk": (C.c_int, [_eng, _f32p, _i32p]),
     "rvb_ctc_greedy": (C.c_int, [_eng, _i32p, _i32p, _i32p]),
     "rvb_ctc_align": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _f32p, _f32p]),
+    "rvb_ctc_align_wild": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, _i32p, C.c_float, _i32p, _i32p, _i32p, _i32p, _f32p, _f32p]),
     "rvb_ctc_align_limits": (C.c_int, [_i32p, _i32p]),
     "rvb_ctc_score": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, _i32p, _f64p, _f32p, _f32p, _f32p, _i32p]),
     "rvb_ctc_prefix_beam": (C.c_int, [_eng, C.c_int]),
@@ -172,6 +173,7 @@ TEST_SIGNATURES = {
     "rvb_test_logsoftmax_topk": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _f32p, _i32p, _f32p]),
     "rvb_test_lse_gather": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, _f32p]),
     "rvb_test_ctc_viterbi": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _f32p]),
+    "rvb_test_ctc_viterbi_wild": (C.c_int, [_f32p, C.c_int, C.c_int, _f32p, C.c_float, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _f32p]),
     "rvb_test_ctc_score": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, _f64p, _f32p, _f32p, _f32p, _i32p]),
     "rvb_test_ctc_score_batch": (C.c_int, [_f32p, _i32p, C.c_int, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _f64p, _f32p, _f32p, _f32p,
                                            _i32p]),

@@ -2,7 +2,9 @@
 log-softmax, force_align, one `<key> [labels]` line per utterance) for one audio file and its transcript, written as
 `<result_dir>/<audio>.<ctm|ali|json>`.  --score also writes `<result_dir>/<audio>.score.json`: the full-sum CTC log-likelihood of
 the transcript (the reference's bin/get_loss.py reports its negative as loss_ctc); with --attention that file also carries the
-attention decoders' loss_att and acc_att and the combined loss.  Praat .lab / TextGrid output (--gen_praat there) is not written."""
+attention decoders' loss_att and acc_att and the combined loss.  --wildcard TOKEN marks, in the transcript, audio that nobody
+transcribed: the aligner gives each marker the frames the rest of the transcript does not explain (at least one), and the marker
+shows up in the result as a word / label / token of its own.  Praat .lab / TextGrid output (--gen_praat there) is not written."""
 from __future__ import annotations
 
 import argparse
@@ -33,8 +35,17 @@ def get_args(argv=None):
                    help="per-token occupancy, mean_time and peak_posterior in --format json and in the --score file")
     p.add_argument("--attention", action="store_true",
                    help="with --score: also loss_ctc, loss_att, acc_att, loss and att_logp of the attention decoders (audio of one chunk)")
+    p.add_argument("--wildcard", default=None, metavar="TOKEN",
+                   help="a marker in the transcript, such as '<star>', that stands for audio left untranscribed")
+    p.add_argument("--wildcard_bias", type=float, default=0.0,
+                   help="penalty (<= 0, nats per frame) on wildcard frames: the misfit above which a marker is preferred to the transcript")
     p.add_argument("--reverse_weight", type=float, default=None, help="weight of the right-to-left decoder in loss_att (default: the config's)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.wildcard is not None and (args.score or args.posteriors):
+        p.error("--wildcard: the full-sum score (--score, --posteriors) is not defined for a transcript with gaps")
+    if not args.wildcard_bias <= 0:
+        p.error("--wildcard_bias must be <= 0")
+    return args
 
 
 def main(argv=None):
@@ -52,7 +63,8 @@ def main(argv=None):
         transcript = " ".join(f.read().split())
     out = reverb.align(args.audio_file, transcript=transcript, format=args.format, verbatimicity=args.verbatimicity,
                        chunk_size=args.chunk_size, timings_adjustment=args.timings_adjustment,
-                       posteriors=args.posteriors and args.format == "json")
+                       posteriors=args.posteriors and args.format == "json", wildcard=args.wildcard,
+                       wildcard_bias=args.wildcard_bias)
     if args.format == "json":
         out = json.dumps(out, ensure_ascii=False, indent=1)
     os.makedirs(args.result_dir, exist_ok=True)

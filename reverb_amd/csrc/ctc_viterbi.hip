@@ -15,6 +15,15 @@
 // memory latency sits between two barriers.  Back-pointers are 2 bits per cell in HBM (a thread's SPT states = one 1 / 4 / 8 byte store
 // per frame); alpha lives in HBM between launches, so the pass advances slab by slab as the engine produces the log-probs.
 // The back-trace is one lane walking T dependent 1-byte loads.  Every loop is bounded by T or SPT.
+//
+// Wildcards (WILD = true; dispatched only when a sequence of the call holds one): a transcript position with the id
+// RVB_CTC_WILDCARD is an ordinary token state (stay / from its blank / from two below when that token is another label; two
+// adjacent wildcards are the same label) whose emission at frame t is ew = w[row] + bias, w = the row's maximum over all V columns,
+// one fp32 addition.  A per-thread bit mask marks the owned wildcards; ew is one more workgroup-uniform value per frame, loaded
+// with eb from a [rows] array beside the slab and double-buffered with it, and a wildcard takes it in place of its gathered
+// column (whose load, of the blank's column, stays in bounds and is discarded).  The select sits where et[k] is consumed, not
+// where it is refilled: ew then travels exactly as eb does and no step waits for a load it issued itself.  Barriers, LDS,
+// back-pointers and the back-trace are those of the plain form.
 #include "engine.h"
 
 #include <algorithm>
@@ -33,10 +42,11 @@ template <> struct BpWord<4> { typedef uint8_t type; };
 template <> struct BpWord<16> { typedef uint32_t type; };
 template <> struct BpWord<32> { typedef unsigned long long type; };
 
-template <int SPT>
+template <int SPT, bool WILD>
 __global__ __launch_bounds__(1024) void ctc_viterbi_forward_kernel(const VitSeq* __restrict__ seqs, const float* __restrict__ lp, int ld,
                                                                    int r0, const int* __restrict__ rows, const int* __restrict__ tokens,
-                                                                   int blank, float* __restrict__ alpha_all, uint8_t* __restrict__ bp_all) {
+                                                                   int blank, float* __restrict__ alpha_all, uint8_t* __restrict__ bp_all,
+                                                                   const float* __restrict__ wmax, float bias) {
   constexpr int NT = SPT / 2;                      // tokens per thread: local state 2k + 1 is token s0 / 2 + k, even states are blank
   typedef typename BpWord<SPT>::type word_t;
   __shared__ float bnd[2][1024];                   // per thread: alpha of its last state (all a right neighbour reads: its first state is a
@@ -56,6 +66,7 @@ __global__ __launch_bounds__(1024) void ctc_viterbi_forward_kernel(const VitSeq*
 
   unsigned tok[NT];                                // byte offset of each token's column in a row of lp (32 bits: uniform row base + lane offset)
   unsigned skip = 0;                               // bit k: state 2k + 1 may be entered from two states below
+  unsigned wild = 0;                               // bit k: token k is a wildcard (WILD only)
   {
     int prev = (s0 >= 2 && s0 / 2 - 1 < q.L) ? y[s0 / 2 - 1] : -1;
 #pragma unroll
@@ -65,7 +76,8 @@ __global__ __launch_bounds__(1024) void ctc_viterbi_forward_kernel(const VitSeq*
       const int id = have ? y[i] : blank;          // a column that exists, for the states past S - 1
       if (have && i >= 1 && id != prev) skip |= 1u << k;
       prev = id;
-      tok[k] = (unsigned)id * 4u;
+      if (WILD && id == RVB_CTC_WILDCARD) wild |= 1u << k;
+      tok[k] = (unsigned)((WILD && id == RVB_CTC_WILDCARD) ? blank : id) * 4u;   // the wildcard's gather: a column that exists
     }
   }
 
@@ -74,22 +86,24 @@ __global__ __launch_bounds__(1024) void ctc_viterbi_forward_kernel(const VitSeq*
   // refills each register right after its use with the emission two frames on: loads stay in flight across two barriers and
   // nothing is copied.  Rows past the last frame of this launch are clamped to it (a harmless in-bounds load).
   float ebA, etA[NT], ebB, etB[NT];
+  float ewA = 0.f, ewB = 0.f;                      // WILD: the wildcard's emission of the frame, buffered with eb
   int f = q.f0;
   auto row_of = [&](int fr) { return rw[min(fr, q.f1 - 1)] - r0; };
-  auto fill = [&](float& eb, float* et, int r) {
+  auto fill = [&](float& eb, float& ew, float* et, int r) {
     const char* row = (const char*)(lp + (size_t)r * ld);
     eb = *(const float*)(row + (unsigned)blank * 4u);
+    if (WILD) ew = wmax[r] + bias;
 #pragma unroll
     for (int k = 0; k < NT; ++k) et[k] = *(const float*)(row + tok[k]);
   };
   constexpr bool TWO = SPT < 32;                   // 32 states per thread: one buffer (refilled one frame ahead) is what fits 128 VGPRs
   constexpr int D = TWO ? 2 : 1;                   // frames between a register's use and the use of its refill
-  fill(ebA, etA, row_of(f));
-  if (TWO) fill(ebB, etB, row_of(f + 1));
+  fill(ebA, ewA, etA, row_of(f));
+  if (TWO) fill(ebB, ewB, etB, row_of(f + 1));
   int rA = row_of(f + D), rB = row_of(f + D + 1);  // the rows the next refill of A / B reads, fetched ahead of their use
   int par = 0;
 
-  auto step = [&](float& eb, float* et, int fr, int refill_row) {
+  auto step = [&](float& eb, float& ew, float* et, int fr, int refill_row) {
     const char* row = (const char*)(lp + (size_t)refill_row * ld);
     const float left = tid > 0 ? bnd[par][tid - 1] : NEG;
     word_t codes = 0;
@@ -102,7 +116,9 @@ __global__ __launch_bounds__(1024) void ctc_viterbi_forward_kernel(const VitSeq*
       if (j & 1) {
         const float c2 = j >= 2 ? a[j - 2] : left;
         if (((skip >> (j >> 1)) & 1u) && c2 > best) { best = c2; code = 2; }
-        a[j] = best + et[j >> 1];                  // states past S - 1 hold junk that no real state reads (predecessors lie below)
+        // states past S - 1 hold junk that no real state reads (predecessors lie below)
+        if (WILD) a[j] = best + (((wild >> (j >> 1)) & 1u) ? ew : et[j >> 1]);
+        else a[j] = best + et[j >> 1];
         et[j >> 1] = *(const float*)(row + tok[j >> 1]);
       } else {
         a[j] = best + eb;
@@ -110,6 +126,7 @@ __global__ __launch_bounds__(1024) void ctc_viterbi_forward_kernel(const VitSeq*
       codes |= (word_t)code << (2 * j);
     }
     eb = *(const float*)(row + (unsigned)blank * 4u);
+    if (WILD) ew = wmax[refill_row] + bias;
     if (nvalid > 0) bp[(size_t)fr * bp_stride] = codes;
     par ^= 1;
     bnd[par][tid] = a[SPT - 1];
@@ -119,8 +136,8 @@ __global__ __launch_bounds__(1024) void ctc_viterbi_forward_kernel(const VitSeq*
   if (f == 0) {
 #pragma unroll
     for (int j = 0; j < SPT; ++j) a[j] = NEG;
-    if (tid == 0) { a[0] = ebA; a[1] = etA[0]; }
-    fill(ebA, etA, rA);
+    if (tid == 0) { a[0] = ebA; a[1] = (WILD && (wild & 1u)) ? ewA : etA[0]; }
+    fill(ebA, ewA, etA, rA);
     rA = row_of(f + 2 * D);
   } else {
 #pragma unroll
@@ -131,19 +148,19 @@ __global__ __launch_bounds__(1024) void ctc_viterbi_forward_kernel(const VitSeq*
   if (TWO) {
     if (f == 0) {
       f = 1;
-      if (f < q.f1) { step(ebB, etB, f, rB); rB = row_of(f + 4); ++f; }
+      if (f < q.f1) { step(ebB, ewB, etB, f, rB); rB = row_of(f + 4); ++f; }
     }
     for (; f + 1 < q.f1; f += 2) {
-      step(ebA, etA, f, rA);
+      step(ebA, ewA, etA, f, rA);
       rA = row_of(f + 4);
-      step(ebB, etB, f + 1, rB);
+      step(ebB, ewB, etB, f + 1, rB);
       rB = row_of(f + 5);
     }
-    if (f < q.f1) step(ebA, etA, f, rA);
+    if (f < q.f1) step(ebA, ewA, etA, f, rA);
   } else {
     if (f == 0) f = 1;
     for (; f < q.f1; ++f) {
-      step(ebA, etA, f, rA);
+      step(ebA, ewA, etA, f, rA);
       rA = row_of(f + 2);
     }
   }
@@ -176,14 +193,22 @@ int spt_for(int S) { return S <= 4096 ? 4 : S <= 16384 ? 16 : 32; }
 }  // namespace
 
 int ctc_viterbi_forward(hipStream_t s, const VitSeq* seqs, int n_seq, int max_S, const float* lp, int ld, int r0, const int* rows,
-                        const int* tokens, int blank, float* alpha, uint8_t* bp) {
+                        const int* tokens, int blank, float* alpha, uint8_t* bp, const float* wmax, float bias) {
   if (n_seq <= 0) return OK;
   if (max_S < 3 || max_S > CTC_ALIGN_MAX_STATES) { set_error("ctc_viterbi_forward: states out of range"); return E_ARG; }
   const int spt = spt_for(max_S);
   const int threads = std::min(1024, ((max_S + spt - 1) / spt + 63) / 64 * 64);
-  if (spt == 4) ctc_viterbi_forward_kernel<4><<<n_seq, threads, 0, s>>>(seqs, lp, ld, r0, rows, tokens, blank, alpha, bp);
-  else if (spt == 16) ctc_viterbi_forward_kernel<16><<<n_seq, threads, 0, s>>>(seqs, lp, ld, r0, rows, tokens, blank, alpha, bp);
-  else ctc_viterbi_forward_kernel<32><<<n_seq, threads, 0, s>>>(seqs, lp, ld, r0, rows, tokens, blank, alpha, bp);
+#define RVB_VIT_(SPT, WILD) ctc_viterbi_forward_kernel<SPT, WILD><<<n_seq, threads, 0, s>>>(seqs, lp, ld, r0, rows, tokens, blank, alpha, bp, wmax, bias)
+  if (wmax) {                                      // some sequence of the call holds a wildcard
+    if (spt == 4) RVB_VIT_(4, true);
+    else if (spt == 16) RVB_VIT_(16, true);
+    else RVB_VIT_(32, true);
+  } else {
+    if (spt == 4) RVB_VIT_(4, false);
+    else if (spt == 16) RVB_VIT_(16, false);
+    else RVB_VIT_(32, false);
+  }
+#undef RVB_VIT_
   RVB_HIP_CHECK(hipGetLastError());
   return OK;
 }
@@ -197,13 +222,13 @@ int ctc_viterbi_backtrace(hipStream_t s, const VitSeq* seqs, int n_seq, const fl
 
 // ------------------------------------------------------------------------------------ host driver (engine + lab hook)
 int CtcAligner::plan(const char* who, const int32_t* tokens, const int32_t* tok_lens, int n_seq,
-                     const std::vector<std::vector<int32_t>>& seq_rows, int V, int blank_id) {
+                     const std::vector<std::vector<int32_t>>& seq_rows, int V, int blank_id, bool allow_wild) {
   const std::string w(who);
   if (!tokens || !tok_lens || n_seq <= 0 || (int)seq_rows.size() != n_seq) { set_error(w + ": null argument or no sequence"); return E_ARG; }
   if (V < 2 || blank_id < 0 || blank_id >= V) { set_error(w + ": blank id outside [0, V)"); return E_ARG; }
   seq.assign(n_seq, VitSeq{});
   h_tokens.clear(); h_rows.clear();
-  max_S = 0; blank = blank_id;
+  max_S = 0; blank = blank_id; has_wild = false;
   size_t alpha_off = 0, bp_off = 0;
   int64_t tok_off = 0, frame_off = 0;
   for (int i = 0; i < n_seq; ++i) {
@@ -223,6 +248,7 @@ int CtcAligner::plan(const char* who, const int32_t* tokens, const int32_t* tok_
     const int32_t* y = tokens + tok_off;
     int repeats = 0;
     for (int k = 0; k < L; ++k) {
+      if (allow_wild && y[k] == RVB_CTC_WILDCARD) { has_wild = true; if (k && y[k - 1] == y[k]) ++repeats; continue; }
       if (y[k] < 0 || y[k] >= V) { set_error(at + "token id " + std::to_string(y[k]) + " outside [0, " + std::to_string(V) + ")"); return E_ARG; }
       if (y[k] == blank_id) { set_error(at + "token " + std::to_string(k) + " is the blank id " + std::to_string(blank_id)); return E_ARG; }
       if (k && y[k] == y[k - 1]) ++repeats;
@@ -278,7 +304,8 @@ bool CtcAligner::touches(int r0, int nrows) const {
   return false;
 }
 
-int CtcAligner::advance(hipStream_t s, const float* lp, int ld, int r0, int nrows) {
+int CtcAligner::advance(hipStream_t s, const float* lp, int ld, int r0, int nrows, const float* wmax, float bias) {
+  if (has_wild && !wmax) { set_error("ctc align: a transcript with wildcards needs the row maxima"); return E_ARG; }
   bool any = false;
   for (auto& q : seq) {
     const int32_t* rw = h_rows.data() + q.frame_off;
@@ -292,7 +319,7 @@ int CtcAligner::advance(hipStream_t s, const float* lp, int ld, int r0, int nrow
   RVB_HIP_CHECK(hipStreamSynchronize(s));
   RVB_HIP_CHECK(hipMemcpy(d_seqs.p, seq.data(), seq.size() * sizeof(VitSeq), hipMemcpyHostToDevice));
   return ctc_viterbi_forward(s, d_seqs.as<VitSeq>(), (int)seq.size(), max_S, lp, ld, r0, d_rows.as<int>(), d_tokens.as<int>(), blank,
-                             d_alpha.as<float>(), d_bp.as<uint8_t>());
+                             d_alpha.as<float>(), d_bp.as<uint8_t>(), has_wild ? wmax : nullptr, bias);
 }
 
 int CtcAligner::finish(hipStream_t s, int32_t* states, float* score) {

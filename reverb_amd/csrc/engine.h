@@ -142,19 +142,22 @@ struct TrieBatch {
 // ---- forced alignment (ctc_viterbi.hip): the host side of a batch of lattices, shared by rvb_ctc_align and the lab hook.
 // plan() validates and lays out (no device work), begin() allocates and uploads, advance() runs the forward kernel over the frames
 // whose rows lie in the slab just computed (slabs in row order), finish() back-traces and returns states and scores.
+// With allow_wild, plan() accepts RVB_CTC_WILDCARD as a token (a label of its own: it counts towards the caps and, next to another
+// wildcard, as a repeat); advance() then needs wmax[nrows], the maximum of each row of the slab, and the per-frame bias <= 0.
 struct CtcAligner {
   std::vector<VitSeq> seq;
   std::vector<int32_t> h_tokens, h_rows;
   int max_S = 0, blank = 0;
+  bool has_wild = false;                           // some sequence of the plan holds a wildcard: the WILD kernels run
   size_t alpha_floats = 0, bp_bytes = 0;
   int64_t total_frames = 0;
   DevBuf d_tokens, d_rows, d_seqs, d_alpha, d_bp, d_states, d_score;
   // seq_rows[i][f]: the (increasing) log-prob row of frame f of sequence i
   int plan(const char* who, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const std::vector<std::vector<int32_t>>& seq_rows,
-           int V, int blank_id);
+           int V, int blank_id, bool allow_wild = false);
   int begin(hipStream_t s);
   bool touches(int r0, int nrows) const;
-  int advance(hipStream_t s, const float* lp, int ld, int r0, int nrows);
+  int advance(hipStream_t s, const float* lp, int ld, int r0, int nrows, const float* wmax = nullptr, float bias = 0.f);
   int finish(hipStream_t s, int32_t* states /* [total_frames] */, float* score /* [n_seq] */);
   void release();
 };

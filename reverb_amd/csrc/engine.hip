@@ -2376,17 +2376,23 @@ int rvb_ctc_align_limits(int32_t* max_tokens, int32_t* max_frames) {
   return OK;
 }
 
-int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,
-                  const int32_t* n_chunks, int32_t* labels, int32_t* begin, int32_t* end, int32_t* peak, float* confidence, float* score) {
+// rvb_ctc_align (wild = false: RVB_CTC_WILDCARD is an id outside the vocabulary) and rvb_ctc_align_wild.  A wildcard emits the row's
+// top-1 log-prob, which align_slab already produces: align_tv[r] = max logit - lse and lp[r][v] = logit[v] - lse are the same fp32
+// subtraction (softmax_topk.hip), so align_tv[r] IS the maximum of the lp row the aligner reads, bit for bit.
+static int ctc_align_impl(const char* who, bool wild, float bias, rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq,
+                          const int32_t* first_chunk, const int32_t* n_chunks, int32_t* labels, int32_t* begin, int32_t* end,
+                          int32_t* peak, float* confidence, float* score) {
   static_assert(CTC_ALIGN_MAX_TOKENS == RVB_CTC_ALIGN_MAX_TOKENS && CTC_ALIGN_MAX_FRAMES == RVB_CTC_ALIGN_MAX_FRAMES, "caps of rvb.h");
-  if (!e) { set_error("rvb_ctc_align: null engine"); return E_ARG; }
-  if (!tokens || !tok_lens || !first_chunk || !n_chunks || n_seq <= 0) { set_error("rvb_ctc_align: null argument or n_seq <= 0"); return E_ARG; }
-  if (e->B <= 0) { set_error("rvb_ctc_align before rvb_encode"); return E_STATE; }
+  const std::string w(who);
+  if (!e) { set_error(w + ": null engine"); return E_ARG; }
+  if (!tokens || !tok_lens || !first_chunk || !n_chunks || n_seq <= 0) { set_error(w + ": null argument or n_seq <= 0"); return E_ARG; }
+  if (wild && !(std::isfinite(bias) && bias <= 0.f)) { set_error(w + ": wildcard_bias must be finite and <= 0"); return E_ARG; }
+  if (e->B <= 0) { set_error(w + " before rvb_encode"); return E_STATE; }
   const int T = e->T2, V = e->cfg.vocab, blank = e->cfg.blank_id, M = e->B * T;
   std::vector<std::vector<int32_t>> seq_rows;
-  RVB_TRY(align_seq_rows(e, "rvb_ctc_align", first_chunk, n_chunks, n_seq, &seq_rows));
+  RVB_TRY(align_seq_rows(e, who, first_chunk, n_chunks, n_seq, &seq_rows));
   CtcAligner& al = e->aligner;
-  RVB_TRY(al.plan("rvb_ctc_align", tokens, tok_lens, n_seq, seq_rows, V, blank));
+  RVB_TRY(al.plan(who, tokens, tok_lens, n_seq, seq_rows, V, blank, wild));
   RVB_HIP_CHECK(hipSetDevice(e->device));
   RVB_TRY(wait_slices(e, -1));
   RVB_TRY(align_workspace(e));
@@ -2396,7 +2402,7 @@ int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens,
     if (!al.touches(r0, rows)) continue;
     RVB_TRY(align_slab(e, r0, rows));
     Scope sc(e, "ctc_viterbi");
-    RVB_TRY(al.advance(e->stream, e->align_lp.as<float>(), V, r0, rows));
+    RVB_TRY(al.advance(e->stream, e->align_lp.as<float>(), V, r0, rows, e->align_tv.as<float>(), bias));
   }
   std::vector<int32_t> states((size_t)al.total_frames);
   std::vector<float> sc_host(n_seq);
@@ -2410,7 +2416,7 @@ int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens,
     const VitSeq& q = al.seq[i];
     for (int t = 0; t < q.T; ++t) {
       const int st = states[q.frame_off + t];
-      lab[q.frame_off + t] = (st & 1) ? tokens[q.tok_off + (st >> 1)] : blank;
+      lab[q.frame_off + t] = (st & 1) ? tokens[q.tok_off + (st >> 1)] : blank;   // a wildcard's state: RVB_CTC_WILDCARD
     }
   }
   if (labels) memcpy(labels, lab.data(), lab.size() * 4);
@@ -2420,14 +2426,15 @@ int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens,
     // lp[t][label[t]] of every frame: the slabs once more, one gather_pairs per slab
     emit.resize(lab.size());
     std::vector<int32_t> grow, gcol, gidx;
-    std::vector<float> gout;
+    std::vector<float> gout, wrow;                        // wrow: the slab's row maxima, what a wildcard frame emitted less the bias
     for (const auto& [r0, rows] : slabs) {
       grow.clear(); gcol.clear(); gidx.clear();
       for (int i = 0; i < n_seq; ++i) {
         const VitSeq& q = al.seq[i];
         const int32_t* rw = al.h_rows.data() + q.frame_off;
         for (int f = (int)(std::lower_bound(rw, rw + q.T, r0) - rw); f < q.T && rw[f] < r0 + rows; ++f) {
-          grow.push_back(rw[f] - r0); gcol.push_back(lab[q.frame_off + f]); gidx.push_back(q.frame_off + f);
+          const int32_t l = lab[q.frame_off + f];
+          grow.push_back(rw[f] - r0); gcol.push_back(l == RVB_CTC_WILDCARD ? blank : l); gidx.push_back(q.frame_off + f);
         }
       }
       if (grow.empty()) continue;
@@ -2439,8 +2446,12 @@ int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens,
                            e->align_out.as<float>()));
       gout.resize(grow.size());
       RVB_HIP_CHECK(hipMemcpyAsync(gout.data(), e->align_out.p, grow.size() * 4, hipMemcpyDeviceToHost, e->stream));
+      if (al.has_wild) {
+        wrow.resize(rows);
+        RVB_HIP_CHECK(hipMemcpyAsync(wrow.data(), e->align_tv.p, (size_t)rows * 4, hipMemcpyDeviceToHost, e->stream));
+      }
       RVB_HIP_CHECK(hipStreamSynchronize(e->stream));     // also: grow / gcol may be rewritten
-      for (size_t k = 0; k < gidx.size(); ++k) emit[gidx[k]] = gout[k];
+      for (size_t k = 0; k < gidx.size(); ++k) emit[gidx[k]] = lab[gidx[k]] == RVB_CTC_WILDCARD ? wrow[grow[k]] : gout[k];
     }
   }
   for (int i = 0; i < n_seq; ++i) {
@@ -2464,6 +2475,18 @@ int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens,
     }
   }
   return OK;
+}
+
+int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,
+                  const int32_t* n_chunks, int32_t* labels, int32_t* begin, int32_t* end, int32_t* peak, float* confidence, float* score) {
+  return ctc_align_impl("rvb_ctc_align", false, 0.f, e, tokens, tok_lens, n_seq, first_chunk, n_chunks, labels, begin, end, peak,
+                        confidence, score);
+}
+int rvb_ctc_align_wild(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,
+                       const int32_t* n_chunks, float wildcard_bias, int32_t* labels, int32_t* begin, int32_t* end, int32_t* peak,
+                       float* confidence, float* score) {
+  return ctc_align_impl("rvb_ctc_align_wild", true, wildcard_bias, e, tokens, tok_lens, n_seq, first_chunk, n_chunks, labels, begin,
+                        end, peak, confidence, score);
 }
 
 // Full-sum score (CTC.forward, transformer/ctc.py:65-104) over the same slabs: a forward sweep, and for per-token outputs the slabs

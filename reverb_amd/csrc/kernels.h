@@ -186,8 +186,9 @@ struct VitSeq {            // one lattice of a batch, as the kernels read it
 };
 // advances every lattice over its frames [f0, f1): frame f reads row rows[frame_off + f] - r0 of lp ([.., ld] fp32 log-probs);
 // bp receives the back-pointers (0 / 1 / 2 states down), alpha the last frame's scores.  max_S selects the instantiation.
+// wmax non-null selects the wildcard form: a token RVB_CTC_WILDCARD emits wmax[row - r0] + bias (wmax: the maximum of each lp row).
 int ctc_viterbi_forward(hipStream_t s, const VitSeq* seqs, int n_seq, int max_S, const float* lp, int ld, int r0, const int* rows,
-                        const int* tokens, int blank, float* alpha, uint8_t* bp);
+                        const int* tokens, int blank, float* alpha, uint8_t* bp, const float* wmax = nullptr, float bias = 0.f);
 // states[frame_off + t] = state of frame t on the best path, score[i] = its fp32 score (-inf: no path)
 int ctc_viterbi_backtrace(hipStream_t s, const VitSeq* seqs, int n_seq, const float* alpha, const uint8_t* bp, int* states, float* score);
 

@@ -116,6 +116,11 @@ int rvb_test_host_pool(int n_threads, int items, int rounds);
  * emit, sizes above the caps of include/rvb.h. */
 int rvb_test_ctc_viterbi(const float* lp, int T, int V, const int32_t* tokens, int L, int blank, int slab_rows, int32_t* labels_out,
                          float* score_out);
+/* the same with wildcards (the kernels rvb_ctc_align_wild runs): tokens may hold RVB_CTC_WILDCARD, which emits w[t] + bias at frame t
+ * (w [T] host-supplied: the tests pass the row maxima of lp) and appears as RVB_CTC_WILDCARD in labels_out.  Refuses what
+ * rvb_test_ctc_viterbi refuses, and a bias that is positive or not finite, before any device work; outputs untouched. */
+int rvb_test_ctc_viterbi_wild(const float* lp, int T, int V, const float* w, float bias, const int32_t* tokens, int L, int blank,
+                              int slab_rows, int32_t* labels_out, float* score_out);
 /* ctc_forward_backward.hip: full-sum score of tokens[L] over host log-probs lp [T][V] with the kernels rvb_ctc_score runs, advancing
  * slab_rows frames per launch in both sweeps (forward ascending, backward descending from the last frame).  loglik_out is fp64; the
  * four per-token outputs [L] are nullable, and with all four null only the forward sweep runs.  Refuses what rvb_test_ctc_viterbi

@@ -553,30 +553,45 @@ int rvb_test_logsoftmax_topk(const float* logits, int M, int V, int k, float bla
   return OK;
 }
 
-int rvb_test_ctc_viterbi(const float* lp, int T, int V, const int32_t* tokens, int L, int blank, int slab_rows, int32_t* labels_out,
-                         float* score_out) {
-  if (!lp || !tokens || !labels_out || !score_out) { set_error("rvb_test_ctc_viterbi: null argument"); return E_ARG; }
-  if (T < 1 || slab_rows < 1) { set_error("rvb_test_ctc_viterbi: need T >= 1 and slab_rows >= 1"); return E_ARG; }
+static int ctc_viterbi_lab(const char* who, bool wild, const float* lp, int T, int V, const float* w, float bias, const int32_t* tokens,
+                           int L, int blank, int slab_rows, int32_t* labels_out, float* score_out) {
+  const std::string me(who);
+  if (!lp || !tokens || !labels_out || !score_out || (wild && !w)) { set_error(me + ": null argument"); return E_ARG; }
+  if (T < 1 || slab_rows < 1) { set_error(me + ": need T >= 1 and slab_rows >= 1"); return E_ARG; }
+  if (wild && !(std::isfinite(bias) && bias <= 0.f)) { set_error(me + ": wildcard bias must be finite and <= 0"); return E_ARG; }
   CtcAligner al;
   std::vector<std::vector<int32_t>> rows(1);
   if (T <= CTC_ALIGN_MAX_FRAMES) { rows[0].resize(T); for (int t = 0; t < T; ++t) rows[0][t] = t; }
   else rows[0].resize((size_t)T);           // over the cap: plan() refuses on the count alone
-  T_TRY(al.plan("rvb_test_ctc_viterbi", tokens, &L, 1, rows, V, blank));
+  T_TRY(al.plan(who, tokens, &L, 1, rows, V, blank, wild));
   T_TRY(need_gpu());
-  Dev dlp;
+  Dev dlp, dw;
   int r = up_raw(dlp, lp, (size_t)T * V * 4);
+  if (r == OK && wild) r = up_raw(dw, w, (size_t)T * 4);
   if (r == OK) r = al.begin(nullptr);
   for (int r0 = 0; r == OK && r0 < T; r0 += slab_rows) {
     const int n = std::min(slab_rows, T - r0);
-    r = al.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, n);
+    r = al.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, n, wild ? (const float*)dw.p + r0 : nullptr, bias);
   }
   std::vector<int32_t> states((size_t)T);
-  if (r == OK) r = al.finish(nullptr, states.data(), score_out);
+  float score = 0.f;
+  if (r == OK) r = al.finish(nullptr, states.data(), &score);
   if (r != OK) (void)hipDeviceSynchronize();
   al.release();
   if (r != OK) return r;
+  *score_out = score;
   for (int t = 0; t < T; ++t) labels_out[t] = (states[t] & 1) ? tokens[states[t] >> 1] : blank;
   return OK;
+}
+
+int rvb_test_ctc_viterbi(const float* lp, int T, int V, const int32_t* tokens, int L, int blank, int slab_rows, int32_t* labels_out,
+                         float* score_out) {
+  return ctc_viterbi_lab("rvb_test_ctc_viterbi", false, lp, T, V, nullptr, 0.f, tokens, L, blank, slab_rows, labels_out, score_out);
+}
+
+int rvb_test_ctc_viterbi_wild(const float* lp, int T, int V, const float* w, float bias, const int32_t* tokens, int L, int blank,
+                              int slab_rows, int32_t* labels_out, float* score_out) {
+  return ctc_viterbi_lab("rvb_test_ctc_viterbi_wild", true, lp, T, V, w, bias, tokens, L, blank, slab_rows, labels_out, score_out);
 }
 
 static int ctc_score_lab(const char* who, const float* lp, const int32_t* T, int V, const int32_t* tokens, const int32_t* L, int n_seq,

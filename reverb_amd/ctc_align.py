@@ -10,6 +10,9 @@ by the reference-generated known answer C2 of SURVEY.md Appendix C (tests/test_h
     is closer than 100 ms, then at the midpoint frame; it ends at its last token's frame, or at the
     midpoint to the next token when that one is closer than 100 ms;
   * word confidence is the maximum of its tokens' confidences (0 when none are given).
+
+Forced alignment with gaps (Engine.align_wild): a token with the id WILDCARD stands for audio the transcript leaves out.  It is a
+word of its own with the caller's marker as its text, it ends the word before it, and its times are those of its run of frames.
 """
 from __future__ import annotations
 
@@ -18,6 +21,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 SPACE_MARK = "▁"
 GAP_MS = 100
+WILDCARD = -2          # RVB_CTC_WILDCARD of include/rvb.h
 
 
 def piece_of(token_id: int, tokenizer) -> str:
@@ -34,20 +38,33 @@ def _blank_word(text: str) -> bool:
 
 
 def ctc_align(hypothesis: Sequence[int], time_stamp: Sequence[int], confidence_scores: Optional[Sequence[float]],
-              tokenizer, frame_shift_ms: int, time_shift_ms: int) -> List[Dict[str, Any]]:
+              tokenizer, frame_shift_ms: int, time_shift_ms: int, wildcard: Optional[str] = None,
+              end_stamp: Optional[Sequence[int]] = None) -> List[Dict[str, Any]]:
+    """`wildcard` (the marker text) and `end_stamp` (last frame of each token's run) are needed only when `hypothesis` holds
+    WILDCARD ids: such a token becomes the word `wildcard` from its first frame to the end of its last one, the word before it
+    ends at its own last token, and the word after it does not start before the wildcard ends."""
     assert len(hypothesis) == len(time_stamp)
     n = len(hypothesis)
-    pieces = [piece_of(t, tokenizer) for t in hypothesis]
+    wild = [t == WILDCARD for t in hypothesis]
+    if any(wild):
+        assert wildcard and end_stamp is not None and len(end_stamp) == n
+    pieces = [wildcard if w else piece_of(t, tokenizer) for t, w in zip(hypothesis, wild)]
 
     def begin_ms(i: int) -> int:
+        if wild[i]:
+            return time_stamp[i] * frame_shift_ms
         ms = max(time_stamp[i] * frame_shift_ms - GAP_MS, 0)
+        if i > 0 and wild[i - 1]:
+            return max(ms, (end_stamp[i - 1] + 1) * frame_shift_ms)
         if i > 0 and (time_stamp[i] - time_stamp[i - 1]) * frame_shift_ms < GAP_MS:
             ms = (time_stamp[i - 1] + time_stamp[i]) // 2 * frame_shift_ms
         return ms
 
     def finish_ms(i: int) -> int:
+        if wild[i]:
+            return (end_stamp[i] + 1) * frame_shift_ms
         ms = time_stamp[i] * frame_shift_ms
-        if i < n - 1 and (time_stamp[i + 1] - time_stamp[i]) * frame_shift_ms < GAP_MS:
+        if i < n - 1 and not wild[i + 1] and (time_stamp[i + 1] - time_stamp[i]) * frame_shift_ms < GAP_MS:
             ms = (time_stamp[i + 1] + time_stamp[i]) // 2 * frame_shift_ms
         return ms
 
@@ -58,6 +75,11 @@ def ctc_align(hypothesis: Sequence[int], time_stamp: Sequence[int], confidence_s
     text, ids, t_begin, first_tok = "", [], -1, -1
     for i, piece in enumerate(pieces):
         following = pieces[i + 1] if i + 1 < n else SPACE_MARK
+        if wild[i]:                                                 # a word of its own, whatever the marker looks like
+            assert text == ""
+            words.append({"word": piece, "unit_id": WILDCARD, "start_time_ms": begin_ms(i) + time_shift_ms,
+                          "end_time_ms": finish_ms(i) + time_shift_ms, "confidence": best_conf(i, i), "unit_ids": [WILDCARD]})
+            continue
         text += piece[len(SPACE_MARK):] if SPACE_MARK in piece else piece
         ids.append(hypothesis[i])
         if t_begin == -1:
@@ -72,7 +94,7 @@ def ctc_align(hypothesis: Sequence[int], time_stamp: Sequence[int], confidence_s
                           "unit_ids": ids})
             text, ids, t_begin, first_tok = "", [], -1, 0
 
-        if SPACE_MARK in following or _looks_special(following):    # next piece opens a new word
+        if SPACE_MARK in following or _looks_special(following) or (i + 1 < n and wild[i + 1]):    # next piece opens a new word
             t_end = finish_ms(i)
             if not _blank_word(text):
                 assert len(ids) > 0
@@ -136,6 +158,11 @@ class AlignResult:
     first_chunk: int = 0
     chunk_lens: List[int] = field(default_factory=list)
 
+    @property
+    def wildcard(self) -> List[bool]:
+        """per token: it is a wildcard (Engine.align_wild); its frames carry WILDCARD in `labels`"""
+        return [int(t) == WILDCARD for t in self.tokens]
+
     def chunk_frame(self, frame: int) -> Tuple[int, int]:
         """sequence frame -> (chunk index in the encoded batch, frame inside that chunk)"""
         if frame < 0:
@@ -154,34 +181,65 @@ class DecodeLike:
     times: List[int]
     tokens_confidence: List[float]
     ctc_frames: Optional[List[int]] = None
+    ends: Optional[List[int]] = None          # last frame of each token's run: what a wildcard's word ends at
 
 
-def split_by_chunk(res: AlignResult):
+def split_by_chunk(res: AlignResult, ends: bool = False):
     """The aligned tokens as one (tokens, times, tokens_confidence) triple per chunk of the sequence, a token going to the chunk
     its `begin` frame lies in, times = begin frames relative to that chunk: what `get_output` takes from a DecodeResult per chunk
-    (the first frame of a token's run is also what ctc_greedy_search stamps a token with)."""
-    parts = [([], [], []) for _ in res.chunk_lens]
-    for tok, b, conf in zip(res.tokens, res.begin, res.confidence):
-        c, t = res.chunk_frame(b)
-        part = parts[c - res.first_chunk]
-        part[0].append(int(tok)); part[1].append(int(t)); part[2].append(float(conf))
-    return parts
+    (the first frame of a token's run is also what ctc_greedy_search stamps a token with).  ends=True adds a fourth list, the last
+    frames alike.  A wildcard whose run crosses into further chunks appears once in each of them, with the frames it has there."""
+    parts = [([], [], [], []) for _ in res.chunk_lens]
+    for tok, b, e, conf in zip(res.tokens, res.begin, res.end, res.confidence):
+        while True:
+            c, t = res.chunk_frame(b)
+            part = parts[c - res.first_chunk]
+            last = t + (e - b)
+            room = res.chunk_lens[c - res.first_chunk] - 1
+            part[0].append(int(tok)); part[1].append(int(t)); part[2].append(float(conf)); part[3].append(int(min(last, room)))
+            if int(tok) != WILDCARD or last <= room:
+                break
+            b += room - t + 1
+    return parts if ends else [p[:3] for p in parts]
 
 
-def align_to_ali(audio_name: str, res: AlignResult) -> str:
-    """The reference's result line: `<key> [label, label, ...]` (asr/wenet/bin/alignment.py:242)."""
-    return "{} {}".format(audio_name, [int(x) for x in res.labels])
+def split_transcript(transcript: str, marker: str, tokenize) -> List[int]:
+    """Text with gap markers -> token ids: the text is split at `marker`, each piece goes through `tokenize` (text -> ids) as a
+    transcript of its own, the pieces are joined with WILDCARD, and markers with nothing but white space between them are one."""
+    if not marker:
+        raise ValueError("the wildcard marker is empty")
+    ids: List[int] = []
+    for k, piece in enumerate(transcript.split(marker)):
+        if k and (not ids or ids[-1] != WILDCARD):
+            ids.append(WILDCARD)
+        if piece.strip():
+            ids.extend(int(t) for t in tokenize(piece.strip()))
+    return ids
 
 
-def align_to_json(res: AlignResult, tokenizer, chunk_size: int, input_frame_ms: int, output_frame_ms: int) -> Dict[str, Any]:
+def align_to_ali(audio_name: str, res: AlignResult, wildcard: Optional[str] = None) -> str:
+    """The reference's result line: `<key> [label, label, ...]` (asr/wenet/bin/alignment.py:242); a wildcard's frames carry the
+    marker in place of an id."""
+    if wildcard is None or WILDCARD not in res.labels:
+        return "{} {}".format(audio_name, [int(x) for x in res.labels])
+    return "{} [{}]".format(audio_name, ", ".join(wildcard if int(x) == WILDCARD else str(int(x)) for x in res.labels))
+
+
+def align_to_json(res: AlignResult, tokenizer, chunk_size: int, input_frame_ms: int, output_frame_ms: int,
+                  wildcard: Optional[str] = None) -> Dict[str, Any]:
     """Per token: piece, id, start_ms = chunk shift + begin * frame, end_ms = chunk shift + (end + 1) * frame (both inside the chunk the
-    frame lies in), confidence; plus the sequence score."""
+    frame lies in), confidence; plus the sequence score.  A wildcard has the marker as its piece and "wildcard": true."""
     def ms(frame: int, extra: int) -> int:
         c, t = res.chunk_frame(frame)
         return c * chunk_size * input_frame_ms + (t + extra) * output_frame_ms
 
-    toks = [{"piece": piece_of(int(tok), tokenizer), "id": int(tok), "start_ms": ms(b, 0), "end_ms": ms(e, 1), "confidence": float(conf)}
-            for tok, b, e, conf in zip(res.tokens, res.begin, res.end, res.confidence)]
+    toks = []
+    for tok, b, e, conf in zip(res.tokens, res.begin, res.end, res.confidence):
+        wild = int(tok) == WILDCARD
+        toks.append({"piece": (wildcard or "") if wild else piece_of(int(tok), tokenizer), "id": int(tok), "start_ms": ms(b, 0),
+                     "end_ms": ms(e, 1), "confidence": float(conf)})
+        if wild:
+            toks[-1]["wildcard"] = True
     return {"score": float(res.score), "tokens": toks}
 
 

@@ -413,6 +413,17 @@ class Engine:
         """Forced alignment (rvb_ctc_align; reference: force_align, utils/ctc_utils.py:105-161) of known token sequences against the
         chunks of the last encode(): sequence i covers the chunks chunk_ranges[i] = (first, count), default one sequence per chunk
         in order (utterance by utterance); ONE sequence with (0, batch) aligns the transcript of the whole batch.  -> List[AlignResult]."""
+        return self._align(token_seqs, chunk_ranges, None)
+
+    def align_wild(self, token_seqs, chunk_ranges=None, wildcard_bias=0.0):
+        """align() for transcripts with gaps (rvb_ctc_align_wild): a token ctc_align.WILDCARD (-2) stands for audio that was not
+        transcribed.  It is a CTC label of its own that takes at least one frame and emits the frame's largest log-prob (blank
+        included) + wildcard_bias (<= 0, nats per frame: the misfit above which the aligner prefers the wildcard to the
+        transcript).  Its frames carry WILDCARD in `labels`, AlignResult.wildcard marks the tokens, its confidence is the largest
+        top-1 probability of its run.  Without a wildcard the results are those of align(), bit for bit."""
+        return self._align(token_seqs, chunk_ranges, float(wildcard_bias))
+
+    def _align(self, token_seqs, chunk_ranges, wildcard_bias):
         from .ctc_align import AlignResult
         seqs = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in token_seqs]
         if chunk_ranges is None:
@@ -429,8 +440,13 @@ class Engine:
         nt = max(int(tl.sum()), 1)
         begin, end, peak = (np.empty(nt, np.int32) for _ in range(3))
         conf, score = np.empty(nt, np.float32), np.empty(len(seqs), np.float32)
-        check(self.lib.rvb_ctc_align(self.handle, iptr(tok), iptr(tl), len(seqs), iptr(first), iptr(count), iptr(labels), iptr(begin),
-                                     iptr(end), iptr(peak), fptr(conf), fptr(score)), "rvb_ctc_align")
+        if wildcard_bias is None:
+            check(self.lib.rvb_ctc_align(self.handle, iptr(tok), iptr(tl), len(seqs), iptr(first), iptr(count), iptr(labels), iptr(begin),
+                                         iptr(end), iptr(peak), fptr(conf), fptr(score)), "rvb_ctc_align")
+        else:
+            check(self.lib.rvb_ctc_align_wild(self.handle, iptr(tok), iptr(tl), len(seqs), iptr(first), iptr(count), wildcard_bias,
+                                              iptr(labels), iptr(begin), iptr(end), iptr(peak), fptr(conf), fptr(score)),
+                  "rvb_ctc_align_wild")
         out, t0, f0 = [], 0, 0
         for i, t in enumerate(seqs):
             n = len(t)

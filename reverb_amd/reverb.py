@@ -275,14 +275,20 @@ class ReverbASR:
                            self.input_frame_length, self.output_frame_length) for mode in modes]
 
     def align(self, audio_file, transcript: Optional[str] = None, tokens=None, format: str = "ctm", verbatimicity: float = 1.0,
-              chunk_size: int = 2051, timings_adjustment: float = 230, posteriors: bool = False):
+              chunk_size: int = 2051, timings_adjustment: float = 230, posteriors: bool = False, wildcard: Optional[str] = None,
+              wildcard_bias: float = 0.0):
         """Forced alignment of a KNOWN transcript (the reference's bin/alignment.py -> force_align, utils/ctc_utils.py:105-161): exactly
         one of `transcript` (text, tokenised with the model's tokenizer) or `tokens` (ids).  The whole file is encoded as
         transcribe_modes does and the transcript aligned as ONE sequence over all chunks.  format: "ctm" / "txt" (through get_output,
         a token going to the chunk its first frame lies in), "ali" (the reference's `<audio> [labels]` line), "json" (dict: per-token
         times + score; with posteriors=True each token also carries occupancy, mean_time and peak_posterior of the full-sum
-        posteriors, see score())."""
-        from .ctc_align import DecodeLike, align_to_ali, align_to_json, posteriors_to_json, split_by_chunk
+        posteriors, see score()).
+        wildcard: a marker such as "<star>" that stands in `transcript` for audio nobody transcribed (hold music, cross-talk, a
+        preamble before the first word).  The text is split at the marker, the pieces are tokenised as usual and joined with the
+        wildcard label (consecutive markers are one); with tokens= the ids may hold ctc_align.WILDCARD.  A wildcard takes at least
+        one frame and costs what the model's own best label costs there + wildcard_bias (<= 0) per frame; its run appears in every
+        format with the marker as its text ("wildcard": true in json).  Full-sum posteriors do not exist for such a transcript."""
+        from .ctc_align import DecodeLike, align_to_ali, align_to_json, posteriors_to_json, split_by_chunk, split_transcript
         if (transcript is None) == (tokens is None):
             raise ValueError("align: give exactly one of transcript= (text) or tokens= (ids)")
         if format not in ("ctm", "txt", "ali", "json"):
@@ -292,22 +298,30 @@ class ReverbASR:
             raise NotImplementedError("the device fbank is built for 80 bins / 25 ms / 10 ms")
         if chunk_size < 7:
             raise ValueError("chunk_size must be at least 7 frames (Conv2dSubsampling4 needs 7 input frames, subsampling.py:201-226)")
+        if wildcard is not None:
+            if posteriors:
+                raise ValueError("align: posteriors come from the full-sum score, which has no wildcards")
+            if tokens is None:
+                tokens = split_transcript(transcript, wildcard, lambda text: self.tokenizer.tokenize(text)[1])
         eng, ids, n_chunks = self._encode_for_align("align", audio_file, transcript, tokens, verbatimicity, chunk_size)
-        res = eng.align([ids], [(0, n_chunks)])[0]
+        if wildcard is None:
+            res = eng.align([ids], [(0, n_chunks)])[0]
+        else:
+            res = eng.align_wild([ids], [(0, n_chunks)], wildcard_bias)[0]
         name = Path(audio_file).name
         if format == "ali":
-            return align_to_ali(name, res)
+            return align_to_ali(name, res, wildcard)
         if format == "json":
-            out = align_to_json(res, self.tokenizer, chunk_size, self.input_frame_length, self.output_frame_length)
+            out = align_to_json(res, self.tokenizer, chunk_size, self.input_frame_length, self.output_frame_length, wildcard)
             if posteriors:
                 post = eng.score([ids], [(0, n_chunks)], posteriors=True)[0]
                 for tok, extra in zip(out["tokens"], posteriors_to_json(res, post, chunk_size, self.input_frame_length,
                                                                         self.output_frame_length)):
                     tok.update(extra)
             return out
-        hyps = [DecodeLike(t, fr, cf) for t, fr, cf in split_by_chunk(res)]
+        hyps = [DecodeLike(t, fr, cf, ends=en) for t, fr, cf, en in split_by_chunk(res, ends=True)]
         return get_output(format, self.tokenizer, name, hyps, timings_adjustment, chunk_size, self.input_frame_length,
-                          self.output_frame_length)
+                          self.output_frame_length, wildcard=wildcard)
 
     def _encode_for_align(self, who: str, audio_file, transcript, tokens, verbatimicity: float, chunk_size: int):
         """Tokenise and encode the whole file as ONE batch, as align() and score() need it -> (engine, ids, n_chunks)."""
@@ -421,8 +435,9 @@ def load_cmvn(cmvn_file: str, is_json: bool):
 
 
 def get_output(format: str, tokenizer, audio_name: str, hyps: List[DecodeResult], timings_adjustment_ms,
-               chunk_size: int, input_frame_length: int, output_frame_length: int) -> str:
-    """DecodeResults of consecutive chunks -> one TXT / CTM string (cli/reverb.py:298-327)."""
+               chunk_size: int, input_frame_length: int, output_frame_length: int, wildcard: Optional[str] = None) -> str:
+    """DecodeResults of consecutive chunks -> one TXT / CTM string (cli/reverb.py:298-327).  wildcard: the marker that the words of
+    wildcard tokens carry (forced alignment with gaps; such hyps also give `ends`)."""
     if format == "txt":
         render, sep = hyps_to_txt, " "
     elif format == "ctm":
@@ -438,7 +453,8 @@ def get_output(format: str, tokenizer, audio_name: str, hyps: List[DecodeResult]
             if format != "txt":
                 raise ValueError("this decoding mode produces no timestamps: use format='txt'")
             times = [0] * len(hyp.tokens)
-        words = ctc_align(hyp.tokens, times, hyp.tokens_confidence, tokenizer, output_frame_length, shift_ms)
+        words = ctc_align(hyp.tokens, times, hyp.tokens_confidence, tokenizer, output_frame_length, shift_ms, wildcard,
+                          getattr(hyp, "ends", None))
         words = adjust_model_time_offset(words, timings_adjustment_ms)
         shift_ms += chunk_size * input_frame_length
         lines.extend(list(render(words)))
