@@ -144,8 +144,26 @@ class AttnTestArgs(C.Structure):
                 [("ran", C.c_int32 * 8)])
 
 
+class NormTestArgs(C.Structure):
+    """rvb_test_norm_args of csrc/test_api.h (rvb_test_rownorm_ex): one rownorm() call on host floats."""
+    _fields_ = ([(n, C.c_int32) for n in ("dtype", "x_bf16", "mode", "silu", "out_f32", "out_fp8", "out2_fp8", "M", "d", "pad0")] +
+                [(n, C.c_float) for n in ("eps", "eps2", "out_scale", "out2_scale")] +
+                [(n, _f32p) for n in ("x", "gamma", "beta", "add", "gamma2", "beta2", "out", "out2")] +
+                [("sat", C.c_uint32), ("sat2", C.c_uint32)])
+
+
+_u32p = C.POINTER(C.c_uint32)
+
 # librvb_test.so (csrc/test_api.h): raw kernel / host-search hooks for tests/ and scripts/ -- not in the product library
 TEST_SIGNATURES = {
+    "rvb_test_rownorm_ex": (C.c_int, [C.POINTER(NormTestArgs)]),
+    "rvb_test_conv1_ex": (C.c_int, [C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
+                                    _f32p, _u32p]),
+    "rvb_test_embed": (C.c_int, [_f32p, C.c_int, _f32p, C.c_int, _i32p, _i32p, _f32p, C.c_int, C.c_int, C.c_float]),
+    "rvb_test_amax_abs": (C.c_int, [C.c_int, _f32p, C.c_int64, _f32p]),
+    "rvb_test_convert_f32": (C.c_int, [C.c_int, _f32p, _f32p, C.c_int64]),
+    "rvb_test_gather_cache": (C.c_int, [C.c_void_p, C.c_void_p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "rvb_test_gather_pairs": (C.c_int, [_f32p, C.c_int, C.c_int64, _i32p, _i32p, C.c_int, _f32p]),
     "rvb_test_gemm": (C.c_int, [C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_float,
                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rvb_test_rownorm": (C.c_int, [C.c_int, _f32p, _f32p, _f32p, C.c_float, C.c_int, C.c_int, _f32p, _f32p, C.c_int,

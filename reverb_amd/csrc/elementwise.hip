@@ -146,6 +146,22 @@ int subsample_conv1(hipStream_t s, int dtype, const float* feats, const float* m
 // second-stage output), so the row loop has no branches and the compiler's waitcnt pass emits COUNTED waits: with the run-time
 // switches (SW = -1) it has to assume that any conditional load may be pending at every join and answers with `s_waitcnt vmcnt(0)`
 // right behind the next row's prefetch and in front of every store -- the loop then runs one memory round trip at a time.
+// The four squares of a vector in the variance, with their roundings written out.  Left to the compiler, the sum was contracted to
+// FMAs in the generic kernels and kept as four products (two v_pk_mul_f32) in the compile-time forms, so at 512 < d <= 1024 the
+// fused pair norm_final(x) + y -> LayerNorm (compile-time) and the one-stage LayerNorm + add (generic) differed in the last bit of rstd,
+// and the second stage did not read "exactly what a separate pass would read".  Now every NV = 4 kernel rounds the products
+// separately, as the compile-time forms always did, and NV = 2 / 8 (generic only) keep the FMA chain they always had: no kernel
+// the engine runs changes a bit.
+template <int NV>
+__device__ inline float sq4(float dx, float dy, float dz, float dw) {
+  if constexpr (NV == 4) {
+#pragma clang fp contract(off)
+    return dx * dx + dy * dy + dz * dz + dw * dw;
+  } else {
+    return fmaf(dw, dw, fmaf(dz, dz, fmaf(dx, dx, dy * dy)));
+  }
+}
+
 template <typename OutT, typename AddT, int NV, bool TWO, int SW>
 __global__ __launch_bounds__(256, (NV <= 4 ? 4 : 2)) void rownorm_kernel(NormArgs a) {
   constexpr bool CT = SW >= 0;
@@ -217,8 +233,7 @@ __global__ __launch_bounds__(256, (NV <= 4 ? 4 : 2)) void rownorm_kernel(NormArg
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
         if (COL(i) < d) {
-          const float dx = v[i].x - mean, dy = v[i].y - mean, dz = v[i].z - mean, dw = v[i].w - mean;
-          sq += dx * dx + dy * dy + dz * dz + dw * dw;
+          sq += sq4<NV>(v[i].x - mean, v[i].y - mean, v[i].z - mean, v[i].w - mean);
         }
       }
       rstd = rsqrtf(wsum(sq) / (float)d + a.eps);
@@ -282,8 +297,7 @@ __global__ __launch_bounds__(256, (NV <= 4 ? 4 : 2)) void rownorm_kernel(NormArg
 #pragma unroll
       for (int i = 0; i < NV; ++i) {
         if (COL(i) < d) {
-          const float dx = v[i].x - mean2, dy = v[i].y - mean2, dz = v[i].z - mean2, dw = v[i].w - mean2;
-          sq += dx * dx + dy * dy + dz * dz + dw * dw;
+          sq += sq4<NV>(v[i].x - mean2, v[i].y - mean2, v[i].z - mean2, v[i].w - mean2);
         }
       }
       const float rstd2 = rsqrtf(wsum(sq) / (float)d + a.eps2);

@@ -35,6 +35,8 @@ int rvb_test_joint_begin(void* h, int t, const float* tv, const int32_t* ti, int
 int rvb_test_joint_finish(void* h, const float* vals);
 int rvb_test_joint_prefix(void* h, int node, int32_t* toks, int32_t* n);
 int rvb_test_joint_result(void* h, int32_t* tokens, int32_t* times, int32_t* end_times, double* conf, int32_t* n, double* score);
+/* `causal`: bit 0 causal, bit 1 bf16 output (bf16 engine), bit 2 the gated form: G is [B][T][d], already a * sigmoid(b) (what the
+ * pointwise GEMM's ACT_GLU epilogue stores) */
 int rvb_test_glu_dwconv(int dtype, const float* G, const float* pw1_bias, const float* dw_w, const float* dw_b,
                         const int32_t* lens, float* out, int B, int T, int d, int K, int causal,
                         const float* hist /* nullable [K-1][2d] */, int hist_rows);
@@ -96,6 +98,36 @@ int rvb_test_gemm_fp8(const float* A, const float* W, const float* bias, const f
                       float a_scale, float alpha, int act, int out_kind, float out_scale, float* a_deq, float* w_deq);
 int rvb_test_rownorm_fp8(const float* x, const float* gamma, const float* beta, float eps, int silu, int M, int d, float scale,
                          float* out, const float* gamma2, const float* beta2, float eps2, float scale2, float* out1_f32, float* out2);
+/* rownorm() with everything NormArgs carries, on host floats.  x goes up as fp32, or as bf16 when x_bf16; add in the compute dtype.
+ * out: bf16 (bf16 engine), fp32 (f32 engine or out_f32) or e4m3 of value / out_scale (out_fp8).  gamma2 non-null adds the fused second
+ * LayerNorm: out2 in the compute dtype, or e4m3 of value / out2_scale (out2_fp8).  fp8 outputs come back de-quantised as
+ * rvb_test_rownorm_fp8 returns them.  The device outputs start as all-ones bytes (a NaN in every output format), so an element the
+ * kernel did not write comes back NaN; when the launcher refuses the call, out / out2 are left as the caller filled them.
+ * sat / sat2 = the two saturation counters after the call. */
+typedef struct rvb_test_norm_args {
+  int32_t dtype, x_bf16, mode, silu, out_f32, out_fp8, out2_fp8, M, d, pad0;
+  float eps, eps2, out_scale, out2_scale;
+  const float* x; const float* gamma; const float* beta; const float* add; const float* gamma2; const float* beta2;
+  float* out; float* out2;
+  uint32_t sat, sat2;
+} rvb_test_norm_args;
+int rvb_test_rownorm_ex(rvb_test_norm_args* a);
+/* subsample_conv1 with its fp8 output (out_fp8_scale > 0: out comes back de-quantised), the running maximum (amax nullable: in = the
+ * slot's initial value, out = the slot after the call) and the saturation counter (sat nullable).  w as rvb_test_conv1 takes it. */
+int rvb_test_conv1_ex(int dtype, const float* feats, const float* mean, const float* istd, const float* w, const float* b, float* out,
+                      int B, int T0, int F0, int d, float out_fp8_scale, float* amax, uint32_t* sat);
+/* embed_tokens: out[r] = E[tok[r]] * scale + pe[pos[r]]; E [vocab][d], pe [n_pos][d]; indices outside the tables are refused */
+int rvb_test_embed(const float* E, int vocab, const float* pe, int n_pos, const int32_t* tok, const int32_t* pos, float* out, int rows,
+                   int d, float scale);
+/* amax_abs over n values (rounded to bf16 on the way up in the bf16 engine); *slot in = the slot's initial value, out = the slot */
+int rvb_test_amax_abs(int dtype, const float* x, int64_t n, float* slot);
+/* convert_f32: dst = the n values as the compute dtype holds them (bf16 widened back to fp32, bit for bit) */
+int rvb_test_convert_f32(int dtype, const float* src, float* dst, int64_t n);
+/* gather_cache on caches [R][L][row_bytes]: dst goes up as the caller filled it and comes back whole */
+int rvb_test_gather_cache(const void* src, void* dst, const int32_t* parent, int R, int L, int rows, int row_bytes);
+/* softmax_topk.hip gather_pairs: out[i] = table[row[i]][col[i]], table fp32 [rows][ld]; pairs outside the table are refused; out goes up
+ * as the caller filled it */
+int rvb_test_gather_pairs(const float* table, int rows, int64_t ld, const int32_t* row, const int32_t* col, int n, float* out);
 int rvb_test_lse_gather_multi(const float* logits, int R, int V, const int32_t* ptr /* [R+1] */, const int32_t* target,
                               int P, float* out /* [P] */);
 /* softmax_topk.hip row_xent on host logits [R][ld] (the first V entries of a row count): logp [ptr[R]] as rvb_test_lse_gather_multi,

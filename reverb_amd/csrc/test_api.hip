@@ -286,7 +286,8 @@ int rvb_test_glu_dwconv(int dtype, const float* G, const float* pw1_bias, const 
                         int hist_rows) {
   T_TRY(need_gpu());
   Dev dG, dpb, dw, db, dl, dout, dh;
-  T_TRY(up_T(dG, dtype, G, (size_t)B * T * 2 * d));
+  const bool gated = (causal & 4) != 0;          // bit 2 of `causal`: G is [B][T][d], gated already (GluDwArgs::gated)
+  T_TRY(up_T(dG, dtype, G, (size_t)B * T * (gated ? 1 : 2) * d));
   T_TRY(up_raw(dpb, pw1_bias, (size_t)2 * d * 4));
   std::vector<float> wt((size_t)d * K);            // the caller passes depthwise_conv.weight as the reference stores it, [d][K]
   for (int c = 0; c < d; ++c)
@@ -297,8 +298,10 @@ int rvb_test_glu_dwconv(int dtype, const float* G, const float* pw1_bias, const 
   const bool o16 = (causal & 2) != 0;            // bit 1 of `causal`: bf16 output (bf16 engine)
   causal &= 1;
   T_TRY(dout.alloc((size_t)B * T * d * 4));
+  RVB_HIP_CHECK(hipMemset(dout.p, 0xff, (size_t)B * T * d * 4));      // NaN in fp32 and in bf16: a frame the kernel skipped shows
   GluDwArgs a;
   a.out_bf16 = o16 ? 1 : 0;
+  a.gated = gated ? 1 : 0;
   a.G = dG.p; a.pw1_bias = (const float*)dpb.p; a.dw_w = (const float*)dw.p; a.dw_b = (const float*)db.p;
   a.lens = (const int*)dl.p; a.out = (float*)dout.p; a.B = B; a.T = T; a.d = d; a.K = K;
   a.causal = causal;
@@ -842,6 +845,164 @@ int rvb_test_rownorm_fp8(const float* x, const float* gamma, const float* beta, 
     RVB_HIP_CHECK(hipMemcpy(q.data(), dout.p, q.size(), hipMemcpyDeviceToHost));
     for (size_t i = 0; i < q.size(); ++i) out[i] = fp8_to_f32_host(q[i]) * scale;
   }
+  return OK;
+}
+
+// e4m3 byte -> float at `scale`; the two NaN codes (what the hooks below pre-fill fp8 outputs with) stay NaN
+static float fp8_deq_or_nan(uint8_t q, float scale) {
+  return (q & 0x7f) == 0x7f ? __builtin_nanf("") : fp8_to_f32_host(q) * scale;
+}
+static int down_fp8(const Dev& d, float* dst, size_t n, float scale) {
+  std::vector<uint8_t> q(n);
+  RVB_HIP_CHECK(hipMemcpy(q.data(), d.p, n, hipMemcpyDeviceToHost));
+  for (size_t i = 0; i < n; ++i) dst[i] = fp8_deq_or_nan(q[i], scale);
+  return OK;
+}
+
+// rownorm() with the whole of NormArgs (test_api.h)
+int rvb_test_rownorm_ex(rvb_test_norm_args* t) {
+  if (!t || !t->x || !t->gamma || !t->beta || !t->out || t->M < 1 || t->d < 1 || (t->dtype != DT_F32 && t->dtype != DT_BF16)) {
+    set_error("rvb_test_rownorm_ex: null argument, M < 1, d < 1 or an unknown dtype"); return E_ARG;
+  }
+  const bool two = t->gamma2 != nullptr;
+  if (two && (!t->beta2 || !t->out2)) { set_error("rvb_test_rownorm_ex: the second stage needs gamma2, beta2 and out2"); return E_ARG; }
+  if ((t->out_fp8 && !(t->out_scale > 0.f)) || (two && t->out2_fp8 && !(t->out2_scale > 0.f))) {
+    set_error("rvb_test_rownorm_ex: an fp8 output needs a positive scale"); return E_ARG;
+  }
+  T_TRY(need_gpu());
+  const int dtype = t->dtype;
+  const size_t n = (size_t)t->M * t->d;
+  Dev dx, dg, db, da, dg2, db2, dout, dout2, dsat;
+  if (t->x_bf16) T_TRY(up_T(dx, DT_BF16, t->x, n)); else T_TRY(up_raw(dx, t->x, n * 4));
+  T_TRY(up_raw(dg, t->gamma, (size_t)t->d * 4)); T_TRY(up_raw(db, t->beta, (size_t)t->d * 4));
+  T_TRY(up_T(da, dtype, t->add, n));
+  T_TRY(up_raw(dg2, t->gamma2, (size_t)t->d * 4)); T_TRY(up_raw(db2, t->beta2, (size_t)t->d * 4));
+  // four bytes per element whatever the output type (a call the launcher is going to refuse may name any combination)
+  T_TRY(dout.alloc(n * 4)); RVB_HIP_CHECK(hipMemset(dout.p, 0xff, n * 4));
+  if (two) { T_TRY(dout2.alloc(n * 4)); RVB_HIP_CHECK(hipMemset(dout2.p, 0xff, n * 4)); }
+  T_TRY(dsat.alloc(8)); RVB_HIP_CHECK(hipMemset(dsat.p, 0, 8));
+  NormArgs a;
+  a.x = (const float*)dx.p; a.x_bf16 = t->x_bf16 ? 1 : 0; a.gamma = (const float*)dg.p; a.beta = (const float*)db.p; a.eps = t->eps;
+  a.mode = t->mode; a.silu = t->silu; a.add = da.p; a.out = dout.p; a.out_f32 = t->out_f32; a.M = t->M; a.d = t->d;
+  a.out_fp8 = t->out_fp8 ? 1 : 0;
+  if (t->out_fp8) a.out_inv_scale = 1.f / t->out_scale;
+  if (two) {
+    a.gamma2 = (const float*)dg2.p; a.beta2 = (const float*)db2.p; a.eps2 = t->eps2; a.out2 = dout2.p;
+    a.out2_fp8 = t->out2_fp8 ? 1 : 0;
+    if (t->out2_fp8) a.out2_inv_scale = 1.f / t->out2_scale;
+  }
+  a.sat = (unsigned*)dsat.p; a.sat2 = (unsigned*)dsat.p + 1;
+  T_TRY(rownorm(nullptr, dtype, a));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  uint32_t sats[2];
+  RVB_HIP_CHECK(hipMemcpy(sats, dsat.p, 8, hipMemcpyDeviceToHost));
+  t->sat = sats[0]; t->sat2 = sats[1];
+  if (t->out_fp8) T_TRY(down_fp8(dout, t->out, n, t->out_scale));
+  else T_TRY(down_T(dout, dtype, t->out_f32 != 0, t->out, n));
+  if (two) {
+    if (t->out2_fp8) T_TRY(down_fp8(dout2, t->out2, n, t->out2_scale));
+    else T_TRY(down_T(dout2, dtype, false, t->out2, n));
+  }
+  return OK;
+}
+
+// subsample_conv1 with its fp8 output, running maximum and saturation counter (test_api.h)
+int rvb_test_conv1_ex(int dtype, const float* feats, const float* mean, const float* istd, const float* w, const float* b, float* out,
+                      int B, int T0, int F0, int d, float out_fp8_scale, float* amax, uint32_t* sat) {
+  if (!feats || !mean || !istd || !w || !b || !out || B < 1 || T0 < 3 || F0 < 3 || d < 1 || (dtype != DT_F32 && dtype != DT_BF16)) {
+    set_error("rvb_test_conv1_ex: null argument, B < 1, fewer than 3 frames or bins, d < 1 or an unknown dtype"); return E_ARG;
+  }
+  T_TRY(need_gpu());
+  const int T1 = (T0 - 3) / 2 + 1, F1 = (F0 - 3) / 2 + 1;
+  Dev df, dm, di, dw, db, dout, dslot;
+  T_TRY(up_raw(df, feats, (size_t)B * T0 * F0 * 4));
+  T_TRY(up_raw(dm, mean, (size_t)F0 * 4));
+  T_TRY(up_raw(di, istd, (size_t)F0 * 4));
+  std::vector<float> wt((size_t)d * 9);            // [d][1][3][3] -> tap-major [9][d]
+  for (int c = 0; c < d; ++c)
+    for (int k = 0; k < 9; ++k) wt[(size_t)k * d + c] = w[(size_t)c * 9 + k];
+  T_TRY(up_raw(dw, wt.data(), (size_t)d * 9 * 4));
+  T_TRY(up_raw(db, b, (size_t)d * 4));
+  const size_t n = (size_t)B * T1 * F1 * d;
+  T_TRY(dout.alloc(n * 4)); RVB_HIP_CHECK(hipMemset(dout.p, 0xff, n * 4));
+  uint32_t slots[2] = {0, 0};                      // {amax as float bits, sat}
+  if (amax) memcpy(&slots[0], amax, 4);
+  T_TRY(up_raw(dslot, slots, 8));
+  T_TRY(subsample_conv1(nullptr, dtype, (const float*)df.p, (const float*)dm.p, (const float*)di.p, (const float*)dw.p,
+                        (const float*)db.p, dout.p, B, T0, F0, d, out_fp8_scale, amax ? (unsigned*)dslot.p : nullptr,
+                        sat ? (unsigned*)dslot.p + 1 : nullptr));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  RVB_HIP_CHECK(hipMemcpy(slots, dslot.p, 8, hipMemcpyDeviceToHost));
+  if (amax) memcpy(amax, &slots[0], 4);
+  if (sat) *sat = slots[1];
+  if (out_fp8_scale > 0.f) return down_fp8(dout, out, n, out_fp8_scale);
+  return down_T(dout, dtype, false, out, n);
+}
+
+int rvb_test_embed(const float* E, int vocab, const float* pe, int n_pos, const int32_t* tok, const int32_t* pos, float* out, int rows,
+                   int d, float scale) {
+  if (!E || !pe || !tok || !pos || !out || vocab < 1 || n_pos < 1 || rows < 1 || d < 1) { set_error("rvb_test_embed: null argument or an empty table"); return E_ARG; }
+  for (int r = 0; r < rows; ++r)
+    if (tok[r] < 0 || tok[r] >= vocab || pos[r] < 0 || pos[r] >= n_pos) { set_error("rvb_test_embed: index outside its table"); return E_ARG; }
+  T_TRY(need_gpu());
+  Dev dE, dp, dt, dq, dout;
+  T_TRY(up_raw(dE, E, (size_t)vocab * d * 4)); T_TRY(up_raw(dp, pe, (size_t)n_pos * d * 4));
+  T_TRY(up_raw(dt, tok, (size_t)rows * 4)); T_TRY(up_raw(dq, pos, (size_t)rows * 4));
+  T_TRY(up_raw(dout, out, (size_t)rows * d * 4));
+  T_TRY(embed_tokens(nullptr, (const float*)dE.p, (const float*)dp.p, (const int*)dt.p, (const int*)dq.p, (float*)dout.p, rows, d, scale));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  RVB_HIP_CHECK(hipMemcpy(out, dout.p, (size_t)rows * d * 4, hipMemcpyDeviceToHost));
+  return OK;
+}
+
+int rvb_test_amax_abs(int dtype, const float* x, int64_t n, float* slot) {
+  if (!x || !slot || n < 1 || (dtype != DT_F32 && dtype != DT_BF16)) { set_error("rvb_test_amax_abs: null argument, n < 1 or an unknown dtype"); return E_ARG; }
+  T_TRY(need_gpu());
+  Dev dx, ds;
+  T_TRY(up_T(dx, dtype, x, (size_t)n));
+  T_TRY(up_raw(ds, slot, 4));
+  T_TRY(amax_abs(nullptr, dtype, dx.p, (size_t)n, (float*)ds.p));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  RVB_HIP_CHECK(hipMemcpy(slot, ds.p, 4, hipMemcpyDeviceToHost));
+  return OK;
+}
+
+int rvb_test_convert_f32(int dtype, const float* src, float* dst, int64_t n) {
+  if (!src || !dst || n < 1 || (dtype != DT_F32 && dtype != DT_BF16)) { set_error("rvb_test_convert_f32: null argument, n < 1 or an unknown dtype"); return E_ARG; }
+  T_TRY(need_gpu());
+  Dev ds, dd;
+  T_TRY(up_raw(ds, src, (size_t)n * 4));
+  T_TRY(dd.alloc((size_t)n * 4)); RVB_HIP_CHECK(hipMemset(dd.p, 0xff, (size_t)n * 4));
+  T_TRY(convert_f32(nullptr, dtype, (const float*)ds.p, dd.p, (size_t)n));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  return down_T(dd, dtype, false, dst, (size_t)n);
+}
+
+int rvb_test_gather_cache(const void* src, void* dst, const int32_t* parent, int R, int L, int rows, int row_bytes) {
+  if (!src || !dst || !parent || R < 1 || L < 1 || rows < 0 || rows > L || row_bytes < 1) { set_error("rvb_test_gather_cache: null argument or not 0 <= rows <= L"); return E_ARG; }
+  for (int r = 0; r < R; ++r)
+    if (parent[r] < 0 || parent[r] >= R) { set_error("rvb_test_gather_cache: parent outside [0, R)"); return E_ARG; }
+  T_TRY(need_gpu());
+  const size_t bytes = (size_t)R * L * row_bytes;
+  Dev ds, dd, dp;
+  T_TRY(up_raw(ds, src, bytes)); T_TRY(up_raw(dd, dst, bytes)); T_TRY(up_raw(dp, parent, (size_t)R * 4));
+  T_TRY(gather_cache(nullptr, ds.p, dd.p, (const int*)dp.p, R, L, rows, row_bytes));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  RVB_HIP_CHECK(hipMemcpy(dst, dd.p, bytes, hipMemcpyDeviceToHost));
+  return OK;
+}
+
+int rvb_test_gather_pairs(const float* table, int rows, int64_t ld, const int32_t* row, const int32_t* col, int n, float* out) {
+  if (!table || rows < 1 || ld < 1 || n < 0 || (n > 0 && (!row || !col || !out))) { set_error("rvb_test_gather_pairs: null argument or an empty table"); return E_ARG; }
+  for (int i = 0; i < n; ++i)
+    if (row[i] < 0 || row[i] >= rows || col[i] < 0 || col[i] >= ld) { set_error("rvb_test_gather_pairs: pair outside the table"); return E_ARG; }
+  T_TRY(need_gpu());
+  Dev dt, dr, dc, dout;
+  T_TRY(up_raw(dt, table, (size_t)rows * ld * 4));
+  if (n > 0) { T_TRY(up_raw(dr, row, (size_t)n * 4)); T_TRY(up_raw(dc, col, (size_t)n * 4)); T_TRY(up_raw(dout, out, (size_t)n * 4)); }
+  T_TRY(gather_pairs(nullptr, (const float*)dt.p, (size_t)ld, (const int*)dr.p, (const int*)dc.p, n, (float*)dout.p));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  if (n > 0) RVB_HIP_CHECK(hipMemcpy(out, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   return OK;
 }
 
