@@ -258,6 +258,34 @@ int rvb_ctc_align_wild(rvb_engine* e, const int32_t* tokens, const int32_t* tok_
 int rvb_ctc_score(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,
                   const int32_t* n_chunks, double* loglik, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame);
 
+/* Phrase search: EVERY occurrence of given short phrases (names, terms) in the audio of the last rvb_encode / rvb_stream_finish, on
+ * the device (csrc/ctc_find.hip, one wave per phrase and sequence).  n_phrases phrases, concatenated in `tokens`, tok_lens[p] ids
+ * each (1 .. RVB_CTC_FIND_MAX_TOKENS, in [0, vocab), none the blank); n_seq sequences of frames given by first_chunk / n_chunks as
+ * for rvb_ctc_align (the VALID frames of the chunks, concatenated, numbered within the sequence), so a hit may straddle a chunk
+ * boundary.  Every phrase is searched in every sequence; pair p * n_seq + i is phrase p in sequence i.
+ * A phrase is the lattice z = [y0, blank, y1, ..., y(L-1)] with a free start and a free end.  Frame t emits
+ * d[t][s] = lp[t][z[s]] - w[t] in fp32, w[t] = the largest log-prob of the frame (what a wildcard frame of rvb_ctc_align_wild
+ * costs): d <= 0, and 0 exactly where the model's own greedy label agrees.  h[t][0] = max(h[t-1][0], 0) + d[t][0], the 0 standing for
+ * "starts here"; h[t][s] = max(h[t-1][s], h[t-1][s-1] (, h[t-1][s-2] if z[s] is a token other than z[s-2])) + d[t][s], the first
+ * maximum in that order (a stay beats a fresh start on a tie), each state carrying the start frame of its chosen path.  Frame t is an
+ * ARRIVAL when the last state is entered (not stayed in) at t; an arrival with score h >= threshold[p] (fp32, total nats, <= 0;
+ * -inf keeps every arrival) is a CANDIDATE (start, end = t, score).  Per pair the first max_candidates candidates in frame order are
+ * kept on the device and then suppressed on the host: by score descending, then end ascending, then start ascending, a candidate
+ * is kept if [start, end] meets no kept span, until max_hits are kept; nothing is suppressed across phrases or sequences.
+ * Outputs: n_hits [n_phrases * n_seq]; start / end / score [n_phrases * n_seq][max_hits], the pair's hits in order of end (score is
+ * the fp32 path score: 0 = the greedy labels spell the phrase; divide by tok_lens[p] to compare phrases); n_candidates (nullable)
+ * [n_phrases * n_seq] = all arrivals at or above the threshold, kept or not: a value above max_candidates says that later arrivals
+ * were dropped and the call should be repeated with a larger cap.  A sequence with fewer frames than a phrase needs is no error: it
+ * has no arrival.  Refused by name before any device work: RVB_E_ARG for an empty phrase, an id outside [0, vocab) or equal to the
+ * blank, n_phrases, n_seq, max_candidates or max_hits < 1, a threshold that is NaN or > 0, a chunk range outside the batch;
+ * RVB_E_UNSUPPORTED for a phrase of more than RVB_CTC_FIND_MAX_TOKENS tokens (locate longer text with rvb_ctc_align_wild and a
+ * wildcard on either side); RVB_E_NOMEM, naming the bytes, if the candidate buffers (12 bytes per pair and candidate) do not fit. */
+#define RVB_CTC_FIND_MAX_TOKENS 32
+int rvb_ctc_find(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_phrases, const float* threshold /* [n_phrases] */,
+                 const int32_t* first_chunk, const int32_t* n_chunks, int n_seq, int max_candidates, int max_hits,
+                 int32_t* n_hits /* [n_phrases*n_seq] */, int32_t* start, int32_t* end, float* score /* [n_phrases*n_seq*max_hits] each */,
+                 int64_t* n_candidates /* [n_phrases*n_seq], nullable: arrivals above threshold, kept or not */);
+
 /* ctc_prefix_beam_search (search.py:124-248), float64 host arithmetic, one host thread per chunk.
  * Results are kept in the engine; read them with rvb_get_nbest. */
 int rvb_ctc_prefix_beam(rvb_engine* e, int beam);
@@ -398,7 +426,7 @@ int rvb_comm_destroy(rvb_engine* e);
 /* Stage timing (HIP events on the engine stream).  level 1: every kernel family is bracketed;
  * names: "fbank","subsample","gemm","attention","rownorm","glu_dwconv","ctc_topk","embed",
  * "lse_gather" (the row kernel after the decoders' output layer: rescoring and rvb_attention_score),"search_host","ctc_align_lp" (rvb_ctc_align: CTC head + log-softmax),"ctc_viterbi" (its
- * forward pass + back-trace),"ctc_forward" / "ctc_backward" (rvb_ctc_score: the two sweeps).  level 2: only the GEMM launches (the dominant kernel; half the
+ * forward pass + back-trace),"ctc_forward" / "ctc_backward" (rvb_ctc_score: the two sweeps),"ctc_find" (rvb_ctc_find: the search kernel).  level 2: only the GEMM launches (the dominant kernel; half the
  * events, ~1 % less perturbation of the step).  level 0: off.
  * flops: algorithmic FLOPs launched (gemm/attention only). */
 int rvb_set_profiling(rvb_engine* e, int level);

@@ -93,6 +93,8 @@ SIGNATURES = {
     "rvb_ctc_align_wild": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, _i32p, C.c_float, _i32p, _i32p, _i32p, _i32p, _f32p, _f32p]),
     "rvb_ctc_align_limits": (C.c_int, [_i32p, _i32p]),
     "rvb_ctc_score": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, _i32p, _f64p, _f32p, _f32p, _f32p, _i32p]),
+    "rvb_ctc_find": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _f32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f32p,
+                               _i64p]),
     "rvb_ctc_prefix_beam": (C.c_int, [_eng, C.c_int]),
     "rvb_set_context_graph": (C.c_int, [_eng, _i32p, _i32p, C.c_int, C.c_double]),
     "rvb_get_nbest_count": (C.c_int, [_eng, C.c_int, _i32p, _i32p]),
@@ -195,6 +197,8 @@ TEST_SIGNATURES = {
     "rvb_test_ctc_score": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, _f64p, _f32p, _f32p, _f32p, _i32p]),
     "rvb_test_ctc_score_batch": (C.c_int, [_f32p, _i32p, C.c_int, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _f64p, _f32p, _f32p, _f32p,
                                            _i32p]),
+    "rvb_test_ctc_find": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, _f32p, _i32p, _i32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                    _i64p, _i32p, _i32p, _f32p, _i32p, _i32p, _i32p, _f32p]),
     "rvb_test_gemm_glu": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int]),
     "rvb_test_gemm_rowadd": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rvb_test_mp3_decode": (C.c_int64, [C.c_char_p, C.c_int64, C.c_int, _f32p, C.c_int64, _i64p, _i64p, C.c_int]),

@@ -9,14 +9,12 @@ from typing import Dict, List, Optional, Sequence
 from .tokenizer import SPACE_MARK, RevBpeTokenizer
 
 
-def tokenize(context_list_path, symbol_table: Dict[str, int], bpe_model=None) -> List[List[int]]:
-    """One phrase per line of the list file -> token ids.  Without a BPE model a phrase is cut into characters, a space becoming
+def tokenize_lines(lines, symbol_table: Dict[str, int], bpe_model=None) -> List[List[int]]:
+    """One phrase per entry of `lines` -> token ids.  Without a BPE model a phrase is cut into characters, a space becoming
     the word-boundary mark; with one, RevBpeTokenizer.text2tokens cuts it (sentencepiece when the model file and the package are
     there, longest match against the unit table otherwise).  A piece the table does not have becomes <unk> if the table has
     that, and is dropped if not; an empty line gives an empty phrase."""
     bpe = RevBpeTokenizer(bpe_model, symbol_table) if bpe_model is not None else None
-    with open(context_list_path, "r", encoding="utf8") as fin:
-        lines = fin.readlines()
     phrases = []
     for line in lines:
         line = line.strip()
@@ -32,6 +30,13 @@ def tokenize(context_list_path, symbol_table: Dict[str, int], bpe_model=None) ->
                 ids.append(symbol_table["<unk>"])
         phrases.append(ids)
     return phrases
+
+
+def tokenize(context_list_path, symbol_table: Dict[str, int], bpe_model=None) -> List[List[int]]:
+    """tokenize_lines over the lines of a list file, one phrase per line."""
+    with open(context_list_path, "r", encoding="utf8") as fin:
+        lines = fin.readlines()
+    return tokenize_lines(lines, symbol_table, bpe_model)
 
 
 class ContextGraph:

@@ -180,6 +180,31 @@ struct CtcScorer {
   void release();
 };
 
+
+// ---- phrase search (ctc_find.hip): the host side shared by rvb_ctc_find and the lab hook.  plan() validates and lays out the
+// (phrase, sequence) pairs (no device work; E_NOMEM if the candidate buffers cannot fit any device), begin() allocates and uploads
+// (E_NOMEM naming the bytes), advance() runs the kernel over the frames whose rows lie in the slab just computed (slabs in row
+// order; wmax[nrows] = the maximum of each row of the slab), finish() copies counts and candidates back and suppresses overlapping
+// candidates on the host.  A sequence shorter than a phrase is no error: it has no arrival.
+struct CtcFinder {
+  std::vector<FindSeq> seq;
+  std::vector<FindPhrase> phr;
+  std::vector<int32_t> h_tokens, h_rows;
+  int blank = 0, max_cand = 0;
+  DevBuf d_tokens, d_rows, d_seqs, d_phr, d_h, d_st, d_count, d_cend, d_cstart, d_cscore;
+  // seq_rows[i][f]: the (increasing) log-prob row of frame f of sequence i; threshold [n_phrases]
+  int plan(const char* who, const int32_t* tokens, const int32_t* tok_lens, int n_phrases, const float* threshold,
+           const std::vector<std::vector<int32_t>>& seq_rows, int V, int blank_id, int max_candidates);
+  int begin(hipStream_t s);
+  bool touches(int r0, int nrows) const;
+  int advance(hipStream_t s, const float* lp, int ld, int r0, int nrows, const float* wmax);
+  // pair p = phrase * n_seq + sequence: n_hits [pairs], start / end / score [pairs][max_hits], n_candidates [pairs] (nullable: all
+  // arrivals at or above the threshold, kept or not); raw_* (nullable) [pairs][max_cand]: the kept candidates as the kernel wrote them
+  int finish(hipStream_t s, int max_hits, int32_t* n_hits, int32_t* start, int32_t* end, float* score, int64_t* n_candidates,
+             int32_t* raw_end = nullptr, int32_t* raw_start = nullptr, float* raw_score = nullptr);
+  void release();
+};
+
 }  // namespace rvb
 
 struct rvb_engine {
@@ -273,6 +298,7 @@ struct rvb_engine {
   // ---- forced alignment (rvb_ctc_align) ----
   rvb::CtcAligner aligner;
   rvb::CtcScorer scorer;           // rvb_ctc_score
+  rvb::CtcFinder finder;           // rvb_ctc_find
   rvb::DevBuf align_lp, align_tv, align_ti, align_row, align_col, align_out;   // fp32 [LOGIT_SLAB][V] log-softmax slab; gather scratch
 
   // ---- RCCL communicator of the C-ABI collectives (comm.hip; optional) ----

@@ -2019,6 +2019,7 @@ void rvb_destroy(rvb_engine* e) {
                     &e->enc_after.g, &e->enc_after.b};
   for (DevBuf* b : bufs) b->release();
   e->aligner.release();
+  e->finder.release();
   e->scorer.release();
   for (DevBuf* b : {&e->align_lp, &e->align_tv, &e->align_ti, &e->align_row, &e->align_col, &e->align_out}) b->release();
   e->d_xlse.release(); e->d_xsum.release(); e->d_xtop.release();
@@ -2526,6 +2527,38 @@ int rvb_ctc_score(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens,
   }
   Scope t(e, "ctc_backward");
   return sc.finish_backward(e->stream, occupancy, mean_frame, peak_post, peak_frame);
+}
+
+// Phrase search (csrc/ctc_find.hip) over the same slabs: align_slab leaves the log-probs in align_lp and each row's maximum in
+// align_tv (the same fp32 subtraction, see ctc_align_impl), which is all the kernel reads.  Everything is checked before any device work.
+int rvb_ctc_find(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_phrases, const float* threshold,
+                 const int32_t* first_chunk, const int32_t* n_chunks, int n_seq, int max_candidates, int max_hits, int32_t* n_hits,
+                 int32_t* start, int32_t* end, float* score, int64_t* n_candidates) {
+  static_assert(CTC_FIND_MAX_TOKENS == RVB_CTC_FIND_MAX_TOKENS, "cap of rvb.h");
+  const char* who = "rvb_ctc_find";
+  if (!e) { set_error("rvb_ctc_find: null engine"); return E_ARG; }
+  if (!tokens || !tok_lens || !threshold || !first_chunk || !n_chunks || !n_hits || !start || !end || !score) {
+    set_error("rvb_ctc_find: null argument"); return E_ARG;
+  }
+  if (n_phrases < 1 || n_seq < 1) { set_error("rvb_ctc_find: need n_phrases >= 1 and n_seq >= 1"); return E_ARG; }
+  if (max_candidates < 1 || max_hits < 1) { set_error("rvb_ctc_find: need max_candidates >= 1 and max_hits >= 1"); return E_ARG; }
+  if (e->B <= 0) { set_error("rvb_ctc_find before rvb_encode"); return E_STATE; }
+  const int V = e->cfg.vocab;
+  std::vector<std::vector<int32_t>> seq_rows;
+  RVB_TRY(align_seq_rows(e, who, first_chunk, n_chunks, n_seq, &seq_rows));
+  CtcFinder& fd = e->finder;
+  RVB_TRY(fd.plan(who, tokens, tok_lens, n_phrases, threshold, seq_rows, V, e->cfg.blank_id, max_candidates));
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(wait_slices(e, -1));
+  RVB_TRY(align_workspace(e));
+  RVB_TRY(fd.begin(e->stream));
+  for (const auto& [r0, rows] : align_slabs(e)) {
+    if (!fd.touches(r0, rows)) continue;
+    RVB_TRY(align_slab(e, r0, rows));
+    Scope sc(e, "ctc_find");
+    RVB_TRY(fd.advance(e->stream, e->align_lp.as<float>(), V, r0, rows, e->align_tv.as<float>()));
+  }
+  return fd.finish(e->stream, max_hits, n_hits, start, end, score, n_candidates);
 }
 
 int rvb_ctc_prefix_beam(rvb_engine* e, int beam) {

@@ -192,6 +192,33 @@ int ctc_viterbi_forward(hipStream_t s, const VitSeq* seqs, int n_seq, int max_S,
 // states[frame_off + t] = state of frame t on the best path, score[i] = its fp32 score (-inf: no path)
 int ctc_viterbi_backtrace(hipStream_t s, const VitSeq* seqs, int n_seq, const float* alpha, const uint8_t* bp, int* states, float* score);
 
+// ---------------------------------------------------------------- ctc_find.hip
+// CTC phrase search: every occurrence of short phrases (z = [y0, b, y1, ..., y(L-1)], free start and end, emission lp - row maximum)
+// in the log-probs, one WAVE per (phrase, sequence) pair.  Pair ph * n_seq + sq owns 64 floats of h, 64 ints of st, one count and
+// max_cand candidate slots.
+enum { CTC_FIND_MAX_TOKENS = 32 };               // per phrase: 2 L - 1 = 63 states = the lanes of one wave less one
+constexpr double CTC_FIND_MAX_CANDIDATE_BYTES = 274877906944.0;   // 256 GiB, most of the device's HBM: above it the request is
+                                                                  // refused (E_NOMEM) before anything is allocated
+struct FindSeq {           // one sequence of frames, as the kernel reads it
+  int frame_off, T;        // its frames in rows[]
+  int f0, f1;              // frames this launch advances (f0 == 0: initialise h; else continue from h / st / count in HBM)
+};
+struct FindPhrase {
+  int tok_off, L;          // its tokens: tokens[tok_off .. tok_off + L)
+  float threshold;         // an arrival with a score >= threshold is a candidate (total nats, <= 0; -inf: every arrival)
+  int pad_;
+};
+// advances every pair over the frames [f0, f1) of its sequence: frame f reads row rows[frame_off + f] - r0 of lp ([.., ld] fp32
+// log-probs) and wmax[that row] (the row's maximum).  Candidates (end, start, score) go to the pair's slots in frame order, the
+// first max_cand of them; count[pair] counts them all.
+int ctc_find_advance(hipStream_t s, const FindSeq* seqs, const FindPhrase* phrases, int n_seq, int n_phrases, const float* lp, int ld,
+                     int r0, const int* rows, const int* tokens, int blank, const float* wmax, float* h, int* st, long long* count,
+                     int max_cand, int* cand_end, int* cand_start, float* cand_score);
+// host: non-maximum suppression of one pair's n candidates (by score descending, end ascending, start ascending; kept if its
+// [start, end] meets no kept span; at most max_hits, the best; returned in order of end) -> number of hits
+int ctc_find_suppress(const int32_t* end, const int32_t* start, const float* score, int n, int max_hits, int32_t* out_start,
+                      int32_t* out_end, float* out_score);
+
 // ---------------------------------------------------------------- ctc_forward_backward.hip
 // CTC full-sum score of a known token sequence (CTC.forward, asr/wenet/transformer/ctc.py:65-104) and per-token posteriors, on the
 // lattices, caps and slab-by-slab feed of ctc_viterbi.hip.  The alpha rows of a lattice start 4 * bp_off floats into arows and take

@@ -165,6 +165,17 @@ int rvb_test_ctc_score(const float* lp, int T, int V, const int32_t* tokens, int
 int rvb_test_ctc_score_batch(const float* lp, const int32_t* T, int V, const int32_t* tokens, const int32_t* L, int n_seq, int blank,
                              int slab_rows, double* loglik_out, float* occupancy, float* mean_frame, float* peak_post,
                              int32_t* peak_frame);
+/* ctc_find.hip: phrase search over host log-probs with exactly the kernel and the host code rvb_ctc_find runs.  lp holds the frames
+ * of n_seq sequences concatenated ([sum T][V]; T[i] >= 0), w [sum T] each row's maximum (null: computed on the host from lp);
+ * n_phrases phrases concatenated in `tokens`; threshold [n_phrases]; slab_rows rows per launch (h, st and the counts carried in HBM).
+ * Pair p * n_seq + i.  RAW candidates as the kernel wrote them: raw_count [pairs] (all arrivals at or above the threshold),
+ * raw_end / raw_start / raw_score [pairs][max_candidates] (the first min(count, max_candidates) slots of a pair are written);
+ * hits after suppression: n_hits [pairs], hit_start / hit_end / hit_score [pairs][max_hits].  Refuses what rvb_ctc_find refuses, in
+ * the same words, and a row maximum that is not finite, before any device work; outputs untouched. */
+int rvb_test_ctc_find(const float* lp, const int32_t* T, int n_seq, int V, const float* w, const int32_t* tokens, const int32_t* tok_lens,
+                      int n_phrases, const float* threshold, int blank, int slab_rows, int max_candidates, int max_hits,
+                      int64_t* raw_count, int32_t* raw_end, int32_t* raw_start, float* raw_score, int32_t* n_hits, int32_t* hit_start,
+                      int32_t* hit_end, float* hit_score);
 int rvb_test_fbank(const int16_t* pcm, int64_t n_samples, float* feats /* [frames,80] */);
 /* native prefix beam search on host arrays: top-k log-probs/indices [T,beam] of one utterance */
 int rvb_test_prefix_beam(const float* topk_val, const int32_t* topk_idx, int T, int beam, int blank,

@@ -649,6 +649,48 @@ int rvb_test_ctc_score_batch(const float* lp, const int32_t* T, int V, const int
                        peak_post, peak_frame);
 }
 
+int rvb_test_ctc_find(const float* lp, const int32_t* T, int n_seq, int V, const float* w, const int32_t* tokens, const int32_t* tok_lens,
+                      int n_phrases, const float* threshold, int blank, int slab_rows, int max_candidates, int max_hits,
+                      int64_t* raw_count, int32_t* raw_end, int32_t* raw_start, float* raw_score, int32_t* n_hits, int32_t* hit_start,
+                      int32_t* hit_end, float* hit_score) {
+  const char* who = "rvb_test_ctc_find";
+  const std::string me(who);
+  if (!lp || !T || !tokens || !tok_lens || !threshold || !raw_count || !raw_end || !raw_start || !raw_score || !n_hits || !hit_start ||
+      !hit_end || !hit_score) { set_error(me + ": null argument"); return E_ARG; }
+  if (n_phrases < 1 || n_seq < 1) { set_error(me + ": need n_phrases >= 1 and n_seq >= 1"); return E_ARG; }
+  if (max_candidates < 1 || max_hits < 1) { set_error(me + ": need max_candidates >= 1 and max_hits >= 1"); return E_ARG; }
+  if (slab_rows < 1) { set_error(me + ": need slab_rows >= 1"); return E_ARG; }
+  std::vector<std::vector<int32_t>> rows(n_seq);
+  int64_t total = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    if (T[i] < 0) { set_error(me + ": sequence " + std::to_string(i) + ": negative frame count"); return E_ARG; }
+    rows[i].resize((size_t)T[i]);               // over the cap: plan() refuses on the count alone
+    if (T[i] <= CTC_ALIGN_MAX_FRAMES) for (int t = 0; t < T[i]; ++t) rows[i][t] = (int32_t)(total + t);
+    total += T[i];
+  }
+  CtcFinder fd;
+  T_TRY(fd.plan(who, tokens, tok_lens, n_phrases, threshold, rows, V, blank, max_candidates));
+  const int M = (int)total;
+  std::vector<float> wmax((size_t)M);
+  for (int r = 0; r < M; ++r) {
+    float m = w ? w[r] : -INFINITY;
+    if (!w) for (int v = 0; v < V; ++v) m = std::max(m, lp[(size_t)r * V + v]);
+    if (!std::isfinite(m)) { set_error(me + ": the row maximum of frame " + std::to_string(r) + " is not finite"); return E_ARG; }
+    wmax[r] = m;
+  }
+  T_TRY(need_gpu());
+  Dev dlp, dw;
+  int r = up_raw(dlp, lp, (size_t)M * V * 4);
+  if (r == OK) r = up_raw(dw, wmax.data(), (size_t)M * 4);
+  if (r == OK) r = fd.begin(nullptr);
+  for (int r0 = 0; r == OK && r0 < M; r0 += slab_rows)
+    r = fd.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, std::min(slab_rows, M - r0), (const float*)dw.p + r0);
+  if (r == OK) r = fd.finish(nullptr, max_hits, n_hits, hit_start, hit_end, hit_score, raw_count, raw_end, raw_start, raw_score);
+  if (r != OK) (void)hipDeviceSynchronize();
+  fd.release();
+  return r;
+}
+
 int rvb_test_lse_gather(const float* logits, int R, int V, const int32_t* target, float* out) {
   T_TRY(need_gpu());
   Dev dl, dt, dout;

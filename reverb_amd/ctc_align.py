@@ -175,6 +175,19 @@ class AlignResult:
 
 
 @dataclass
+class Hit:
+    """One occurrence of a phrase (Engine.find / rvb_ctc_find): frames are numbered within the searched sequence (the valid encoder
+    frames of its chunks, concatenated); `chunk` / `frame_in_chunk` place start_frame in the encoded batch.  score is the fp32 path
+    score in nats (<= 0; 0 = the model's greedy labels spell the phrase), score_per_token = score / tokens of the phrase."""
+    start_frame: int
+    end_frame: int                    # the first frame of the last token
+    score: float
+    score_per_token: float
+    chunk: int
+    frame_in_chunk: int
+
+
+@dataclass
 class DecodeLike:
     """What get_output reads of a DecodeResult."""
     tokens: List[int]

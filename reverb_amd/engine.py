@@ -456,6 +456,61 @@ class Engine:
             t0 += n; f0 += frames[i]
         return out
 
+    def find(self, phrases, chunk_ranges=None, min_score=-1.0, max_hits=64, max_candidates=None):
+        """Phrase search (rvb_ctc_find, csrc/ctc_find.hip): EVERY occurrence of each token phrase (1 .. 32 ids, none the blank) in the
+        chunks of the last encode().  Sequence i covers the chunks chunk_ranges[i] = (first, count); the default is ONE sequence
+        over the whole batch, so a hit may straddle a chunk boundary.  A frame costs what the phrase's label loses against the
+        model's own best label there, so a score of 0 means the greedy labels spell the phrase.  min_score is in nats PER TOKEN:
+        a phrase of L tokens keeps the occurrences with score >= float32(min_score * L) (-inf: every arrival).  Overlapping
+        occurrences of one phrase in one sequence are suppressed, best first; at most max_hits per phrase and sequence.
+        -> hits[phrase][sequence] = List[Hit], in order of end_frame; frames are numbered within the sequence.
+        The device keeps max_candidates candidates per phrase and sequence (default: 4 max_hits, at least 256); if more arrive the
+        call is repeated ONCE with the largest count reported, and RvbError is raised if that still overflows."""
+        from .ctc_align import Hit
+        seqs = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in phrases]
+        if not seqs:
+            raise RvbError("find: at least one phrase")
+        if chunk_ranges is None:
+            chunk_ranges = [(0, self.batch)]
+        lens = self.encoder_lens()
+        first = np.array([r[0] for r in chunk_ranges], np.int32)
+        count = np.array([r[1] for r in chunk_ranges], np.int32)
+        tok = np.ascontiguousarray(np.concatenate(seqs) if sum(map(len, seqs)) else np.zeros(1, np.int32), np.int32)
+        tl = np.array([len(t) for t in seqs], np.int32)
+        thr = np.array([np.float32(min_score * len(t)) for t in seqs], np.float32)
+        thr[np.isnan(thr) & (tl == 0)] = 0.0                 # -inf * 0: the empty phrase is refused below, by its own name
+        n_p, n_s, max_hits = len(seqs), len(chunk_ranges), int(max_hits)
+        cap = int(max_candidates) if max_candidates is not None else max(4 * max_hits, 256)
+        n_hits = np.zeros(max(n_p * n_s, 1), np.int32)
+        start, end = (np.zeros(max(n_p * n_s * max(max_hits, 1), 1), np.int32) for _ in range(2))
+        score = np.zeros(start.size, np.float32)
+        n_cand = np.zeros(n_hits.size, np.int64)
+        self.last_find = {"calls": 0, "max_candidates": cap}
+        for attempt in range(2):
+            check(self.lib.rvb_ctc_find(self.handle, iptr(tok), iptr(tl), n_p, fptr(thr), iptr(first), iptr(count), n_s, cap, max_hits,
+                                        iptr(n_hits), iptr(start), iptr(end), fptr(score), n_cand.ctypes.data_as(_lib._i64p)), "rvb_ctc_find")
+            self.last_find = {"calls": attempt + 1, "max_candidates": cap}
+            worst = int(n_cand.max())
+            if worst <= cap:
+                break
+            if attempt == 1:
+                raise RvbError(f"find: {worst} candidates of one phrase and sequence still exceed the cap of {cap} after one retry")
+            cap = worst
+        out = []
+        for p, t in enumerate(seqs):
+            per_seq = []
+            for i in range(n_s):
+                k = p * n_s + i
+                ends = np.cumsum(lens[first[i]:first[i] + count[i]])
+                hits = []
+                for j in range(int(n_hits[k])):
+                    b, e, v = int(start[k * max_hits + j]), int(end[k * max_hits + j]), float(score[k * max_hits + j])
+                    c = int(np.searchsorted(ends, b, side="right"))
+                    hits.append(Hit(b, e, v, v / len(t), int(first[i]) + c, b - (int(ends[c - 1]) if c else 0)))
+                per_seq.append(hits)
+            out.append(per_seq)
+        return out
+
     def score(self, token_seqs, chunk_ranges=None, posteriors=False, attention=False, reverse_weight=None, lsm_weight=None,
               ctc_weight=None):
         """Full-sum CTC score (rvb_ctc_score; reference: CTC.forward, transformer/ctc.py:65-104 = -CTCLoss(reduction='sum')) of known

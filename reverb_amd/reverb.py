@@ -378,6 +378,71 @@ class ReverbASR:
                 out[key] = att[key]
         return out
 
+    def find(self, audio_file, phrases: Optional[List[str]] = None, phrase_file: Optional[str] = None, min_score: float = -1.0,
+             max_hits: int = 64, verbatimicity: float = 1.0, chunk_size: int = 2051, timings_adjustment: float = 230):
+        """Where in the audio are these phrases spoken?  Exactly one of `phrases` (texts) or `phrase_file` (one phrase per line, empty
+        lines skipped); each is cut into tokens as the hot words of a context list are (context_graph.tokenize_lines) and searched
+        with Engine.find: every occurrence whose score per token is at least min_score (nats; 0 = the model's own best labels
+        spell the phrase), overlapping occurrences of a phrase suppressed best first, at most max_hits per phrase and batch.
+        The file is encoded batch by batch (the engine's max_chunks) and each batch searched as ONE sequence, its frames offset by
+        the batches before it: a hit may straddle chunks, but an occurrence that straddles two BATCHES is not found.
+        -> one dict per phrase: phrase, tokens, hits = [{start, end (seconds: start_frame and end_frame + 1 through the frame -> ms
+        conversion of align's json, shifted earlier by up to timings_adjustment ms), start_frame, end_frame (within the file),
+        score, score_per_token, confidence = exp(score_per_token)}] in order of time.  end is the end of the FIRST frame of the
+        last token (token times inside a hit are not computed)."""
+        from .context_graph import tokenize_lines
+        if (phrases is None) == (phrase_file is None):
+            raise ValueError("find: give exactly one of phrases= (texts) or phrase_file=")
+        if phrase_file is not None:
+            with open(phrase_file, encoding="utf-8") as f:
+                phrases = [line.strip() for line in f if line.strip()]
+        if not phrases:
+            raise ValueError("find: no phrase given")
+        fc = self.test_conf["fbank_conf"]
+        if (fc["num_mel_bins"], fc["frame_length"], fc["frame_shift"]) != (80, 25, 10):
+            raise NotImplementedError("the device fbank is built for 80 bins / 25 ms / 10 ms")
+        if chunk_size < 7:
+            raise ValueError("chunk_size must be at least 7 frames (Conv2dSubsampling4 needs 7 input frames, subsampling.py:201-226)")
+        tc = self.configs["tokenizer_conf"]
+        char = self.configs.get("tokenizer", "rev_bpe") == "char"
+        ids = tokenize_lines(phrases, self.tokenizer.symbol_table, None if char else tc["bpe_path"] or "")
+        for text, t in zip(phrases, ids):
+            if not t:
+                raise ValueError(f"find: the phrase {text!r} has no token in the model's table")
+        eng = self._engine_for_chunk(chunk_size)
+        eng.upload_pcm(*self._load_pcm(audio_file, 16000))
+        eng.set_cat_embs([verbatimicity, 1.0 - verbatimicity])
+        eng.apply_decoding_chunk(-1, -1)
+        n_frames = eng.fbank()
+        n_chunks = -(-n_frames // chunk_size)
+        out = [{"phrase": text, "tokens": [int(x) for x in t], "hits": []} for text, t in zip(phrases, ids)]
+        frame0 = 0                                            # encoder frames of the batches before this one
+        for c0 in range(0, n_chunks, eng.cfg.max_chunks):
+            nb = min(eng.cfg.max_chunks, n_chunks - c0)
+            lens = np.full(nb, chunk_size, np.int32)
+            if c0 + nb == n_chunks:
+                lens[-1] = n_frames - (n_chunks - 1) * chunk_size
+            eng.encode(None, lens, 1, 0.0, first_chunk=c0, T0=chunk_size)
+            found = eng.find(ids, [(0, nb)], min_score, max_hits)
+            for rec, t, per_seq in zip(out, ids, found):
+                for h in per_seq[0]:
+                    ec, et = self._chunk_frame(eng, h.end_frame)
+                    start_ms = (c0 + h.chunk) * chunk_size * self.input_frame_length + h.frame_in_chunk * self.output_frame_length
+                    end_ms = (c0 + ec) * chunk_size * self.input_frame_length + (et + 1) * self.output_frame_length
+                    move = min(timings_adjustment, start_ms)
+                    rec["hits"].append({"start": (start_ms - move) / 1000.0, "end": (end_ms - move) / 1000.0,
+                                        "start_frame": frame0 + h.start_frame, "end_frame": frame0 + h.end_frame, "score": h.score,
+                                        "score_per_token": h.score_per_token, "confidence": float(np.exp(h.score_per_token))})
+            frame0 += int(eng.encoder_lens().sum())
+        return out
+
+    @staticmethod
+    def _chunk_frame(eng: Engine, frame: int):
+        """frame of the one sequence over the encoded batch -> (chunk, frame inside it)"""
+        ends = np.cumsum(eng.encoder_lens())
+        c = int(np.searchsorted(ends, frame, side="right"))
+        return c, frame - (int(ends[c - 1]) if c else 0)
+
     def _engine_for_chunk(self, chunk_size: int) -> Engine:
         """The reference accepts any --chunk_size (cli/reverb.py:188, recognize_wav.py:66-70).  The engine sizes its
         positional tables and workspace for `chunk_frames` input frames per chunk: smaller chunks run on the same
