@@ -243,6 +243,36 @@ int rvb_ctc_align_wild(rvb_engine* e, const int32_t* tokens, const int32_t* tok_
                        const int32_t* n_chunks, float wildcard_bias, int32_t* labels, int32_t* begin, int32_t* end, int32_t* peak,
                        float* confidence, float* score);
 
+/* rvb_ctc_align_wild for a transcript with ALTERNATIVES and OPTIONAL words: each sequence is a left-to-right token GRAPH, and one
+ * Viterbi pass (csrc/ctc_graph.hip) picks the reading that was spoken and aligns it.  Sequence i has n_nodes[i] >= 1 nodes in
+ * topological order (node_tokens, is_final: concatenated over the sequences).  Node j has a label (a vocab id other than the blank,
+ * or RVB_CTC_WILDCARD) and an ordered, duplicate-free predecessor list preds[pred_off[j] .. pred_off[j + 1]) of at least one entry,
+ * each a node index < j or -1 for "start"; pred_off holds n_nodes[i] + 1 offsets per sequence (concatenated; the offsets count
+ * within the sequence's own predecessors, whose lists are concatenated in `preds`).  At least one node is final and at least one
+ * has a start predecessor.  Lattice states: B_start (the leading blank) and per node T_j (emits the label; a wildcard emits
+ * w[t] + wildcard_bias as in rvb_ctc_align_wild) and B_j (the blank after it).  Frame 0: B_start, and T_j where -1 is a predecessor.
+ * Frame t >= 1, candidates in order, the FIRST maximum wins: B_start: stay; B_j: stay, T_j; T_j: stay, then per predecessor in list
+ * order B_pred (B_start for -1), then T_pred if the predecessor is a node of another label (two wildcards are one label).  The path
+ * ends in the best of B_f, T_f over the final nodes in ascending order, first maximum.  On a chain (pred[j] = {j - 1}, pred[0] =
+ * {-1}, the last node final) every output is bit-identical to rvb_ctc_align_wild's.
+ * Outputs (each nullable): labels / frame_node [sum of the sequences' frames]: per frame the label (blank id on a blank) and the
+ * node index within the sequence (-1 on a blank); path_len [n_seq] = nodes on the chosen path; path_nodes / begin / end / peak /
+ * confidence: per path position, sequence i's starting at its node offset (sum of n_nodes[..i)), as rvb_ctc_align defines them per
+ * token; score [n_seq].  Refused by name with sequence and node (RVB_E_ARG), writing nothing: an empty graph, a label outside
+ * [0, vocab) that is not the wildcard, a blank label, a predecessor >= j or < -1, a duplicate predecessor, an empty list, no final
+ * node, no start predecessor, a bias that is positive or not finite, a chunk range outside the batch, a graph no path of which
+ * the frames can emit with a finite score.  Caps per graph (RVB_E_UNSUPPORTED, before any device work;
+ * rvb_ctc_align_graph_limits), frames as RVB_CTC_ALIGN_MAX_FRAMES; back-pointers take 1 byte per frame and node of device memory
+ * (RVB_E_NOMEM naming the bytes if they do not fit): */
+#define RVB_CTC_GRAPH_MAX_NODES 8192        /* every node's scores of two frames live in one workgroup's LDS (128 KiB of 160) */
+#define RVB_CTC_GRAPH_MAX_IN_DEGREE 64      /* the winning predecessor's index takes 7 bits of the back-pointer byte */
+#define RVB_CTC_GRAPH_MAX_ARCS 32768        /* predecessors of all nodes of one graph */
+int rvb_ctc_align_graph(rvb_engine* e, const int32_t* node_tokens, const int32_t* n_nodes, const int32_t* pred_off,
+                        const int32_t* preds, const uint8_t* is_final, int n_seq, const int32_t* first_chunk, const int32_t* n_chunks,
+                        float wildcard_bias, int32_t* labels, int32_t* frame_node, int32_t* path_len, int32_t* path_nodes,
+                        int32_t* begin, int32_t* end, int32_t* peak, float* confidence, float* score);
+int rvb_ctc_align_graph_limits(int32_t* max_nodes, int32_t* max_in_degree, int32_t* max_arcs, int32_t* max_frames);
+
 /* Full-sum CTC score of a KNOWN transcript: log p(tokens | frames) summed over every alignment, the quantity the reference calls
  * the CTC loss (CTC.forward, asr/wenet/transformer/ctc.py:65-104 = torch.nn.CTCLoss(reduction='sum') over
  * log_softmax(ctc_lo(encoder_out)), reported by bin/get_loss.py): loglik = -loss.  Valid after rvb_encode / rvb_stream_finish; the
@@ -426,7 +456,8 @@ int rvb_comm_destroy(rvb_engine* e);
 /* Stage timing (HIP events on the engine stream).  level 1: every kernel family is bracketed;
  * names: "fbank","subsample","gemm","attention","rownorm","glu_dwconv","ctc_topk","embed",
  * "lse_gather" (the row kernel after the decoders' output layer: rescoring and rvb_attention_score),"search_host","ctc_align_lp" (rvb_ctc_align: CTC head + log-softmax),"ctc_viterbi" (its
- * forward pass + back-trace),"ctc_forward" / "ctc_backward" (rvb_ctc_score: the two sweeps),"ctc_find" (rvb_ctc_find: the search kernel).  level 2: only the GEMM launches (the dominant kernel; half the
+ * forward pass + back-trace),"ctc_forward" / "ctc_backward" (rvb_ctc_score: the two sweeps),"ctc_find" (rvb_ctc_find: the search kernel),"ctc_graph" (rvb_ctc_align_graph:
+ * forward pass + back-trace).  level 2: only the GEMM launches (the dominant kernel; half the
  * events, ~1 % less perturbation of the step).  level 0: off.
  * flops: algorithmic FLOPs launched (gemm/attention only). */
 int rvb_set_profiling(rvb_engine* e, int level);

@@ -49,6 +49,7 @@ _f64p = C.POINTER(C.c_double)
 _i32p = C.POINTER(C.c_int32)
 _i16p = C.POINTER(C.c_int16)
 _i64p = C.POINTER(C.c_int64)
+_u8p = C.POINTER(C.c_uint8)
 _eng = C.c_void_p
 
 # every exported symbol of include/rvb.h: name -> (restype, argtypes)
@@ -92,6 +93,9 @@ SIGNATURES = {
     "rvb_ctc_align": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _f32p, _f32p]),
     "rvb_ctc_align_wild": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, _i32p, C.c_float, _i32p, _i32p, _i32p, _i32p, _f32p, _f32p]),
     "rvb_ctc_align_limits": (C.c_int, [_i32p, _i32p]),
+    "rvb_ctc_align_graph": (C.c_int, [_eng, _i32p, _i32p, _i32p, _i32p, _u8p, C.c_int, _i32p, _i32p, C.c_float, _i32p, _i32p, _i32p, _i32p,
+                                      _i32p, _i32p, _i32p, _f32p, _f32p]),
+    "rvb_ctc_align_graph_limits": (C.c_int, [_i32p, _i32p, _i32p, _i32p]),
     "rvb_ctc_score": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, _i32p, _f64p, _f32p, _f32p, _f32p, _i32p]),
     "rvb_ctc_find": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _f32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f32p,
                                _i64p]),
@@ -194,6 +198,8 @@ TEST_SIGNATURES = {
     "rvb_test_lse_gather": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, _f32p]),
     "rvb_test_ctc_viterbi": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _f32p]),
     "rvb_test_ctc_viterbi_wild": (C.c_int, [_f32p, C.c_int, C.c_int, _f32p, C.c_float, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _f32p]),
+    "rvb_test_ctc_viterbi_graph": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, _f32p, C.c_float, _i32p, _i32p, _i32p, _i32p, _u8p, C.c_int,
+                                             C.c_int, _i32p, _i32p, _f32p]),
     "rvb_test_ctc_score": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, _f64p, _f32p, _f32p, _f32p, _i32p]),
     "rvb_test_ctc_score_batch": (C.c_int, [_f32p, _i32p, C.c_int, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _f64p, _f32p, _f32p, _f32p,
                                            _i32p]),
@@ -342,6 +348,12 @@ def iptr(a):
     if a is None:
         return None
     return a.ctypes.data_as(_i32p)
+
+
+def u8ptr(a):
+    if a is None:
+        return None
+    return a.ctypes.data_as(_u8p)
 
 
 def dptr(a):

@@ -4,7 +4,8 @@ log-softmax, force_align, one `<key> [labels]` line per utterance) for one audio
 the transcript (the reference's bin/get_loss.py reports its negative as loss_ctc); with --attention that file also carries the
 attention decoders' loss_att and acc_att and the combined loss.  --wildcard TOKEN marks, in the transcript, audio that nobody
 transcribed: the aligner gives each marker the frames the rest of the transcript does not explain (at least one), and the marker
-shows up in the result as a word / label / token of its own.  Praat .lab / TextGrid output (--gen_praat there) is not written."""
+shows up in the result as a word / label / token of its own.  --alternatives reads choices and optional words in the transcript,
+`it is {twenty|two zero} [um] goodbye`, and aligns the reading that was spoken.  Praat .lab / TextGrid output (--gen_praat there) is not written."""
 from __future__ import annotations
 
 import argparse
@@ -39,10 +40,14 @@ def get_args(argv=None):
                    help="a marker in the transcript, such as '<star>', that stands for audio left untranscribed")
     p.add_argument("--wildcard_bias", type=float, default=0.0,
                    help="penalty (<= 0, nats per frame) on wildcard frames: the misfit above which a marker is preferred to the transcript")
+    p.add_argument("--alternatives", action="store_true",
+                   help="the transcript holds choices {a|b c|} and optional words [x]: align the reading that was spoken")
     p.add_argument("--reverse_weight", type=float, default=None, help="weight of the right-to-left decoder in loss_att (default: the config's)")
     args = p.parse_args(argv)
     if args.wildcard is not None and (args.score or args.posteriors):
         p.error("--wildcard: the full-sum score (--score, --posteriors) is not defined for a transcript with gaps")
+    if args.alternatives and (args.score or args.posteriors):
+        p.error("--alternatives: the full-sum score (--score, --posteriors) is not defined for a transcript with alternatives")
     if not args.wildcard_bias <= 0:
         p.error("--wildcard_bias must be <= 0")
     return args
@@ -64,7 +69,7 @@ def main(argv=None):
     out = reverb.align(args.audio_file, transcript=transcript, format=args.format, verbatimicity=args.verbatimicity,
                        chunk_size=args.chunk_size, timings_adjustment=args.timings_adjustment,
                        posteriors=args.posteriors and args.format == "json", wildcard=args.wildcard,
-                       wildcard_bias=args.wildcard_bias)
+                       wildcard_bias=args.wildcard_bias, alternatives=args.alternatives)
     if args.format == "json":
         out = json.dumps(out, ensure_ascii=False, indent=1)
     os.makedirs(args.result_dir, exist_ok=True)

@@ -162,6 +162,27 @@ struct CtcAligner {
   void release();
 };
 
+// ---- alignment over a token graph (ctc_graph.hip): CtcAligner's plan / begin / touches / advance / finish / release for lattices
+// with alternatives, shared by rvb_ctc_align_graph and the lab hook.  plan() takes the graphs as the C ABI does (pred_off: n_nodes + 1
+// offsets per sequence, concatenated, within the sequence's predecessors), refuses by sequence and node, and encodes the arcs.
+struct CtcGraphAligner {
+  std::vector<GraphSeq> seq;
+  std::vector<int32_t> h_tokens, h_arc_off, h_finals, h_rows;
+  std::vector<uint32_t> h_arcs;
+  int max_N = 0, blank = 0;
+  bool has_wild = false;                           // some node of the plan is a wildcard: advance() needs the row maxima
+  size_t alpha_floats = 0, bp_bytes = 0;
+  int64_t total_frames = 0;
+  DevBuf d_tokens, d_arc_off, d_arcs, d_finals, d_rows, d_seqs, d_alpha, d_bp, d_states, d_score;
+  int plan(const char* who, const int32_t* node_tokens, const int32_t* n_nodes, const int32_t* pred_off, const int32_t* preds,
+           const uint8_t* is_final, int n_seq, const std::vector<std::vector<int32_t>>& seq_rows, int V, int blank_id);
+  int begin(hipStream_t s);
+  bool touches(int r0, int nrows) const;
+  int advance(hipStream_t s, const float* lp, int ld, int r0, int nrows, const float* wmax = nullptr, float bias = 0.f);
+  int finish(hipStream_t s, int32_t* states /* [total_frames]: 2 * slot + token bit */, float* score /* [n_seq] */);
+  void release();
+};
+
 // ---- full-sum scoring (ctc_forward_backward.hip): the host side shared by rvb_ctc_score and the lab hook.  The lattices are the
 // aligner's: plan() is CtcAligner::plan (same checks, refusals and layout).  begin() allocates (with posteriors: the alpha rows, or
 // E_NOMEM naming their size), advance() runs the forward kernel over a slab (slabs in row order), finish_forward() returns loglik;
@@ -299,6 +320,7 @@ struct rvb_engine {
   rvb::CtcAligner aligner;
   rvb::CtcScorer scorer;           // rvb_ctc_score
   rvb::CtcFinder finder;           // rvb_ctc_find
+  rvb::CtcGraphAligner graph_aligner;   // rvb_ctc_align_graph
   rvb::DevBuf align_lp, align_tv, align_ti, align_row, align_col, align_out;   // fp32 [LOGIT_SLAB][V] log-softmax slab; gather scratch
 
   // ---- RCCL communicator of the C-ABI collectives (comm.hip; optional) ----

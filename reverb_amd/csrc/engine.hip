@@ -2019,6 +2019,7 @@ void rvb_destroy(rvb_engine* e) {
                     &e->enc_after.g, &e->enc_after.b};
   for (DevBuf* b : bufs) b->release();
   e->aligner.release();
+  e->graph_aligner.release();
   e->finder.release();
   e->scorer.release();
   for (DevBuf* b : {&e->align_lp, &e->align_tv, &e->align_ti, &e->align_row, &e->align_col, &e->align_out}) b->release();
@@ -2371,6 +2372,43 @@ static std::vector<std::pair<int, int>> align_slabs(const rvb_engine* e) {
   return slabs;
 }
 
+// lp[t][label[t]] of every frame of every lattice (spans: {frame_off, T} into rows / lab): the slabs once more, one gather_pairs per
+// slab.  A wildcard frame's emission is the row maximum, what it emitted less the bias.
+static int align_emissions(rvb_engine* e, const std::vector<std::pair<int, int>>& slabs, const std::vector<std::pair<int, int>>& spans,
+                           const std::vector<int32_t>& h_rows, const std::vector<int32_t>& lab, bool has_wild, std::vector<float>* emit_out) {
+  const int V = e->cfg.vocab, blank = e->cfg.blank_id;
+  std::vector<float>& emit = *emit_out;
+  emit.resize(lab.size());
+  std::vector<int32_t> grow, gcol, gidx;
+  std::vector<float> gout, wrow;
+  for (const auto& [r0, rows] : slabs) {
+    grow.clear(); gcol.clear(); gidx.clear();
+    for (const auto& [frame_off, T] : spans) {
+      const int32_t* rw = h_rows.data() + frame_off;
+      for (int f = (int)(std::lower_bound(rw, rw + T, r0) - rw); f < T && rw[f] < r0 + rows; ++f) {
+        const int32_t l = lab[frame_off + f];
+        grow.push_back(rw[f] - r0); gcol.push_back(l == RVB_CTC_WILDCARD ? blank : l); gidx.push_back(frame_off + f);
+      }
+    }
+    if (grow.empty()) continue;
+    RVB_TRY(align_slab(e, r0, rows));
+    RVB_TRY(upload_i32(e, e->align_row, grow.data(), grow.size()));
+    RVB_TRY(upload_i32(e, e->align_col, gcol.data(), gcol.size()));
+    RVB_TRY(e->align_out.ensure(grow.size() * 4));
+    RVB_TRY(gather_pairs(e->stream, e->align_lp.as<float>(), (size_t)V, e->align_row.as<int>(), e->align_col.as<int>(), (int)grow.size(),
+                         e->align_out.as<float>()));
+    gout.resize(grow.size());
+    RVB_HIP_CHECK(hipMemcpyAsync(gout.data(), e->align_out.p, grow.size() * 4, hipMemcpyDeviceToHost, e->stream));
+    if (has_wild) {
+      wrow.resize(rows);
+      RVB_HIP_CHECK(hipMemcpyAsync(wrow.data(), e->align_tv.p, (size_t)rows * 4, hipMemcpyDeviceToHost, e->stream));
+    }
+    RVB_HIP_CHECK(hipStreamSynchronize(e->stream));     // also: grow / gcol may be rewritten
+    for (size_t k = 0; k < gidx.size(); ++k) emit[gidx[k]] = lab[gidx[k]] == RVB_CTC_WILDCARD ? wrow[grow[k]] : gout[k];
+  }
+  return OK;
+}
+
 int rvb_ctc_align_limits(int32_t* max_tokens, int32_t* max_frames) {
   if (max_tokens) *max_tokens = CTC_ALIGN_MAX_TOKENS;
   if (max_frames) *max_frames = CTC_ALIGN_MAX_FRAMES;
@@ -2424,36 +2462,9 @@ static int ctc_align_impl(const char* who, bool wild, float bias, rvb_engine* e,
   if (!begin && !end && !peak && !confidence) return OK;
   std::vector<float> emit;
   if (peak || confidence) {
-    // lp[t][label[t]] of every frame: the slabs once more, one gather_pairs per slab
-    emit.resize(lab.size());
-    std::vector<int32_t> grow, gcol, gidx;
-    std::vector<float> gout, wrow;                        // wrow: the slab's row maxima, what a wildcard frame emitted less the bias
-    for (const auto& [r0, rows] : slabs) {
-      grow.clear(); gcol.clear(); gidx.clear();
-      for (int i = 0; i < n_seq; ++i) {
-        const VitSeq& q = al.seq[i];
-        const int32_t* rw = al.h_rows.data() + q.frame_off;
-        for (int f = (int)(std::lower_bound(rw, rw + q.T, r0) - rw); f < q.T && rw[f] < r0 + rows; ++f) {
-          const int32_t l = lab[q.frame_off + f];
-          grow.push_back(rw[f] - r0); gcol.push_back(l == RVB_CTC_WILDCARD ? blank : l); gidx.push_back(q.frame_off + f);
-        }
-      }
-      if (grow.empty()) continue;
-      RVB_TRY(align_slab(e, r0, rows));
-      RVB_TRY(upload_i32(e, e->align_row, grow.data(), grow.size()));
-      RVB_TRY(upload_i32(e, e->align_col, gcol.data(), gcol.size()));
-      RVB_TRY(e->align_out.ensure(grow.size() * 4));
-      RVB_TRY(gather_pairs(e->stream, e->align_lp.as<float>(), (size_t)V, e->align_row.as<int>(), e->align_col.as<int>(), (int)grow.size(),
-                           e->align_out.as<float>()));
-      gout.resize(grow.size());
-      RVB_HIP_CHECK(hipMemcpyAsync(gout.data(), e->align_out.p, grow.size() * 4, hipMemcpyDeviceToHost, e->stream));
-      if (al.has_wild) {
-        wrow.resize(rows);
-        RVB_HIP_CHECK(hipMemcpyAsync(wrow.data(), e->align_tv.p, (size_t)rows * 4, hipMemcpyDeviceToHost, e->stream));
-      }
-      RVB_HIP_CHECK(hipStreamSynchronize(e->stream));     // also: grow / gcol may be rewritten
-      for (size_t k = 0; k < gidx.size(); ++k) emit[gidx[k]] = lab[gidx[k]] == RVB_CTC_WILDCARD ? wrow[grow[k]] : gout[k];
-    }
+    std::vector<std::pair<int, int>> spans;
+    for (const VitSeq& q : al.seq) spans.push_back({q.frame_off, q.T});
+    RVB_TRY(align_emissions(e, slabs, spans, al.h_rows, lab, al.has_wild, &emit));
   }
   for (int i = 0; i < n_seq; ++i) {
     const VitSeq& q = al.seq[i];
@@ -2488,6 +2499,97 @@ int rvb_ctc_align_wild(rvb_engine* e, const int32_t* tokens, const int32_t* tok_
                        float* confidence, float* score) {
   return ctc_align_impl("rvb_ctc_align_wild", true, wildcard_bias, e, tokens, tok_lens, n_seq, first_chunk, n_chunks, labels, begin,
                         end, peak, confidence, score);
+}
+
+// Alignment over token graphs (ctc_graph.hip): the slabs, the wildcard's emission and the second sweep for the confidences are those
+// of ctc_align_impl; what differs is the lattice and that the per-token outputs follow the chosen path.
+int rvb_ctc_align_graph_limits(int32_t* max_nodes, int32_t* max_in_degree, int32_t* max_arcs, int32_t* max_frames) {
+  if (max_nodes) *max_nodes = CTC_GRAPH_MAX_NODES;
+  if (max_in_degree) *max_in_degree = CTC_GRAPH_MAX_IN_DEGREE;
+  if (max_arcs) *max_arcs = CTC_GRAPH_MAX_ARCS;
+  if (max_frames) *max_frames = CTC_ALIGN_MAX_FRAMES;
+  return OK;
+}
+
+int rvb_ctc_align_graph(rvb_engine* e, const int32_t* node_tokens, const int32_t* n_nodes, const int32_t* pred_off, const int32_t* preds,
+                        const uint8_t* is_final, int n_seq, const int32_t* first_chunk, const int32_t* n_chunks, float wildcard_bias,
+                        int32_t* labels, int32_t* frame_node, int32_t* path_len, int32_t* path_nodes, int32_t* begin, int32_t* end,
+                        int32_t* peak, float* confidence, float* score) {
+  static_assert(CTC_GRAPH_MAX_NODES == RVB_CTC_GRAPH_MAX_NODES && CTC_GRAPH_MAX_IN_DEGREE == RVB_CTC_GRAPH_MAX_IN_DEGREE &&
+                CTC_GRAPH_MAX_ARCS == RVB_CTC_GRAPH_MAX_ARCS, "caps of rvb.h");
+  const std::string w("rvb_ctc_align_graph");
+  if (!e) { set_error(w + ": null engine"); return E_ARG; }
+  if (!node_tokens || !n_nodes || !pred_off || !preds || !is_final || !first_chunk || !n_chunks || n_seq <= 0) {
+    set_error(w + ": null argument or n_seq <= 0");
+    return E_ARG;
+  }
+  if (!(std::isfinite(wildcard_bias) && wildcard_bias <= 0.f)) { set_error(w + ": wildcard_bias must be finite and <= 0"); return E_ARG; }
+  if (e->B <= 0) { set_error(w + " before rvb_encode"); return E_STATE; }
+  const int V = e->cfg.vocab, blank = e->cfg.blank_id;
+  std::vector<std::vector<int32_t>> seq_rows;
+  RVB_TRY(align_seq_rows(e, w.c_str(), first_chunk, n_chunks, n_seq, &seq_rows));
+  CtcGraphAligner& al = e->graph_aligner;
+  RVB_TRY(al.plan(w.c_str(), node_tokens, n_nodes, pred_off, preds, is_final, n_seq, seq_rows, V, blank));
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(wait_slices(e, -1));
+  RVB_TRY(align_workspace(e));
+  const std::vector<std::pair<int, int>> slabs = align_slabs(e);
+  RVB_TRY(al.begin(e->stream));
+  for (const auto& [r0, rows] : slabs) {
+    if (!al.touches(r0, rows)) continue;
+    RVB_TRY(align_slab(e, r0, rows));
+    Scope sc(e, "ctc_graph");
+    RVB_TRY(al.advance(e->stream, e->align_lp.as<float>(), V, r0, rows, e->align_tv.as<float>(), wildcard_bias));   // align_tv: the row maxima
+  }
+  std::vector<int32_t> states((size_t)al.total_frames);
+  std::vector<float> sc_host(n_seq);
+  {
+    Scope sc(e, "ctc_graph");
+    RVB_TRY(al.finish(e->stream, states.data(), sc_host.data()));
+  }
+  std::vector<int32_t> lab(states.size()), node(states.size());
+  for (int i = 0; i < n_seq; ++i) {
+    const GraphSeq& q = al.seq[i];
+    for (int t = 0; t < q.T; ++t) {
+      const int st = states[q.frame_off + t], j = (st >> 1) - 1;
+      node[q.frame_off + t] = (st & 1) ? j : -1;
+      lab[q.frame_off + t] = (st & 1) ? node_tokens[q.node_off + j] : blank;
+    }
+  }
+  std::vector<float> emit;
+  if (peak || confidence) {
+    std::vector<std::pair<int, int>> spans;
+    for (const GraphSeq& q : al.seq) spans.push_back({q.frame_off, q.T});
+    RVB_TRY(align_emissions(e, slabs, spans, al.h_rows, lab, al.has_wild, &emit));
+  }
+  // nothing was written so far: a refusal leaves every output untouched
+  if (score) memcpy(score, sc_host.data(), (size_t)n_seq * 4);
+  if (labels) memcpy(labels, lab.data(), lab.size() * 4);
+  if (frame_node) memcpy(frame_node, node.data(), node.size() * 4);
+  for (int i = 0; i < n_seq; ++i) {
+    const GraphSeq& q = al.seq[i];
+    int n_path = 0;
+    for (int t = 0; t < q.T;) {
+      const int j = node[q.frame_off + t];
+      int t1 = t;
+      while (t1 + 1 < q.T && node[q.frame_off + t1 + 1] == j) ++t1;
+      if (j >= 0) {
+        const int k = q.node_off + n_path++;
+        if (path_nodes) path_nodes[k] = j;
+        if (begin) begin[k] = t;
+        if (end) end[k] = t1;
+        if (peak || confidence) {
+          int pk = t;
+          for (int u = t + 1; u <= t1; ++u) if (emit[q.frame_off + u] > emit[q.frame_off + pk]) pk = u;
+          if (peak) peak[k] = pk;
+          if (confidence) confidence[k] = std::exp(emit[q.frame_off + pk]);
+        }
+      }
+      t = t1 + 1;
+    }
+    if (path_len) path_len[i] = n_path;
+  }
+  return OK;
 }
 
 // Full-sum score (CTC.forward, transformer/ctc.py:65-104) over the same slabs: a forward sweep, and for per-token outputs the slabs

@@ -192,6 +192,33 @@ int ctc_viterbi_forward(hipStream_t s, const VitSeq* seqs, int n_seq, int max_S,
 // states[frame_off + t] = state of frame t on the best path, score[i] = its fp32 score (-inf: no path)
 int ctc_viterbi_backtrace(hipStream_t s, const VitSeq* seqs, int n_seq, const float* alpha, const uint8_t* bp, int* states, float* score);
 
+// ---------------------------------------------------------------- ctc_graph.hip
+// CTC forced alignment over a token graph (alternatives, optional words): one workgroup per lattice, every node's {T, B} of the last
+// frame published in LDS.  Caps (refused with E_UNSUPPORTED before any device work):
+enum { CTC_GRAPH_MAX_NODES = 8192,               // per graph: 2 x 8193 x 8 bytes of LDS = 128 KiB, 1024 threads x 8 nodes
+       CTC_GRAPH_MAX_IN_DEGREE = 64,             // per node: the winner's index fits 7 bits of the back-pointer byte
+       CTC_GRAPH_MAX_ARCS = 32768 };             // per graph
+struct GraphSeq {          // one lattice of a batch, as the kernels read it
+  int N, T;                // nodes, frames
+  int index;               // its position in the batch: its N + 1 arc offsets start at arc_off[node_off + index]
+  int node_off;            // its labels: node_tok[node_off .. node_off + N)
+  int arc_off;             // its arcs: arcs[arc_off + offset]
+  int frame_off;           // its frames in rows[] / states[]
+  int fin_off, n_final;    // its final nodes, ascending: finals[fin_off .. fin_off + n_final)
+  int f0, f1;              // frames this launch advances (f0 == 0: initialise alpha; else continue from alpha in HBM)
+  long long alpha_off;     // floats into alpha: {T, B} per slot, slot 0 = start, slot j + 1 = node j
+  long long bp_off;        // bytes into bp
+  long long bp_stride;     // bytes per frame: 1 byte per node, nodes padded to a multiple of 64
+};
+// advances every lattice over its frames [f0, f1), as ctc_viterbi_forward does; an arc word is (predecessor + 1) | 0x8000 when the
+// predecessor is a node of another label (its token state may enter).  max_N selects the instantiation and sizes the LDS.
+int ctc_graph_forward(hipStream_t s, const GraphSeq* seqs, int n_seq, int max_N, const float* lp, int ld, int r0, const int* rows,
+                      const int* node_tok, const int* arc_off, const unsigned* arcs, int blank, float* alpha, uint8_t* bp,
+                      const float* wmax = nullptr, float bias = 0.f);
+// states[frame_off + t] = 2 * slot + (1 on the token state) of frame t on the best path, score[i] = its fp32 score (-inf: no path)
+int ctc_graph_backtrace(hipStream_t s, const GraphSeq* seqs, int n_seq, const int* arc_off, const unsigned* arcs, const int* finals,
+                        const float* alpha, const uint8_t* bp, int* states, float* score);
+
 // ---------------------------------------------------------------- ctc_find.hip
 // CTC phrase search: every occurrence of short phrases (z = [y0, b, y1, ..., y(L-1)], free start and end, emission lp - row maximum)
 // in the log-probs, one WAVE per (phrase, sequence) pair.  Pair ph * n_seq + sq owns 64 floats of h, 64 ints of st, one count and

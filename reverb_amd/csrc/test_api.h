@@ -153,6 +153,14 @@ int rvb_test_ctc_viterbi(const float* lp, int T, int V, const int32_t* tokens, i
  * rvb_test_ctc_viterbi refuses, and a bias that is positive or not finite, before any device work; outputs untouched. */
 int rvb_test_ctc_viterbi_wild(const float* lp, int T, int V, const float* w, float bias, const int32_t* tokens, int L, int blank,
                               int slab_rows, int32_t* labels_out, float* score_out);
+/* ctc_graph.hip: alignment of n_seq token graphs (arguments as rvb_ctc_align_graph) over host log-probs with the kernels
+ * rvb_ctc_align_graph runs: lp is the lattices' frames concatenated ([sum T][V]), w [sum T] the wildcard's emission less the bias
+ * (nullable when no node is a wildcard), slab_rows frames per launch (a slab may end inside a lattice or span several).
+ * labels_out / frame_node_out [sum T]: the label (blank on a blank) and node (-1 on a blank) per frame; score_out [n_seq].  Refuses
+ * what rvb_ctc_align_graph refuses, in the same words, before any device work; outputs untouched. */
+int rvb_test_ctc_viterbi_graph(const float* lp, const int32_t* T, int n_seq, int V, const float* w, float bias, const int32_t* node_tokens,
+                               const int32_t* n_nodes, const int32_t* pred_off, const int32_t* preds, const uint8_t* is_final, int blank,
+                               int slab_rows, int32_t* labels_out, int32_t* frame_node_out, float* score_out);
 /* ctc_forward_backward.hip: full-sum score of tokens[L] over host log-probs lp [T][V] with the kernels rvb_ctc_score runs, advancing
  * slab_rows frames per launch in both sweeps (forward ascending, backward descending from the last frame).  loglik_out is fp64; the
  * four per-token outputs [L] are nullable, and with all four null only the forward sweep runs.  Refuses what rvb_test_ctc_viterbi

@@ -597,6 +597,54 @@ int rvb_test_ctc_viterbi_wild(const float* lp, int T, int V, const float* w, flo
   return ctc_viterbi_lab("rvb_test_ctc_viterbi_wild", true, lp, T, V, w, bias, tokens, L, blank, slab_rows, labels_out, score_out);
 }
 
+int rvb_test_ctc_viterbi_graph(const float* lp, const int32_t* T, int n_seq, int V, const float* w, float bias, const int32_t* node_tokens,
+                               const int32_t* n_nodes, const int32_t* pred_off, const int32_t* preds, const uint8_t* is_final, int blank,
+                               int slab_rows, int32_t* labels_out, int32_t* frame_node_out, float* score_out) {
+  const std::string me("rvb_test_ctc_viterbi_graph");
+  if (!lp || !T || !node_tokens || !n_nodes || !pred_off || !preds || !is_final || !labels_out || !frame_node_out || !score_out) {
+    set_error(me + ": null argument");
+    return E_ARG;
+  }
+  if (n_seq < 1 || slab_rows < 1) { set_error(me + ": need n_seq >= 1 and slab_rows >= 1"); return E_ARG; }
+  if (!(std::isfinite(bias) && bias <= 0.f)) { set_error(me + ": wildcard_bias must be finite and <= 0"); return E_ARG; }
+  CtcGraphAligner al;
+  std::vector<std::vector<int32_t>> rows(n_seq);
+  int64_t M = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    if (T[i] < 1) { set_error(me + ": sequence " + std::to_string(i) + ": need T >= 1"); return E_ARG; }
+    rows[i].resize((size_t)T[i]);
+    if (T[i] <= CTC_ALIGN_MAX_FRAMES) for (int t = 0; t < T[i]; ++t) rows[i][t] = (int32_t)(M + t);   // over the cap: refused on the count
+    M += T[i];
+  }
+  T_TRY(al.plan(me.c_str(), node_tokens, n_nodes, pred_off, preds, is_final, n_seq, rows, V, blank));
+  if (al.has_wild && !w) { set_error(me + ": a graph with wildcards needs w"); return E_ARG; }
+  T_TRY(need_gpu());
+  Dev dlp, dw;
+  int r = up_raw(dlp, lp, (size_t)M * V * 4);
+  if (r == OK && w) r = up_raw(dw, w, (size_t)M * 4);
+  if (r == OK) r = al.begin(nullptr);
+  for (int64_t r0 = 0; r == OK && r0 < M; r0 += slab_rows) {
+    const int n = (int)std::min<int64_t>(slab_rows, M - r0);
+    r = al.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, (int)r0, n, w ? (const float*)dw.p + r0 : nullptr, bias);
+  }
+  std::vector<int32_t> states((size_t)M);
+  std::vector<float> score(n_seq);
+  if (r == OK) r = al.finish(nullptr, states.data(), score.data());
+  if (r != OK) (void)hipDeviceSynchronize();
+  al.release();
+  if (r != OK) return r;
+  memcpy(score_out, score.data(), (size_t)n_seq * 4);
+  for (int i = 0; i < n_seq; ++i) {
+    const GraphSeq& q = al.seq[i];
+    for (int t = 0; t < q.T; ++t) {
+      const int st = states[q.frame_off + t], node = (st >> 1) - 1;
+      frame_node_out[q.frame_off + t] = (st & 1) ? node : -1;
+      labels_out[q.frame_off + t] = (st & 1) ? node_tokens[q.node_off + node] : blank;
+    }
+  }
+  return OK;
+}
+
 static int ctc_score_lab(const char* who, const float* lp, const int32_t* T, int V, const int32_t* tokens, const int32_t* L, int n_seq,
                          int blank, int slab_rows, double* loglik_out, float* occupancy, float* mean_frame, float* peak_post,
                          int32_t* peak_frame) {

@@ -157,6 +157,7 @@ class AlignResult:
     score: float                      # fp32 Viterbi path score
     first_chunk: int = 0
     chunk_lens: List[int] = field(default_factory=list)
+    nodes: Optional[List[int]] = None     # Engine.align_graph: the graph node of each entry of `tokens` (the chosen path)
 
     @property
     def wildcard(self) -> List[bool]:
@@ -241,7 +242,8 @@ def align_to_ali(audio_name: str, res: AlignResult, wildcard: Optional[str] = No
 def align_to_json(res: AlignResult, tokenizer, chunk_size: int, input_frame_ms: int, output_frame_ms: int,
                   wildcard: Optional[str] = None) -> Dict[str, Any]:
     """Per token: piece, id, start_ms = chunk shift + begin * frame, end_ms = chunk shift + (end + 1) * frame (both inside the chunk the
-    frame lies in), confidence; plus the sequence score.  A wildcard has the marker as its piece and "wildcard": true."""
+    frame lies in), confidence; plus the sequence score.  A wildcard has the marker as its piece and "wildcard": true; a result of
+    Engine.align_graph carries the graph node of each token as "node"."""
     def ms(frame: int, extra: int) -> int:
         c, t = res.chunk_frame(frame)
         return c * chunk_size * input_frame_ms + (t + extra) * output_frame_ms
@@ -253,6 +255,8 @@ def align_to_json(res: AlignResult, tokenizer, chunk_size: int, input_frame_ms: 
                      "end_ms": ms(e, 1), "confidence": float(conf)})
         if wild:
             toks[-1]["wildcard"] = True
+    for tok, node in zip(toks, res.nodes or []):
+        tok["node"] = int(node)
     return {"score": float(res.score), "tokens": toks}
 
 

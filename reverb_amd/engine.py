@@ -456,6 +456,42 @@ class Engine:
             t0 += n; f0 += frames[i]
         return out
 
+    def align_graph(self, graphs, chunk_ranges=None, wildcard_bias=0.0):
+        """align_wild() for transcripts with alternatives and optional words (rvb_ctc_align_graph, csrc/ctc_graph.hip): each sequence
+        is a token_graph.TokenGraph, and one Viterbi pass picks the reading that was spoken and aligns it.  -> List[AlignResult]
+        whose `nodes` is the chosen path and whose `tokens` / begin / end / peak / confidence describe the nodes on it, so everything
+        that reads an align() result reads this one.  On TokenGraph.chain(ids) the result is that of align_wild(ids), bit for bit."""
+        from .ctc_align import AlignResult
+        from ._lib import u8ptr
+        graphs = list(graphs)
+        if chunk_ranges is None:
+            chunk_ranges = [(i, 1) for i in range(len(graphs))]
+        if len(chunk_ranges) != len(graphs) or not graphs:
+            raise RvbError("align_graph: one chunk range per graph, at least one graph")
+        arrs = [g.arrays() for g in graphs]
+        tok, off, prd, fin = (np.ascontiguousarray(np.concatenate([a[k] for a in arrs])) for k in range(4))
+        nn = np.array([len(g) for g in graphs], np.int32)
+        lens = self.encoder_lens()
+        first = np.array([r[0] for r in chunk_ranges], np.int32)
+        count = np.array([r[1] for r in chunk_ranges], np.int32)
+        frames = [int(lens[f:f + c].sum()) if 0 <= f and c >= 1 and f + c <= self.batch else 0 for f, c in zip(first, count)]
+        labels, fnode = (np.empty(max(sum(frames), 1), np.int32) for _ in range(2))
+        nt = int(nn.sum())
+        path, begin, end, peak = (np.empty(nt, np.int32) for _ in range(4))
+        plen, conf, score = np.empty(len(graphs), np.int32), np.empty(nt, np.float32), np.empty(len(graphs), np.float32)
+        check(self.lib.rvb_ctc_align_graph(self.handle, iptr(tok), iptr(nn), iptr(off), iptr(prd), u8ptr(fin), len(graphs), iptr(first),
+                                           iptr(count), float(wildcard_bias), iptr(labels), iptr(fnode), iptr(plen), iptr(path),
+                                           iptr(begin), iptr(end), iptr(peak), fptr(conf), fptr(score)), "rvb_ctc_align_graph")
+        out, t0, f0 = [], 0, 0
+        for i, g in enumerate(graphs):
+            n = int(plen[i])
+            nodes = path[t0:t0 + n].tolist()
+            out.append(AlignResult([g.tokens[j] for j in nodes], labels[f0:f0 + frames[i]].tolist(), begin[t0:t0 + n].tolist(),
+                                   end[t0:t0 + n].tolist(), peak[t0:t0 + n].tolist(), conf[t0:t0 + n].tolist(), float(score[i]),
+                                   int(first[i]), lens[first[i]:first[i] + count[i]].tolist(), nodes))
+            t0 += len(g); f0 += frames[i]
+        return out
+
     def find(self, phrases, chunk_ranges=None, min_score=-1.0, max_hits=64, max_candidates=None):
         """Phrase search (rvb_ctc_find, csrc/ctc_find.hip): EVERY occurrence of each token phrase (1 .. 32 ids, none the blank) in the
         chunks of the last encode().  Sequence i covers the chunks chunk_ranges[i] = (first, count); the default is ONE sequence

@@ -276,7 +276,7 @@ class ReverbASR:
 
     def align(self, audio_file, transcript: Optional[str] = None, tokens=None, format: str = "ctm", verbatimicity: float = 1.0,
               chunk_size: int = 2051, timings_adjustment: float = 230, posteriors: bool = False, wildcard: Optional[str] = None,
-              wildcard_bias: float = 0.0):
+              wildcard_bias: float = 0.0, alternatives: bool = False):
         """Forced alignment of a KNOWN transcript (the reference's bin/alignment.py -> force_align, utils/ctc_utils.py:105-161): exactly
         one of `transcript` (text, tokenised with the model's tokenizer) or `tokens` (ids).  The whole file is encoded as
         transcribe_modes does and the transcript aligned as ONE sequence over all chunks.  format: "ctm" / "txt" (through get_output,
@@ -287,7 +287,12 @@ class ReverbASR:
         preamble before the first word).  The text is split at the marker, the pieces are tokenised as usual and joined with the
         wildcard label (consecutive markers are one); with tokens= the ids may hold ctc_align.WILDCARD.  A wildcard takes at least
         one frame and costs what the model's own best label costs there + wildcard_bias (<= 0) per frame; its run appears in every
-        format with the marker as its text ("wildcard": true in json).  Full-sum posteriors do not exist for such a transcript."""
+        format with the marker as its text ("wildcard": true in json).  Full-sum posteriors do not exist for such a transcript.
+        alternatives=True: `transcript` holds choices and optional words in the syntax of token_graph.parse_alternatives --
+        "it is {twenty|two zero} [um] [<star>] goodbye" -- and ONE pass over the graph of all readings (Engine.align_graph) picks the
+        reading that was spoken and aligns it.  [<star>] (with wildcard="<star>") is a gap marker that may be empty.  Every format
+        shows the chosen reading; json adds "text" (that reading) and "node" (the graph node) per token.  tokens= and posteriors=True
+        are refused: a graph is written as text, and the full-sum score has no graphs."""
         from .ctc_align import DecodeLike, align_to_ali, align_to_json, posteriors_to_json, split_by_chunk, split_transcript
         if (transcript is None) == (tokens is None):
             raise ValueError("align: give exactly one of transcript= (text) or tokens= (ids)")
@@ -298,13 +303,22 @@ class ReverbASR:
             raise NotImplementedError("the device fbank is built for 80 bins / 25 ms / 10 ms")
         if chunk_size < 7:
             raise ValueError("chunk_size must be at least 7 frames (Conv2dSubsampling4 needs 7 input frames, subsampling.py:201-226)")
-        if wildcard is not None:
+        graph = None
+        if alternatives:
+            from .token_graph import parse_alternatives
+            if tokens is not None or posteriors:
+                raise ValueError("align: alternatives=True takes transcript= (text) and has no posteriors")
+            graph = parse_alternatives(transcript, lambda text: self.tokenizer.tokenize(text)[1], wildcard)
+            tokens = []                                       # nothing to tokenise below
+        elif wildcard is not None:
             if posteriors:
                 raise ValueError("align: posteriors come from the full-sum score, which has no wildcards")
             if tokens is None:
                 tokens = split_transcript(transcript, wildcard, lambda text: self.tokenizer.tokenize(text)[1])
         eng, ids, n_chunks = self._encode_for_align("align", audio_file, transcript, tokens, verbatimicity, chunk_size)
-        if wildcard is None:
+        if graph is not None:
+            res = eng.align_graph([graph], [(0, n_chunks)], wildcard_bias)[0]
+        elif wildcard is None:
             res = eng.align([ids], [(0, n_chunks)])[0]
         else:
             res = eng.align_wild([ids], [(0, n_chunks)], wildcard_bias)[0]
@@ -313,6 +327,8 @@ class ReverbASR:
             return align_to_ali(name, res, wildcard)
         if format == "json":
             out = align_to_json(res, self.tokenizer, chunk_size, self.input_frame_length, self.output_frame_length, wildcard)
+            if graph is not None:
+                out["text"] = graph.text_of(res.nodes)
             if posteriors:
                 post = eng.score([ids], [(0, n_chunks)], posteriors=True)[0]
                 for tok, extra in zip(out["tokens"], posteriors_to_json(res, post, chunk_size, self.input_frame_length,
