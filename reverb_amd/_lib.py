@@ -205,6 +205,7 @@ TEST_SIGNATURES = {
                                            _i32p]),
     "rvb_test_ctc_find": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, _f32p, _i32p, _i32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     _i64p, _i32p, _i32p, _f32p, _i32p, _i32p, _i32p, _f32p]),
+    "rvb_test_slab_windows": (C.c_int, [C.c_char_p, _i32p, _i32p, C.c_int, _i32p, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p]),
     "rvb_test_gemm_glu": (C.c_int, [_f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int]),
     "rvb_test_gemm_rowadd": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rvb_test_mp3_decode": (C.c_int64, [C.c_char_p, C.c_int64, C.c_int, _f32p, C.c_int64, _i64p, _i64p, C.c_int]),

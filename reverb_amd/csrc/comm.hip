@@ -15,8 +15,6 @@
 
 #include "engine.h"
 
-#define RVB_TRY_RC(expr) do { int _r = (expr); if (_r != rvb::OK) return _r; } while (0)
-
 namespace {
 
 typedef int (*GetUniqueIdFn)(void*);
@@ -78,7 +76,7 @@ extern "C" {
 
 int rvb_comm_unique_id(void* id128) {
   if (!id128) { set_error("rvb_comm_unique_id: null argument"); return E_ARG; }
-  RVB_TRY_RC(load_rccl());
+  RVB_TRY(load_rccl());
   const int rc = g_rccl.get_id(id128);
   return rc == 0 ? OK : nccl_fail("ncclGetUniqueId", rc);
 }
@@ -130,7 +128,7 @@ static int comm_wait(rvb_comm* c, const char* what) {
 
 int rvb_comm_create(int device, int world, int rank, const void* id128, rvb_comm** out) {
   if (!out || !id128 || world < 1 || rank < 0 || rank >= world) { set_error("rvb_comm_create: bad argument"); return E_ARG; }
-  RVB_TRY_RC(load_rccl());
+  RVB_TRY(load_rccl());
   RVB_HIP_CHECK(hipSetDevice(device));
   Id128 id;
   memcpy(id.b, id128, 128);
@@ -167,7 +165,7 @@ int rvb_comm_set_timeout(rvb_comm* c, double seconds) {
   if (seconds > 0.0) {
     // without ncclCommAbort a timed-out collective cannot be torn down: its kernel and the copy into the caller's host
     // buffer would stay queued and could land after the caller has freed that buffer -- refuse the timeout
-    RVB_TRY_RC(load_rccl());
+    RVB_TRY(load_rccl());
     if (!g_rccl.abort) { set_error("rvb_comm_set_timeout: this librccl has no ncclCommAbort; collectives cannot be given a deadline"); return E_UNSUPPORTED; }
   }
   c->timeout_s = seconds;
@@ -279,7 +277,7 @@ int rvb_comm_free(rvb_comm* c) {
 int rvb_comm_init(rvb_engine* e, int world, int rank, const void* id128) {
   if (!e || !id128 || world < 1 || rank < 0 || rank >= world) { set_error("rvb_comm_init: bad argument"); return E_ARG; }
   if (e->comm) { set_error("rvb_comm_init: the engine already has a communicator"); return E_STATE; }
-  RVB_TRY_RC(load_rccl());
+  RVB_TRY(load_rccl());
   RVB_HIP_CHECK(hipSetDevice(e->device));
   Id128 id;
   memcpy(id.b, id128, 128);

@@ -183,6 +183,9 @@ enum { OK = 0, E_ARG = -1, E_HIP = -2, E_STATE = -3, E_NOMEM = -4, E_UNSUPPORTED
     }                                                                                   \
   } while (0)
 
+// hands a failed status (whose callee has set the error text) on to the caller
+#define RVB_TRY(expr) do { int _r = (expr); if (_r != rvb::OK) return _r; } while (0)
+
 namespace rvb {
 void set_error(const std::string& msg);  // thread-local last error (engine.hip)
 const char* last_error();

@@ -40,8 +40,6 @@
 #include <cstdio>
 #include <limits>
 
-#define RVB_TRY_(expr) do { int _r = (expr); if (_r != rvb::OK) return _r; } while (0)
-
 namespace rvb {
 
 namespace {
@@ -188,16 +186,9 @@ int CtcFinder::plan(const char* who, const int32_t* tokens, const int32_t* tok_l
   for (int i = 0; i < n_seq; ++i) {
     const int64_t T = (int64_t)seq_rows[i].size();
     const std::string at = w + ": sequence " + std::to_string(i) + ": ";
-    if (T > CTC_ALIGN_MAX_FRAMES) {
-      set_error(at + std::to_string(T) + " frames exceed the cap of " + std::to_string(CTC_ALIGN_MAX_FRAMES) + " frames per sequence");
-      return E_UNSUPPORTED;
-    }
-    for (int64_t f = 1; f < T; ++f)
-      if (seq_rows[i][f] <= seq_rows[i][f - 1]) { set_error(at + "frame rows must increase"); return E_ARG; }
+    RVB_TRY(slab_frame_cap(at, T, CTC_ALIGN_MAX_FRAMES, "sequence"));
     seq[i].frame_off = (int)frame_off; seq[i].T = (int)T;
-    h_rows.insert(h_rows.end(), seq_rows[i].begin(), seq_rows[i].end());
-    frame_off += T;
-    if (frame_off > std::numeric_limits<int32_t>::max() / 2) { set_error(w + ": too many frames in one call"); return E_UNSUPPORTED; }
+    RVB_TRY(slab_take_rows(w, at, seq_rows[i], &h_rows, &frame_off));
   }
   const double pairs = (double)n_phr * n_seq;
   const double bytes = pairs * max_candidates * 12.0;
@@ -213,13 +204,13 @@ int CtcFinder::plan(const char* who, const int32_t* tokens, const int32_t* tok_l
 
 int CtcFinder::begin(hipStream_t s) {
   const size_t pairs = phr.size() * seq.size();
-  RVB_TRY_(d_tokens.ensure(h_tokens.size() * 4));
-  RVB_TRY_(d_rows.ensure(h_rows.size() * 4));
-  RVB_TRY_(d_seqs.ensure(seq.size() * sizeof(FindSeq)));
-  RVB_TRY_(d_phr.ensure(phr.size() * sizeof(FindPhrase)));
-  RVB_TRY_(d_h.ensure(pairs * 64 * 4));
-  RVB_TRY_(d_st.ensure(pairs * 64 * 4));
-  RVB_TRY_(d_count.ensure(pairs * 8));
+  RVB_TRY(d_tokens.ensure(h_tokens.size() * 4));
+  RVB_TRY(d_rows.ensure(h_rows.size() * 4));
+  RVB_TRY(d_seqs.ensure(seq.size() * sizeof(FindSeq)));
+  RVB_TRY(d_phr.ensure(phr.size() * sizeof(FindPhrase)));
+  RVB_TRY(d_h.ensure(pairs * 64 * 4));
+  RVB_TRY(d_st.ensure(pairs * 64 * 4));
+  RVB_TRY(d_count.ensure(pairs * 8));
   const size_t cand = pairs * (size_t)max_cand;
   for (DevBuf* b : {&d_cend, &d_cstart, &d_cscore})
     if (int r = b->ensure(cand * 4)) {
@@ -234,29 +225,12 @@ int CtcFinder::begin(hipStream_t s) {
   return OK;
 }
 
-bool CtcFinder::touches(int r0, int nrows) const {
-  for (const auto& q : seq) {
-    const int32_t* rw = h_rows.data() + q.frame_off;
-    const int32_t* lo = std::lower_bound(rw, rw + q.T, r0);
-    if (lo != rw + q.T && *lo < r0 + nrows) return true;
-  }
-  return false;
-}
-
 int CtcFinder::advance(hipStream_t s, const float* lp, int ld, int r0, int nrows, const float* wmax) {
   if (!lp || !wmax) { set_error("ctc find: the slab and its row maxima are needed"); return E_ARG; }
-  bool any = false;
-  for (auto& q : seq) {
-    const int32_t* rw = h_rows.data() + q.frame_off;
-    const int f0 = (int)(std::lower_bound(rw, rw + q.T, r0) - rw), f1 = (int)(std::lower_bound(rw, rw + q.T, r0 + nrows) - rw);
-    if (f0 < f1 && f0 != q.f1) { set_error("ctc find: slabs must arrive in row order"); return E_STATE; }
-    q.f0 = f0 < f1 ? f0 : q.f1; if (f0 < f1) q.f1 = f1;
-    any = any || f0 < f1;
-  }
+  bool any;
+  RVB_TRY(slab_window("ctc find", false, seq, h_rows, r0, nrows, &any));
   if (!any) return OK;
-  // the descriptors of this launch: a synchronous copy, so the host vector may change for the next slab
-  RVB_HIP_CHECK(hipStreamSynchronize(s));
-  RVB_HIP_CHECK(hipMemcpy(d_seqs.p, seq.data(), seq.size() * sizeof(FindSeq), hipMemcpyHostToDevice));
+  RVB_TRY(slab_upload(s, d_seqs.p, seq));
   return ctc_find_advance(s, d_seqs.as<FindSeq>(), d_phr.as<FindPhrase>(), (int)seq.size(), (int)phr.size(), lp, ld, r0, d_rows.as<int>(),
                           d_tokens.as<int>(), blank, wmax, d_h.as<float>(), d_st.as<int>(), d_count.as<long long>(), max_cand,
                           d_cend.as<int>(), d_cstart.as<int>(), d_cscore.as<float>());
@@ -288,8 +262,7 @@ int ctc_find_suppress(const int32_t* end, const int32_t* start, const float* sco
 
 int CtcFinder::finish(hipStream_t s, int max_hits, int32_t* n_hits, int32_t* start, int32_t* end, float* score, int64_t* n_candidates,
                       int32_t* raw_end, int32_t* raw_start, float* raw_score) {
-  for (const auto& q : seq)
-    if (q.f1 != q.T) { set_error("ctc find: the slabs did not cover every frame of a sequence"); return E_STATE; }
+  RVB_TRY(slab_covered("ctc find", false, seq));
   const size_t pairs = phr.size() * seq.size();
   std::vector<long long> count(pairs);
   RVB_HIP_CHECK(hipMemcpyAsync(count.data(), d_count.p, pairs * 8, hipMemcpyDeviceToHost, s));

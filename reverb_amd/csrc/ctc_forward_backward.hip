@@ -35,8 +35,6 @@
 #include <cstdlib>
 #include <cstring>
 
-#define RVB_TRY_(expr) do { int _r = (expr); if (_r != rvb::OK) return _r; } while (0)
-
 namespace rvb {
 
 namespace {
@@ -357,16 +355,13 @@ __global__ __launch_bounds__(1024) void ctc_fb_backward_kernel(const VitSeq* __r
   }
 }
 
-int fb_spt_for(int S) { return S <= 4096 ? 4 : S <= 16384 ? 16 : 32; }
-int fb_threads(int max_S, int spt) { return std::min(1024, ((max_S + spt - 1) / spt + 63) / 64 * 64); }
-
 }  // namespace
 
 int ctc_fb_forward(hipStream_t s, const VitSeq* seqs, int n_seq, int max_S, const float* lp, int ld, int r0, const int* rows,
                    const int* tokens, int blank, float* alpha, double* csum, float* coff, float* arows) {
   if (n_seq <= 0) return OK;
   if (max_S < 3 || max_S > CTC_ALIGN_MAX_STATES) { set_error("ctc_fb_forward: states out of range"); return E_ARG; }
-  const int spt = fb_spt_for(max_S), threads = fb_threads(max_S, spt);
+  const int spt = ctc_spt_for(max_S), threads = ctc_threads(max_S, spt);
   if (spt == 4) ctc_fb_forward_kernel<4><<<n_seq, threads, 0, s>>>(seqs, lp, ld, r0, rows, tokens, blank, alpha, csum, coff, arows);
   else if (spt == 16) ctc_fb_forward_kernel<16><<<n_seq, threads, 0, s>>>(seqs, lp, ld, r0, rows, tokens, blank, alpha, csum, coff, arows);
   else ctc_fb_forward_kernel<32><<<n_seq, threads, 0, s>>>(seqs, lp, ld, r0, rows, tokens, blank, alpha, csum, coff, arows);
@@ -386,7 +381,7 @@ int ctc_fb_backward(hipStream_t s, const VitSeq* seqs, int n_seq, int max_S, con
                     float* occ, float* tsum, float* peak, int* peak_frame) {
   if (n_seq <= 0) return OK;
   if (max_S < 3 || max_S > CTC_ALIGN_MAX_STATES) { set_error("ctc_fb_backward: states out of range"); return E_ARG; }
-  const int spt = fb_spt_for(max_S), threads = fb_threads(max_S, spt);
+  const int spt = ctc_spt_for(max_S), threads = ctc_threads(max_S, spt);
   const FbAcc acc{occ, tsum, peak, peak_frame};
   if (spt == 4)
     ctc_fb_backward_kernel<4><<<n_seq, threads, 0, s>>>(seqs, lp, ld, r0, rows, tokens, blank, beta, coff, arows, llhat, zcarry, acc);
@@ -407,13 +402,13 @@ int CtcScorer::plan(const char* who, const int32_t* tokens, const int32_t* tok_l
 int CtcScorer::begin(hipStream_t s, bool posteriors) {
   post = posteriors;
   const size_t n_seq = lat.seq.size(), n_tok = lat.h_tokens.size();
-  RVB_TRY_(lat.d_tokens.ensure(n_tok * 4));
-  RVB_TRY_(lat.d_rows.ensure(lat.h_rows.size() * 4));
-  RVB_TRY_(lat.d_seqs.ensure(n_seq * sizeof(VitSeq)));
-  RVB_TRY_(lat.d_alpha.ensure(lat.alpha_floats * 4));
-  RVB_TRY_(d_csum.ensure(n_seq * 8));
-  RVB_TRY_(d_loglik.ensure(n_seq * 8));
-  RVB_TRY_(d_llhat.ensure(n_seq * 4));
+  RVB_TRY(lat.d_tokens.ensure(n_tok * 4));
+  RVB_TRY(lat.d_rows.ensure(lat.h_rows.size() * 4));
+  RVB_TRY(lat.d_seqs.ensure(n_seq * sizeof(VitSeq)));
+  RVB_TRY(lat.d_alpha.ensure(lat.alpha_floats * 4));
+  RVB_TRY(d_csum.ensure(n_seq * 8));
+  RVB_TRY(d_loglik.ensure(n_seq * 8));
+  RVB_TRY(d_llhat.ensure(n_seq * 4));
   if (post) {
     const size_t row_bytes = lat.bp_bytes * 16;    // the layout of the 2-bit back-pointers at 4 bytes per frame and state
     const std::string what = "ctc score: " + std::to_string(row_bytes) + " bytes of alpha rows (4 bytes per frame and state) do not fit: ";
@@ -422,10 +417,10 @@ int CtcScorer::begin(hipStream_t s, bool posteriors) {
       if ((double)row_bytes > atof(f)) { set_error(what + "hipMalloc refused (RVB_CTC_SCORE_FAKE_NOMEM_ABOVE)"); return E_NOMEM; }
     }
     if (int r = d_arows.ensure(row_bytes)) { set_error(what + last_error()); return r; }
-    RVB_TRY_(d_coff.ensure((size_t)lat.total_frames * 4));
-    RVB_TRY_(d_beta.ensure(lat.alpha_floats * 4));
-    RVB_TRY_(d_z.ensure(n_seq * 4));
-    RVB_TRY_(d_acc.ensure(n_tok * 16));
+    RVB_TRY(d_coff.ensure((size_t)lat.total_frames * 4));
+    RVB_TRY(d_beta.ensure(lat.alpha_floats * 4));
+    RVB_TRY(d_z.ensure(n_seq * 4));
+    RVB_TRY(d_acc.ensure(n_tok * 16));
   }
   RVB_HIP_CHECK(hipMemcpyAsync(lat.d_tokens.p, lat.h_tokens.data(), n_tok * 4, hipMemcpyHostToDevice, s));
   RVB_HIP_CHECK(hipMemcpyAsync(lat.d_rows.p, lat.h_rows.data(), lat.h_rows.size() * 4, hipMemcpyHostToDevice, s));
@@ -433,59 +428,32 @@ int CtcScorer::begin(hipStream_t s, bool posteriors) {
   return OK;
 }
 
-// the descriptors of one launch: a synchronous copy, so the host vector may change for the next slab
-static int upload_seqs(hipStream_t s, CtcAligner& lat) {
-  RVB_HIP_CHECK(hipStreamSynchronize(s));
-  RVB_HIP_CHECK(hipMemcpy(lat.d_seqs.p, lat.seq.data(), lat.seq.size() * sizeof(VitSeq), hipMemcpyHostToDevice));
-  return OK;
-}
-
 int CtcScorer::advance(hipStream_t s, const float* lp, int ld, int r0, int nrows) {
-  bool any = false;
-  for (auto& q : lat.seq) {
-    const int32_t* rw = lat.h_rows.data() + q.frame_off;
-    const int f0 = (int)(std::lower_bound(rw, rw + q.T, r0) - rw), f1 = (int)(std::lower_bound(rw, rw + q.T, r0 + nrows) - rw);
-    if (f0 < f1 && f0 != q.f1) { set_error("ctc score: slabs must arrive in row order"); return E_STATE; }
-    q.f0 = f0 < f1 ? f0 : q.f1; if (f0 < f1) q.f1 = f1;
-    any = any || f0 < f1;
-  }
+  bool any;
+  RVB_TRY(slab_window("ctc score", false, lat.seq, lat.h_rows, r0, nrows, &any));
   if (!any) return OK;
-  RVB_TRY_(upload_seqs(s, lat));
+  RVB_TRY(slab_upload(s, lat.d_seqs.p, lat.seq));
   return ctc_fb_forward(s, lat.d_seqs.as<VitSeq>(), (int)lat.seq.size(), lat.max_S, lp, ld, r0, lat.d_rows.as<int>(), lat.d_tokens.as<int>(),
                         lat.blank, lat.d_alpha.as<float>(), d_csum.as<double>(), post ? d_coff.as<float>() : nullptr,
                         post ? d_arows.as<float>() : nullptr);
 }
 
 int CtcScorer::finish_forward(hipStream_t s, double* loglik) {
-  for (auto& q : lat.seq) {
-    if (q.f1 != q.T) { set_error("ctc score: the slabs did not cover every frame of a sequence"); return E_STATE; }
-    q.f0 = q.f1 = q.T;                             // the backward sweep starts above the last frame
-  }
-  RVB_TRY_(ctc_fb_loglik(s, lat.d_seqs.as<VitSeq>(), (int)lat.seq.size(), lat.d_alpha.as<float>(), d_csum.as<double>(), d_loglik.as<double>(),
+  RVB_TRY(slab_covered("ctc score", false, lat.seq));
+  for (auto& q : lat.seq) q.f0 = q.f1 = q.T;       // the backward sweep starts above the last frame
+  RVB_TRY(ctc_fb_loglik(s, lat.d_seqs.as<VitSeq>(), (int)lat.seq.size(), lat.d_alpha.as<float>(), d_csum.as<double>(), d_loglik.as<double>(),
                          d_llhat.as<float>()));
   RVB_HIP_CHECK(hipMemcpyAsync(loglik, d_loglik.p, lat.seq.size() * 8, hipMemcpyDeviceToHost, s));
   RVB_HIP_CHECK(hipStreamSynchronize(s));
-  for (size_t i = 0; i < lat.seq.size(); ++i)
-    if (!(loglik[i] > -INFINITY)) {
-      set_error("ctc score: sequence " + std::to_string(i) + ": infeasible: no path of " + std::to_string(lat.seq[i].T) +
-                " frames emits the transcript with a finite score");
-      return E_ARG;
-    }
-  return OK;
+  return slab_feasible("ctc score", lat.seq, loglik, "emits the transcript");
 }
 
 int CtcScorer::advance_backward(hipStream_t s, const float* lp, int ld, int r0, int nrows) {
   if (!post) { set_error("ctc score: backward sweep without alpha rows"); return E_STATE; }
-  bool any = false;
-  for (auto& q : lat.seq) {
-    const int32_t* rw = lat.h_rows.data() + q.frame_off;
-    const int f0 = (int)(std::lower_bound(rw, rw + q.T, r0) - rw), f1 = (int)(std::lower_bound(rw, rw + q.T, r0 + nrows) - rw);
-    if (f0 < f1 && f1 != q.f0) { set_error("ctc score: the backward sweep takes the slabs in descending row order"); return E_STATE; }
-    if (f0 < f1) { q.f1 = f1; q.f0 = f0; } else q.f1 = q.f0;
-    any = any || f0 < f1;
-  }
+  bool any;
+  RVB_TRY(slab_window("ctc score", true, lat.seq, lat.h_rows, r0, nrows, &any));
   if (!any) return OK;
-  RVB_TRY_(upload_seqs(s, lat));
+  RVB_TRY(slab_upload(s, lat.d_seqs.p, lat.seq));
   float* acc = d_acc.as<float>();
   const size_t n_tok = lat.h_tokens.size();
   return ctc_fb_backward(s, lat.d_seqs.as<VitSeq>(), (int)lat.seq.size(), lat.max_S, lp, ld, r0, lat.d_rows.as<int>(), lat.d_tokens.as<int>(),
@@ -494,8 +462,7 @@ int CtcScorer::advance_backward(hipStream_t s, const float* lp, int ld, int r0, 
 }
 
 int CtcScorer::finish_backward(hipStream_t s, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame) {
-  for (const auto& q : lat.seq)
-    if (q.f0 != 0) { set_error("ctc score: the backward sweep did not reach the first frame of a sequence"); return E_STATE; }
+  RVB_TRY(slab_covered("ctc score", true, lat.seq));
   const size_t n_tok = lat.h_tokens.size();
   std::vector<float> h(4 * n_tok);
   RVB_HIP_CHECK(hipMemcpyAsync(h.data(), d_acc.p, n_tok * 16, hipMemcpyDeviceToHost, s));

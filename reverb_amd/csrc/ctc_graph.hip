@@ -34,8 +34,6 @@
 #include <cstring>
 #include <limits>
 
-#define RVB_TRY_(expr) do { int _r = (expr); if (_r != rvb::OK) return _r; } while (0)
-
 namespace rvb {
 
 namespace {
@@ -236,10 +234,10 @@ int ctc_graph_forward(hipStream_t s, const GraphSeq* seqs, int n_seq, int max_N,
   if (n_seq <= 0) return OK;
   if (max_N < 1 || max_N > CTC_GRAPH_MAX_NODES) { set_error("ctc_graph_forward: nodes out of range"); return E_ARG; }
   const int npt = npt_for(max_N);
-  const int threads = std::min(1024, ((max_N + npt - 1) / npt + 63) / 64 * 64);
+  const int threads = ctc_threads(max_N, npt);
   const int slots = max_N + 1;
   const size_t lds = (size_t)2 * slots * sizeof(float2);
-#define RVB_GRAPH_(NPT) RVB_TRY_(launch_forward<NPT>(s, n_seq, threads, lds, seqs, lp, ld, r0, rows, node_tok, arc_off, arcs, blank, alpha, bp, wmax, bias, slots))
+#define RVB_GRAPH_(NPT) RVB_TRY(launch_forward<NPT>(s, n_seq, threads, lds, seqs, lp, ld, r0, rows, node_tok, arc_off, arcs, blank, alpha, bp, wmax, bias, slots))
   if (npt == 1) RVB_GRAPH_(1);
   else if (npt == 2) RVB_GRAPH_(2);
   else if (npt == 4) RVB_GRAPH_(4);
@@ -281,10 +279,7 @@ int CtcGraphAligner::plan(const char* who, const int32_t* node_tokens, const int
       set_error(at + std::to_string(N) + " nodes exceed the cap of " + std::to_string(CTC_GRAPH_MAX_NODES) + " nodes per graph");
       return E_UNSUPPORTED;
     }
-    if (T > CTC_ALIGN_MAX_FRAMES) {
-      set_error(at + std::to_string(T) + " frames exceed the cap of " + std::to_string(CTC_ALIGN_MAX_FRAMES) + " frames per lattice");
-      return E_UNSUPPORTED;
-    }
+    RVB_TRY(slab_frame_cap(at, T, CTC_ALIGN_MAX_FRAMES, "lattice"));
     const int32_t* y = node_tokens + node_off;
     const int32_t* po = pred_off + node_off + i;                 // N + 1 offsets, within this sequence's predecessors
     const int32_t* pr = preds + arc_off;
@@ -328,8 +323,6 @@ int CtcGraphAligner::plan(const char* who, const int32_t* node_tokens, const int
     if (!any_final) { set_error(at + "no final node"); return E_ARG; }
     // defence only: node 0's non-empty list can hold nothing but -1, so a graph that passed the checks above has a start
     if (!any_start) { set_error(at + "no node with a start predecessor (-1)"); return E_ARG; }
-    for (int64_t f = 1; f < T; ++f)
-      if (seq_rows[i][f] <= seq_rows[i][f - 1]) { set_error(at + "frame rows must increase"); return E_ARG; }
     if (T < 1) { set_error(at + "infeasible: no frame"); return E_ARG; }
     GraphSeq& q = seq[i];
     q.N = N; q.T = (int)T; q.index = i;
@@ -342,27 +335,24 @@ int CtcGraphAligner::plan(const char* who, const int32_t* node_tokens, const int
     max_N = std::max(max_N, N);
     h_tokens.insert(h_tokens.end(), y, y + N);
     h_arc_off.insert(h_arc_off.end(), po, po + N + 1);
-    h_rows.insert(h_rows.end(), seq_rows[i].begin(), seq_rows[i].end());
-    node_off += N; arc_off += po[N]; frame_off += T;
-    if (frame_off > std::numeric_limits<int32_t>::max() / 2 || arc_off > std::numeric_limits<int32_t>::max() / 2) {
-      set_error(w + ": too many frames or arcs in one call");
-      return E_UNSUPPORTED;
-    }
+    node_off += N; arc_off += po[N];
+    RVB_TRY(slab_take_rows(w, at, seq_rows[i], &h_rows, &frame_off, "frames or arcs"));
+    if (arc_off > std::numeric_limits<int32_t>::max() / 2) { set_error(w + ": too many frames or arcs in one call"); return E_UNSUPPORTED; }
   }
   alpha_floats = alpha_off; bp_bytes = bp_off; total_frames = frame_off;
   return OK;
 }
 
 int CtcGraphAligner::begin(hipStream_t s) {
-  RVB_TRY_(d_tokens.ensure(h_tokens.size() * 4));
-  RVB_TRY_(d_arc_off.ensure(h_arc_off.size() * 4));
-  RVB_TRY_(d_arcs.ensure(h_arcs.size() * 4));
-  RVB_TRY_(d_finals.ensure(h_finals.size() * 4));
-  RVB_TRY_(d_rows.ensure(h_rows.size() * 4));
-  RVB_TRY_(d_seqs.ensure(seq.size() * sizeof(GraphSeq)));
-  RVB_TRY_(d_alpha.ensure(alpha_floats * 4));
-  RVB_TRY_(d_states.ensure((size_t)total_frames * 4));
-  RVB_TRY_(d_score.ensure(seq.size() * 4));
+  RVB_TRY(d_tokens.ensure(h_tokens.size() * 4));
+  RVB_TRY(d_arc_off.ensure(h_arc_off.size() * 4));
+  RVB_TRY(d_arcs.ensure(h_arcs.size() * 4));
+  RVB_TRY(d_finals.ensure(h_finals.size() * 4));
+  RVB_TRY(d_rows.ensure(h_rows.size() * 4));
+  RVB_TRY(d_seqs.ensure(seq.size() * sizeof(GraphSeq)));
+  RVB_TRY(d_alpha.ensure(alpha_floats * 4));
+  RVB_TRY(d_states.ensure((size_t)total_frames * 4));
+  RVB_TRY(d_score.ensure(seq.size() * 4));
   if (int r = d_bp.ensure(bp_bytes)) {
     set_error("ctc align graph: " + std::to_string(bp_bytes) + " bytes of back-pointers (1 byte per frame and node) do not fit: " + last_error());
     return r;
@@ -376,49 +366,25 @@ int CtcGraphAligner::begin(hipStream_t s) {
   return OK;
 }
 
-bool CtcGraphAligner::touches(int r0, int nrows) const {
-  for (const auto& q : seq) {
-    const int32_t* rw = h_rows.data() + q.frame_off;
-    const int32_t* lo = std::lower_bound(rw, rw + q.T, r0);
-    if (lo != rw + q.T && *lo < r0 + nrows) return true;
-  }
-  return false;
-}
-
 int CtcGraphAligner::advance(hipStream_t s, const float* lp, int ld, int r0, int nrows, const float* wmax, float bias) {
   if (has_wild && !wmax) { set_error("ctc align graph: a graph with wildcards needs the row maxima"); return E_ARG; }
-  bool any = false;
-  for (auto& q : seq) {
-    const int32_t* rw = h_rows.data() + q.frame_off;
-    const int f0 = (int)(std::lower_bound(rw, rw + q.T, r0) - rw), f1 = (int)(std::lower_bound(rw, rw + q.T, r0 + nrows) - rw);
-    if (f0 < f1 && f0 != q.f1) { set_error("ctc align graph: slabs must arrive in row order"); return E_STATE; }
-    q.f0 = f0 < f1 ? f0 : q.f1; if (f0 < f1) q.f1 = f1;
-    any = any || f0 < f1;
-  }
+  bool any;
+  RVB_TRY(slab_window("ctc align graph", false, seq, h_rows, r0, nrows, &any));
   if (!any) return OK;
-  // the descriptors of this launch: a synchronous copy, so the host vector may change for the next slab
-  RVB_HIP_CHECK(hipStreamSynchronize(s));
-  RVB_HIP_CHECK(hipMemcpy(d_seqs.p, seq.data(), seq.size() * sizeof(GraphSeq), hipMemcpyHostToDevice));
+  RVB_TRY(slab_upload(s, d_seqs.p, seq));
   return ctc_graph_forward(s, d_seqs.as<GraphSeq>(), (int)seq.size(), max_N, lp, ld, r0, d_rows.as<int>(), d_tokens.as<int>(),
                            d_arc_off.as<int>(), d_arcs.as<unsigned>(), blank, d_alpha.as<float>(), d_bp.as<uint8_t>(),
                            has_wild ? wmax : nullptr, bias);
 }
 
 int CtcGraphAligner::finish(hipStream_t s, int32_t* states, float* score) {
-  for (const auto& q : seq)
-    if (q.f1 != q.T) { set_error("ctc align graph: the slabs did not cover every frame of a sequence"); return E_STATE; }
-  RVB_TRY_(ctc_graph_backtrace(s, d_seqs.as<GraphSeq>(), (int)seq.size(), d_arc_off.as<int>(), d_arcs.as<unsigned>(), d_finals.as<int>(),
+  RVB_TRY(slab_covered("ctc align graph", false, seq));
+  RVB_TRY(ctc_graph_backtrace(s, d_seqs.as<GraphSeq>(), (int)seq.size(), d_arc_off.as<int>(), d_arcs.as<unsigned>(), d_finals.as<int>(),
                                d_alpha.as<float>(), d_bp.as<uint8_t>(), d_states.as<int>(), d_score.as<float>()));
   RVB_HIP_CHECK(hipMemcpyAsync(states, d_states.p, (size_t)total_frames * 4, hipMemcpyDeviceToHost, s));
   RVB_HIP_CHECK(hipMemcpyAsync(score, d_score.p, seq.size() * 4, hipMemcpyDeviceToHost, s));
   RVB_HIP_CHECK(hipStreamSynchronize(s));
-  for (size_t i = 0; i < seq.size(); ++i)
-    if (!(score[i] > -INFINITY)) {
-      set_error("ctc align graph: sequence " + std::to_string(i) + ": infeasible: no path of " + std::to_string(seq[i].T) +
-                " frames through the graph ends in a final node with a finite score");
-      return E_ARG;
-    }
-  return OK;
+  return slab_feasible("ctc align graph", seq, score, "through the graph ends in a final node");
 }
 
 void CtcGraphAligner::release() {

@@ -29,9 +29,6 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <limits>
-
-#define RVB_TRY_(expr) do { int _r = (expr); if (_r != rvb::OK) return _r; } while (0)
 
 namespace rvb {
 
@@ -188,16 +185,13 @@ __global__ void ctc_viterbi_backtrace_kernel(const VitSeq* __restrict__ seqs, co
   out[0] = st;
 }
 
-int spt_for(int S) { return S <= 4096 ? 4 : S <= 16384 ? 16 : 32; }
-
 }  // namespace
 
 int ctc_viterbi_forward(hipStream_t s, const VitSeq* seqs, int n_seq, int max_S, const float* lp, int ld, int r0, const int* rows,
                         const int* tokens, int blank, float* alpha, uint8_t* bp, const float* wmax, float bias) {
   if (n_seq <= 0) return OK;
   if (max_S < 3 || max_S > CTC_ALIGN_MAX_STATES) { set_error("ctc_viterbi_forward: states out of range"); return E_ARG; }
-  const int spt = spt_for(max_S);
-  const int threads = std::min(1024, ((max_S + spt - 1) / spt + 63) / 64 * 64);
+  const int spt = ctc_spt_for(max_S), threads = ctc_threads(max_S, spt);
 #define RVB_VIT_(SPT, WILD) ctc_viterbi_forward_kernel<SPT, WILD><<<n_seq, threads, 0, s>>>(seqs, lp, ld, r0, rows, tokens, blank, alpha, bp, wmax, bias)
   if (wmax) {                                      // some sequence of the call holds a wildcard
     if (spt == 4) RVB_VIT_(4, true);
@@ -241,10 +235,7 @@ int CtcAligner::plan(const char* who, const int32_t* tokens, const int32_t* tok_
                 std::to_string(CTC_ALIGN_MAX_STATES) + " states) per lattice");
       return E_UNSUPPORTED;
     }
-    if (T > CTC_ALIGN_MAX_FRAMES) {
-      set_error(at + std::to_string(T) + " frames exceed the cap of " + std::to_string(CTC_ALIGN_MAX_FRAMES) + " frames per lattice");
-      return E_UNSUPPORTED;
-    }
+    RVB_TRY(slab_frame_cap(at, T, CTC_ALIGN_MAX_FRAMES, "lattice"));
     const int32_t* y = tokens + tok_off;
     int repeats = 0;
     for (int k = 0; k < L; ++k) {
@@ -268,23 +259,20 @@ int CtcAligner::plan(const char* who, const int32_t* tokens, const int32_t* tok_
     bp_off += (size_t)T * (s_pad / 4);
     max_S = std::max(max_S, q.S);
     h_tokens.insert(h_tokens.end(), y, y + L);
-    h_rows.insert(h_rows.end(), seq_rows[i].begin(), seq_rows[i].end());
-    for (int64_t f = 1; f < T; ++f)
-      if (seq_rows[i][f] <= seq_rows[i][f - 1]) { set_error(at + "frame rows must increase"); return E_ARG; }
-    tok_off += L; frame_off += T;
-    if (frame_off > std::numeric_limits<int32_t>::max() / 2) { set_error(w + ": too many frames in one call"); return E_UNSUPPORTED; }
+    tok_off += L;
+    RVB_TRY(slab_take_rows(w, at, seq_rows[i], &h_rows, &frame_off));
   }
   alpha_floats = alpha_off; bp_bytes = bp_off; total_frames = frame_off;
   return OK;
 }
 
 int CtcAligner::begin(hipStream_t s) {
-  RVB_TRY_(d_tokens.ensure(h_tokens.size() * 4));
-  RVB_TRY_(d_rows.ensure(h_rows.size() * 4));
-  RVB_TRY_(d_seqs.ensure(seq.size() * sizeof(VitSeq)));
-  RVB_TRY_(d_alpha.ensure(alpha_floats * 4));
-  RVB_TRY_(d_states.ensure((size_t)total_frames * 4));
-  RVB_TRY_(d_score.ensure(seq.size() * 4));
+  RVB_TRY(d_tokens.ensure(h_tokens.size() * 4));
+  RVB_TRY(d_rows.ensure(h_rows.size() * 4));
+  RVB_TRY(d_seqs.ensure(seq.size() * sizeof(VitSeq)));
+  RVB_TRY(d_alpha.ensure(alpha_floats * 4));
+  RVB_TRY(d_states.ensure((size_t)total_frames * 4));
+  RVB_TRY(d_score.ensure(seq.size() * 4));
   if (int r = d_bp.ensure(bp_bytes)) {
     set_error("ctc align: " + std::to_string(bp_bytes) + " bytes of back-pointers (2 bits per frame and state) do not fit: " + last_error());
     return r;
@@ -295,48 +283,24 @@ int CtcAligner::begin(hipStream_t s) {
   return OK;
 }
 
-bool CtcAligner::touches(int r0, int nrows) const {
-  for (const auto& q : seq) {
-    const int32_t* rw = h_rows.data() + q.frame_off;
-    const int32_t* lo = std::lower_bound(rw, rw + q.T, r0);
-    if (lo != rw + q.T && *lo < r0 + nrows) return true;
-  }
-  return false;
-}
-
 int CtcAligner::advance(hipStream_t s, const float* lp, int ld, int r0, int nrows, const float* wmax, float bias) {
   if (has_wild && !wmax) { set_error("ctc align: a transcript with wildcards needs the row maxima"); return E_ARG; }
-  bool any = false;
-  for (auto& q : seq) {
-    const int32_t* rw = h_rows.data() + q.frame_off;
-    const int f0 = (int)(std::lower_bound(rw, rw + q.T, r0) - rw), f1 = (int)(std::lower_bound(rw, rw + q.T, r0 + nrows) - rw);
-    if (f0 < f1 && f0 != q.f1) { set_error("ctc align: slabs must arrive in row order"); return E_STATE; }
-    q.f0 = f0 < f1 ? f0 : q.f1; if (f0 < f1) q.f1 = f1;
-    any = any || f0 < f1;
-  }
+  bool any;
+  RVB_TRY(slab_window("ctc align", false, seq, h_rows, r0, nrows, &any));
   if (!any) return OK;
-  // the descriptors of this launch: a synchronous copy, so the host vector may change for the next slab
-  RVB_HIP_CHECK(hipStreamSynchronize(s));
-  RVB_HIP_CHECK(hipMemcpy(d_seqs.p, seq.data(), seq.size() * sizeof(VitSeq), hipMemcpyHostToDevice));
+  RVB_TRY(slab_upload(s, d_seqs.p, seq));
   return ctc_viterbi_forward(s, d_seqs.as<VitSeq>(), (int)seq.size(), max_S, lp, ld, r0, d_rows.as<int>(), d_tokens.as<int>(), blank,
                              d_alpha.as<float>(), d_bp.as<uint8_t>(), has_wild ? wmax : nullptr, bias);
 }
 
 int CtcAligner::finish(hipStream_t s, int32_t* states, float* score) {
-  for (const auto& q : seq)
-    if (q.f1 != q.T) { set_error("ctc align: the slabs did not cover every frame of a sequence"); return E_STATE; }
-  RVB_TRY_(ctc_viterbi_backtrace(s, d_seqs.as<VitSeq>(), (int)seq.size(), d_alpha.as<float>(), d_bp.as<uint8_t>(), d_states.as<int>(),
+  RVB_TRY(slab_covered("ctc align", false, seq));
+  RVB_TRY(ctc_viterbi_backtrace(s, d_seqs.as<VitSeq>(), (int)seq.size(), d_alpha.as<float>(), d_bp.as<uint8_t>(), d_states.as<int>(),
                                  d_score.as<float>()));
   RVB_HIP_CHECK(hipMemcpyAsync(states, d_states.p, (size_t)total_frames * 4, hipMemcpyDeviceToHost, s));
   RVB_HIP_CHECK(hipMemcpyAsync(score, d_score.p, seq.size() * 4, hipMemcpyDeviceToHost, s));
   RVB_HIP_CHECK(hipStreamSynchronize(s));
-  for (size_t i = 0; i < seq.size(); ++i)
-    if (!(score[i] > -INFINITY)) {
-      set_error("ctc align: sequence " + std::to_string(i) + ": infeasible: no path of " + std::to_string(seq[i].T) +
-                " frames emits the transcript with a finite score");
-      return E_ARG;
-    }
-  return OK;
+  return slab_feasible("ctc align", seq, score, "emits the transcript");
 }
 
 void CtcAligner::release() {

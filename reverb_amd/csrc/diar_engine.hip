@@ -12,8 +12,6 @@
 
 using namespace rvb;
 
-#define RVD_TRY(expr) do { int _r = (expr); if (_r != OK) return _r; } while (0)
-
 namespace {
 struct LstmLayer { Linear ih; DevBuf whh; int in_pad = 0; };
 constexpr int SINC_K = 251, SINC_STRIDE = 10, CONV_K = 5;
@@ -119,16 +117,16 @@ void drain(rvd_engine* e) {
 }
 
 int up_f32(rvd_engine* e, DevBuf& dst, const float* src, size_t n) {
-  RVD_TRY(dst.ensure(n * 4));
+  RVB_TRY(dst.ensure(n * 4));
   RVB_HIP_CHECK(hipMemcpyAsync(dst.p, src, n * 4, hipMemcpyHostToDevice, e->stream));
   RVB_HIP_CHECK(hipStreamSynchronize(e->stream));   // src may be a temporary
   return OK;
 }
 int pack_T(rvd_engine* e, DevBuf& dst, const float* src, size_t n) {
-  RVD_TRY(dst.ensure(n * dt_size(e->dtype)));
+  RVB_TRY(dst.ensure(n * dt_size(e->dtype)));
   if (e->dtype == DT_F32) return up_f32(e, dst, src, n);
-  RVD_TRY(up_f32(e, e->stage, src, n));
-  RVD_TRY(convert_f32(e->stream, e->dtype, e->stage.as<float>(), dst.p, n));
+  RVB_TRY(up_f32(e, e->stage, src, n));
+  RVB_TRY(convert_f32(e->stream, e->dtype, e->stage.as<float>(), dst.p, n));
   RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
   return OK;
 }
@@ -144,10 +142,10 @@ int need(rvd_engine* e, const std::string& name, size_t numel, const HostTensor*
 }
 int pack_norm(rvd_engine* e, LNorm& n, const std::string& p, int d) {
   const HostTensor *g, *b;
-  RVD_TRY(need(e, p + ".weight", d, &g));
-  RVD_TRY(need(e, p + ".bias", d, &b));
+  RVB_TRY(need(e, p + ".weight", d, &g));
+  RVB_TRY(need(e, p + ".bias", d, &b));
   n.eps = 1e-5f;
-  RVD_TRY(up_f32(e, n.g, g->data.data(), d));
+  RVB_TRY(up_f32(e, n.g, g->data.data(), d));
   return up_f32(e, n.b, b->data.data(), d);
 }
 
@@ -187,8 +185,8 @@ void sinc_filters(const float* low_hz_, const float* band_hz_, int npair, int sr
 // its K = k*in_pad columns run on into frames t+1..t+4, which are contiguous in memory)
 int pack_conv1d(rvd_engine* e, Linear& L, const std::string& p, int out, int in, int out_pad, int in_pad) {
   const HostTensor *w, *b;
-  RVD_TRY(need(e, p + ".weight", (size_t)out * in * CONV_K, &w));
-  RVD_TRY(need(e, p + ".bias", out, &b));
+  RVB_TRY(need(e, p + ".weight", (size_t)out * in * CONV_K, &w));
+  RVB_TRY(need(e, p + ".bias", out, &b));
   std::vector<float> pw((size_t)out_pad * CONV_K * in_pad, 0.f), pb(out_pad, 0.f);
   for (int o = 0; o < out; ++o) {
     pb[o] = b->data[o];
@@ -196,7 +194,7 @@ int pack_conv1d(rvd_engine* e, Linear& L, const std::string& p, int out, int in,
       for (int k = 0; k < CONV_K; ++k) pw[((size_t)o * CONV_K + k) * in_pad + c] = w->data[((size_t)o * in + c) * CONV_K + k];
   }
   L.out = out_pad; L.in = CONV_K * in_pad;
-  RVD_TRY(pack_T(e, L.w, pw.data(), pw.size()));
+  RVB_TRY(pack_T(e, L.w, pw.data(), pw.size()));
   return up_f32(e, L.b, pb.data(), pb.size());
 }
 
@@ -227,21 +225,21 @@ int finalize_impl(rvd_engine* e) {
   const std::string S = "segmentation.";
   const HostTensor *t1, *t2;
   // --- SincNet ---
-  RVD_TRY(need(e, S + "sincnet.wav_norm1d.weight", 1, &t1));
-  RVD_TRY(need(e, S + "sincnet.wav_norm1d.bias", 1, &t2));
+  RVB_TRY(need(e, S + "sincnet.wav_norm1d.weight", 1, &t1));
+  RVB_TRY(need(e, S + "sincnet.wav_norm1d.bias", 1, &t2));
   e->wn_gamma = t1->data[0]; e->wn_beta = t2->data[0];
   const int npair = c.sinc_filters / 2;
-  RVD_TRY(need(e, S + "sincnet.conv1d.0.filterbank.low_hz_", npair, &t1));
-  RVD_TRY(need(e, S + "sincnet.conv1d.0.filterbank.band_hz_", npair, &t2));
+  RVB_TRY(need(e, S + "sincnet.conv1d.0.filterbank.low_hz_", npair, &t1));
+  RVB_TRY(need(e, S + "sincnet.conv1d.0.filterbank.band_hz_", npair, &t2));
   std::vector<float> filt, fsum;
   sinc_filters(t1->data.data(), t2->data.data(), npair, c.sample_rate, &filt, &fsum);
-  RVD_TRY(up_f32(e, e->filt, filt.data(), filt.size()));
-  RVD_TRY(up_f32(e, e->fsum, fsum.data(), fsum.size()));
-  RVD_TRY(pack_norm(e, e->norm[0], S + "sincnet.norm1d.0", c.sinc_filters));
-  RVD_TRY(pack_norm(e, e->norm[1], S + "sincnet.norm1d.1", c.sinc_channels));
-  RVD_TRY(pack_norm(e, e->norm[2], S + "sincnet.norm1d.2", c.sinc_channels));
-  RVD_TRY(pack_conv1d(e, e->conv2, S + "sincnet.conv1d.1", c.sinc_channels, c.sinc_filters, e->cpad, c.sinc_filters));
-  RVD_TRY(pack_conv1d(e, e->conv3, S + "sincnet.conv1d.2", c.sinc_channels, c.sinc_channels, e->cpad, e->cpad));
+  RVB_TRY(up_f32(e, e->filt, filt.data(), filt.size()));
+  RVB_TRY(up_f32(e, e->fsum, fsum.data(), fsum.size()));
+  RVB_TRY(pack_norm(e, e->norm[0], S + "sincnet.norm1d.0", c.sinc_filters));
+  RVB_TRY(pack_norm(e, e->norm[1], S + "sincnet.norm1d.1", c.sinc_channels));
+  RVB_TRY(pack_norm(e, e->norm[2], S + "sincnet.norm1d.2", c.sinc_channels));
+  RVB_TRY(pack_conv1d(e, e->conv2, S + "sincnet.conv1d.1", c.sinc_channels, c.sinc_filters, e->cpad, c.sinc_filters));
+  RVB_TRY(pack_conv1d(e, e->conv3, S + "sincnet.conv1d.2", c.sinc_channels, c.sinc_channels, e->cpad, e->cpad));
   // --- LSTM: both directions' input projections as one [8H][in_pad] operand, bias = b_ih + b_hh ---
   const int H = c.lstm_hidden;
   e->lstm.resize(c.lstm_layers);
@@ -252,10 +250,10 @@ int finalize_impl(rvd_engine* e) {
     for (int d = 0; d < 2; ++d) {
       const std::string suf = "_l" + std::to_string(l) + (d ? "_reverse" : "");
       const HostTensor *wi, *wh, *bi, *bh;
-      RVD_TRY(need(e, S + "lstm.weight_ih" + suf, (size_t)4 * H * in, &wi));
-      RVD_TRY(need(e, S + "lstm.weight_hh" + suf, (size_t)4 * H * H, &wh));
-      RVD_TRY(need(e, S + "lstm.bias_ih" + suf, (size_t)4 * H, &bi));
-      RVD_TRY(need(e, S + "lstm.bias_hh" + suf, (size_t)4 * H, &bh));
+      RVB_TRY(need(e, S + "lstm.weight_ih" + suf, (size_t)4 * H * in, &wi));
+      RVB_TRY(need(e, S + "lstm.weight_hh" + suf, (size_t)4 * H * H, &wh));
+      RVB_TRY(need(e, S + "lstm.bias_ih" + suf, (size_t)4 * H, &bi));
+      RVB_TRY(need(e, S + "lstm.bias_hh" + suf, (size_t)4 * H, &bh));
       // The projection's output columns are laid out for the recurrence kernel (diar.hip lstm_pack_inproj)
       lstm_pack_inproj(wi->data.data(), bi->data.data(), bh->data.data(), H, in, in_pad, &wih[(size_t)d * 4 * H * in_pad],
                        &bias[(size_t)d * 4 * H]);
@@ -264,27 +262,27 @@ int finalize_impl(rvd_engine* e) {
     LstmLayer& L = e->lstm[l];
     L.in_pad = in_pad;
     L.ih.out = 8 * H; L.ih.in = in_pad;
-    RVD_TRY(pack_T(e, L.ih.w, wih.data(), wih.size()));
-    RVD_TRY(up_f32(e, L.ih.b, bias.data(), bias.size()));
-    RVD_TRY(pack_T(e, L.whh, whh.data(), whh.size()));
+    RVB_TRY(pack_T(e, L.ih.w, wih.data(), wih.size()));
+    RVB_TRY(up_f32(e, L.ih.b, bias.data(), bias.size()));
+    RVB_TRY(pack_T(e, L.whh, whh.data(), whh.size()));
   }
   // --- linears + classifier ---
   e->lin.resize(c.linear_layers);
   for (int i = 0; i < c.linear_layers; ++i) {
     const int in = i == 0 ? 2 * H : c.linear_dim;
     const std::string p = S + "linear." + std::to_string(i);
-    RVD_TRY(need(e, p + ".weight", (size_t)c.linear_dim * in, &t1));
-    RVD_TRY(need(e, p + ".bias", c.linear_dim, &t2));
+    RVB_TRY(need(e, p + ".weight", (size_t)c.linear_dim * in, &t1));
+    RVB_TRY(need(e, p + ".bias", c.linear_dim, &t2));
     e->lin[i].out = c.linear_dim; e->lin[i].in = in;
-    RVD_TRY(pack_T(e, e->lin[i].w, t1->data.data(), t1->data.size()));
-    RVD_TRY(up_f32(e, e->lin[i].b, t2->data.data(), t2->data.size()));
+    RVB_TRY(pack_T(e, e->lin[i].w, t1->data.data(), t1->data.size()));
+    RVB_TRY(up_f32(e, e->lin[i].b, t2->data.data(), t2->data.size()));
   }
   const int cls_in = c.linear_layers ? c.linear_dim : 2 * H;
-  RVD_TRY(need(e, S + "classifier.weight", (size_t)c.num_classes * cls_in, &t1));
-  RVD_TRY(need(e, S + "classifier.bias", c.num_classes, &t2));
-  RVD_TRY(up_f32(e, e->cls_w, t1->data.data(), t1->data.size()));
-  RVD_TRY(up_f32(e, e->cls_b, t2->data.data(), t2->data.size()));
-  if (c.emb_channels > 0) RVD_TRY(finalize_embedding(e));
+  RVB_TRY(need(e, S + "classifier.weight", (size_t)c.num_classes * cls_in, &t1));
+  RVB_TRY(need(e, S + "classifier.bias", c.num_classes, &t2));
+  RVB_TRY(up_f32(e, e->cls_w, t1->data.data(), t1->data.size()));
+  RVB_TRY(up_f32(e, e->cls_b, t2->data.data(), t2->data.size()));
+  if (c.emb_channels > 0) RVB_TRY(finalize_embedding(e));
   e->host.clear();
   e->stage.release();
   e->finalized = true;
@@ -299,22 +297,22 @@ int segment_impl(rvd_engine* e, int64_t first, int W, float* logp_out) {
   const int H = c.lstm_hidden, CP = e->cpad, NF = c.sinc_filters;
   const int64_t R1 = (int64_t)W * e->p1, R2 = (int64_t)W * e->p2, R3 = (int64_t)W * e->p3;
   if (R1 > 0x7fffffffLL / 4) { set_error("rvd_segment: too many windows in one call (limit 100k frames rows)"); return E_ARG; }
-  RVD_TRY(e->stats.ensure((size_t)W * 8));
-  RVD_TRY(e->a1.ensure((size_t)(R1 + 8) * NF * ts));
-  RVD_TRY(e->c2.ensure((size_t)R1 * CP * ts));
-  RVD_TRY(e->a2.ensure((size_t)(R2 + 8) * CP * ts));
-  RVD_TRY(e->c3.ensure((size_t)R2 * CP * ts));
-  RVD_TRY(e->a3.ensure((size_t)R3 * CP * ts));
-  RVD_TRY(e->xproj.ensure((size_t)R3 * 8 * H * ts));
-  RVD_TRY(e->hA.ensure((size_t)R3 * 2 * H * ts));
-  RVD_TRY(e->hB.ensure((size_t)R3 * 2 * H * ts));
-  RVD_TRY(e->l0.ensure((size_t)R3 * c.linear_dim * ts));
-  RVD_TRY(e->l1.ensure((size_t)R3 * c.linear_dim * ts));
-  RVD_TRY(e->logp.ensure((size_t)R3 * c.num_classes * 4));
-  RVD_TRY(e->cls.ensure((size_t)R3));
+  RVB_TRY(e->stats.ensure((size_t)W * 8));
+  RVB_TRY(e->a1.ensure((size_t)(R1 + 8) * NF * ts));
+  RVB_TRY(e->c2.ensure((size_t)R1 * CP * ts));
+  RVB_TRY(e->a2.ensure((size_t)(R2 + 8) * CP * ts));
+  RVB_TRY(e->c3.ensure((size_t)R2 * CP * ts));
+  RVB_TRY(e->a3.ensure((size_t)R3 * CP * ts));
+  RVB_TRY(e->xproj.ensure((size_t)R3 * 8 * H * ts));
+  RVB_TRY(e->hA.ensure((size_t)R3 * 2 * H * ts));
+  RVB_TRY(e->hB.ensure((size_t)R3 * 2 * H * ts));
+  RVB_TRY(e->l0.ensure((size_t)R3 * c.linear_dim * ts));
+  RVB_TRY(e->l1.ensure((size_t)R3 * c.linear_dim * ts));
+  RVB_TRY(e->logp.ensure((size_t)R3 * c.num_classes * 4));
+  RVB_TRY(e->cls.ensure((size_t)R3));
 
   { DScope sc(e, "window_stats");
-    RVD_TRY(window_stats(e->stream, e->wave.as<float>(), first, W, c.step_samples, c.window_samples, 1e-5f, e->stats.as<float>())); }
+    RVB_TRY(window_stats(e->stream, e->wave.as<float>(), first, W, c.step_samples, c.window_samples, 1e-5f, e->stats.as<float>())); }
   PoolNormArgs pn{};
   pn.W = W; pn.eps = 1e-5f;
   { DScope sc(e, "pool_norm");
@@ -323,35 +321,35 @@ int segment_impl(rvd_engine* e, int64_t first, int W, float* logp_out) {
     pn.craw = e->craw.p; pn.craw_frame0 = first * (c.step_samples / SINC_STRIDE);
     pn.craw_frames_per_step = c.step_samples / SINC_STRIDE;
     pn.stats = e->stats.as<float>(); pn.fsum = e->fsum.as<float>(); pn.wn_gamma = e->wn_gamma; pn.wn_beta = e->wn_beta;
-    RVD_TRY(pool_norm(e->stream, e->dtype, pn)); }
-  RVD_TRY(run_sincnet_conv(e, e->a1.p, NF, e->conv2, e->c2.p, CP, R1));
+    RVB_TRY(pool_norm(e->stream, e->dtype, pn)); }
+  RVB_TRY(run_sincnet_conv(e, e->a1.p, NF, e->conv2, e->c2.p, CP, R1));
   { DScope sc(e, "pool_norm");
     pn.x = e->c2.p; pn.rows_in = e->p1; pn.ld_in = CP; pn.frames_in = e->f2; pn.C = c.sinc_channels; pn.ld_out = CP;
     pn.gamma = e->norm[1].g.as<float>(); pn.beta = e->norm[1].b.as<float>(); pn.out = e->a2.p;
-    RVD_TRY(pool_norm(e->stream, e->dtype, pn)); }
-  RVD_TRY(run_sincnet_conv(e, e->a2.p, CP, e->conv3, e->c3.p, CP, R2));
+    RVB_TRY(pool_norm(e->stream, e->dtype, pn)); }
+  RVB_TRY(run_sincnet_conv(e, e->a2.p, CP, e->conv3, e->c3.p, CP, R2));
   { DScope sc(e, "pool_norm");
     pn.x = e->c3.p; pn.rows_in = e->p2; pn.ld_in = CP; pn.frames_in = e->f3; pn.C = c.sinc_channels; pn.ld_out = CP;
     pn.gamma = e->norm[2].g.as<float>(); pn.beta = e->norm[2].b.as<float>(); pn.out = e->a3.p;
-    RVD_TRY(pool_norm(e->stream, e->dtype, pn)); }
+    RVB_TRY(pool_norm(e->stream, e->dtype, pn)); }
 
   const void* x = e->a3.p;
   int ldx = CP;
   for (int l = 0; l < c.lstm_layers; ++l) {
-    RVD_TRY(run_gemm(e, "lstm_inproj", x, ldx, e->lstm[l].ih, e->xproj.p, 8 * H, R3, ACT_NONE));
+    RVB_TRY(run_gemm(e, "lstm_inproj", x, ldx, e->lstm[l].ih, e->xproj.p, 8 * H, R3, ACT_NONE));
     void* out = (l & 1) ? e->hB.p : e->hA.p;
     { DScope sc(e, "lstm_recurrence", 2.0 * (double)R3 * 8 * H * H);
-      RVD_TRY(lstm_recurrence(e->stream, e->dtype, e->xproj.p, e->lstm[l].whh.p, out, W, e->p3)); }
+      RVB_TRY(lstm_recurrence(e->stream, e->dtype, e->xproj.p, e->lstm[l].whh.p, out, W, e->p3)); }
     x = out; ldx = 2 * H;
   }
   e->last_lstm = x;
   for (int i = 0; i < c.linear_layers; ++i) {
     void* out = (i & 1) ? e->l1.p : e->l0.p;
-    RVD_TRY(run_gemm(e, "linear", x, ldx, e->lin[i], out, c.linear_dim, R3, ACT_LRELU));
+    RVB_TRY(run_gemm(e, "linear", x, ldx, e->lin[i], out, c.linear_dim, R3, ACT_LRELU));
     x = out; ldx = c.linear_dim;
   }
   { DScope sc(e, "classifier");
-    RVD_TRY(classifier_logsoftmax(e->stream, e->dtype, x, ldx, e->cls_w.as<float>(), e->cls_b.as<float>(), e->logp.as<float>(),
+    RVB_TRY(classifier_logsoftmax(e->stream, e->dtype, x, ldx, e->cls_w.as<float>(), e->cls_b.as<float>(), e->logp.as<float>(),
                                   e->cls.as<uint8_t>(), R3, ldx, c.num_classes)); }
   e->last_W = W;
   if (logp_out) {
@@ -381,21 +379,21 @@ int make_hamming_fbank_tables(rvd_engine* e) {
     }
     if (hi[m] == 0) lo[m] = 0;
   }
-  RVD_TRY(up_f32(e, e->fb_window, win.data(), win.size()));
-  RVD_TRY(up_f32(e, e->fb_twiddle, tw.data(), tw.size()));
-  RVD_TRY(up_f32(e, e->fb_melw, melw.data(), melw.size()));
-  RVD_TRY(up_f32(e, e->fb_lo, (const float*)lo.data(), lo.size()));   // raw 4-byte copies
+  RVB_TRY(up_f32(e, e->fb_window, win.data(), win.size()));
+  RVB_TRY(up_f32(e, e->fb_twiddle, tw.data(), tw.size()));
+  RVB_TRY(up_f32(e, e->fb_melw, melw.data(), melw.size()));
+  RVB_TRY(up_f32(e, e->fb_lo, (const float*)lo.data(), lo.size()));   // raw 4-byte copies
   return up_f32(e, e->fb_hi, (const float*)hi.data(), hi.size());
 }
 
 // Conv2d weight [cout][cin][k][k] + eval-mode BatchNorm -> [tap][cin/CK][cout][CK] (T) and bias (fp32)
 int pack_conv_bn(rvd_engine* e, ConvW& c, const std::string& conv, const std::string& bn, int cout, int cin, int k, int stride) {
   const HostTensor *w, *g, *b, *m, *v;
-  RVD_TRY(need(e, conv + ".weight", (size_t)cout * cin * k * k, &w));
-  RVD_TRY(need(e, bn + ".weight", cout, &g));
-  RVD_TRY(need(e, bn + ".bias", cout, &b));
-  RVD_TRY(need(e, bn + ".running_mean", cout, &m));
-  RVD_TRY(need(e, bn + ".running_var", cout, &v));
+  RVB_TRY(need(e, conv + ".weight", (size_t)cout * cin * k * k, &w));
+  RVB_TRY(need(e, bn + ".weight", cout, &g));
+  RVB_TRY(need(e, bn + ".bias", cout, &b));
+  RVB_TRY(need(e, bn + ".running_mean", cout, &m));
+  RVB_TRY(need(e, bn + ".running_var", cout, &v));
   const int CK = 64 / (int)dt_size(e->dtype);
   if (cin % CK) { set_error("embedding conv " + conv + ": input channels must be a multiple of " + std::to_string(CK)); return E_UNSUPPORTED; }
   const int taps = k * k;
@@ -406,7 +404,7 @@ int pack_conv_bn(rvd_engine* e, ConvW& c, const std::string& conv, const std::st
   }
   conv_pack_direct(w->data.data(), sc.data(), cout, cin, taps, CK, pw.data());
   c.cin = cin; c.cout = cout; c.taps = taps; c.stride = stride;
-  RVD_TRY(pack_T(e, c.w, pw.data(), pw.size()));
+  RVB_TRY(pack_T(e, c.w, pw.data(), pw.size()));
   // implicit-GEMM kernel (conv_gemm.hip) for the 128- and 256-channel stride-1 convolutions: second weight layout
   // [cout][tap][cin].  Validated on hardware in round 2 (tests/test_diar_gpu.py: both kernels against the oracle and
   // against each other; 806 / 1150 TFLOP/s vs 555-598 for the direct kernel); RVD_CONV_IGEMM=0 selects the direct kernel.
@@ -414,7 +412,7 @@ int pack_conv_bn(rvd_engine* e, ConvW& c, const std::string& conv, const std::st
   if (conv_igemm_packed(e->dtype, k, stride, cin, cout)) {
     std::vector<float> pg((size_t)cout * taps * cin);
     conv_pack_igemm(w->data.data(), sc.data(), cout, cin, taps, (size_t)taps * cin, pg.data());
-    RVD_TRY(pack_T(e, c.w_ig, pg.data(), pg.size()));
+    RVB_TRY(pack_T(e, c.w_ig, pg.data(), pg.size()));
     if (e->emb_fp8 && cin % 128 == 0) {          // e4m3 copy, one scale per output channel (as engine.hip's pack_linear)
       std::vector<uint8_t> q(pg.size());
       std::vector<float> ws(cout);
@@ -426,9 +424,9 @@ int pack_conv_bn(rvd_engine* e, ConvW& c, const std::string& conv, const std::st
         const float inv = 1.f / ws[o];
         for (size_t kk = 0; kk < K; ++kk) q[(size_t)o * K + kk] = f32_to_fp8_host(pg[(size_t)o * K + kk] * inv);
       }
-      RVD_TRY(c.w8.ensure(q.size()));
+      RVB_TRY(c.w8.ensure(q.size()));
       RVB_HIP_CHECK(hipMemcpyAsync(c.w8.p, q.data(), q.size(), hipMemcpyHostToDevice, e->stream));
-      RVD_TRY(up_f32(e, c.w8s, ws.data(), ws.size()));
+      RVB_TRY(up_f32(e, c.w8s, ws.data(), ws.size()));
       RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
     }
   }
@@ -444,16 +442,16 @@ int pack_fused_shortcut(rvd_engine* e, ResBlock& B, const std::string& p) {
   if ((f && atoi(f) == 0) || !B.has_sc || !B.c2.w_ig.p || B.sc.cin % 64 || B.sc.taps != 1) return OK;
   const int cout = B.c2.cout, cin = B.c2.cin, c2 = B.sc.cin;
   const HostTensor *w, *g, *b, *m, *v, *ws, *gs, *bs, *ms, *vs;
-  RVD_TRY(need(e, p + ".conv2.weight", (size_t)cout * cin * 9, &w));
-  RVD_TRY(need(e, p + ".bn2.weight", cout, &g));
-  RVD_TRY(need(e, p + ".bn2.bias", cout, &b));
-  RVD_TRY(need(e, p + ".bn2.running_mean", cout, &m));
-  RVD_TRY(need(e, p + ".bn2.running_var", cout, &v));
-  RVD_TRY(need(e, p + ".shortcut.0.weight", (size_t)cout * c2, &ws));
-  RVD_TRY(need(e, p + ".shortcut.1.weight", cout, &gs));
-  RVD_TRY(need(e, p + ".shortcut.1.bias", cout, &bs));
-  RVD_TRY(need(e, p + ".shortcut.1.running_mean", cout, &ms));
-  RVD_TRY(need(e, p + ".shortcut.1.running_var", cout, &vs));
+  RVB_TRY(need(e, p + ".conv2.weight", (size_t)cout * cin * 9, &w));
+  RVB_TRY(need(e, p + ".bn2.weight", cout, &g));
+  RVB_TRY(need(e, p + ".bn2.bias", cout, &b));
+  RVB_TRY(need(e, p + ".bn2.running_mean", cout, &m));
+  RVB_TRY(need(e, p + ".bn2.running_var", cout, &v));
+  RVB_TRY(need(e, p + ".shortcut.0.weight", (size_t)cout * c2, &ws));
+  RVB_TRY(need(e, p + ".shortcut.1.weight", cout, &gs));
+  RVB_TRY(need(e, p + ".shortcut.1.bias", cout, &bs));
+  RVB_TRY(need(e, p + ".shortcut.1.running_mean", cout, &ms));
+  RVB_TRY(need(e, p + ".shortcut.1.running_var", cout, &vs));
   std::vector<float> pg((size_t)cout * (9 * (size_t)cin + c2)), pb(cout), sc(cout), ss(cout);
   for (int o = 0; o < cout; ++o) {
     sc[o] = g->data[o] / std::sqrt(v->data[o] + 1e-5f);
@@ -461,7 +459,7 @@ int pack_fused_shortcut(rvd_engine* e, ResBlock& B, const std::string& p) {
     pb[o] = (b->data[o] - m->data[o] * sc[o]) + (bs->data[o] - ms->data[o] * ss[o]);
   }
   conv_pack_fused_shortcut(w->data.data(), sc.data(), ws->data.data(), ss.data(), cout, cin, c2, pg.data());
-  RVD_TRY(pack_T(e, B.c2.w_ig_sc, pg.data(), pg.size()));
+  RVB_TRY(pack_T(e, B.c2.w_ig_sc, pg.data(), pg.size()));
   return up_f32(e, B.c2.b_sc, pb.data(), pb.size());
 }
 
@@ -474,19 +472,19 @@ int finalize_embedding(rvd_engine* e) {
   { const char* f8 = lab_env("RVD_EMB_FP8"); e->emb_fp8 = (e->want_fp8 || (f8 && atoi(f8) == 1)) && e->dtype == DT_BF16; e->emb_f8_state = 0; }
   // stem: Conv2d(1, m, 3) + BN folded, fp32 weights [m][9]
   const HostTensor *w, *g, *b, *mu, *v;
-  RVD_TRY(need(e, S + "conv1.weight", (size_t)m * 9, &w));
-  RVD_TRY(need(e, S + "bn1.weight", m, &g));
-  RVD_TRY(need(e, S + "bn1.bias", m, &b));
-  RVD_TRY(need(e, S + "bn1.running_mean", m, &mu));
-  RVD_TRY(need(e, S + "bn1.running_var", m, &v));
+  RVB_TRY(need(e, S + "conv1.weight", (size_t)m * 9, &w));
+  RVB_TRY(need(e, S + "bn1.weight", m, &g));
+  RVB_TRY(need(e, S + "bn1.bias", m, &b));
+  RVB_TRY(need(e, S + "bn1.running_mean", m, &mu));
+  RVB_TRY(need(e, S + "bn1.running_var", m, &v));
   std::vector<float> sw((size_t)m * 9), sb(m);
   for (int o = 0; o < m; ++o) {
     const float sc = g->data[o] / std::sqrt(v->data[o] + 1e-5f);
     sb[o] = b->data[o] - mu->data[o] * sc;
     for (int t = 0; t < 9; ++t) sw[(size_t)o * 9 + t] = w->data[(size_t)o * 9 + t] * sc;
   }
-  RVD_TRY(up_f32(e, e->stem_w, sw.data(), sw.size()));
-  RVD_TRY(up_f32(e, e->stem_b, sb.data(), sb.size()));
+  RVB_TRY(up_f32(e, e->stem_w, sw.data(), sw.size()));
+  RVB_TRY(up_f32(e, e->stem_b, sb.data(), sb.size()));
   const int nblk[4] = {3, 4, 6, 3};
   e->stages.assign(4, {});
   int cin = m;
@@ -497,21 +495,21 @@ int finalize_embedding(rvd_engine* e) {
       ResBlock& B = e->stages[li][bi];
       const int stride = (bi == 0 && li > 0) ? 2 : 1;
       const std::string p = S + "layer" + std::to_string(li + 1) + "." + std::to_string(bi);
-      RVD_TRY(pack_conv_bn(e, B.c1, p + ".conv1", p + ".bn1", cout, cin, 3, stride));
-      RVD_TRY(pack_conv_bn(e, B.c2, p + ".conv2", p + ".bn2", cout, cout, 3, 1));
+      RVB_TRY(pack_conv_bn(e, B.c1, p + ".conv1", p + ".bn1", cout, cin, 3, stride));
+      RVB_TRY(pack_conv_bn(e, B.c2, p + ".conv2", p + ".bn2", cout, cout, 3, 1));
       B.has_sc = stride != 1 || cin != cout;
-      if (B.has_sc) RVD_TRY(pack_conv_bn(e, B.sc, p + ".shortcut.0", p + ".shortcut.1", cout, cin, 1, stride));
-      RVD_TRY(pack_fused_shortcut(e, B, p));
+      if (B.has_sc) RVB_TRY(pack_conv_bn(e, B.sc, p + ".shortcut.0", p + ".shortcut.1", cout, cin, 1, stride));
+      RVB_TRY(pack_fused_shortcut(e, B, p));
       cin = cout;
     }
   }
   const int stats = (FB_MEL / 8) * (m << 3) * 2;
-  RVD_TRY(need(e, S + "seg_1.weight", (size_t)c.emb_dim * stats, &w));
-  RVD_TRY(need(e, S + "seg_1.bias", c.emb_dim, &b));
+  RVB_TRY(need(e, S + "seg_1.weight", (size_t)c.emb_dim * stats, &w));
+  RVB_TRY(need(e, S + "seg_1.bias", c.emb_dim, &b));
   e->seg1.out = c.emb_dim; e->seg1.in = stats;
-  RVD_TRY(pack_T(e, e->seg1.w, w->data.data(), w->data.size()));
-  RVD_TRY(up_f32(e, e->seg1.b, b->data.data(), b->data.size()));
-  RVD_TRY(make_hamming_fbank_tables(e));
+  RVB_TRY(pack_T(e, e->seg1.w, w->data.data(), w->data.size()));
+  RVB_TRY(up_f32(e, e->seg1.b, b->data.data(), b->data.size()));
+  RVB_TRY(make_hamming_fbank_tables(e));
   e->nfr = (c.window_samples - FB_WIN) / FB_SHIFT + 1;
   e->has_emb = true;
   return OK;
@@ -536,10 +534,10 @@ int ensure_emb_workspace(rvd_engine* e, int B) {
     const size_t bytes = (size_t)B * (d.F + 2) * (d.T + 2) * d.C * ts;
     for (int k = 0; k < 4; ++k) {
       if (k == 3 && li == 0) continue;            // stage 1 has no projection shortcut
-      RVD_TRY(e->act[li][k].ensure(bytes));
+      RVB_TRY(e->act[li][k].ensure(bytes));
       RVB_HIP_CHECK(hipMemsetAsync(e->act[li][k].p, 0, bytes, e->stream));   // the zero border is never written again
       if (e->emb_fp8 && li >= 2 && k < 3) {
-        RVD_TRY(e->act8[li][k].ensure(bytes / ts));
+        RVB_TRY(e->act8[li][k].ensure(bytes / ts));
         RVB_HIP_CHECK(hipMemsetAsync(e->act8[li][k].p, 0, bytes / ts, e->stream));
       }
     }
@@ -571,7 +569,7 @@ int run_trunk(rvd_engine* e, int B, const void** trunk_out) {
   const int fps = c.step_samples / FB_SHIFT;
   const StageDims d0 = stage_dims(e, 0);
   { DScope sc(e, "emb_stem", 2.0 * (double)B * d0.F * d0.T * d0.C * 9);
-    RVD_TRY(emb_conv1(e->stream, e->dtype, e->emb_fb.as<float>(), e->e_win.as<int64_t>(), e->e_mean.as<float>(), e->stem_w.as<float>(),
+    RVB_TRY(emb_conv1(e->stream, e->dtype, e->emb_fb.as<float>(), e->e_win.as<int64_t>(), e->e_mean.as<float>(), e->stem_w.as<float>(),
                       e->stem_b.as<float>(), e->act[0][0].p, B, d0.F, d0.T, fps, d0.C)); }
   const void* x = e->act[0][0].p;
   StageDims dx = d0;
@@ -593,7 +591,7 @@ int run_trunk(rvd_engine* e, int B, const void** trunk_out) {
         a.B = B; a.F = d.F; a.T = d.T;
         e->prof["emb_conv_block"].launches += 1;
         { DScope sc(e, "emb_conv_32", 2.0 * 2.0 * (double)B * d.F * d.T * 32 * 32 * 9);
-          RVD_TRY(conv_block32(e->stream, a)); }
+          RVB_TRY(conv_block32(e->stream, a)); }
         x = out; dx = d; xi = oi;
         continue;
       }
@@ -619,16 +617,16 @@ int run_trunk(rvd_engine* e, int B, const void** trunk_out) {
           return conv_igemm8(e->stream, a);
         };
         if (bi == 0) {
-          RVD_TRY(run_conv(e, Bk.c1, x, dx, nullptr, tmp, d, B, 1));
-          RVD_TRY(act_quant_fp8(e->stream, tmp, tmp8, n_el, s_tmp, sat));
+          RVB_TRY(run_conv(e, Bk.c1, x, dx, nullptr, tmp, d, B, 1));
+          RVB_TRY(act_quant_fp8(e->stream, tmp, tmp8, n_el, s_tmp, sat));
           if (Bk.has_sc) {
-            RVD_TRY(run_conv(e, Bk.sc, x, dx, nullptr, e->act[li][3].p, d, B, 0));
+            RVB_TRY(run_conv(e, Bk.sc, x, dx, nullptr, e->act[li][3].p, d, B, 0));
             res = e->act[li][3].p;
           }
         } else {
-          RVD_TRY(conv8(Bk.c1, e->act8[li][xi].p, e->scale8[si - 1], nullptr, nullptr, tmp8, s_tmp));      // x8 = the previous block's e4m3 output
+          RVB_TRY(conv8(Bk.c1, e->act8[li][xi].p, e->scale8[si - 1], nullptr, nullptr, tmp8, s_tmp));      // x8 = the previous block's e4m3 output
         }
-        RVD_TRY(conv8(Bk.c2, tmp8, s_tmp, res, out, out8, s_out));
+        RVB_TRY(conv8(Bk.c2, tmp8, s_tmp, res, out, out8, s_out));
         x = out; dx = d; xi = oi;
         continue;
       }
@@ -643,13 +641,13 @@ int run_trunk(rvd_engine* e, int B, const void** trunk_out) {
         e->prof["emb_conv_s2sc"].launches += 1;
         { DScope sc(e, ("emb_conv_s2_" + std::to_string(Bk.c1.cout)).c_str(),
                     2.0 * (double)B * d.F * d.T * Bk.c1.cout * ((double)Bk.c1.cin * 9 + Bk.sc.cin));
-          RVD_TRY(conv_s2sc(e->stream, a)); }
+          RVB_TRY(conv_s2sc(e->stream, a)); }
         sc_done = true;
       } else {
-        RVD_TRY(run_conv(e, Bk.c1, x, dx, nullptr, tmp, d, B, 1));
+        RVB_TRY(run_conv(e, Bk.c1, x, dx, nullptr, tmp, d, B, 1));
       }
       if (f8blk && e->emb_f8_state == 1)
-        RVD_TRY(act_amax_bf16(e->stream, tmp, (size_t)B * (d.F + 2) * (d.T + 2) * d.C, e->d_amax8.as<unsigned>() + ((li - 2) * 8 + (int)bi) * 2));
+        RVB_TRY(act_amax_bf16(e->stream, tmp, (size_t)B * (d.F + 2) * (d.T + 2) * d.C, e->d_amax8.as<unsigned>() + ((li - 2) * 8 + (int)bi) * 2));
       if (Bk.has_sc && Bk.c2.w_ig_sc.p) {        // the projection shortcut inside the second convolution's K loop (RVD_CONV_SC_FUSE=1)
         ConvArgs a{};
         a.in = tmp; a.w = Bk.c2.w.p; a.bias = Bk.c2.b_sc.as<float>(); a.res = nullptr; a.out = out;
@@ -662,18 +660,18 @@ int run_trunk(rvd_engine* e, int B, const void** trunk_out) {
         e->prof["emb_conv_sc_fused"].launches += 1;
         { DScope sc(e, ("emb_conv_" + std::to_string(Bk.c2.cout)).c_str(),
                     2.0 * (double)B * d.F * d.T * Bk.c2.cout * ((double)Bk.c2.cin * 9 + Bk.sc.cin));
-          RVD_TRY(conv2d(e->stream, e->dtype, a)); }
+          RVB_TRY(conv2d(e->stream, e->dtype, a)); }
         x = out; dx = d; xi = oi;
         continue;
       }
       const void* res = x;
       if (Bk.has_sc) {
-        if (!sc_done) RVD_TRY(run_conv(e, Bk.sc, x, dx, nullptr, e->act[li][3].p, d, B, 0));
+        if (!sc_done) RVB_TRY(run_conv(e, Bk.sc, x, dx, nullptr, e->act[li][3].p, d, B, 0));
         res = e->act[li][3].p;
       }
-      RVD_TRY(run_conv(e, Bk.c2, tmp, d, res, out, d, B, 1));
+      RVB_TRY(run_conv(e, Bk.c2, tmp, d, res, out, d, B, 1));
       if (f8blk && e->emb_f8_state == 1)
-        RVD_TRY(act_amax_bf16(e->stream, out, (size_t)B * (d.F + 2) * (d.T + 2) * d.C, e->d_amax8.as<unsigned>() + ((li - 2) * 8 + (int)bi) * 2 + 1));
+        RVB_TRY(act_amax_bf16(e->stream, out, (size_t)B * (d.F + 2) * (d.T + 2) * d.C, e->d_amax8.as<unsigned>() + ((li - 2) * 8 + (int)bi) * 2 + 1));
       x = out; dx = d; xi = oi;
     }
   }
@@ -718,24 +716,24 @@ int embed_impl(rvd_engine* e, const int64_t* win, const float* mask, int n, floa
       }
       if (rc != OK) return rc;
     }
-    RVD_TRY(e->e_win.ensure((size_t)B * 8));
-    RVD_TRY(e->e_item_b.ensure((size_t)ni * 4));
-    RVD_TRY(e->e_mask.ensure((size_t)ni * frames * 4));
-    RVD_TRY(e->e_stats.ensure((size_t)ni * stats * dt_size(e->dtype)));
-    RVD_TRY(e->e_out.ensure((size_t)ni * c.emb_dim * 4));
+    RVB_TRY(e->e_win.ensure((size_t)B * 8));
+    RVB_TRY(e->e_item_b.ensure((size_t)ni * 4));
+    RVB_TRY(e->e_mask.ensure((size_t)ni * frames * 4));
+    RVB_TRY(e->e_stats.ensure((size_t)ni * stats * dt_size(e->dtype)));
+    RVB_TRY(e->e_out.ensure((size_t)ni * c.emb_dim * 4));
     RVB_HIP_CHECK(hipMemcpyAsync(e->e_win.p, uniq.data(), (size_t)B * 8, hipMemcpyHostToDevice, e->stream));
     RVB_HIP_CHECK(hipMemcpyAsync(e->e_item_b.p, item_b.data(), (size_t)ni * 4, hipMemcpyHostToDevice, e->stream));
     RVB_HIP_CHECK(hipMemcpyAsync(e->e_mask.p, mask + (size_t)i0 * frames, (size_t)ni * frames * 4, hipMemcpyHostToDevice, e->stream));
     RVB_HIP_CHECK(hipStreamSynchronize(e->stream));    // uniq / item_b are locals
     const void* trunk = nullptr;
     if (e->emb_fp8 && e->emb_f8_state == 0) {          // the first trunk pass of an fp8 engine runs in bf16 and records the ranges
-      RVD_TRY(e->d_amax8.ensure(32 * 4));
-      RVD_TRY(e->d_sat8.ensure(4));
+      RVB_TRY(e->d_amax8.ensure(32 * 4));
+      RVB_TRY(e->d_sat8.ensure(4));
       RVB_HIP_CHECK(hipMemsetAsync(e->d_amax8.p, 0, 32 * 4, e->stream));
       RVB_HIP_CHECK(hipMemsetAsync(e->d_sat8.p, 0, 4, e->stream));
       e->emb_f8_state = 1;
     }
-    RVD_TRY(run_trunk(e, B, &trunk));
+    RVB_TRY(run_trunk(e, B, &trunk));
     if (e->emb_f8_state == 1) {
       float am[32];
       RVB_HIP_CHECK(hipMemcpyAsync(am, e->d_amax8.p, sizeof(am), hipMemcpyDeviceToHost, e->stream));
@@ -746,13 +744,13 @@ int embed_impl(rvd_engine* e, const int64_t* win, const float* mask, int n, floa
       e->emb_f8_state = 2;
     }
     { DScope sc(e, "emb_pool");
-      RVD_TRY(tstp_pool(e->stream, e->dtype, trunk, e->e_item_b.as<int>(), e->e_mask.as<float>(), frames, ni, d3.F, d3.T, d3.C, e->e_stats.p)); }
+      RVB_TRY(tstp_pool(e->stream, e->dtype, trunk, e->e_item_b.as<int>(), e->e_mask.as<float>(), frames, ni, d3.F, d3.T, d3.C, e->e_stats.p)); }
     { DScope sc(e, "emb_linear", 2.0 * (double)ni * stats * c.emb_dim);
       GemmArgs g{};
       g.A = e->e_stats.p; g.W = e->seg1.w.p; g.bias = e->seg1.b.as<float>(); g.C = e->e_out.p;
       g.M = ni; g.N = c.emb_dim; g.K = stats; g.lda = stats; g.ldw = stats; g.ldc = c.emb_dim; g.alpha = 1.f; g.act = ACT_NONE;
       g.out_f32 = 1;
-      RVD_TRY(gemm(e->stream, e->dtype, g)); }
+      RVB_TRY(gemm(e->stream, e->dtype, g)); }
     RVB_HIP_CHECK(hipMemcpyAsync(emb_out + (size_t)i0 * c.emb_dim, e->e_out.p, (size_t)ni * c.emb_dim * 4, hipMemcpyDeviceToHost, e->stream));
     RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
     i0 = i1;
@@ -880,7 +878,7 @@ int rvd_upload_pcm(rvd_engine* e, const int16_t* pcm, int64_t n) {
   if (!e || !pcm || n <= 0) { set_error("rvd_upload_pcm: null or empty audio"); return E_ARG; }
   if (!e->finalized) { set_error("rvd_upload_pcm: finalize the model first"); return E_STATE; }
   RVB_HIP_CHECK(hipSetDevice(e->device));
-  RVD_TRY(e->pcm.ensure((size_t)n * 2));
+  RVB_TRY(e->pcm.ensure((size_t)n * 2));
   { DScope sc(e, "h2d");
     RVB_HIP_CHECK(hipMemcpyAsync(e->pcm.p, pcm, (size_t)n * 2, hipMemcpyHostToDevice, e->stream)); }
   return prepare_audio(e, n);
@@ -931,26 +929,26 @@ static int prepare_audio(rvd_engine* e, int64_t n) {
   e->n_windows = rvd_num_windows(e, n);
   e->n_pad = (e->n_windows - 1) * c.step_samples + c.window_samples;
   e->craw_frames = (e->n_pad - SINC_K) / SINC_STRIDE + 1;
-  RVD_TRY(e->wave.ensure((size_t)e->n_pad * 4));
-  RVD_TRY(e->craw.ensure((size_t)e->craw_frames * c.sinc_filters * dt_size(e->dtype)));
+  RVB_TRY(e->wave.ensure((size_t)e->n_pad * 4));
+  RVB_TRY(e->craw.ensure((size_t)e->craw_frames * c.sinc_filters * dt_size(e->dtype)));
   { DScope sc(e, "pcm_to_float");
-    RVD_TRY(pcm_to_float(e->stream, e->pcm.as<int16_t>(), n, e->wave.as<float>(), e->n_pad)); }
+    RVB_TRY(pcm_to_float(e->stream, e->pcm.as<int16_t>(), n, e->wave.as<float>(), e->n_pad)); }
   { DScope sc(e, "sinc_conv", 2.0 * (double)e->craw_frames * c.sinc_filters * SINC_K);
-    RVD_TRY(sinc_conv(e->stream, e->dtype, e->wave.as<float>(), e->filt.as<float>(), e->craw.p, e->craw_frames, c.sinc_filters,
+    RVB_TRY(sinc_conv(e->stream, e->dtype, e->wave.as<float>(), e->filt.as<float>(), e->craw.p, e->craw_frames, c.sinc_filters,
                       SINC_K, SINC_STRIDE)); }
   if (e->has_emb) {
     // hamming log-mel of the zero-extended file, shared by all windows (frame j of window w = frame w*step/160 + j)
     e->emb_frames = (e->n_pad - FB_WIN) / FB_SHIFT + 1;
-    RVD_TRY(e->pcm_pad.ensure((size_t)e->n_pad * 2));
-    RVD_TRY(e->emb_fb.ensure((size_t)e->emb_frames * FB_MEL * 4));
+    RVB_TRY(e->pcm_pad.ensure((size_t)e->n_pad * 2));
+    RVB_TRY(e->emb_fb.ensure((size_t)e->emb_frames * FB_MEL * 4));
     RVB_HIP_CHECK(hipMemsetAsync(e->pcm_pad.p, 0, (size_t)e->n_pad * 2, e->stream));
     RVB_HIP_CHECK(hipMemcpyAsync(e->pcm_pad.p, e->pcm.p, (size_t)n * 2, hipMemcpyDeviceToDevice, e->stream));
     DScope sc(e, "emb_fbank");
     FbankTables t{e->fb_window.as<float>(), e->fb_twiddle.as<float>(), e->fb_melw.as<float>(), e->fb_lo.as<int>(), e->fb_hi.as<int>()};
-    RVD_TRY(fbank(e->stream, e->pcm_pad.as<int16_t>(), e->emb_frames, e->emb_fb.as<float>(), t));
+    RVB_TRY(fbank(e->stream, e->pcm_pad.as<int16_t>(), e->emb_frames, e->emb_fb.as<float>(), t));
     // per-window CMN means for every window of the file (one block each)
-    RVD_TRY(e->e_mean.ensure((size_t)e->n_windows * FB_MEL * 4));
-    RVD_TRY(emb_window_mean(e->stream, e->emb_fb.as<float>(), nullptr, (int)e->n_windows, c.step_samples / FB_SHIFT, e->nfr, e->e_mean.as<float>()));
+    RVB_TRY(e->e_mean.ensure((size_t)e->n_windows * FB_MEL * 4));
+    RVB_TRY(emb_window_mean(e->stream, e->emb_fb.as<float>(), nullptr, (int)e->n_windows, c.step_samples / FB_SHIFT, e->nfr, e->e_mean.as<float>()));
   }
   RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
   return OK;
@@ -1075,7 +1073,7 @@ int rvd_set_emb_fp8_scales(rvd_engine* e, const float* scales, int32_t n) {
   for (int i = 0; i < 32; ++i)
     if (!(scales[i] > 0.f) || !std::isfinite(scales[i])) { set_error("rvd_set_emb_fp8_scales: scales must be positive and finite"); return E_ARG; }
   RVB_HIP_CHECK(hipSetDevice(e->device));
-  RVD_TRY(e->d_sat8.ensure(4));
+  RVB_TRY(e->d_sat8.ensure(4));
   RVB_HIP_CHECK(hipMemsetAsync(e->d_sat8.p, 0, 4, e->stream));
   e->scale8.assign(scales, scales + 32);
   e->emb_f8_state = 2;

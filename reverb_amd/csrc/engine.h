@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/rvb.h"
+#include "ctc_slabs.h"
 #include "kernels.h"
 #include "search.h"
 
@@ -144,6 +145,7 @@ struct TrieBatch {
 // whose rows lie in the slab just computed (slabs in row order), finish() back-traces and returns states and scores.
 // With allow_wild, plan() accepts RVB_CTC_WILDCARD as a token (a label of its own: it counts towards the caps and, next to another
 // wildcard, as a repeat); advance() then needs wmax[nrows], the maximum of each row of the slab, and the per-frame bias <= 0.
+// The four drivers below share their slab feed (row checks, frame windows per slab, coverage, descriptor upload): ctc_slabs.h.
 struct CtcAligner {
   std::vector<VitSeq> seq;
   std::vector<int32_t> h_tokens, h_rows;
@@ -156,7 +158,7 @@ struct CtcAligner {
   int plan(const char* who, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const std::vector<std::vector<int32_t>>& seq_rows,
            int V, int blank_id, bool allow_wild = false);
   int begin(hipStream_t s);
-  bool touches(int r0, int nrows) const;
+  bool touches(int r0, int nrows) const { return slab_touches(seq, h_rows, r0, nrows); }
   int advance(hipStream_t s, const float* lp, int ld, int r0, int nrows, const float* wmax = nullptr, float bias = 0.f);
   int finish(hipStream_t s, int32_t* states /* [total_frames] */, float* score /* [n_seq] */);
   void release();
@@ -177,7 +179,7 @@ struct CtcGraphAligner {
   int plan(const char* who, const int32_t* node_tokens, const int32_t* n_nodes, const int32_t* pred_off, const int32_t* preds,
            const uint8_t* is_final, int n_seq, const std::vector<std::vector<int32_t>>& seq_rows, int V, int blank_id);
   int begin(hipStream_t s);
-  bool touches(int r0, int nrows) const;
+  bool touches(int r0, int nrows) const { return slab_touches(seq, h_rows, r0, nrows); }
   int advance(hipStream_t s, const float* lp, int ld, int r0, int nrows, const float* wmax = nullptr, float bias = 0.f);
   int finish(hipStream_t s, int32_t* states /* [total_frames]: 2 * slot + token bit */, float* score /* [n_seq] */);
   void release();
@@ -217,7 +219,7 @@ struct CtcFinder {
   int plan(const char* who, const int32_t* tokens, const int32_t* tok_lens, int n_phrases, const float* threshold,
            const std::vector<std::vector<int32_t>>& seq_rows, int V, int blank_id, int max_candidates);
   int begin(hipStream_t s);
-  bool touches(int r0, int nrows) const;
+  bool touches(int r0, int nrows) const { return slab_touches(seq, h_rows, r0, nrows); }
   int advance(hipStream_t s, const float* lp, int ld, int r0, int nrows, const float* wmax);
   // pair p = phrase * n_seq + sequence: n_hits [pairs], start / end / score [pairs][max_hits], n_candidates [pairs] (nullable: all
   // arrivals at or above the threshold, kept or not); raw_* (nullable) [pairs][max_cand]: the kept candidates as the kernel wrote them

@@ -38,8 +38,6 @@ int DevBuf::ensure(size_t n) {
 }
 void DevBuf::release() { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
 
-#define RVB_TRY(expr) do { int _r = (expr); if (_r != OK) return _r; } while (0)
-
 // ------------------------------------------------------------------------------------ profiling
 struct Scope {
   rvb_engine* e; hipEvent_t a = nullptr, b = nullptr; std::string name;
@@ -2341,9 +2339,12 @@ static int align_slab(rvb_engine* e, int r0, int rows) {
                          e->align_ti.as<int>(), e->align_lp.as<float>());
 }
 
+// The lattice entry points (rvb_ctc_align, _align_wild, _align_graph, _score, _find) begin alike once their own arguments are checked:
+// align_seq_rows, the driver's plan() (so every refusal comes before any device work), align_workspace, the driver's begin().
 // the log-prob rows of each sequence: the valid encoder frames of its chunks, in order
 static int align_seq_rows(rvb_engine* e, const char* who, const int32_t* first_chunk, const int32_t* n_chunks, int n_seq,
                           std::vector<std::vector<int32_t>>* seq_rows) {
+  if (e->B <= 0) { set_error(std::string(who) + " before rvb_encode"); return E_STATE; }
   seq_rows->assign(n_seq, {});
   for (int i = 0; i < n_seq; ++i) {
     if (first_chunk[i] < 0 || n_chunks[i] < 1 || (int64_t)first_chunk[i] + n_chunks[i] > e->B) {
@@ -2355,13 +2356,6 @@ static int align_seq_rows(rvb_engine* e, const char* who, const int32_t* first_c
   }
   return OK;
 }
-static int align_workspace(rvb_engine* e) {
-  const int V = e->cfg.vocab, Vld = (V + 3) & ~3, slab = std::min(LOGIT_SLAB, e->B * e->T2);
-  RVB_TRY(e->logits.ensure((size_t)LOGIT_SLAB * Vld * 4));
-  RVB_TRY(e->align_lp.ensure((size_t)slab * V * 4));
-  RVB_TRY(e->align_tv.ensure((size_t)slab * 4));
-  return e->align_ti.ensure((size_t)slab * 4);
-}
 // the slabs rvb_encode computed its log-probs in (per slice of the batch, LOGIT_SLAB rows at a time): the same GEMM launches, so
 // the same bits as the top-k the searches saw
 static std::vector<std::pair<int, int>> align_slabs(const rvb_engine* e) {
@@ -2371,10 +2365,25 @@ static std::vector<std::pair<int, int>> align_slabs(const rvb_engine* e) {
   for (const auto& sl : e->slices) add_range(sl.c0 * e->T2, sl.nb * e->T2);
   return slabs;
 }
+// the device side of the beginning: the encoded batch is waited for, the slab buffers exist, *slabs = the slabs to sweep
+static int align_workspace(rvb_engine* e, std::vector<std::pair<int, int>>* slabs) {
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(wait_slices(e, -1));
+  const int V = e->cfg.vocab, Vld = (V + 3) & ~3, slab = std::min(LOGIT_SLAB, e->B * e->T2);
+  RVB_TRY(e->logits.ensure((size_t)LOGIT_SLAB * Vld * 4));
+  RVB_TRY(e->align_lp.ensure((size_t)slab * V * 4));
+  RVB_TRY(e->align_tv.ensure((size_t)slab * 4));
+  RVB_TRY(e->align_ti.ensure((size_t)slab * 4));
+  *slabs = align_slabs(e);
+  return OK;
+}
 
-// lp[t][label[t]] of every frame of every lattice (spans: {frame_off, T} into rows / lab): the slabs once more, one gather_pairs per
+}  // extern "C" (reopened below: the templates the lattice entry points share)
+
+// lp[t][label[t]] of every frame of every lattice (seq: frame_off and T into rows / lab): the slabs once more, one gather_pairs per
 // slab.  A wildcard frame's emission is the row maximum, what it emitted less the bias.
-static int align_emissions(rvb_engine* e, const std::vector<std::pair<int, int>>& slabs, const std::vector<std::pair<int, int>>& spans,
+template <typename Seq>
+static int align_emissions(rvb_engine* e, const std::vector<std::pair<int, int>>& slabs, const std::vector<Seq>& seq,
                            const std::vector<int32_t>& h_rows, const std::vector<int32_t>& lab, bool has_wild, std::vector<float>* emit_out) {
   const int V = e->cfg.vocab, blank = e->cfg.blank_id;
   std::vector<float>& emit = *emit_out;
@@ -2383,7 +2392,8 @@ static int align_emissions(rvb_engine* e, const std::vector<std::pair<int, int>>
   std::vector<float> gout, wrow;
   for (const auto& [r0, rows] : slabs) {
     grow.clear(); gcol.clear(); gidx.clear();
-    for (const auto& [frame_off, T] : spans) {
+    for (const Seq& q : seq) {
+      const int frame_off = q.frame_off, T = q.T;
       const int32_t* rw = h_rows.data() + frame_off;
       for (int f = (int)(std::lower_bound(rw, rw + T, r0) - rw); f < T && rw[f] < r0 + rows; ++f) {
         const int32_t l = lab[frame_off + f];
@@ -2409,6 +2419,62 @@ static int align_emissions(rvb_engine* e, const std::vector<std::pair<int, int>>
   return OK;
 }
 
+// One sweep over the slabs, in row order or backwards.  A slab that holds a frame of the driver's sequences is computed (align_slab:
+// one GEMM, one log-softmax) and handed to advance(r0, rows) under the profile name `name`; a slab that holds none costs nothing.
+template <typename Driver, typename Advance>
+static int sweep_slabs(rvb_engine* e, const std::vector<std::pair<int, int>>& slabs, bool descending, const char* name, const Driver& d,
+                       Advance advance) {
+  for (size_t i = 0; i < slabs.size(); ++i) {
+    const auto& [r0, rows] = slabs[descending ? slabs.size() - 1 - i : i];
+    if (!d.touches(r0, rows)) continue;
+    RVB_TRY(align_slab(e, r0, rows));
+    Scope sc(e, name);
+    RVB_TRY(advance(r0, rows));
+  }
+  return OK;
+}
+
+// The forward sweep and the back-trace of either aligner (align_tv: the row maxima a wildcard emits): the state of every frame and
+// the score of every lattice.
+template <typename Aligner>
+static int align_sweep(rvb_engine* e, const std::vector<std::pair<int, int>>& slabs, const char* name, Aligner& al, float bias,
+                       std::vector<int32_t>* states, std::vector<float>* score) {
+  RVB_TRY(sweep_slabs(e, slabs, false, name, al, [&](int r0, int rows) {
+    return al.advance(e->stream, e->align_lp.as<float>(), e->cfg.vocab, r0, rows, e->align_tv.as<float>(), bias);
+  }));
+  states->resize((size_t)al.total_frames);
+  score->resize(al.seq.size());
+  Scope sc(e, name);
+  return al.finish(e->stream, states->data(), score->data());
+}
+
+// The runs of equal values in id[frame_off .. frame_off + T): the state, or the node, of each frame of one lattice's best path.
+// slot(value) says where the outputs of a run go (< 0: a blank's run, which has none).  A run yields its first and last frame and,
+// from emit (lp[t][label[t]]; filled when peak or confidence is asked for), the frame of its largest emission and that probability.
+template <typename Slot>
+static void run_outputs(const std::vector<int32_t>& id, const std::vector<float>& emit, int frame_off, int T, Slot slot, int32_t* begin,
+                        int32_t* end, int32_t* peak, float* confidence) {
+  for (int t = 0; t < T;) {
+    const int v = id[frame_off + t];
+    int t1 = t;
+    while (t1 + 1 < T && id[frame_off + t1 + 1] == v) ++t1;
+    const int k = slot(v);
+    if (k >= 0) {
+      if (begin) begin[k] = t;
+      if (end) end[k] = t1;
+      if (peak || confidence) {
+        int pk = t;
+        for (int u = t + 1; u <= t1; ++u) if (emit[frame_off + u] > emit[frame_off + pk]) pk = u;
+        if (peak) peak[k] = pk;
+        if (confidence) confidence[k] = std::exp(emit[frame_off + pk]);
+      }
+    }
+    t = t1 + 1;
+  }
+}
+
+extern "C" {
+
 int rvb_ctc_align_limits(int32_t* max_tokens, int32_t* max_frames) {
   if (max_tokens) *max_tokens = CTC_ALIGN_MAX_TOKENS;
   if (max_frames) *max_frames = CTC_ALIGN_MAX_FRAMES;
@@ -2426,29 +2492,17 @@ static int ctc_align_impl(const char* who, bool wild, float bias, rvb_engine* e,
   if (!e) { set_error(w + ": null engine"); return E_ARG; }
   if (!tokens || !tok_lens || !first_chunk || !n_chunks || n_seq <= 0) { set_error(w + ": null argument or n_seq <= 0"); return E_ARG; }
   if (wild && !(std::isfinite(bias) && bias <= 0.f)) { set_error(w + ": wildcard_bias must be finite and <= 0"); return E_ARG; }
-  if (e->B <= 0) { set_error(w + " before rvb_encode"); return E_STATE; }
-  const int T = e->T2, V = e->cfg.vocab, blank = e->cfg.blank_id, M = e->B * T;
+  const int V = e->cfg.vocab, blank = e->cfg.blank_id;
+  CtcAligner& al = e->aligner;
   std::vector<std::vector<int32_t>> seq_rows;
   RVB_TRY(align_seq_rows(e, who, first_chunk, n_chunks, n_seq, &seq_rows));
-  CtcAligner& al = e->aligner;
   RVB_TRY(al.plan(who, tokens, tok_lens, n_seq, seq_rows, V, blank, wild));
-  RVB_HIP_CHECK(hipSetDevice(e->device));
-  RVB_TRY(wait_slices(e, -1));
-  RVB_TRY(align_workspace(e));
-  const std::vector<std::pair<int, int>> slabs = align_slabs(e);
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
   RVB_TRY(al.begin(e->stream));
-  for (const auto& [r0, rows] : slabs) {
-    if (!al.touches(r0, rows)) continue;
-    RVB_TRY(align_slab(e, r0, rows));
-    Scope sc(e, "ctc_viterbi");
-    RVB_TRY(al.advance(e->stream, e->align_lp.as<float>(), V, r0, rows, e->align_tv.as<float>(), bias));
-  }
-  std::vector<int32_t> states((size_t)al.total_frames);
-  std::vector<float> sc_host(n_seq);
-  {
-    Scope sc(e, "ctc_viterbi");
-    RVB_TRY(al.finish(e->stream, states.data(), sc_host.data()));
-  }
+  std::vector<int32_t> states;
+  std::vector<float> sc_host;
+  RVB_TRY(align_sweep(e, slabs, "ctc_viterbi", al, bias, &states, &sc_host));
   if (score) memcpy(score, sc_host.data(), (size_t)n_seq * 4);
   std::vector<int32_t> lab(states.size());
   for (int i = 0; i < n_seq; ++i) {
@@ -2461,31 +2515,9 @@ static int ctc_align_impl(const char* who, bool wild, float bias, rvb_engine* e,
   if (labels) memcpy(labels, lab.data(), lab.size() * 4);
   if (!begin && !end && !peak && !confidence) return OK;
   std::vector<float> emit;
-  if (peak || confidence) {
-    std::vector<std::pair<int, int>> spans;
-    for (const VitSeq& q : al.seq) spans.push_back({q.frame_off, q.T});
-    RVB_TRY(align_emissions(e, slabs, spans, al.h_rows, lab, al.has_wild, &emit));
-  }
-  for (int i = 0; i < n_seq; ++i) {
-    const VitSeq& q = al.seq[i];
-    for (int t = 0; t < q.T;) {
-      const int st = states[q.frame_off + t];
-      int t1 = t;
-      while (t1 + 1 < q.T && states[q.frame_off + t1 + 1] == st) ++t1;
-      if (st & 1) {
-        const int k = q.tok_off + (st >> 1);
-        if (begin) begin[k] = t;
-        if (end) end[k] = t1;
-        if (peak || confidence) {
-          int pk = t;
-          for (int u = t + 1; u <= t1; ++u) if (emit[q.frame_off + u] > emit[q.frame_off + pk]) pk = u;
-          if (peak) peak[k] = pk;
-          if (confidence) confidence[k] = std::exp(emit[q.frame_off + pk]);
-        }
-      }
-      t = t1 + 1;
-    }
-  }
+  if (peak || confidence) RVB_TRY(align_emissions(e, slabs, al.seq, al.h_rows, lab, al.has_wild, &emit));
+  for (const VitSeq& q : al.seq)                   // a run is a state; a token state's outputs go to its token
+    run_outputs(states, emit, q.frame_off, q.T, [&](int st) { return (st & 1) ? q.tok_off + (st >> 1) : -1; }, begin, end, peak, confidence);
   return OK;
 }
 
@@ -2524,29 +2556,17 @@ int rvb_ctc_align_graph(rvb_engine* e, const int32_t* node_tokens, const int32_t
     return E_ARG;
   }
   if (!(std::isfinite(wildcard_bias) && wildcard_bias <= 0.f)) { set_error(w + ": wildcard_bias must be finite and <= 0"); return E_ARG; }
-  if (e->B <= 0) { set_error(w + " before rvb_encode"); return E_STATE; }
   const int V = e->cfg.vocab, blank = e->cfg.blank_id;
+  CtcGraphAligner& al = e->graph_aligner;
   std::vector<std::vector<int32_t>> seq_rows;
   RVB_TRY(align_seq_rows(e, w.c_str(), first_chunk, n_chunks, n_seq, &seq_rows));
-  CtcGraphAligner& al = e->graph_aligner;
   RVB_TRY(al.plan(w.c_str(), node_tokens, n_nodes, pred_off, preds, is_final, n_seq, seq_rows, V, blank));
-  RVB_HIP_CHECK(hipSetDevice(e->device));
-  RVB_TRY(wait_slices(e, -1));
-  RVB_TRY(align_workspace(e));
-  const std::vector<std::pair<int, int>> slabs = align_slabs(e);
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
   RVB_TRY(al.begin(e->stream));
-  for (const auto& [r0, rows] : slabs) {
-    if (!al.touches(r0, rows)) continue;
-    RVB_TRY(align_slab(e, r0, rows));
-    Scope sc(e, "ctc_graph");
-    RVB_TRY(al.advance(e->stream, e->align_lp.as<float>(), V, r0, rows, e->align_tv.as<float>(), wildcard_bias));   // align_tv: the row maxima
-  }
-  std::vector<int32_t> states((size_t)al.total_frames);
-  std::vector<float> sc_host(n_seq);
-  {
-    Scope sc(e, "ctc_graph");
-    RVB_TRY(al.finish(e->stream, states.data(), sc_host.data()));
-  }
+  std::vector<int32_t> states;
+  std::vector<float> sc_host;
+  RVB_TRY(align_sweep(e, slabs, "ctc_graph", al, wildcard_bias, &states, &sc_host));
   std::vector<int32_t> lab(states.size()), node(states.size());
   for (int i = 0; i < n_seq; ++i) {
     const GraphSeq& q = al.seq[i];
@@ -2557,11 +2577,7 @@ int rvb_ctc_align_graph(rvb_engine* e, const int32_t* node_tokens, const int32_t
     }
   }
   std::vector<float> emit;
-  if (peak || confidence) {
-    std::vector<std::pair<int, int>> spans;
-    for (const GraphSeq& q : al.seq) spans.push_back({q.frame_off, q.T});
-    RVB_TRY(align_emissions(e, slabs, spans, al.h_rows, lab, al.has_wild, &emit));
-  }
+  if (peak || confidence) RVB_TRY(align_emissions(e, slabs, al.seq, al.h_rows, lab, al.has_wild, &emit));
   // nothing was written so far: a refusal leaves every output untouched
   if (score) memcpy(score, sc_host.data(), (size_t)n_seq * 4);
   if (labels) memcpy(labels, lab.data(), lab.size() * 4);
@@ -2569,24 +2585,13 @@ int rvb_ctc_align_graph(rvb_engine* e, const int32_t* node_tokens, const int32_t
   for (int i = 0; i < n_seq; ++i) {
     const GraphSeq& q = al.seq[i];
     int n_path = 0;
-    for (int t = 0; t < q.T;) {
-      const int j = node[q.frame_off + t];
-      int t1 = t;
-      while (t1 + 1 < q.T && node[q.frame_off + t1 + 1] == j) ++t1;
-      if (j >= 0) {
-        const int k = q.node_off + n_path++;
-        if (path_nodes) path_nodes[k] = j;
-        if (begin) begin[k] = t;
-        if (end) end[k] = t1;
-        if (peak || confidence) {
-          int pk = t;
-          for (int u = t + 1; u <= t1; ++u) if (emit[q.frame_off + u] > emit[q.frame_off + pk]) pk = u;
-          if (peak) peak[k] = pk;
-          if (confidence) confidence[k] = std::exp(emit[q.frame_off + pk]);
-        }
-      }
-      t = t1 + 1;
-    }
+    auto next_on_path = [&](int j) {               // a run is a node; its outputs go to the next position of the chosen path
+      if (j < 0) return -1;
+      const int k = q.node_off + n_path++;
+      if (path_nodes) path_nodes[k] = j;
+      return k;
+    };
+    run_outputs(node, emit, q.frame_off, q.T, next_on_path, begin, end, peak, confidence);
     if (path_len) path_len[i] = n_path;
   }
   return OK;
@@ -2598,35 +2603,25 @@ int rvb_ctc_score(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens,
                   const int32_t* n_chunks, double* loglik, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame) {
   if (!e) { set_error("rvb_ctc_score: null engine"); return E_ARG; }
   if (!tokens || !tok_lens || !first_chunk || !n_chunks || !loglik || n_seq <= 0) { set_error("rvb_ctc_score: null argument or n_seq <= 0"); return E_ARG; }
-  if (e->B <= 0) { set_error("rvb_ctc_score before rvb_encode"); return E_STATE; }
+  const char* who = "rvb_ctc_score";
   const int V = e->cfg.vocab;
-  std::vector<std::vector<int32_t>> seq_rows;
-  RVB_TRY(align_seq_rows(e, "rvb_ctc_score", first_chunk, n_chunks, n_seq, &seq_rows));
   CtcScorer& sc = e->scorer;
-  RVB_TRY(sc.plan("rvb_ctc_score", tokens, tok_lens, n_seq, seq_rows, V, e->cfg.blank_id));
-  RVB_HIP_CHECK(hipSetDevice(e->device));
-  RVB_TRY(wait_slices(e, -1));
-  RVB_TRY(align_workspace(e));
-  const std::vector<std::pair<int, int>> slabs = align_slabs(e);
   const bool post = occupancy || mean_frame || peak_post || peak_frame;
+  std::vector<std::vector<int32_t>> seq_rows;
+  RVB_TRY(align_seq_rows(e, who, first_chunk, n_chunks, n_seq, &seq_rows));
+  RVB_TRY(sc.plan(who, tokens, tok_lens, n_seq, seq_rows, V, e->cfg.blank_id));
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
   RVB_TRY(sc.begin(e->stream, post));
-  for (const auto& [r0, rows] : slabs) {
-    if (!sc.lat.touches(r0, rows)) continue;
-    RVB_TRY(align_slab(e, r0, rows));
-    Scope t(e, "ctc_forward");
-    RVB_TRY(sc.advance(e->stream, e->align_lp.as<float>(), V, r0, rows));
-  }
+  RVB_TRY(sweep_slabs(e, slabs, false, "ctc_forward", sc.lat,
+                      [&](int r0, int rows) { return sc.advance(e->stream, e->align_lp.as<float>(), V, r0, rows); }));
   {
     Scope t(e, "ctc_forward");
     RVB_TRY(sc.finish_forward(e->stream, loglik));
   }
   if (!post) return OK;
-  for (auto it = slabs.rbegin(); it != slabs.rend(); ++it) {
-    if (!sc.lat.touches(it->first, it->second)) continue;
-    RVB_TRY(align_slab(e, it->first, it->second));
-    Scope t(e, "ctc_backward");
-    RVB_TRY(sc.advance_backward(e->stream, e->align_lp.as<float>(), V, it->first, it->second));
-  }
+  RVB_TRY(sweep_slabs(e, slabs, true, "ctc_backward", sc.lat,
+                      [&](int r0, int rows) { return sc.advance_backward(e->stream, e->align_lp.as<float>(), V, r0, rows); }));
   Scope t(e, "ctc_backward");
   return sc.finish_backward(e->stream, occupancy, mean_frame, peak_post, peak_frame);
 }
@@ -2644,22 +2639,17 @@ int rvb_ctc_find(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, 
   }
   if (n_phrases < 1 || n_seq < 1) { set_error("rvb_ctc_find: need n_phrases >= 1 and n_seq >= 1"); return E_ARG; }
   if (max_candidates < 1 || max_hits < 1) { set_error("rvb_ctc_find: need max_candidates >= 1 and max_hits >= 1"); return E_ARG; }
-  if (e->B <= 0) { set_error("rvb_ctc_find before rvb_encode"); return E_STATE; }
   const int V = e->cfg.vocab;
+  CtcFinder& fd = e->finder;
   std::vector<std::vector<int32_t>> seq_rows;
   RVB_TRY(align_seq_rows(e, who, first_chunk, n_chunks, n_seq, &seq_rows));
-  CtcFinder& fd = e->finder;
   RVB_TRY(fd.plan(who, tokens, tok_lens, n_phrases, threshold, seq_rows, V, e->cfg.blank_id, max_candidates));
-  RVB_HIP_CHECK(hipSetDevice(e->device));
-  RVB_TRY(wait_slices(e, -1));
-  RVB_TRY(align_workspace(e));
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
   RVB_TRY(fd.begin(e->stream));
-  for (const auto& [r0, rows] : align_slabs(e)) {
-    if (!fd.touches(r0, rows)) continue;
-    RVB_TRY(align_slab(e, r0, rows));
-    Scope sc(e, "ctc_find");
-    RVB_TRY(fd.advance(e->stream, e->align_lp.as<float>(), V, r0, rows, e->align_tv.as<float>()));
-  }
+  RVB_TRY(sweep_slabs(e, slabs, false, "ctc_find", fd, [&](int r0, int rows) {
+    return fd.advance(e->stream, e->align_lp.as<float>(), V, r0, rows, e->align_tv.as<float>());
+  }));
   return fd.finish(e->stream, max_hits, n_hits, start, end, score, n_candidates);
 }
 

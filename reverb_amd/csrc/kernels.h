@@ -174,6 +174,10 @@ int convert_f32(hipStream_t s, int dtype, const float* src, void* dst, size_t n)
 enum { CTC_ALIGN_MAX_TOKENS = 16383,             // per lattice: 2 L + 1 = 32 767 states = 1024 threads x 32 states
        CTC_ALIGN_MAX_STATES = 2 * CTC_ALIGN_MAX_TOKENS + 1,
        CTC_ALIGN_MAX_FRAMES = 1 << 20 };         // per lattice (11.6 h of audio at 40 ms per frame)
+// launch shape of the one-workgroup-per-lattice kernels (Viterbi, forward, backward, graph): the states a thread owns for the largest
+// lattice of the batch, and the threads that cover n states (or nodes) at per_thread each: whole waves, 1024 at the most
+inline int ctc_spt_for(int S) { return S <= 4096 ? 4 : S <= 16384 ? 16 : 32; }
+inline int ctc_threads(int n, int per_thread) { const int t = ((n + per_thread - 1) / per_thread + 63) / 64 * 64; return t < 1024 ? t : 1024; }
 struct VitSeq {            // one lattice of a batch, as the kernels read it
   int L, S, T;             // tokens, states 2 L + 1, frames
   int tok_off;             // its tokens: tokens[tok_off .. tok_off + L)

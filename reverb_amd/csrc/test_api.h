@@ -184,6 +184,15 @@ int rvb_test_ctc_find(const float* lp, const int32_t* T, int n_seq, int V, const
                       int n_phrases, const float* threshold, int blank, int slab_rows, int max_candidates, int max_hits,
                       int64_t* raw_count, int32_t* raw_end, int32_t* raw_start, float* raw_score, int32_t* n_hits, int32_t* hit_start,
                       int32_t* hit_end, float* hit_score);
+/* host only, no device: the slab feed the four drivers above share (ctc_slabs.h) over plain descriptors.  rows: the row lists of
+ * n_seq sequences back to back, T[i] >= 0 of them each, taken as a plan() takes them; slabs [n_slabs][2] = (r0, nrows), fed in the
+ * order given: the ascending step from f0 = f1 = 0 or, with descending != 0, the backward step from f0 = f1 = T; then the sweep's
+ * coverage check.  `who` is the prefix of the messages ("ctc align", ...).  Per slab fed: touches_out / any_out [n_slabs] and
+ * windows_out [n_slabs][n_seq][2] = every sequence's (f0, f1) after it.  fed_out: the slabs fed before a refusal; covered_out: 1 when
+ * the coverage check passed.  Returns the first refusal (rvb_last_error), RVB_OK when there was none. */
+int rvb_test_slab_windows(const char* who, const int32_t* rows, const int32_t* T, int n_seq, const int32_t* slabs, int n_slabs,
+                          int descending, int32_t* windows_out, int32_t* any_out, int32_t* touches_out, int32_t* fed_out,
+                          int32_t* covered_out);
 int rvb_test_fbank(const int16_t* pcm, int64_t n_samples, float* feats /* [frames,80] */);
 /* native prefix beam search on host arrays: top-k log-probs/indices [T,beam] of one utterance */
 int rvb_test_prefix_beam(const float* topk_val, const int32_t* topk_idx, int T, int beam, int blank,

@@ -49,14 +49,53 @@ int need_gpu() {
   if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) { set_error("no HIP device available: librvb has no CPU fallback"); return E_HIP; }
   return OK;
 }
-#define T_TRY(x) do { int _r = (x); if (_r != OK) return _r; } while (0)
+// the frame rows of n_seq lattices whose frames lie back to back: rows[i][t] = (frames before lattice i) + t.  A count over the cap
+// keeps its size and gets no values: plan() refuses it on the count alone.  -> the rows in all
+int64_t lab_rows(const int32_t* T, int n_seq, std::vector<std::vector<int32_t>>* rows) {
+  rows->assign(n_seq, {});
+  int64_t total = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    (*rows)[i].resize((size_t)T[i]);
+    if (T[i] <= CTC_ALIGN_MAX_FRAMES) for (int t = 0; t < T[i]; ++t) (*rows)[i][t] = (int32_t)(total + t);
+    total += T[i];
+  }
+  return total;
+}
+// feeds M rows to advance(r0, nrows), slab_rows at a time, for as long as r stays OK: ascending from row 0, or descending in slabs
+// that END at the last row, so that the two sweeps of the scorer cut at different frames
+template <typename F> int feed_slabs(int r, int64_t M, int slab_rows, bool descending, F advance) {
+  for (int64_t done = 0; r == OK && done < M; done += slab_rows) {
+    const int n = (int)std::min<int64_t>(slab_rows, M - done);
+    r = advance((int)(descending ? M - done - n : done), n);
+  }
+  return r;
+}
+// the lab run of either aligner over M rows of host log-probs (w: their maxima, null without wildcards): upload, begin, the slabs,
+// the back-trace into states [M] and score [sequences]; the aligner's buffers are released whatever happens
+template <typename Aligner>
+int lab_align(Aligner& al, const float* lp, const float* w, int64_t M, int V, int slab_rows, float bias, std::vector<int32_t>* states,
+              float* score) {
+  RVB_TRY(need_gpu());
+  Dev dlp, dw;
+  int r = up_raw(dlp, lp, (size_t)M * V * 4);
+  if (r == OK) r = up_raw(dw, w, (size_t)M * 4);
+  if (r == OK) r = al.begin(nullptr);
+  r = feed_slabs(r, M, slab_rows, false, [&](int r0, int n) {
+    return al.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, n, w ? (const float*)dw.p + r0 : nullptr, bias);
+  });
+  states->resize((size_t)M);
+  if (r == OK) r = al.finish(nullptr, states->data(), score);
+  if (r != OK) (void)hipDeviceSynchronize();
+  al.release();
+  return r;
+}
 }  // namespace
 
 extern "C" {
 
 int rvb_test_gemm(int dtype, const float* A, const float* W, const float* bias, const float* res, float* C, int M,
                   int N, int K, float alpha, int act, int out_f32, int conv, int cT1, int cF1, int cC, int cB) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dA, dW, dB, dR, dC;
   GemmArgs g;
   memset(&g, 0, sizeof(g));
@@ -67,35 +106,35 @@ int rvb_test_gemm(int dtype, const float* A, const float* W, const float* bias, 
     a_elems = (size_t)cB * cT1 * cF1 * cC;
     g.conv = 1; g.cT1 = cT1; g.cF1 = cF1; g.cT2 = T2; g.cF2 = F2; g.cC = cC;
   }
-  T_TRY(up_T(dA, dtype, A, a_elems));
-  T_TRY(up_T(dW, dtype, W, (size_t)N * K));
-  T_TRY(up_raw(dB, bias, (size_t)N * 4));
-  T_TRY(up_raw(dR, res, (size_t)M * N * 4));
+  RVB_TRY(up_T(dA, dtype, A, a_elems));
+  RVB_TRY(up_T(dW, dtype, W, (size_t)N * K));
+  RVB_TRY(up_raw(dB, bias, (size_t)N * 4));
+  RVB_TRY(up_raw(dR, res, (size_t)M * N * 4));
   const bool f32out = dtype == DT_F32 || out_f32;
-  T_TRY(dC.alloc((size_t)M * N * (f32out ? 4 : 2)));
+  RVB_TRY(dC.alloc((size_t)M * N * (f32out ? 4 : 2)));
   g.A = dA.p; g.W = dW.p; g.bias = (const float*)dB.p; g.res = (const float*)dR.p; g.C = dC.p;
   g.M = M; g.N = N; g.K = K; g.lda = conv ? cC : K; g.ldw = K; g.ldc = N; g.ldres = N;
   g.alpha = alpha; g.act = act; g.out_f32 = out_f32;
-  T_TRY(gemm(nullptr, dtype, g));
+  RVB_TRY(gemm(nullptr, dtype, g));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(dC, dtype, f32out, C, (size_t)M * N);
 }
 
 int rvb_test_gemm_rowadd(const float* A, const float* W, const float* bias, const float* add, float* C, int M, int N, int K,
                          int add_rows, int add_col0, int add_cols) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dA, dW, dB, dP, dC;
   GemmArgs g;
   memset(&g, 0, sizeof(g));
-  T_TRY(up_T(dA, DT_BF16, A, (size_t)M * K));
-  T_TRY(up_T(dW, DT_BF16, W, (size_t)N * K));
-  T_TRY(up_raw(dB, bias, (size_t)N * 4));
-  T_TRY(up_T(dP, DT_BF16, add, (size_t)add_rows * add_cols));
-  T_TRY(dC.alloc((size_t)M * N * 2));
+  RVB_TRY(up_T(dA, DT_BF16, A, (size_t)M * K));
+  RVB_TRY(up_T(dW, DT_BF16, W, (size_t)N * K));
+  RVB_TRY(up_raw(dB, bias, (size_t)N * 4));
+  RVB_TRY(up_T(dP, DT_BF16, add, (size_t)add_rows * add_cols));
+  RVB_TRY(dC.alloc((size_t)M * N * 2));
   g.A = dA.p; g.W = dW.p; g.bias = (const float*)dB.p; g.C = dC.p;
   g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N; g.alpha = 1.f; g.act = ACT_NONE;
   g.rowadd = dP.p; g.rowadd_rows = add_rows; g.rowadd_ld = add_cols; g.rowadd_col0 = add_col0; g.rowadd_cols = add_cols;
-  T_TRY(gemm(nullptr, DT_BF16, g));
+  RVB_TRY(gemm(nullptr, DT_BF16, g));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(dC, DT_BF16, false, C, (size_t)M * N);
 }
@@ -103,18 +142,18 @@ int rvb_test_gemm_rowadd(const float* A, const float* W, const float* bias, cons
 // bf16 GEMM with the ACT_GLU epilogue: W rows / bias / output columns interleaved as the engine packs them (row 2c = a_c, 2c + 1 = b_c);
 // C [M, N / 2] = a * sigmoid(b)
 int rvb_test_gemm_glu(const float* A, const float* W, const float* bias, float* C, int M, int N, int K) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dA, dW, dB, dC;
   GemmArgs g;
   memset(&g, 0, sizeof(g));
-  T_TRY(up_T(dA, DT_BF16, A, (size_t)M * K));
-  T_TRY(up_T(dW, DT_BF16, W, (size_t)N * K));
-  T_TRY(up_raw(dB, bias, (size_t)N * 4));
-  T_TRY(dC.alloc((size_t)M * (N / 2) * 2));
+  RVB_TRY(up_T(dA, DT_BF16, A, (size_t)M * K));
+  RVB_TRY(up_T(dW, DT_BF16, W, (size_t)N * K));
+  RVB_TRY(up_raw(dB, bias, (size_t)N * 4));
+  RVB_TRY(dC.alloc((size_t)M * (N / 2) * 2));
   g.A = dA.p; g.W = dW.p; g.bias = (const float*)dB.p; g.C = dC.p;
   g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N / 2; g.alpha = 1.f; g.act = ACT_GLU;
   if (!gemm_glu_supported(DT_BF16, g)) { set_error("rvb_test_gemm_glu: shape not supported by the ACT_GLU epilogue"); return E_UNSUPPORTED; }
-  T_TRY(gemm(nullptr, DT_BF16, g));
+  RVB_TRY(gemm(nullptr, DT_BF16, g));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(dC, DT_BF16, false, C, (size_t)M * (N / 2));
 }
@@ -149,41 +188,41 @@ int rvb_test_mp3_huffman(int t, uint16_t* codes, uint8_t* lens, int32_t* linbits
 
 int rvb_test_rownorm(int dtype, const float* x, const float* gamma, const float* beta, float eps, int mode, int silu,
                      const float* add, float* out, int out_f32, int M, int d) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dx, dg, db, da, dout;
   const bool x16 = (mode & 256) != 0;            // bit 8 of `mode`: x is handed to the kernel as bf16 (bf16 engine, conv-module norm)
   mode &= 255;
-  if (x16) T_TRY(up_T(dx, DT_BF16, x, (size_t)M * d)); else T_TRY(up_raw(dx, x, (size_t)M * d * 4));
-  T_TRY(up_raw(dg, gamma, (size_t)d * 4));
-  T_TRY(up_raw(db, beta, (size_t)d * 4));
-  T_TRY(up_T(da, dtype, add, (size_t)M * d));
+  if (x16) RVB_TRY(up_T(dx, DT_BF16, x, (size_t)M * d)); else RVB_TRY(up_raw(dx, x, (size_t)M * d * 4));
+  RVB_TRY(up_raw(dg, gamma, (size_t)d * 4));
+  RVB_TRY(up_raw(db, beta, (size_t)d * 4));
+  RVB_TRY(up_T(da, dtype, add, (size_t)M * d));
   const bool f32out = dtype == DT_F32 || out_f32;
-  T_TRY(dout.alloc((size_t)M * d * (f32out ? 4 : 2)));
+  RVB_TRY(dout.alloc((size_t)M * d * (f32out ? 4 : 2)));
   NormArgs a;
   a.x = (const float*)dx.p; a.gamma = (const float*)dg.p; a.beta = (const float*)db.p; a.eps = eps; a.mode = mode;
   a.silu = silu; a.add = da.p; a.out = dout.p; a.out_f32 = out_f32; a.M = M; a.d = d;
   a.x_bf16 = x16 ? 1 : 0;
-  T_TRY(rownorm(nullptr, dtype, a));
+  RVB_TRY(rownorm(nullptr, dtype, a));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(dout, dtype, f32out, out, (size_t)M * d);
 }
 
 int rvb_test_conv1(int dtype, const float* feats, const float* mean, const float* istd, const float* w, const float* b,
                    float* out, int B, int T0, int F0, int d) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   const int T1 = (T0 - 3) / 2 + 1, F1 = (F0 - 3) / 2 + 1;
   Dev df, dm, di, dw, db, dout;
-  T_TRY(up_raw(df, feats, (size_t)B * T0 * F0 * 4));
-  T_TRY(up_raw(dm, mean, (size_t)F0 * 4));
-  T_TRY(up_raw(di, istd, (size_t)F0 * 4));
+  RVB_TRY(up_raw(df, feats, (size_t)B * T0 * F0 * 4));
+  RVB_TRY(up_raw(dm, mean, (size_t)F0 * 4));
+  RVB_TRY(up_raw(di, istd, (size_t)F0 * 4));
   std::vector<float> wt((size_t)d * 9);            // the caller passes conv.0.weight as the reference stores it, [d][1][3][3]
   for (int c = 0; c < d; ++c)
     for (int k = 0; k < 9; ++k) wt[(size_t)k * d + c] = w[(size_t)c * 9 + k];
-  T_TRY(up_raw(dw, wt.data(), (size_t)d * 9 * 4));
-  T_TRY(up_raw(db, b, (size_t)d * 4));
+  RVB_TRY(up_raw(dw, wt.data(), (size_t)d * 9 * 4));
+  RVB_TRY(up_raw(db, b, (size_t)d * 4));
   const size_t n = (size_t)B * T1 * F1 * d;
-  T_TRY(dout.alloc(n * dt_size(dtype)));
-  T_TRY(subsample_conv1(nullptr, dtype, (const float*)df.p, (const float*)dm.p, (const float*)di.p, (const float*)dw.p,
+  RVB_TRY(dout.alloc(n * dt_size(dtype)));
+  RVB_TRY(subsample_conv1(nullptr, dtype, (const float*)df.p, (const float*)dm.p, (const float*)di.p, (const float*)dw.p,
                         (const float*)db.p, dout.p, B, T0, F0, d));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(dout, dtype, false, out, n);
@@ -192,7 +231,7 @@ int rvb_test_conv1(int dtype, const float* feats, const float* mean, const float
 // conv_block.hip on host floats: x [B][F][T][32] (unbordered NHWC), wa / wb [32][32][3][3] as torch stores Conv2d weights (BatchNorm
 // already folded by the caller), ba / bb [32]; out [B][F][T][32].  Builds the bordered planes and conv2d's weight layout.
 int rvb_test_conv_block32(const float* x, const float* wa, const float* ba, const float* wb, const float* bb, float* out, int B, int F, int T) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   if (!x || !wa || !ba || !wb || !bb || !out || B < 1 || F < 1 || T < 1) { set_error("rvb_test_conv_block32: bad argument"); return E_ARG; }
   const int FP = F + 2, TP = T + 2;
   const size_t np = (size_t)B * FP * TP * 32;
@@ -210,13 +249,13 @@ int rvb_test_conv_block32(const float* x, const float* wa, const float* ba, cons
   };
   const std::vector<bf16_t> pa = pack_w(wa), pb = pack_w(wb);
   Dev dx, dwa, dwb, dba, dbb, dout;
-  T_TRY(up_raw(dx, xb.data(), np * 2)); T_TRY(up_raw(dwa, pa.data(), pa.size() * 2)); T_TRY(up_raw(dwb, pb.data(), pb.size() * 2));
-  T_TRY(up_raw(dba, ba, 32 * 4)); T_TRY(up_raw(dbb, bb, 32 * 4));
-  T_TRY(dout.alloc(np * 2 + 256)); RVB_HIP_CHECK(hipMemset(dout.p, 0, np * 2 + 256));
+  RVB_TRY(up_raw(dx, xb.data(), np * 2)); RVB_TRY(up_raw(dwa, pa.data(), pa.size() * 2)); RVB_TRY(up_raw(dwb, pb.data(), pb.size() * 2));
+  RVB_TRY(up_raw(dba, ba, 32 * 4)); RVB_TRY(up_raw(dbb, bb, 32 * 4));
+  RVB_TRY(dout.alloc(np * 2 + 256)); RVB_HIP_CHECK(hipMemset(dout.p, 0, np * 2 + 256));
   if (!conv_block32_applicable(DT_BF16, 32, 32, 32, 1, 1, 9, 9, F, T)) { set_error("rvb_test_conv_block32: the fused block is switched off (RVD_CONV_BLOCK=0)"); return E_STATE; }
   ConvBlockArgs a{};
   a.in = dx.p; a.wa = dwa.p; a.ba = (const float*)dba.p; a.wb = dwb.p; a.bb = (const float*)dbb.p; a.out = dout.p; a.B = B; a.F = F; a.T = T;
-  T_TRY(conv_block32(nullptr, a));
+  RVB_TRY(conv_block32(nullptr, a));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   std::vector<bf16_t> ob(np);
   RVB_HIP_CHECK(hipMemcpy(ob.data(), dout.p, np * 2, hipMemcpyDeviceToHost));
@@ -235,7 +274,7 @@ int rvb_test_conv_block32(const float* x, const float* wa, const float* ba, cons
 }
 
 int rvb_test_conv_s2sc(const float* x, const float* w, const float* b, const float* wsc, const float* bsc, float* out, float* sc, int B, int Fi, int Ti) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   if (!x || !w || !b || !wsc || !bsc || !out || !sc || B < 1 || Fi < 1 || Ti < 1) { set_error("rvb_test_conv_s2sc: bad argument"); return E_ARG; }
   const int Fo = (Fi - 1) / 2 + 1, To = (Ti - 1) / 2 + 1;
   const int FPi = Fi + 2, TPi = Ti + 2, FPo = Fo + 2, TPo = To + 2;
@@ -252,15 +291,15 @@ int rvb_test_conv_s2sc(const float* x, const float* w, const float* b, const flo
       ps[(size_t)o * 32 + ci] = f32_to_bf16(wsc[(size_t)o * 32 + ci]);
     }
   Dev dx, dw, ds, db, dbs, dout, dsc;
-  T_TRY(up_raw(dx, xb.data(), ni * 2)); T_TRY(up_raw(dw, pw.data(), pw.size() * 2)); T_TRY(up_raw(ds, ps.data(), ps.size() * 2));
-  T_TRY(up_raw(db, b, 64 * 4)); T_TRY(up_raw(dbs, bsc, 64 * 4));
-  T_TRY(dout.alloc(no * 2 + 256)); RVB_HIP_CHECK(hipMemset(dout.p, 0, no * 2 + 256));
-  T_TRY(dsc.alloc(no * 2 + 256)); RVB_HIP_CHECK(hipMemset(dsc.p, 0, no * 2 + 256));
+  RVB_TRY(up_raw(dx, xb.data(), ni * 2)); RVB_TRY(up_raw(dw, pw.data(), pw.size() * 2)); RVB_TRY(up_raw(ds, ps.data(), ps.size() * 2));
+  RVB_TRY(up_raw(db, b, 64 * 4)); RVB_TRY(up_raw(dbs, bsc, 64 * 4));
+  RVB_TRY(dout.alloc(no * 2 + 256)); RVB_HIP_CHECK(hipMemset(dout.p, 0, no * 2 + 256));
+  RVB_TRY(dsc.alloc(no * 2 + 256)); RVB_HIP_CHECK(hipMemset(dsc.p, 0, no * 2 + 256));
   if (!conv_s2sc_applicable(DT_BF16, 32, 64, 2, 9, 32, 64, 2, 1, Fi, Ti, Fo, To)) { set_error("rvb_test_conv_s2sc: switched off (RVD_CONV_S2SC=0)"); return E_STATE; }
   ConvS2Args a{};
   a.in = dx.p; a.w = dw.p; a.bias = (const float*)db.p; a.wsc = ds.p; a.bsc = (const float*)dbs.p; a.out = dout.p; a.sc = dsc.p;
   a.B = B; a.Fi = Fi; a.Ti = Ti; a.Fo = Fo; a.To = To;
-  T_TRY(conv_s2sc(nullptr, a));
+  RVB_TRY(conv_s2sc(nullptr, a));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   std::vector<bf16_t> ob(no), sb(no);
   RVB_HIP_CHECK(hipMemcpy(ob.data(), dout.p, no * 2, hipMemcpyDeviceToHost));
@@ -284,20 +323,20 @@ int rvb_test_conv_s2sc(const float* x, const float* w, const float* b, const flo
 int rvb_test_glu_dwconv(int dtype, const float* G, const float* pw1_bias, const float* dw_w, const float* dw_b,
                         const int32_t* lens, float* out, int B, int T, int d, int K, int causal, const float* hist,
                         int hist_rows) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dG, dpb, dw, db, dl, dout, dh;
   const bool gated = (causal & 4) != 0;          // bit 2 of `causal`: G is [B][T][d], gated already (GluDwArgs::gated)
-  T_TRY(up_T(dG, dtype, G, (size_t)B * T * (gated ? 1 : 2) * d));
-  T_TRY(up_raw(dpb, pw1_bias, (size_t)2 * d * 4));
+  RVB_TRY(up_T(dG, dtype, G, (size_t)B * T * (gated ? 1 : 2) * d));
+  RVB_TRY(up_raw(dpb, pw1_bias, (size_t)2 * d * 4));
   std::vector<float> wt((size_t)d * K);            // the caller passes depthwise_conv.weight as the reference stores it, [d][K]
   for (int c = 0; c < d; ++c)
     for (int k = 0; k < K; ++k) wt[(size_t)k * d + c] = dw_w[(size_t)c * K + k];
-  T_TRY(up_raw(dw, wt.data(), (size_t)d * K * 4));
-  T_TRY(up_raw(db, dw_b, (size_t)d * 4));
-  T_TRY(up_raw(dl, lens, (size_t)B * 4));
+  RVB_TRY(up_raw(dw, wt.data(), (size_t)d * K * 4));
+  RVB_TRY(up_raw(db, dw_b, (size_t)d * 4));
+  RVB_TRY(up_raw(dl, lens, (size_t)B * 4));
   const bool o16 = (causal & 2) != 0;            // bit 1 of `causal`: bf16 output (bf16 engine)
   causal &= 1;
-  T_TRY(dout.alloc((size_t)B * T * d * 4));
+  RVB_TRY(dout.alloc((size_t)B * T * d * 4));
   RVB_HIP_CHECK(hipMemset(dout.p, 0xff, (size_t)B * T * d * 4));      // NaN in fp32 and in bf16: a frame the kernel skipped shows
   GluDwArgs a;
   a.out_bf16 = o16 ? 1 : 0;
@@ -306,10 +345,10 @@ int rvb_test_glu_dwconv(int dtype, const float* G, const float* pw1_bias, const 
   a.lens = (const int*)dl.p; a.out = (float*)dout.p; a.B = B; a.T = T; a.d = d; a.K = K;
   a.causal = causal;
   if (hist && hist_rows > 0) {      // [K-1][2d], the last hist_rows rows are real frames
-    T_TRY(up_T(dh, dtype, hist, (size_t)(K - 1) * 2 * d));
+    RVB_TRY(up_T(dh, dtype, hist, (size_t)(K - 1) * 2 * d));
     a.hist = dh.p; a.hist_rows = hist_rows;
   }
-  T_TRY(glu_dwconv(nullptr, dtype, a));
+  RVB_TRY(glu_dwconv(nullptr, dtype, a));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   if (o16) return down_T(dout, DT_BF16, false, out, (size_t)B * T * d);
   RVB_HIP_CHECK(hipMemcpy(out, dout.p, (size_t)B * T * d * 4, hipMemcpyDeviceToHost));
@@ -320,10 +359,10 @@ int rvb_test_attention(int dtype, const float* q, const float* k, const float* v
                        const float* bias_v, float* out, int q_rows, int kv_rows, int p_rows, int heads, int dk,
                        const int32_t* q_start, const int32_t* q_len, const int32_t* kv_start, const int32_t* kv_len,
                        int nseq, int causal) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   const int d = heads * dk;
   Dev dq, dkk, dv, dp, du, dvv, dout, qs, ql, ks, kl;
-  T_TRY(up_T(dq, dtype, q, (size_t)q_rows * d));
+  RVB_TRY(up_T(dq, dtype, q, (size_t)q_rows * d));
   // bit 2 of `causal` (with bit 1, bf16): the keys go up PREFOLDED, K' = k + p[position of the key in its sequence] summed in fp32 and
   // rounded once -- what the qkv GEMM's epilogue writes in the engine (GemmArgs::rowadd); the kernel then runs with k_prefolded
   const bool prefolded = (causal & 6) == 6 && p && dtype == DT_BF16;
@@ -332,19 +371,19 @@ int rvb_test_attention(int dtype, const float* q, const float* k, const float* v
     for (int i = 0; i < nseq; ++i)
       for (int j = 0; j < kv_len[i] && j < p_rows; ++j)
         for (int c = 0; c < d; ++c) kp[(size_t)(kv_start[i] + j) * d + c] += p[(size_t)j * d + c];
-    T_TRY(up_T(dkk, dtype, kp.data(), (size_t)kv_rows * d));
+    RVB_TRY(up_T(dkk, dtype, kp.data(), (size_t)kv_rows * d));
   } else {
-    T_TRY(up_T(dkk, dtype, k, (size_t)kv_rows * d));
+    RVB_TRY(up_T(dkk, dtype, k, (size_t)kv_rows * d));
   }
-  T_TRY(up_T(dv, dtype, v, (size_t)kv_rows * d));
-  T_TRY(up_T(dp, dtype, p, (size_t)p_rows * d));
-  T_TRY(up_raw(du, bias_u, (size_t)d * 4));
-  T_TRY(up_raw(dvv, bias_v, (size_t)d * 4));
-  T_TRY(up_raw(qs, q_start, (size_t)nseq * 4));
-  T_TRY(up_raw(ql, q_len, (size_t)nseq * 4));
-  T_TRY(up_raw(ks, kv_start, (size_t)nseq * 4));
-  T_TRY(up_raw(kl, kv_len, (size_t)nseq * 4));
-  T_TRY(dout.alloc((size_t)q_rows * d * dt_size(dtype)));
+  RVB_TRY(up_T(dv, dtype, v, (size_t)kv_rows * d));
+  RVB_TRY(up_T(dp, dtype, p, (size_t)p_rows * d));
+  RVB_TRY(up_raw(du, bias_u, (size_t)d * 4));
+  RVB_TRY(up_raw(dvv, bias_v, (size_t)d * 4));
+  RVB_TRY(up_raw(qs, q_start, (size_t)nseq * 4));
+  RVB_TRY(up_raw(ql, q_len, (size_t)nseq * 4));
+  RVB_TRY(up_raw(ks, kv_start, (size_t)nseq * 4));
+  RVB_TRY(up_raw(kl, kv_len, (size_t)nseq * 4));
+  RVB_TRY(dout.alloc((size_t)q_rows * d * dt_size(dtype)));
   RVB_HIP_CHECK(hipMemset(dout.p, 0, (size_t)q_rows * d * dt_size(dtype)));
   AttnArgs a;
   memset(&a, 0, sizeof(a));
@@ -361,8 +400,8 @@ int rvb_test_attention(int dtype, const float* q, const float* k, const float* v
   // bit 1 of `causal`: the bf16 encoder form with the positional term folded into per-key constants (as the engine runs it)
   Dev dc;
   if ((causal & 2) && p && dtype == DT_BF16) {
-    T_TRY(dc.alloc((size_t)heads * p_rows * 4));
-    T_TRY(attention_pos_bias(nullptr, dp.p, p_rows, d, (const float*)du.p, (const float*)dvv.p, heads, dk, 1.44269504f / sqrtf((float)dk),
+    RVB_TRY(dc.alloc((size_t)heads * p_rows * 4));
+    RVB_TRY(attention_pos_bias(nullptr, dp.p, p_rows, d, (const float*)du.p, (const float*)dvv.p, heads, dk, 1.44269504f / sqrtf((float)dk),
                              (float*)dc.p));
     a.pos_bias = (const float*)dc.p; a.pos_bias_stride = p_rows;
     int mk = 0;
@@ -371,7 +410,7 @@ int rvb_test_attention(int dtype, const float* q, const float* k, const float* v
     a.k_prefolded = prefolded ? 1 : 0;
   }
   attention_lab_switches(a);      // RVB_ATTN_* of the lab build, as the engine passes them
-  T_TRY(attention(nullptr, dtype, a));
+  RVB_TRY(attention(nullptr, dtype, a));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(dout, dtype, false, out, (size_t)q_rows * d);
 }
@@ -381,16 +420,16 @@ int rvb_test_attention(int dtype, const float* q, const float* k, const float* v
 int rvb_test_attention_trie(int dtype, const float* q, const float* k, const float* v, float* out, int rows, int heads, int dk,
                             const int32_t* q_start, const int32_t* q_len, const int32_t* q_pos0, const int32_t* kv_start,
                             const int32_t* kv_len, const int32_t* kv_index, int n_index, int nseq, int q_block) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   const int d = heads * dk;
   Dev dq, dkk, dv, dout, qs, ql, qp, ks, kl, ki, wk;
-  T_TRY(up_T(dq, dtype, q, (size_t)rows * d));
-  T_TRY(up_T(dkk, dtype, k, (size_t)rows * d));
-  T_TRY(up_T(dv, dtype, v, (size_t)rows * d));
-  T_TRY(up_raw(qs, q_start, (size_t)nseq * 4)); T_TRY(up_raw(ql, q_len, (size_t)nseq * 4)); T_TRY(up_raw(qp, q_pos0, (size_t)nseq * 4));
-  T_TRY(up_raw(ks, kv_start, (size_t)nseq * 4)); T_TRY(up_raw(kl, kv_len, (size_t)nseq * 4));
-  T_TRY(up_raw(ki, kv_index, (size_t)n_index * 4));
-  T_TRY(dout.alloc((size_t)rows * d * dt_size(dtype)));
+  RVB_TRY(up_T(dq, dtype, q, (size_t)rows * d));
+  RVB_TRY(up_T(dkk, dtype, k, (size_t)rows * d));
+  RVB_TRY(up_T(dv, dtype, v, (size_t)rows * d));
+  RVB_TRY(up_raw(qs, q_start, (size_t)nseq * 4)); RVB_TRY(up_raw(ql, q_len, (size_t)nseq * 4)); RVB_TRY(up_raw(qp, q_pos0, (size_t)nseq * 4));
+  RVB_TRY(up_raw(ks, kv_start, (size_t)nseq * 4)); RVB_TRY(up_raw(kl, kv_len, (size_t)nseq * 4));
+  RVB_TRY(up_raw(ki, kv_index, (size_t)n_index * 4));
+  RVB_TRY(dout.alloc((size_t)rows * d * dt_size(dtype)));
   RVB_HIP_CHECK(hipMemset(dout.p, 0, (size_t)rows * d * dt_size(dtype)));
   AttnArgs a;
   memset(&a, 0, sizeof(a));
@@ -408,11 +447,11 @@ int rvb_test_attention_trie(int dtype, const float* q, const float* k, const flo
   }
   a.max_q = mq;
   if (q_block == 16) {      // the work-list launch (what the engine uses); q_block 0: the plain (x, z) grid
-    T_TRY(up_raw(wk, work.data(), work.size() * 4));
+    RVB_TRY(up_raw(wk, work.data(), work.size() * 4));
     a.work = (const int*)wk.p; a.n_work = (int)work.size() / 2;
   }
   attention_lab_switches(a);      // RVB_ATTN_* of the lab build, as the engine passes them
-  T_TRY(attention(nullptr, dtype, a));
+  RVB_TRY(attention(nullptr, dtype, a));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(dout, dtype, false, out, (size_t)rows * d);
 }
@@ -468,26 +507,26 @@ int rvb_test_attention_ex(rvb_test_attn_args* tp) {
   if (!tp) { set_error("rvb_test_attention_ex: null"); return E_ARG; }
   rvb_test_attn_args& t = *tp;
   for (int i = 0; i < 8; ++i) t.ran[i] = 0;
-  T_TRY(attn_ex_check(t));
-  T_TRY(need_gpu());
+  RVB_TRY(attn_ex_check(t));
+  RVB_TRY(need_gpu());
   const int dtype = t.dtype, d = t.heads * t.dk;
   const size_t es = dt_size(dtype);
   Dev dq, dkk, dv, dp, du, dvv, dout, dc, qs, ql, ks, kl, qp, ki, wk;
-  T_TRY(up_T(dq, dtype, t.q, (size_t)t.q_rows * t.q_stride));
-  if (t.k != t.q) T_TRY(up_T(dkk, dtype, t.k, (size_t)t.k_rows * t.k_stride));
-  if (t.v != t.q && t.v != t.k) T_TRY(up_T(dv, dtype, t.v, (size_t)t.v_rows * t.v_stride));
+  RVB_TRY(up_T(dq, dtype, t.q, (size_t)t.q_rows * t.q_stride));
+  if (t.k != t.q) RVB_TRY(up_T(dkk, dtype, t.k, (size_t)t.k_rows * t.k_stride));
+  if (t.v != t.q && t.v != t.k) RVB_TRY(up_T(dv, dtype, t.v, (size_t)t.v_rows * t.v_stride));
   const char* bq = (const char*)dq.p;
   const char* bk = t.k == t.q ? bq : (const char*)dkk.p;
   const char* bv = t.v == t.q ? bq : t.v == t.k ? bk : (const char*)dv.p;
-  T_TRY(up_T(dout, dtype, t.out, (size_t)t.o_rows * t.o_stride));
-  if (t.p) T_TRY(up_T(dp, dtype, t.p, (size_t)t.p_rows * t.p_stride));
-  T_TRY(up_raw(du, t.bias_u, (size_t)d * 4));
-  T_TRY(up_raw(dvv, t.bias_v, (size_t)d * 4));
-  T_TRY(up_raw(qs, t.q_start, (size_t)t.nseq * 4)); T_TRY(up_raw(ql, t.q_len, (size_t)t.nseq * 4));
-  T_TRY(up_raw(ks, t.kv_start, (size_t)t.nseq * 4)); T_TRY(up_raw(kl, t.kv_len, (size_t)t.nseq * 4));
-  T_TRY(up_raw(qp, t.q_pos0, (size_t)t.nseq * 4));
-  T_TRY(up_raw(ki, t.kv_index, (size_t)t.n_index * 4));
-  T_TRY(up_raw(wk, t.work, (size_t)t.n_work * 8));
+  RVB_TRY(up_T(dout, dtype, t.out, (size_t)t.o_rows * t.o_stride));
+  if (t.p) RVB_TRY(up_T(dp, dtype, t.p, (size_t)t.p_rows * t.p_stride));
+  RVB_TRY(up_raw(du, t.bias_u, (size_t)d * 4));
+  RVB_TRY(up_raw(dvv, t.bias_v, (size_t)d * 4));
+  RVB_TRY(up_raw(qs, t.q_start, (size_t)t.nseq * 4)); RVB_TRY(up_raw(ql, t.q_len, (size_t)t.nseq * 4));
+  RVB_TRY(up_raw(ks, t.kv_start, (size_t)t.nseq * 4)); RVB_TRY(up_raw(kl, t.kv_len, (size_t)t.nseq * 4));
+  RVB_TRY(up_raw(qp, t.q_pos0, (size_t)t.nseq * 4));
+  RVB_TRY(up_raw(ki, t.kv_index, (size_t)t.n_index * 4));
+  RVB_TRY(up_raw(wk, t.work, (size_t)t.n_work * 8));
   AttnArgs a;
   memset(&a, 0, sizeof(a));
   a.q = bq + (size_t)t.q_col * es; a.k = bk + (size_t)t.k_col * es; a.v = bv + (size_t)t.v_col * es;
@@ -504,8 +543,8 @@ int rvb_test_attention_ex(rvb_test_attn_args* tp) {
     for (int i = 0; i < t.nseq; ++i) a.max_q = t.q_len[i] > a.max_q ? t.q_len[i] : a.max_q;
   if (t.fold) {
     const int rows = t.p_rows - t.p_off;
-    T_TRY(dc.alloc((size_t)t.heads * rows * 4));
-    T_TRY(attention_pos_bias(nullptr, a.p, rows, t.p_stride, a.bias_u, a.bias_v, t.heads, t.dk, 1.44269504f / sqrtf((float)t.dk), (float*)dc.p));
+    RVB_TRY(dc.alloc((size_t)t.heads * rows * 4));
+    RVB_TRY(attention_pos_bias(nullptr, a.p, rows, t.p_stride, a.bias_u, a.bias_v, t.heads, t.dk, 1.44269504f / sqrtf((float)t.dk), (float*)dc.p));
     a.pos_bias = (const float*)dc.p; a.pos_bias_stride = rows; a.fold_kv_cap = t.fold_kv_cap; a.k_prefolded = t.k_prefolded ? 1 : 0;
   }
   (void)attention_last_form(true);
@@ -514,7 +553,7 @@ int rvb_test_attention_ex(rvb_test_attn_args* tp) {
   const int ran[8] = {f.elem_size, f.dkp, f.has_pos, f.nw, f.fold, f.padk, f.occ, f.mf};
   for (int i = 0; i < 8; ++i) t.ran[i] = ran[i];
   RVB_HIP_CHECK(hipDeviceSynchronize());
-  T_TRY(down_T(dout, dtype, false, t.out, (size_t)t.o_rows * t.o_stride));      // also after a refusal: the sentinel must be intact
+  RVB_TRY(down_T(dout, dtype, false, t.out, (size_t)t.o_rows * t.o_stride));      // also after a refusal: the sentinel must be intact
   return rc;
 }
 
@@ -525,14 +564,14 @@ int rvb_test_attention_pos_bias(const float* p, int p_rows, int p_stride, int p_
     set_error("rvb_test_attention_pos_bias: head columns outside the row, or p_off past the last row");
     return E_ARG;
   }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dp, du, dvv, dc;
   const int rows = p_rows - p_off;
-  T_TRY(up_T(dp, DT_BF16, p, (size_t)p_rows * p_stride));
-  T_TRY(up_raw(du, bias_u, (size_t)heads * dk * 4));
-  T_TRY(up_raw(dvv, bias_v, (size_t)heads * dk * 4));
-  T_TRY(dc.alloc((size_t)heads * rows * 4));
-  T_TRY(attention_pos_bias(nullptr, (const bf16_t*)dp.p + (size_t)p_off * p_stride + p_col, rows, p_stride, (const float*)du.p, (const float*)dvv.p,
+  RVB_TRY(up_T(dp, DT_BF16, p, (size_t)p_rows * p_stride));
+  RVB_TRY(up_raw(du, bias_u, (size_t)heads * dk * 4));
+  RVB_TRY(up_raw(dvv, bias_v, (size_t)heads * dk * 4));
+  RVB_TRY(dc.alloc((size_t)heads * rows * 4));
+  RVB_TRY(attention_pos_bias(nullptr, (const bf16_t*)dp.p + (size_t)p_off * p_stride + p_col, rows, p_stride, (const float*)du.p, (const float*)dvv.p,
                            heads, dk, scale, (float*)dc.p));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   RVB_HIP_CHECK(hipMemcpy(out, dc.p, (size_t)heads * rows * 4, hipMemcpyDeviceToHost));
@@ -541,13 +580,13 @@ int rvb_test_attention_pos_bias(const float* p, int p_rows, int p_stride, int p_
 
 int rvb_test_logsoftmax_topk(const float* logits, int M, int V, int k, float blank_penalty, int blank_id,
                              float* topk_val, int32_t* topk_idx, float* logp) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dl, dv, di, dp;
-  T_TRY(up_raw(dl, logits, (size_t)M * V * 4));
-  T_TRY(dv.alloc((size_t)M * k * 4));
-  T_TRY(di.alloc((size_t)M * k * 4));
-  if (logp) T_TRY(dp.alloc((size_t)M * V * 4));
-  T_TRY(logsoftmax_topk(nullptr, (const float*)dl.p, M, V, V, k, blank_penalty, blank_id, (float*)dv.p, (int*)di.p,
+  RVB_TRY(up_raw(dl, logits, (size_t)M * V * 4));
+  RVB_TRY(dv.alloc((size_t)M * k * 4));
+  RVB_TRY(di.alloc((size_t)M * k * 4));
+  if (logp) RVB_TRY(dp.alloc((size_t)M * V * 4));
+  RVB_TRY(logsoftmax_topk(nullptr, (const float*)dl.p, M, V, V, k, blank_penalty, blank_id, (float*)dv.p, (int*)di.p,
                         (float*)dp.p));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   RVB_HIP_CHECK(hipMemcpy(topk_val, dv.p, (size_t)M * k * 4, hipMemcpyDeviceToHost));
@@ -563,25 +602,12 @@ static int ctc_viterbi_lab(const char* who, bool wild, const float* lp, int T, i
   if (T < 1 || slab_rows < 1) { set_error(me + ": need T >= 1 and slab_rows >= 1"); return E_ARG; }
   if (wild && !(std::isfinite(bias) && bias <= 0.f)) { set_error(me + ": wildcard bias must be finite and <= 0"); return E_ARG; }
   CtcAligner al;
-  std::vector<std::vector<int32_t>> rows(1);
-  if (T <= CTC_ALIGN_MAX_FRAMES) { rows[0].resize(T); for (int t = 0; t < T; ++t) rows[0][t] = t; }
-  else rows[0].resize((size_t)T);           // over the cap: plan() refuses on the count alone
-  T_TRY(al.plan(who, tokens, &L, 1, rows, V, blank, wild));
-  T_TRY(need_gpu());
-  Dev dlp, dw;
-  int r = up_raw(dlp, lp, (size_t)T * V * 4);
-  if (r == OK && wild) r = up_raw(dw, w, (size_t)T * 4);
-  if (r == OK) r = al.begin(nullptr);
-  for (int r0 = 0; r == OK && r0 < T; r0 += slab_rows) {
-    const int n = std::min(slab_rows, T - r0);
-    r = al.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, n, wild ? (const float*)dw.p + r0 : nullptr, bias);
-  }
-  std::vector<int32_t> states((size_t)T);
+  std::vector<std::vector<int32_t>> rows;
+  lab_rows(&T, 1, &rows);
+  RVB_TRY(al.plan(who, tokens, &L, 1, rows, V, blank, wild));
+  std::vector<int32_t> states;
   float score = 0.f;
-  if (r == OK) r = al.finish(nullptr, states.data(), &score);
-  if (r != OK) (void)hipDeviceSynchronize();
-  al.release();
-  if (r != OK) return r;
+  RVB_TRY(lab_align(al, lp, wild ? w : nullptr, T, V, slab_rows, bias, &states, &score));
   *score_out = score;
   for (int t = 0; t < T; ++t) labels_out[t] = (states[t] & 1) ? tokens[states[t] >> 1] : blank;
   return OK;
@@ -608,31 +634,15 @@ int rvb_test_ctc_viterbi_graph(const float* lp, const int32_t* T, int n_seq, int
   if (n_seq < 1 || slab_rows < 1) { set_error(me + ": need n_seq >= 1 and slab_rows >= 1"); return E_ARG; }
   if (!(std::isfinite(bias) && bias <= 0.f)) { set_error(me + ": wildcard_bias must be finite and <= 0"); return E_ARG; }
   CtcGraphAligner al;
-  std::vector<std::vector<int32_t>> rows(n_seq);
-  int64_t M = 0;
-  for (int i = 0; i < n_seq; ++i) {
+  for (int i = 0; i < n_seq; ++i)
     if (T[i] < 1) { set_error(me + ": sequence " + std::to_string(i) + ": need T >= 1"); return E_ARG; }
-    rows[i].resize((size_t)T[i]);
-    if (T[i] <= CTC_ALIGN_MAX_FRAMES) for (int t = 0; t < T[i]; ++t) rows[i][t] = (int32_t)(M + t);   // over the cap: refused on the count
-    M += T[i];
-  }
-  T_TRY(al.plan(me.c_str(), node_tokens, n_nodes, pred_off, preds, is_final, n_seq, rows, V, blank));
+  std::vector<std::vector<int32_t>> rows;
+  const int64_t M = lab_rows(T, n_seq, &rows);
+  RVB_TRY(al.plan(me.c_str(), node_tokens, n_nodes, pred_off, preds, is_final, n_seq, rows, V, blank));
   if (al.has_wild && !w) { set_error(me + ": a graph with wildcards needs w"); return E_ARG; }
-  T_TRY(need_gpu());
-  Dev dlp, dw;
-  int r = up_raw(dlp, lp, (size_t)M * V * 4);
-  if (r == OK && w) r = up_raw(dw, w, (size_t)M * 4);
-  if (r == OK) r = al.begin(nullptr);
-  for (int64_t r0 = 0; r == OK && r0 < M; r0 += slab_rows) {
-    const int n = (int)std::min<int64_t>(slab_rows, M - r0);
-    r = al.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, (int)r0, n, w ? (const float*)dw.p + r0 : nullptr, bias);
-  }
-  std::vector<int32_t> states((size_t)M);
+  std::vector<int32_t> states;
   std::vector<float> score(n_seq);
-  if (r == OK) r = al.finish(nullptr, states.data(), score.data());
-  if (r != OK) (void)hipDeviceSynchronize();
-  al.release();
-  if (r != OK) return r;
+  RVB_TRY(lab_align(al, lp, w, M, V, slab_rows, bias, &states, score.data()));
   memcpy(score_out, score.data(), (size_t)n_seq * 4);
   for (int i = 0; i < n_seq; ++i) {
     const GraphSeq& q = al.seq[i];
@@ -652,31 +662,20 @@ static int ctc_score_lab(const char* who, const float* lp, const int32_t* T, int
   if (!lp || !T || !tokens || !L || !loglik_out || n_seq < 1) { set_error(w + ": null argument"); return E_ARG; }
   if (slab_rows < 1) { set_error(w + ": need T >= 1 and slab_rows >= 1"); return E_ARG; }
   CtcScorer sc;
-  std::vector<std::vector<int32_t>> rows(n_seq);
-  int64_t total = 0;
-  for (int i = 0; i < n_seq; ++i) {
+  for (int i = 0; i < n_seq; ++i)
     if (T[i] < 1) { set_error(w + ": need T >= 1 and slab_rows >= 1"); return E_ARG; }
-    rows[i].resize((size_t)T[i]);             // over the cap: plan() refuses on the count alone
-    if (T[i] <= CTC_ALIGN_MAX_FRAMES) for (int t = 0; t < T[i]; ++t) rows[i][t] = (int32_t)(total + t);
-    total += T[i];
-  }
-  T_TRY(sc.plan(who, tokens, L, n_seq, rows, V, blank));
-  T_TRY(need_gpu());
+  std::vector<std::vector<int32_t>> rows;
+  const int64_t M = lab_rows(T, n_seq, &rows);
+  RVB_TRY(sc.plan(who, tokens, L, n_seq, rows, V, blank));
+  RVB_TRY(need_gpu());
   const bool post = occupancy || mean_frame || peak_post || peak_frame;
-  const int M = (int)total;
   Dev dlp;
   int r = up_raw(dlp, lp, (size_t)M * V * 4);
   if (r == OK) r = sc.begin(nullptr, post);
-  for (int r0 = 0; r == OK && r0 < M; r0 += slab_rows)
-    r = sc.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, std::min(slab_rows, M - r0));
+  r = feed_slabs(r, M, slab_rows, false, [&](int r0, int n) { return sc.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, n); });
   if (r == OK) r = sc.finish_forward(nullptr, loglik_out);
   if (r == OK && post) {
-    // descending slabs that END at the last row, so that with the forward slabs (which START at row 0) the boundaries of the two
-    // sweeps fall on different frames
-    for (int r1 = M; r == OK && r1 > 0; r1 -= slab_rows) {
-      const int rb = std::max(0, r1 - slab_rows);
-      r = sc.advance_backward(nullptr, (const float*)dlp.p + (size_t)rb * V, V, rb, r1 - rb);
-    }
+    r = feed_slabs(r, M, slab_rows, true, [&](int r0, int n) { return sc.advance_backward(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, n); });
     if (r == OK) r = sc.finish_backward(nullptr, occupancy, mean_frame, peak_post, peak_frame);
   }
   if (r != OK) (void)hipDeviceSynchronize();
@@ -708,17 +707,12 @@ int rvb_test_ctc_find(const float* lp, const int32_t* T, int n_seq, int V, const
   if (n_phrases < 1 || n_seq < 1) { set_error(me + ": need n_phrases >= 1 and n_seq >= 1"); return E_ARG; }
   if (max_candidates < 1 || max_hits < 1) { set_error(me + ": need max_candidates >= 1 and max_hits >= 1"); return E_ARG; }
   if (slab_rows < 1) { set_error(me + ": need slab_rows >= 1"); return E_ARG; }
-  std::vector<std::vector<int32_t>> rows(n_seq);
-  int64_t total = 0;
-  for (int i = 0; i < n_seq; ++i) {
+  for (int i = 0; i < n_seq; ++i)
     if (T[i] < 0) { set_error(me + ": sequence " + std::to_string(i) + ": negative frame count"); return E_ARG; }
-    rows[i].resize((size_t)T[i]);               // over the cap: plan() refuses on the count alone
-    if (T[i] <= CTC_ALIGN_MAX_FRAMES) for (int t = 0; t < T[i]; ++t) rows[i][t] = (int32_t)(total + t);
-    total += T[i];
-  }
+  std::vector<std::vector<int32_t>> rows;
+  const int M = (int)lab_rows(T, n_seq, &rows);
   CtcFinder fd;
-  T_TRY(fd.plan(who, tokens, tok_lens, n_phrases, threshold, rows, V, blank, max_candidates));
-  const int M = (int)total;
+  RVB_TRY(fd.plan(who, tokens, tok_lens, n_phrases, threshold, rows, V, blank, max_candidates));
   std::vector<float> wmax((size_t)M);
   for (int r = 0; r < M; ++r) {
     float m = w ? w[r] : -INFINITY;
@@ -726,39 +720,73 @@ int rvb_test_ctc_find(const float* lp, const int32_t* T, int n_seq, int V, const
     if (!std::isfinite(m)) { set_error(me + ": the row maximum of frame " + std::to_string(r) + " is not finite"); return E_ARG; }
     wmax[r] = m;
   }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dlp, dw;
   int r = up_raw(dlp, lp, (size_t)M * V * 4);
   if (r == OK) r = up_raw(dw, wmax.data(), (size_t)M * 4);
   if (r == OK) r = fd.begin(nullptr);
-  for (int r0 = 0; r == OK && r0 < M; r0 += slab_rows)
-    r = fd.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, std::min(slab_rows, M - r0), (const float*)dw.p + r0);
+  r = feed_slabs(r, M, slab_rows, false, [&](int r0, int n) {
+    return fd.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, n, (const float*)dw.p + r0);
+  });
   if (r == OK) r = fd.finish(nullptr, max_hits, n_hits, hit_start, hit_end, hit_score, raw_count, raw_end, raw_start, raw_score);
   if (r != OK) (void)hipDeviceSynchronize();
   fd.release();
   return r;
 }
 
+int rvb_test_slab_windows(const char* who, const int32_t* rows, const int32_t* T, int n_seq, const int32_t* slabs, int n_slabs,
+                          int descending, int32_t* windows_out, int32_t* any_out, int32_t* touches_out, int32_t* fed_out,
+                          int32_t* covered_out) {
+  if (!who || !rows || !T || !slabs || !windows_out || !any_out || !touches_out || !fed_out || !covered_out || n_seq < 1 || n_slabs < 0) {
+    set_error("rvb_test_slab_windows: null argument or no sequence");
+    return E_ARG;
+  }
+  *fed_out = 0; *covered_out = 0;
+  std::vector<FindSeq> seq(n_seq, FindSeq{});
+  std::vector<int32_t> h_rows;
+  int64_t frame_off = 0;
+  for (int i = 0; i < n_seq; ++i) {
+    if (T[i] < 0) { set_error("rvb_test_slab_windows: negative frame count"); return E_ARG; }
+    seq[i].frame_off = (int)frame_off; seq[i].T = T[i];
+    seq[i].f0 = seq[i].f1 = descending ? T[i] : 0;            // as begin() / CtcScorer::finish_forward leave them
+    const int32_t* rw = rows + frame_off;
+    RVB_TRY(slab_take_rows(who, std::string(who) + ": sequence " + std::to_string(i) + ": ", std::vector<int32_t>(rw, rw + T[i]), &h_rows,
+                           &frame_off));
+  }
+  for (int k = 0; k < n_slabs; ++k) {
+    const int r0 = slabs[2 * k], nrows = slabs[2 * k + 1];
+    touches_out[k] = slab_touches(seq, h_rows, r0, nrows);
+    bool any = false;
+    RVB_TRY(slab_window(who, descending, seq, h_rows, r0, nrows, &any));
+    any_out[k] = any;
+    for (int i = 0; i < n_seq; ++i) { windows_out[((size_t)k * n_seq + i) * 2] = seq[i].f0; windows_out[((size_t)k * n_seq + i) * 2 + 1] = seq[i].f1; }
+    *fed_out = k + 1;
+  }
+  RVB_TRY(slab_covered(who, descending, seq));
+  *covered_out = 1;
+  return OK;
+}
+
 int rvb_test_lse_gather(const float* logits, int R, int V, const int32_t* target, float* out) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dl, dt, dout;
-  T_TRY(up_raw(dl, logits, (size_t)R * V * 4));
-  T_TRY(up_raw(dt, target, (size_t)R * 4));
-  T_TRY(dout.alloc((size_t)R * 4));
-  T_TRY(lse_gather(nullptr, (const float*)dl.p, R, V, V, (const int*)dt.p, (float*)dout.p));
+  RVB_TRY(up_raw(dl, logits, (size_t)R * V * 4));
+  RVB_TRY(up_raw(dt, target, (size_t)R * 4));
+  RVB_TRY(dout.alloc((size_t)R * 4));
+  RVB_TRY(lse_gather(nullptr, (const float*)dl.p, R, V, V, (const int*)dt.p, (float*)dout.p));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   RVB_HIP_CHECK(hipMemcpy(out, dout.p, (size_t)R * 4, hipMemcpyDeviceToHost));
   return OK;
 }
 
 int rvb_test_lse_gather_multi(const float* logits, int R, int V, const int32_t* ptr, const int32_t* target, int P, float* out) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dl, dp, dt, dout;
-  T_TRY(up_raw(dl, logits, (size_t)R * V * 4));
-  T_TRY(up_raw(dp, ptr, (size_t)(R + 1) * 4));
-  T_TRY(up_raw(dt, target, (size_t)P * 4));
-  T_TRY(dout.alloc((size_t)(P > 0 ? P : 1) * 4));
-  T_TRY(lse_gather_multi(nullptr, (const float*)dl.p, R, V, V, (const int*)dp.p, (const int*)dt.p, (float*)dout.p));
+  RVB_TRY(up_raw(dl, logits, (size_t)R * V * 4));
+  RVB_TRY(up_raw(dp, ptr, (size_t)(R + 1) * 4));
+  RVB_TRY(up_raw(dt, target, (size_t)P * 4));
+  RVB_TRY(dout.alloc((size_t)(P > 0 ? P : 1) * 4));
+  RVB_TRY(lse_gather_multi(nullptr, (const float*)dl.p, R, V, V, (const int*)dp.p, (const int*)dt.p, (float*)dout.p));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   if (P > 0) RVB_HIP_CHECK(hipMemcpy(out, dout.p, (size_t)P * 4, hipMemcpyDeviceToHost));
   return OK;
@@ -772,14 +800,14 @@ int rvb_test_row_xent(const float* logits, int R, int V, int ld, const int32_t* 
   const int P = ptr[R];
   if (P > 0 && (!target || !logp)) { set_error("rvb_test_row_xent: targets without target / logp arrays"); return E_ARG; }
   for (int p = 0; p < P; ++p) if (target[p] < 0 || target[p] >= V) { set_error("rvb_test_row_xent: target outside [0, V)"); return E_ARG; }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dl, dp, dt, dlogp, dlse, dsum, dtop;
-  T_TRY(up_raw(dl, logits, (size_t)R * ld * 4));
-  T_TRY(up_raw(dp, ptr, (size_t)(R + 1) * 4));
-  if (P > 0) { T_TRY(up_raw(dt, target, (size_t)P * 4)); } else { T_TRY(dt.alloc(4)); }
-  T_TRY(dlogp.alloc((size_t)(P > 0 ? P : 1) * 4));
-  T_TRY(dlse.alloc((size_t)R * 4)); T_TRY(dsum.alloc((size_t)R * 8)); T_TRY(dtop.alloc((size_t)R * 4));
-  T_TRY(row_xent(nullptr, (const float*)dl.p, R, V, ld, (const int*)dp.p, (const int*)dt.p, (float*)dlogp.p, (float*)dlse.p,
+  RVB_TRY(up_raw(dl, logits, (size_t)R * ld * 4));
+  RVB_TRY(up_raw(dp, ptr, (size_t)(R + 1) * 4));
+  if (P > 0) { RVB_TRY(up_raw(dt, target, (size_t)P * 4)); } else { RVB_TRY(dt.alloc(4)); }
+  RVB_TRY(dlogp.alloc((size_t)(P > 0 ? P : 1) * 4));
+  RVB_TRY(dlse.alloc((size_t)R * 4)); RVB_TRY(dsum.alloc((size_t)R * 8)); RVB_TRY(dtop.alloc((size_t)R * 4));
+  RVB_TRY(row_xent(nullptr, (const float*)dl.p, R, V, ld, (const int*)dp.p, (const int*)dt.p, (float*)dlogp.p, (float*)dlse.p,
                  (double*)dsum.p, (int*)dtop.p));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   if (P > 0) RVB_HIP_CHECK(hipMemcpy(logp, dlogp.p, (size_t)P * 4, hipMemcpyDeviceToHost));
@@ -794,7 +822,7 @@ int rvb_test_row_xent(const float* logits, int R, int V, int ld, const int32_t* 
 // isolates the kernel from the quantisation.  out_kind 0 bf16, 1 fp32, 2 fp8 (values are returned de-quantised).
 int rvb_test_gemm_fp8(const float* A, const float* W, const float* bias, const float* res, float* C, int M, int N, int K,
                       float a_scale, float alpha, int act, int out_kind, float out_scale, float* a_deq, float* w_deq) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   std::vector<uint8_t> qa((size_t)M * K), qw((size_t)N * K);
   std::vector<float> ws(N);
   for (size_t i = 0; i < qa.size(); ++i) { qa[i] = f32_to_fp8_host(A[i] / a_scale); if (a_deq) a_deq[i] = fp8_to_f32_host(qa[i]) * a_scale; }
@@ -808,17 +836,17 @@ int rvb_test_gemm_fp8(const float* A, const float* W, const float* bias, const f
     }
   }
   Dev dA, dW, dS, dB, dR, dC;
-  T_TRY(up_raw(dA, qa.data(), qa.size())); T_TRY(up_raw(dW, qw.data(), qw.size())); T_TRY(up_raw(dS, ws.data(), (size_t)N * 4));
-  T_TRY(up_raw(dB, bias, (size_t)N * 4)); T_TRY(up_raw(dR, res, (size_t)M * N * 4));
+  RVB_TRY(up_raw(dA, qa.data(), qa.size())); RVB_TRY(up_raw(dW, qw.data(), qw.size())); RVB_TRY(up_raw(dS, ws.data(), (size_t)N * 4));
+  RVB_TRY(up_raw(dB, bias, (size_t)N * 4)); RVB_TRY(up_raw(dR, res, (size_t)M * N * 4));
   const size_t osz = out_kind == 1 ? 4 : out_kind == 2 ? 1 : 2;
-  T_TRY(dC.alloc((size_t)M * N * osz));
+  RVB_TRY(dC.alloc((size_t)M * N * osz));
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   g.A = dA.p; g.W = dW.p; g.bias = (const float*)dB.p; g.res = (const float*)dR.p; g.C = dC.p;
   g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = N; g.ldres = N; g.alpha = alpha; g.act = act;
   g.out_f32 = out_kind == 1; g.out_fp8 = out_kind == 2; g.in_fp8 = 1; g.a_scale = a_scale; g.w_scale = (const float*)dS.p;
   g.out_inv_scale = 1.f / out_scale;
-  T_TRY(gemm(nullptr, DT_BF16, g));
+  RVB_TRY(gemm(nullptr, DT_BF16, g));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   if (out_kind == 1) return down_T(dC, DT_F32, true, C, (size_t)M * N);
   if (out_kind == 0) return down_T(dC, DT_BF16, false, C, (size_t)M * N);
@@ -836,7 +864,7 @@ int rvb_test_gemm_fp8(const float* A, const float* W, const float* bias, const f
 int rvb_test_conv_igemm_fp8(const float* x, const float* w, const float* bias, const float* res, float* out, float* out8, int B,
                             int Fi, int Ti, int Cin, int Cout, int stride, int relu, float a_scale, float out8_scale, float* x_deq,
                             float* w_deq, float* amax) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   const int Fo = (Fi - 1) / stride + 1, To = (Ti - 1) / stride + 1;
   const size_t npi = (size_t)B * (Fi + 2) * (Ti + 2) * Cin, npo = (size_t)B * (Fo + 2) * (To + 2) * Cout;
   std::vector<uint8_t> qx(npi, 0), qw((size_t)Cout * 9 * Cin);
@@ -861,8 +889,8 @@ int rvb_test_conv_igemm_fp8(const float* x, const float* w, const float* bias, c
     }
   }
   Dev dx, dw, ds, db, dr, dout, dout8, dam;
-  T_TRY(up_raw(dx, qx.data(), qx.size())); T_TRY(up_raw(dw, qw.data(), qw.size())); T_TRY(up_raw(ds, ws.data(), (size_t)Cout * 4));
-  T_TRY(up_raw(db, bias, (size_t)Cout * 4));
+  RVB_TRY(up_raw(dx, qx.data(), qx.size())); RVB_TRY(up_raw(dw, qw.data(), qw.size())); RVB_TRY(up_raw(ds, ws.data(), (size_t)Cout * 4));
+  RVB_TRY(up_raw(db, bias, (size_t)Cout * 4));
   if (res) {
     std::vector<bf16_t> rb(npo, 0);
     for (int b = 0; b < B; ++b)
@@ -870,18 +898,18 @@ int rvb_test_conv_igemm_fp8(const float* x, const float* w, const float* bias, c
         for (int t = 0; t < To; ++t)
           for (int c = 0; c < Cout; ++c)
             rb[(((size_t)b * (Fo + 2) + f + 1) * (To + 2) + t + 1) * Cout + c] = f32_to_bf16(res[(((size_t)b * Fo + f) * To + t) * Cout + c]);
-    T_TRY(up_raw(dr, rb.data(), npo * 2));
+    RVB_TRY(up_raw(dr, rb.data(), npo * 2));
   }
-  if (out) { T_TRY(dout.alloc(npo * 2)); RVB_HIP_CHECK(hipMemset(dout.p, 0, npo * 2)); }
-  if (out8) { T_TRY(dout8.alloc(npo)); RVB_HIP_CHECK(hipMemset(dout8.p, 0, npo)); }
-  T_TRY(dam.alloc(4)); RVB_HIP_CHECK(hipMemset(dam.p, 0, 4));
+  if (out) { RVB_TRY(dout.alloc(npo * 2)); RVB_HIP_CHECK(hipMemset(dout.p, 0, npo * 2)); }
+  if (out8) { RVB_TRY(dout8.alloc(npo)); RVB_HIP_CHECK(hipMemset(dout8.p, 0, npo)); }
+  RVB_TRY(dam.alloc(4)); RVB_HIP_CHECK(hipMemset(dam.p, 0, 4));
   ConvArgs a{};
   a.bias = (const float*)db.p; a.res = dr.p; a.out = dout.p;
   a.B = B; a.Fi = Fi; a.Ti = Ti; a.Cin = Cin; a.Fo = Fo; a.To = To; a.Cout = Cout; a.stride = stride; a.taps = 9; a.relu = relu;
   a.in8 = dx.p; a.w8 = dw.p; a.w8_scale = (const float*)ds.p; a.a_scale = a_scale; a.out8 = dout8.p; a.out8_inv_scale = 1.f / out8_scale;
   a.amax8 = (unsigned*)dam.p;
   if (!conv_igemm8_applicable(DT_BF16, a)) { set_error("rvb_test_conv_igemm_fp8: shape not supported (channels multiples of 128, 3x3, stride 1 | 2)"); return E_ARG; }
-  T_TRY(conv_igemm8(nullptr, a));
+  RVB_TRY(conv_igemm8(nullptr, a));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   if (amax) RVB_HIP_CHECK(hipMemcpy(amax, dam.p, 4, hipMemcpyDeviceToHost));
   if (out) {
@@ -908,23 +936,23 @@ int rvb_test_conv_igemm_fp8(const float* x, const float* w, const float* bias, c
 // LayerNorm with fp8 outputs (first stage and / or the fused second LayerNorm); results returned de-quantised
 int rvb_test_rownorm_fp8(const float* x, const float* gamma, const float* beta, float eps, int silu, int M, int d, float scale,
                          float* out, const float* gamma2, const float* beta2, float eps2, float scale2, float* out1_f32, float* out2) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dx, dg, db, dg2, db2, dout, dout2;
-  T_TRY(up_raw(dx, x, (size_t)M * d * 4)); T_TRY(up_raw(dg, gamma, (size_t)d * 4)); T_TRY(up_raw(db, beta, (size_t)d * 4));
-  T_TRY(up_raw(dg2, gamma2, (size_t)d * 4)); T_TRY(up_raw(db2, beta2, (size_t)d * 4));
+  RVB_TRY(up_raw(dx, x, (size_t)M * d * 4)); RVB_TRY(up_raw(dg, gamma, (size_t)d * 4)); RVB_TRY(up_raw(db, beta, (size_t)d * 4));
+  RVB_TRY(up_raw(dg2, gamma2, (size_t)d * 4)); RVB_TRY(up_raw(db2, beta2, (size_t)d * 4));
   NormArgs a;
   a.x = (const float*)dx.p; a.gamma = (const float*)dg.p; a.beta = (const float*)db.p; a.eps = eps; a.mode = NORM_LN; a.silu = silu;
   a.add = nullptr; a.M = M; a.d = d;
   const bool two = gamma2 != nullptr;
   if (two) {       // stage 1 fp32 (in place semantics of norm_final), stage 2 fp8
-    T_TRY(dout.alloc((size_t)M * d * 4)); T_TRY(dout2.alloc((size_t)M * d));
+    RVB_TRY(dout.alloc((size_t)M * d * 4)); RVB_TRY(dout2.alloc((size_t)M * d));
     a.out = dout.p; a.out_f32 = 1; a.gamma2 = (const float*)dg2.p; a.beta2 = (const float*)db2.p; a.eps2 = eps2; a.out2 = dout2.p;
     a.out2_fp8 = 1; a.out2_inv_scale = 1.f / scale2;
   } else {
-    T_TRY(dout.alloc((size_t)M * d));
+    RVB_TRY(dout.alloc((size_t)M * d));
     a.out = dout.p; a.out_f32 = 0; a.out_fp8 = 1; a.out_inv_scale = 1.f / scale;
   }
-  T_TRY(rownorm(nullptr, DT_BF16, a));
+  RVB_TRY(rownorm(nullptr, DT_BF16, a));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   std::vector<uint8_t> q((size_t)M * d);
   if (two) {
@@ -959,18 +987,18 @@ int rvb_test_rownorm_ex(rvb_test_norm_args* t) {
   if ((t->out_fp8 && !(t->out_scale > 0.f)) || (two && t->out2_fp8 && !(t->out2_scale > 0.f))) {
     set_error("rvb_test_rownorm_ex: an fp8 output needs a positive scale"); return E_ARG;
   }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   const int dtype = t->dtype;
   const size_t n = (size_t)t->M * t->d;
   Dev dx, dg, db, da, dg2, db2, dout, dout2, dsat;
-  if (t->x_bf16) T_TRY(up_T(dx, DT_BF16, t->x, n)); else T_TRY(up_raw(dx, t->x, n * 4));
-  T_TRY(up_raw(dg, t->gamma, (size_t)t->d * 4)); T_TRY(up_raw(db, t->beta, (size_t)t->d * 4));
-  T_TRY(up_T(da, dtype, t->add, n));
-  T_TRY(up_raw(dg2, t->gamma2, (size_t)t->d * 4)); T_TRY(up_raw(db2, t->beta2, (size_t)t->d * 4));
+  if (t->x_bf16) RVB_TRY(up_T(dx, DT_BF16, t->x, n)); else RVB_TRY(up_raw(dx, t->x, n * 4));
+  RVB_TRY(up_raw(dg, t->gamma, (size_t)t->d * 4)); RVB_TRY(up_raw(db, t->beta, (size_t)t->d * 4));
+  RVB_TRY(up_T(da, dtype, t->add, n));
+  RVB_TRY(up_raw(dg2, t->gamma2, (size_t)t->d * 4)); RVB_TRY(up_raw(db2, t->beta2, (size_t)t->d * 4));
   // four bytes per element whatever the output type (a call the launcher is going to refuse may name any combination)
-  T_TRY(dout.alloc(n * 4)); RVB_HIP_CHECK(hipMemset(dout.p, 0xff, n * 4));
-  if (two) { T_TRY(dout2.alloc(n * 4)); RVB_HIP_CHECK(hipMemset(dout2.p, 0xff, n * 4)); }
-  T_TRY(dsat.alloc(8)); RVB_HIP_CHECK(hipMemset(dsat.p, 0, 8));
+  RVB_TRY(dout.alloc(n * 4)); RVB_HIP_CHECK(hipMemset(dout.p, 0xff, n * 4));
+  if (two) { RVB_TRY(dout2.alloc(n * 4)); RVB_HIP_CHECK(hipMemset(dout2.p, 0xff, n * 4)); }
+  RVB_TRY(dsat.alloc(8)); RVB_HIP_CHECK(hipMemset(dsat.p, 0, 8));
   NormArgs a;
   a.x = (const float*)dx.p; a.x_bf16 = t->x_bf16 ? 1 : 0; a.gamma = (const float*)dg.p; a.beta = (const float*)db.p; a.eps = t->eps;
   a.mode = t->mode; a.silu = t->silu; a.add = da.p; a.out = dout.p; a.out_f32 = t->out_f32; a.M = t->M; a.d = t->d;
@@ -982,16 +1010,16 @@ int rvb_test_rownorm_ex(rvb_test_norm_args* t) {
     if (t->out2_fp8) a.out2_inv_scale = 1.f / t->out2_scale;
   }
   a.sat = (unsigned*)dsat.p; a.sat2 = (unsigned*)dsat.p + 1;
-  T_TRY(rownorm(nullptr, dtype, a));
+  RVB_TRY(rownorm(nullptr, dtype, a));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   uint32_t sats[2];
   RVB_HIP_CHECK(hipMemcpy(sats, dsat.p, 8, hipMemcpyDeviceToHost));
   t->sat = sats[0]; t->sat2 = sats[1];
-  if (t->out_fp8) T_TRY(down_fp8(dout, t->out, n, t->out_scale));
-  else T_TRY(down_T(dout, dtype, t->out_f32 != 0, t->out, n));
+  if (t->out_fp8) RVB_TRY(down_fp8(dout, t->out, n, t->out_scale));
+  else RVB_TRY(down_T(dout, dtype, t->out_f32 != 0, t->out, n));
   if (two) {
-    if (t->out2_fp8) T_TRY(down_fp8(dout2, t->out2, n, t->out2_scale));
-    else T_TRY(down_T(dout2, dtype, false, t->out2, n));
+    if (t->out2_fp8) RVB_TRY(down_fp8(dout2, t->out2, n, t->out2_scale));
+    else RVB_TRY(down_T(dout2, dtype, false, t->out2, n));
   }
   return OK;
 }
@@ -1002,23 +1030,23 @@ int rvb_test_conv1_ex(int dtype, const float* feats, const float* mean, const fl
   if (!feats || !mean || !istd || !w || !b || !out || B < 1 || T0 < 3 || F0 < 3 || d < 1 || (dtype != DT_F32 && dtype != DT_BF16)) {
     set_error("rvb_test_conv1_ex: null argument, B < 1, fewer than 3 frames or bins, d < 1 or an unknown dtype"); return E_ARG;
   }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   const int T1 = (T0 - 3) / 2 + 1, F1 = (F0 - 3) / 2 + 1;
   Dev df, dm, di, dw, db, dout, dslot;
-  T_TRY(up_raw(df, feats, (size_t)B * T0 * F0 * 4));
-  T_TRY(up_raw(dm, mean, (size_t)F0 * 4));
-  T_TRY(up_raw(di, istd, (size_t)F0 * 4));
+  RVB_TRY(up_raw(df, feats, (size_t)B * T0 * F0 * 4));
+  RVB_TRY(up_raw(dm, mean, (size_t)F0 * 4));
+  RVB_TRY(up_raw(di, istd, (size_t)F0 * 4));
   std::vector<float> wt((size_t)d * 9);            // [d][1][3][3] -> tap-major [9][d]
   for (int c = 0; c < d; ++c)
     for (int k = 0; k < 9; ++k) wt[(size_t)k * d + c] = w[(size_t)c * 9 + k];
-  T_TRY(up_raw(dw, wt.data(), (size_t)d * 9 * 4));
-  T_TRY(up_raw(db, b, (size_t)d * 4));
+  RVB_TRY(up_raw(dw, wt.data(), (size_t)d * 9 * 4));
+  RVB_TRY(up_raw(db, b, (size_t)d * 4));
   const size_t n = (size_t)B * T1 * F1 * d;
-  T_TRY(dout.alloc(n * 4)); RVB_HIP_CHECK(hipMemset(dout.p, 0xff, n * 4));
+  RVB_TRY(dout.alloc(n * 4)); RVB_HIP_CHECK(hipMemset(dout.p, 0xff, n * 4));
   uint32_t slots[2] = {0, 0};                      // {amax as float bits, sat}
   if (amax) memcpy(&slots[0], amax, 4);
-  T_TRY(up_raw(dslot, slots, 8));
-  T_TRY(subsample_conv1(nullptr, dtype, (const float*)df.p, (const float*)dm.p, (const float*)di.p, (const float*)dw.p,
+  RVB_TRY(up_raw(dslot, slots, 8));
+  RVB_TRY(subsample_conv1(nullptr, dtype, (const float*)df.p, (const float*)dm.p, (const float*)di.p, (const float*)dw.p,
                         (const float*)db.p, dout.p, B, T0, F0, d, out_fp8_scale, amax ? (unsigned*)dslot.p : nullptr,
                         sat ? (unsigned*)dslot.p + 1 : nullptr));
   RVB_HIP_CHECK(hipDeviceSynchronize());
@@ -1034,12 +1062,12 @@ int rvb_test_embed(const float* E, int vocab, const float* pe, int n_pos, const 
   if (!E || !pe || !tok || !pos || !out || vocab < 1 || n_pos < 1 || rows < 1 || d < 1) { set_error("rvb_test_embed: null argument or an empty table"); return E_ARG; }
   for (int r = 0; r < rows; ++r)
     if (tok[r] < 0 || tok[r] >= vocab || pos[r] < 0 || pos[r] >= n_pos) { set_error("rvb_test_embed: index outside its table"); return E_ARG; }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dE, dp, dt, dq, dout;
-  T_TRY(up_raw(dE, E, (size_t)vocab * d * 4)); T_TRY(up_raw(dp, pe, (size_t)n_pos * d * 4));
-  T_TRY(up_raw(dt, tok, (size_t)rows * 4)); T_TRY(up_raw(dq, pos, (size_t)rows * 4));
-  T_TRY(up_raw(dout, out, (size_t)rows * d * 4));
-  T_TRY(embed_tokens(nullptr, (const float*)dE.p, (const float*)dp.p, (const int*)dt.p, (const int*)dq.p, (float*)dout.p, rows, d, scale));
+  RVB_TRY(up_raw(dE, E, (size_t)vocab * d * 4)); RVB_TRY(up_raw(dp, pe, (size_t)n_pos * d * 4));
+  RVB_TRY(up_raw(dt, tok, (size_t)rows * 4)); RVB_TRY(up_raw(dq, pos, (size_t)rows * 4));
+  RVB_TRY(up_raw(dout, out, (size_t)rows * d * 4));
+  RVB_TRY(embed_tokens(nullptr, (const float*)dE.p, (const float*)dp.p, (const int*)dt.p, (const int*)dq.p, (float*)dout.p, rows, d, scale));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   RVB_HIP_CHECK(hipMemcpy(out, dout.p, (size_t)rows * d * 4, hipMemcpyDeviceToHost));
   return OK;
@@ -1047,11 +1075,11 @@ int rvb_test_embed(const float* E, int vocab, const float* pe, int n_pos, const 
 
 int rvb_test_amax_abs(int dtype, const float* x, int64_t n, float* slot) {
   if (!x || !slot || n < 1 || (dtype != DT_F32 && dtype != DT_BF16)) { set_error("rvb_test_amax_abs: null argument, n < 1 or an unknown dtype"); return E_ARG; }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dx, ds;
-  T_TRY(up_T(dx, dtype, x, (size_t)n));
-  T_TRY(up_raw(ds, slot, 4));
-  T_TRY(amax_abs(nullptr, dtype, dx.p, (size_t)n, (float*)ds.p));
+  RVB_TRY(up_T(dx, dtype, x, (size_t)n));
+  RVB_TRY(up_raw(ds, slot, 4));
+  RVB_TRY(amax_abs(nullptr, dtype, dx.p, (size_t)n, (float*)ds.p));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   RVB_HIP_CHECK(hipMemcpy(slot, ds.p, 4, hipMemcpyDeviceToHost));
   return OK;
@@ -1059,11 +1087,11 @@ int rvb_test_amax_abs(int dtype, const float* x, int64_t n, float* slot) {
 
 int rvb_test_convert_f32(int dtype, const float* src, float* dst, int64_t n) {
   if (!src || !dst || n < 1 || (dtype != DT_F32 && dtype != DT_BF16)) { set_error("rvb_test_convert_f32: null argument, n < 1 or an unknown dtype"); return E_ARG; }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev ds, dd;
-  T_TRY(up_raw(ds, src, (size_t)n * 4));
-  T_TRY(dd.alloc((size_t)n * 4)); RVB_HIP_CHECK(hipMemset(dd.p, 0xff, (size_t)n * 4));
-  T_TRY(convert_f32(nullptr, dtype, (const float*)ds.p, dd.p, (size_t)n));
+  RVB_TRY(up_raw(ds, src, (size_t)n * 4));
+  RVB_TRY(dd.alloc((size_t)n * 4)); RVB_HIP_CHECK(hipMemset(dd.p, 0xff, (size_t)n * 4));
+  RVB_TRY(convert_f32(nullptr, dtype, (const float*)ds.p, dd.p, (size_t)n));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(dd, dtype, false, dst, (size_t)n);
 }
@@ -1072,11 +1100,11 @@ int rvb_test_gather_cache(const void* src, void* dst, const int32_t* parent, int
   if (!src || !dst || !parent || R < 1 || L < 1 || rows < 0 || rows > L || row_bytes < 1) { set_error("rvb_test_gather_cache: null argument or not 0 <= rows <= L"); return E_ARG; }
   for (int r = 0; r < R; ++r)
     if (parent[r] < 0 || parent[r] >= R) { set_error("rvb_test_gather_cache: parent outside [0, R)"); return E_ARG; }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   const size_t bytes = (size_t)R * L * row_bytes;
   Dev ds, dd, dp;
-  T_TRY(up_raw(ds, src, bytes)); T_TRY(up_raw(dd, dst, bytes)); T_TRY(up_raw(dp, parent, (size_t)R * 4));
-  T_TRY(gather_cache(nullptr, ds.p, dd.p, (const int*)dp.p, R, L, rows, row_bytes));
+  RVB_TRY(up_raw(ds, src, bytes)); RVB_TRY(up_raw(dd, dst, bytes)); RVB_TRY(up_raw(dp, parent, (size_t)R * 4));
+  RVB_TRY(gather_cache(nullptr, ds.p, dd.p, (const int*)dp.p, R, L, rows, row_bytes));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   RVB_HIP_CHECK(hipMemcpy(dst, dd.p, bytes, hipMemcpyDeviceToHost));
   return OK;
@@ -1086,11 +1114,11 @@ int rvb_test_gather_pairs(const float* table, int rows, int64_t ld, const int32_
   if (!table || rows < 1 || ld < 1 || n < 0 || (n > 0 && (!row || !col || !out))) { set_error("rvb_test_gather_pairs: null argument or an empty table"); return E_ARG; }
   for (int i = 0; i < n; ++i)
     if (row[i] < 0 || row[i] >= rows || col[i] < 0 || col[i] >= ld) { set_error("rvb_test_gather_pairs: pair outside the table"); return E_ARG; }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dt, dr, dc, dout;
-  T_TRY(up_raw(dt, table, (size_t)rows * ld * 4));
-  if (n > 0) { T_TRY(up_raw(dr, row, (size_t)n * 4)); T_TRY(up_raw(dc, col, (size_t)n * 4)); T_TRY(up_raw(dout, out, (size_t)n * 4)); }
-  T_TRY(gather_pairs(nullptr, (const float*)dt.p, (size_t)ld, (const int*)dr.p, (const int*)dc.p, n, (float*)dout.p));
+  RVB_TRY(up_raw(dt, table, (size_t)rows * ld * 4));
+  if (n > 0) { RVB_TRY(up_raw(dr, row, (size_t)n * 4)); RVB_TRY(up_raw(dc, col, (size_t)n * 4)); RVB_TRY(up_raw(dout, out, (size_t)n * 4)); }
+  RVB_TRY(gather_pairs(nullptr, (const float*)dt.p, (size_t)ld, (const int*)dr.p, (const int*)dc.p, n, (float*)dout.p));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   if (n > 0) RVB_HIP_CHECK(hipMemcpy(out, dout.p, (size_t)n * 4, hipMemcpyDeviceToHost));
   return OK;
@@ -1231,25 +1259,25 @@ extern "C" int rvb_test_set_gemm2_opts(int flags, int group_m) { g_gemm2_flags =
 // per-workgroup phase timestamps of one bf16 gemm2 launch (scripts/gemm_timeline.py): out[6 * wg + {0..3}] = start / stage 0
 // landed / main loop done / stores drained (10 ns ticks of the constant clock), [4] = HW_ID, [5] = XCC_ID
 extern "C" int rvb_test_gemm_timeline(int M, int N, int K, int act, int out_f32, int with_res, long long* out, int cap, int* n_wg) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dA, dW, dB, dR, dC, dT;
-  T_TRY(dA.alloc((size_t)M * K * 2)); T_TRY(dW.alloc((size_t)N * K * 2)); T_TRY(dB.alloc((size_t)N * 4));
+  RVB_TRY(dA.alloc((size_t)M * K * 2)); RVB_TRY(dW.alloc((size_t)N * K * 2)); RVB_TRY(dB.alloc((size_t)N * 4));
   const int padc = getenv("RVB_BENCH_PADC") ? atoi(getenv("RVB_BENCH_PADC")) : 0;      // probe: output / residual row stride off the power of two
   const int ldc = N + padc;
-  T_TRY(dR.alloc((size_t)M * ldc * 4)); T_TRY(dC.alloc((size_t)M * ldc * (out_f32 ? 4 : 2)));
+  RVB_TRY(dR.alloc((size_t)M * ldc * 4)); RVB_TRY(dC.alloc((size_t)M * ldc * (out_f32 ? 4 : 2)));
   fill<bf16_t>(dA.p, (size_t)M * K, 1u, 1.0f); fill<bf16_t>(dW.p, (size_t)N * K, 2u, 1.0f / sqrtf((float)K));
   fill<float>(dB.p, N, 3u, 1.0f); fill<float>(dR.p, (size_t)M * ldc, 4u, 1.0f);
   const int wgs = ((M + 255) / 256) * ((N + 255) / 256);
   if (wgs > cap) { set_error("rvb_test_gemm_timeline: output too small"); return E_ARG; }
-  T_TRY(dT.alloc((size_t)wgs * 6 * 8));
+  RVB_TRY(dT.alloc((size_t)wgs * 6 * 8));
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   g.A = dA.p; g.W = dW.p; g.bias = (const float*)dB.p; g.res = with_res ? (const float*)dR.p : nullptr; g.C = dC.p;
   g.M = M; g.N = N; g.K = K; g.lda = K; g.ldw = K; g.ldc = ldc; g.ldres = ldc; g.alpha = 0.5f; g.act = act; g.out_f32 = out_f32;
   if (!gemm2_applicable(DT_BF16, g)) { set_error("rvb_test_gemm_timeline: shape not handled by gemm2"); return E_ARG; }
-  for (int i = 0; i < 3; ++i) T_TRY(gemm2(nullptr, DT_BF16, g));
+  for (int i = 0; i < 3; ++i) RVB_TRY(gemm2(nullptr, DT_BF16, g));
   g.dbg = (long long*)dT.p;
-  T_TRY(gemm2(nullptr, DT_BF16, g));
+  RVB_TRY(gemm2(nullptr, DT_BF16, g));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   RVB_HIP_CHECK(hipMemcpy(out, dT.p, (size_t)wgs * 6 * 8, hipMemcpyDeviceToHost));
   *n_wg = wgs;
@@ -1258,16 +1286,16 @@ extern "C" int rvb_test_gemm_timeline(int M, int N, int K, int act, int out_f32,
 
 extern "C" int rvb_test_gemm_bench(int dtype, int M, int N, int K, int variant, int iters, int act, int out_f32,
                                    int with_res, double* ms_out, double* max_abs_diff) {
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dA, dW, dB, dR, dC, dC1;
   const size_t es = dt_size(dtype);
   const bool f32out = dtype == DT_F32 || out_f32;
   // RVB_BENCH_PAD=<elements>: pad the leading dimensions of A and W (probe for channel camping of 2^n row strides)
   const int pad = getenv("RVB_BENCH_PAD") ? atoi(getenv("RVB_BENCH_PAD")) : 0;
   const int ldk = K + pad;
-  T_TRY(dA.alloc((size_t)M * ldk * es)); T_TRY(dW.alloc((size_t)N * ldk * es)); T_TRY(dB.alloc((size_t)N * 4));
-  T_TRY(dR.alloc((size_t)M * N * 4)); T_TRY(dC.alloc((size_t)M * N * (f32out ? 4 : 2)));
-  T_TRY(dC1.alloc((size_t)M * N * (f32out ? 4 : 2)));
+  RVB_TRY(dA.alloc((size_t)M * ldk * es)); RVB_TRY(dW.alloc((size_t)N * ldk * es)); RVB_TRY(dB.alloc((size_t)N * 4));
+  RVB_TRY(dR.alloc((size_t)M * N * 4)); RVB_TRY(dC.alloc((size_t)M * N * (f32out ? 4 : 2)));
+  RVB_TRY(dC1.alloc((size_t)M * N * (f32out ? 4 : 2)));
   if (dtype == DT_BF16) { fill<bf16_t>(dA.p, (size_t)M * ldk, 1u, 1.0f); fill<bf16_t>(dW.p, (size_t)N * ldk, 2u, 1.0f / sqrtf((float)K)); }
   else { fill<float>(dA.p, (size_t)M * ldk, 1u, 1.0f); fill<float>(dW.p, (size_t)N * ldk, 2u, 1.0f / sqrtf((float)K)); }
   fill<float>(dB.p, N, 3u, 1.0f);
@@ -1325,11 +1353,11 @@ extern "C" int rvb_test_window_stats(const float* wave, int64_t n, int64_t first
   if (!wave || !stats || n < 1 || first < 0 || nwin < 1 || step < 1 || len < 1 || (first + nwin - 1) * step + len > n) {
     set_error("rvb_test_window_stats: bad argument"); return E_ARG;
   }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dw, ds;
-  T_TRY(up_T(dw, DT_F32, wave, (size_t)n));
-  T_TRY(ds.alloc((size_t)nwin * 2 * 4));
-  T_TRY(window_stats(nullptr, (const float*)dw.p, first, nwin, step, len, eps, (float*)ds.p));
+  RVB_TRY(up_T(dw, DT_F32, wave, (size_t)n));
+  RVB_TRY(ds.alloc((size_t)nwin * 2 * 4));
+  RVB_TRY(window_stats(nullptr, (const float*)dw.p, first, nwin, step, len, eps, (float*)ds.p));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(ds, DT_F32, true, stats, (size_t)nwin * 2);
 }
@@ -1341,12 +1369,12 @@ extern "C" int rvb_test_sinc_conv(int dtype, const float* wave, int64_t n_sample
       (dtype != DT_F32 && dtype != DT_BF16)) {
     set_error("rvb_test_sinc_conv: bad argument"); return E_ARG;
   }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dw, df, dout;
-  T_TRY(up_T(dw, DT_F32, wave, (size_t)n_samples));
-  T_TRY(up_T(df, DT_F32, filt, (size_t)nf * ksize));
-  T_TRY(dout.alloc((size_t)n_frames * nf * dt_size(dtype)));
-  T_TRY(sinc_conv(nullptr, dtype, (const float*)dw.p, (const float*)df.p, dout.p, n_frames, nf, ksize, stride));
+  RVB_TRY(up_T(dw, DT_F32, wave, (size_t)n_samples));
+  RVB_TRY(up_T(df, DT_F32, filt, (size_t)nf * ksize));
+  RVB_TRY(dout.alloc((size_t)n_frames * nf * dt_size(dtype)));
+  RVB_TRY(sinc_conv(nullptr, dtype, (const float*)dw.p, (const float*)df.p, dout.p, n_frames, nf, ksize, stride));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(dout, dtype, false, out, (size_t)n_frames * nf);
 }
@@ -1363,27 +1391,27 @@ extern "C" int rvb_test_pool_norm(int dtype, int first_block, const float* x, in
                         craw_frame0 + (int64_t)(W - 1) * craw_frames_per_step + 3 * TP <= craw_rows;
   else ok = ok && x && rows_in >= frames_in && ld_in >= C;
   if (!ok) { set_error("rvb_test_pool_norm: bad argument"); return E_ARG; }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dx, dcr, dst, dfs, dg, db, dout;
   PoolNormArgs a{};
   if (first_block) {
-    T_TRY(up_T(dcr, dtype, craw, (size_t)craw_rows * C));
-    T_TRY(up_T(dst, DT_F32, stats, (size_t)W * 2));
-    T_TRY(up_T(dfs, DT_F32, fsum, (size_t)C));
+    RVB_TRY(up_T(dcr, dtype, craw, (size_t)craw_rows * C));
+    RVB_TRY(up_T(dst, DT_F32, stats, (size_t)W * 2));
+    RVB_TRY(up_T(dfs, DT_F32, fsum, (size_t)C));
     a.craw = dcr.p; a.craw_frame0 = craw_frame0; a.craw_frames_per_step = craw_frames_per_step;
     a.stats = (const float*)dst.p; a.fsum = (const float*)dfs.p; a.wn_gamma = wn_gamma; a.wn_beta = wn_beta;
   } else {
-    T_TRY(up_T(dx, dtype, x, (size_t)W * rows_in * ld_in));
+    RVB_TRY(up_T(dx, dtype, x, (size_t)W * rows_in * ld_in));
     a.x = dx.p; a.rows_in = rows_in; a.ld_in = ld_in;
   }
-  T_TRY(up_T(dg, DT_F32, gamma, (size_t)C));
-  T_TRY(up_T(db, DT_F32, beta, (size_t)C));
+  RVB_TRY(up_T(dg, DT_F32, gamma, (size_t)C));
+  RVB_TRY(up_T(db, DT_F32, beta, (size_t)C));
   const size_t no = (size_t)W * TP * ld_out;
-  T_TRY(dout.alloc(no * dt_size(dtype)));
+  RVB_TRY(dout.alloc(no * dt_size(dtype)));
   RVB_HIP_CHECK(hipMemset(dout.p, 0x7f, no * dt_size(dtype)));      // unwritten pad columns show up as 3.4e38 / 3.3e38
   a.frames_in = frames_in; a.C = C; a.ld_out = ld_out; a.gamma = (const float*)dg.p; a.beta = (const float*)db.p; a.eps = eps;
   a.out = dout.p; a.W = W;
-  T_TRY(pool_norm(nullptr, dtype, a));
+  RVB_TRY(pool_norm(nullptr, dtype, a));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(dout, dtype, false, out, no);
 }
@@ -1393,7 +1421,7 @@ extern "C" int rvb_test_pool_norm(int dtype, int first_block, const float* x, in
 // (diar_engine.hip: [64][5][cin]); the device input has M + 8 rows as the engine's, rows M + 4 .. M + 7 hold 1e30 (nobody reads them).
 extern "C" int rvb_test_conv1d5(int cin, const float* A, int64_t rows, const float* W, const float* bias, float* out, int64_t M) {
   if (!A || !W || !bias || !out || (cin != 80 && cin != 64) || M < 1 || rows < M + 4) { set_error("rvb_test_conv1d5: bad argument"); return E_ARG; }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   const int cr = cin == 80 ? 80 : 60, NO = 60, NP = 64, K = 5;
   std::vector<float> pw((size_t)NP * K * cin, 0.f), pb(NP, 0.f);
   for (int o = 0; o < NO; ++o) {
@@ -1404,11 +1432,11 @@ extern "C" int rvb_test_conv1d5(int cin, const float* A, int64_t rows, const flo
   std::vector<bf16_t> ab((size_t)(M + 8) * cin, f32_to_bf16(1e30f));
   for (size_t i = 0; i < (size_t)(M + 4) * cin; ++i) ab[i] = f32_to_bf16(A[i]);
   Dev da, dw, db, dout;
-  T_TRY(up_raw(da, ab.data(), ab.size() * 2));
-  T_TRY(up_T(dw, DT_BF16, pw.data(), pw.size()));
-  T_TRY(up_T(db, DT_F32, pb.data(), pb.size()));
-  T_TRY(dout.alloc((size_t)M * NP * 2));
-  T_TRY(conv1d5(nullptr, DT_BF16, da.p, cin, dw.p, (const float*)db.p, dout.p, M));
+  RVB_TRY(up_raw(da, ab.data(), ab.size() * 2));
+  RVB_TRY(up_T(dw, DT_BF16, pw.data(), pw.size()));
+  RVB_TRY(up_T(db, DT_F32, pb.data(), pb.size()));
+  RVB_TRY(dout.alloc((size_t)M * NP * 2));
+  RVB_TRY(conv1d5(nullptr, DT_BF16, da.p, cin, dw.p, (const float*)db.p, dout.p, M));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(dout, DT_BF16, false, out, (size_t)M * NP);
 }
@@ -1423,25 +1451,25 @@ extern "C" int rvb_test_lstm_layer(int dtype, const float* x, int W, int T, int 
       (dtype != DT_F32 && dtype != DT_BF16)) {
     set_error("rvb_test_lstm_layer: bad argument"); return E_ARG;
   }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   std::vector<float> wih((size_t)8 * H * in, 0.f), bias((size_t)8 * H, 0.f);
   for (int d = 0; d < 2; ++d)
     lstm_pack_inproj(w_ih + (size_t)d * 4 * H * in, b_ih + (size_t)d * 4 * H, b_hh + (size_t)d * 4 * H, H, in, in,
                      &wih[(size_t)d * 4 * H * in], &bias[(size_t)d * 4 * H]);
   const size_t R = (size_t)W * T;
   Dev dx, dwi, db, dwh, dxp, dout;
-  T_TRY(up_T(dx, dtype, x, R * in));
-  T_TRY(up_T(dwi, dtype, wih.data(), wih.size()));
-  T_TRY(up_T(db, DT_F32, bias.data(), bias.size()));
-  T_TRY(up_T(dwh, dtype, w_hh, (size_t)8 * H * H));
-  T_TRY(dxp.alloc(R * 8 * H * dt_size(dtype)));
-  T_TRY(dout.alloc(R * 2 * H * dt_size(dtype)));
+  RVB_TRY(up_T(dx, dtype, x, R * in));
+  RVB_TRY(up_T(dwi, dtype, wih.data(), wih.size()));
+  RVB_TRY(up_T(db, DT_F32, bias.data(), bias.size()));
+  RVB_TRY(up_T(dwh, dtype, w_hh, (size_t)8 * H * H));
+  RVB_TRY(dxp.alloc(R * 8 * H * dt_size(dtype)));
+  RVB_TRY(dout.alloc(R * 2 * H * dt_size(dtype)));
   GemmArgs g;
   memset(&g, 0, sizeof(g));
   g.A = dx.p; g.W = dwi.p; g.bias = (const float*)db.p; g.C = dxp.p;
   g.M = (int)R; g.N = 8 * H; g.K = in; g.lda = in; g.ldw = in; g.ldc = 8 * H; g.alpha = 1.f; g.act = ACT_NONE;
-  T_TRY(gemm(nullptr, dtype, g));
-  T_TRY(lstm_recurrence(nullptr, dtype, dxp.p, dwh.p, dout.p, W, T));
+  RVB_TRY(gemm(nullptr, dtype, g));
+  RVB_TRY(lstm_recurrence(nullptr, dtype, dxp.p, dwh.p, dout.p, W, T));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(dout, dtype, false, out, R * 2 * H);
 }
@@ -1452,14 +1480,14 @@ extern "C" int rvb_test_classifier(int dtype, const float* x, int ldx, const flo
   if (!x || !w || !b || !logp || M < 1 || C < 1 || in < 1 || ldx < in || (dtype != DT_F32 && dtype != DT_BF16)) {
     set_error("rvb_test_classifier: bad argument"); return E_ARG;
   }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dx, dw, db, dl, dc;
-  T_TRY(up_T(dx, dtype, x, (size_t)M * ldx));
-  T_TRY(up_T(dw, DT_F32, w, (size_t)C * in));
-  T_TRY(up_T(db, DT_F32, b, (size_t)C));
-  T_TRY(dl.alloc((size_t)M * C * 4));
-  if (cls) T_TRY(dc.alloc((size_t)M));
-  T_TRY(classifier_logsoftmax(nullptr, dtype, dx.p, ldx, (const float*)dw.p, (const float*)db.p, (float*)dl.p, (uint8_t*)dc.p, M, in, C));
+  RVB_TRY(up_T(dx, dtype, x, (size_t)M * ldx));
+  RVB_TRY(up_T(dw, DT_F32, w, (size_t)C * in));
+  RVB_TRY(up_T(db, DT_F32, b, (size_t)C));
+  RVB_TRY(dl.alloc((size_t)M * C * 4));
+  if (cls) RVB_TRY(dc.alloc((size_t)M));
+  RVB_TRY(classifier_logsoftmax(nullptr, dtype, dx.p, ldx, (const float*)dw.p, (const float*)db.p, (float*)dl.p, (uint8_t*)dc.p, M, in, C));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   if (cls) RVB_HIP_CHECK(hipMemcpy(cls, dc.p, (size_t)M, hipMemcpyDeviceToHost));
   return down_T(dl, DT_F32, true, logp, (size_t)M * C);
@@ -1473,7 +1501,7 @@ extern "C" int rvb_test_tstp(int dtype, const float* x, int B, const int32_t* it
             (dtype == DT_F32 || dtype == DT_BF16);
   for (int i = 0; ok && i < n_items; ++i) ok = item_b[i] >= 0 && item_b[i] < B;
   if (!ok) { set_error("rvb_test_tstp: bad argument"); return E_ARG; }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   const size_t np = (size_t)B * (F + 2) * (TT + 2) * C;
   std::vector<float> xb(np, 1e3f);
   for (int b = 0; b < B; ++b)
@@ -1481,11 +1509,11 @@ extern "C" int rvb_test_tstp(int dtype, const float* x, int B, const int32_t* it
       for (int t = 0; t < TT; ++t)
         memcpy(&xb[(((size_t)b * (F + 2) + f + 1) * (TT + 2) + t + 1) * C], &x[(((size_t)b * F + f) * TT + t) * C], (size_t)C * 4);
   Dev dx, di, dm, ds;
-  T_TRY(up_T(dx, dtype, xb.data(), np));
-  T_TRY(up_raw(di, item_b, (size_t)n_items * 4));
-  T_TRY(up_T(dm, DT_F32, mask, (size_t)n_items * mask_len));
-  T_TRY(ds.alloc((size_t)n_items * 2 * C * F * dt_size(dtype)));
-  T_TRY(tstp_pool(nullptr, dtype, dx.p, (const int*)di.p, (const float*)dm.p, mask_len, n_items, F, TT, C, ds.p));
+  RVB_TRY(up_T(dx, dtype, xb.data(), np));
+  RVB_TRY(up_raw(di, item_b, (size_t)n_items * 4));
+  RVB_TRY(up_T(dm, DT_F32, mask, (size_t)n_items * mask_len));
+  RVB_TRY(ds.alloc((size_t)n_items * 2 * C * F * dt_size(dtype)));
+  RVB_TRY(tstp_pool(nullptr, dtype, dx.p, (const int*)di.p, (const float*)dm.p, mask_len, n_items, F, TT, C, ds.p));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_T(ds, dtype, false, stats, (size_t)n_items * 2 * C * F);
 }
@@ -1495,7 +1523,7 @@ namespace {
 // unbordered NHWC [B][F][T][C] host floats -> bordered [B][F + 2][T + 2][C] in dtype (zero border) + `slack` zero bytes behind it
 int up_bordered(Dev& d, int dtype, const float* src, int B, int F, int T, int C, size_t slack) {
   const size_t n = (size_t)B * (F + 2) * (T + 2) * C, es = dt_size(dtype);
-  T_TRY(d.alloc(n * es + slack));
+  RVB_TRY(d.alloc(n * es + slack));
   RVB_HIP_CHECK(hipMemset(d.p, 0, n * es + slack));
   std::vector<float> p(n, 0.f);
   for (int b = 0; b < B; ++b)
@@ -1575,33 +1603,33 @@ extern "C" int rvb_test_conv2d(int dtype, int path, const float* x, const float*
   else if (path == 3) kind = !x2 && conv_row64_applicable(dtype, a) ? 3 : 0;
   else kind = !x2 && conv_stream_applicable(dtype, a) ? 4 : 0;
   if (kind == 0) { set_error("rvb_test_conv2d: the path does not apply to this shape (or is switched off)"); return E_STATE; }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dx, dw, dwg, db, dr, dout, dx2;
-  T_TRY(up_bordered(dx, dtype, x, B, Fi, Ti, Cin, kSlack));
-  if (res) T_TRY(up_bordered(dr, dtype, res, B, Fo, To, Cout, kSlack));
-  if (x2) T_TRY(up_bordered(dx2, dtype, x2, B, Fi2, Ti2, Cin2, kSlack));
+  RVB_TRY(up_bordered(dx, dtype, x, B, Fi, Ti, Cin, kSlack));
+  if (res) RVB_TRY(up_bordered(dr, dtype, res, B, Fo, To, Cout, kSlack));
+  if (x2) RVB_TRY(up_bordered(dx2, dtype, x2, B, Fi2, Ti2, Cin2, kSlack));
   std::vector<float> pw((size_t)taps * Cin * Cout);
   conv_pack_direct(w, nullptr, Cout, Cin, taps, ck, pw.data());
-  T_TRY(up_T(dw, dtype, pw.data(), pw.size()));
+  RVB_TRY(up_T(dw, dtype, pw.data(), pw.size()));
   if (kind == 2) {
     std::vector<float> pg((size_t)Cout * ((size_t)taps * Cin + (x2 ? Cin2 : 0)));
     if (x2) conv_pack_fused_shortcut(w, nullptr, w2, nullptr, Cout, Cin, Cin2, pg.data());
     else conv_pack_igemm(w, nullptr, Cout, Cin, taps, (size_t)taps * Cin, pg.data());
-    T_TRY(up_T(dwg, DT_BF16, pg.data(), pg.size()));
+    RVB_TRY(up_T(dwg, DT_BF16, pg.data(), pg.size()));
   }
-  T_TRY(up_raw(db, bias, (size_t)Cout * 4));
+  RVB_TRY(up_raw(db, bias, (size_t)Cout * 4));
   const size_t no = (size_t)B * (Fo + 2) * (To + 2) * Cout * dt_size(dtype);
-  T_TRY(dout.alloc(no + kSlack));
+  RVB_TRY(dout.alloc(no + kSlack));
   RVB_HIP_CHECK(hipMemset(dout.p, 0, no + kSlack));
   a.in = dx.p; a.w = dw.p; a.bias = (const float*)db.p; a.res = dr.p; a.out = dout.p; a.w_ig = kind == 2 ? dwg.p : nullptr;
   a.in2 = dx2.p;
   ran[0] = kind;
   ran[1] = kind == 1 ? conv2d_direct_nt(a) : kind == 2 ? (conv_igemm_wide(a) ? 512 : 256) : kind == 4 ? conv_stream_split(a) : 0;
-  if (path == 0) T_TRY(conv2d(nullptr, dtype, a));
-  else if (kind == 1) T_TRY(conv2d_direct(nullptr, dtype, a));
-  else if (kind == 2) T_TRY(conv_igemm(nullptr, a));
-  else if (kind == 3) T_TRY(conv_row64(nullptr, a));
-  else T_TRY(conv_stream(nullptr, a));
+  if (path == 0) RVB_TRY(conv2d(nullptr, dtype, a));
+  else if (kind == 1) RVB_TRY(conv2d_direct(nullptr, dtype, a));
+  else if (kind == 2) RVB_TRY(conv_igemm(nullptr, a));
+  else if (kind == 3) RVB_TRY(conv_row64(nullptr, a));
+  else RVB_TRY(conv_stream(nullptr, a));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   return down_bordered(dout, dtype, out, B, Fo, To, Cout, kSlack, "rvb_test_conv2d");
 }
@@ -1616,18 +1644,18 @@ extern "C" int rvb_test_emb_stem(int dtype, const float* fb, int64_t n_rows, con
             (int64_t)(n_windows - 1) * frames_per_step + nfr <= n_rows && (int64_t)B * (F + 2) * (nfr + 2) * C < ((int64_t)1 << 31);
   for (int b = 0; ok && b < B; ++b) ok = win[b] >= 0 && win[b] < n_windows && win[b] * frames_per_step + nfr <= n_rows;
   if (!ok) { set_error("rvb_test_emb_stem: bad argument"); return E_ARG; }
-  T_TRY(need_gpu());
+  RVB_TRY(need_gpu());
   Dev dfb, dwin, dmean, dw, db, dout;
-  T_TRY(up_raw(dfb, fb, (size_t)n_rows * 80 * 4));
-  T_TRY(up_raw(dwin, win, (size_t)B * 8));
-  T_TRY(dmean.alloc((size_t)n_windows * 80 * 4));
-  T_TRY(up_raw(dw, w, (size_t)C * 9 * 4));
-  T_TRY(up_raw(db, bias, (size_t)C * 4));
+  RVB_TRY(up_raw(dfb, fb, (size_t)n_rows * 80 * 4));
+  RVB_TRY(up_raw(dwin, win, (size_t)B * 8));
+  RVB_TRY(dmean.alloc((size_t)n_windows * 80 * 4));
+  RVB_TRY(up_raw(dw, w, (size_t)C * 9 * 4));
+  RVB_TRY(up_raw(db, bias, (size_t)C * 4));
   const size_t no = (size_t)B * (F + 2) * (nfr + 2) * C * dt_size(dtype);
-  T_TRY(dout.alloc(no + kSlack));
+  RVB_TRY(dout.alloc(no + kSlack));
   RVB_HIP_CHECK(hipMemset(dout.p, 0, no + kSlack));
-  T_TRY(emb_window_mean(nullptr, (const float*)dfb.p, nullptr, n_windows, frames_per_step, nfr, (float*)dmean.p));
-  T_TRY(emb_conv1(nullptr, dtype, (const float*)dfb.p, (const int64_t*)dwin.p, (const float*)dmean.p, (const float*)dw.p, (const float*)db.p,
+  RVB_TRY(emb_window_mean(nullptr, (const float*)dfb.p, nullptr, n_windows, frames_per_step, nfr, (float*)dmean.p));
+  RVB_TRY(emb_conv1(nullptr, dtype, (const float*)dfb.p, (const int64_t*)dwin.p, (const float*)dmean.p, (const float*)dw.p, (const float*)db.p,
                   dout.p, B, F, nfr, frames_per_step, C));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   RVB_HIP_CHECK(hipMemcpy(mean, dmean.p, (size_t)n_windows * 80 * 4, hipMemcpyDeviceToHost));

@@ -409,6 +409,27 @@ class Engine:
             res.append(r)
         return res
 
+    def _chunk_spans(self, n, chunk_ranges, default, mismatch=None):
+        """The chunks behind the n sequences of an align / score / find call: chunk_ranges[i] = (first, count), None -> default.
+        -> (lens, first, count, frames): the batch's valid encoder frames per chunk, and per sequence its first chunk, its chunk
+        count and its frames (0 for a range outside the batch, which the library refuses by name).  mismatch: the RvbError text
+        when there is not one range per sequence, or no sequence at all."""
+        if chunk_ranges is None:
+            chunk_ranges = default
+        if mismatch is not None and (len(chunk_ranges) != n or not n):
+            raise RvbError(mismatch)
+        lens = self.encoder_lens()
+        first = np.array([r[0] for r in chunk_ranges], np.int32)
+        count = np.array([r[1] for r in chunk_ranges], np.int32)
+        frames = [int(lens[f:f + c].sum()) if 0 <= f and c >= 1 and f + c <= self.batch else 0 for f, c in zip(first, count)]
+        return lens, first, count, frames
+
+    @staticmethod
+    def _pack_tokens(seqs):
+        """int32 id sequences -> (their ids concatenated, one zero if there is none; their lengths), as the C ABI takes them."""
+        tok = np.ascontiguousarray(np.concatenate(seqs) if sum(map(len, seqs)) else np.zeros(1, np.int32), np.int32)
+        return tok, np.array([len(t) for t in seqs], np.int32)
+
     def align(self, token_seqs, chunk_ranges=None):
         """Forced alignment (rvb_ctc_align; reference: force_align, utils/ctc_utils.py:105-161) of known token sequences against the
         chunks of the last encode(): sequence i covers the chunks chunk_ranges[i] = (first, count), default one sequence per chunk
@@ -426,16 +447,9 @@ class Engine:
     def _align(self, token_seqs, chunk_ranges, wildcard_bias):
         from .ctc_align import AlignResult
         seqs = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in token_seqs]
-        if chunk_ranges is None:
-            chunk_ranges = [(i, 1) for i in range(len(seqs))]
-        if len(chunk_ranges) != len(seqs) or not seqs:
-            raise RvbError("align: one chunk range per token sequence, at least one sequence")
-        lens = self.encoder_lens()
-        first = np.array([r[0] for r in chunk_ranges], np.int32)
-        count = np.array([r[1] for r in chunk_ranges], np.int32)
-        tok = np.ascontiguousarray(np.concatenate(seqs) if sum(map(len, seqs)) else np.zeros(1, np.int32), np.int32)
-        tl = np.array([len(t) for t in seqs], np.int32)
-        frames = [int(lens[f:f + c].sum()) if 0 <= f and c >= 1 and f + c <= self.batch else 0 for f, c in zip(first, count)]
+        lens, first, count, frames = self._chunk_spans(len(seqs), chunk_ranges, [(i, 1) for i in range(len(seqs))],
+                                                       "align: one chunk range per token sequence, at least one sequence")
+        tok, tl = self._pack_tokens(seqs)
         labels = np.empty(max(sum(frames), 1), np.int32)
         nt = max(int(tl.sum()), 1)
         begin, end, peak = (np.empty(nt, np.int32) for _ in range(3))
@@ -464,17 +478,11 @@ class Engine:
         from .ctc_align import AlignResult
         from ._lib import u8ptr
         graphs = list(graphs)
-        if chunk_ranges is None:
-            chunk_ranges = [(i, 1) for i in range(len(graphs))]
-        if len(chunk_ranges) != len(graphs) or not graphs:
-            raise RvbError("align_graph: one chunk range per graph, at least one graph")
+        lens, first, count, frames = self._chunk_spans(len(graphs), chunk_ranges, [(i, 1) for i in range(len(graphs))],
+                                                       "align_graph: one chunk range per graph, at least one graph")
         arrs = [g.arrays() for g in graphs]
         tok, off, prd, fin = (np.ascontiguousarray(np.concatenate([a[k] for a in arrs])) for k in range(4))
         nn = np.array([len(g) for g in graphs], np.int32)
-        lens = self.encoder_lens()
-        first = np.array([r[0] for r in chunk_ranges], np.int32)
-        count = np.array([r[1] for r in chunk_ranges], np.int32)
-        frames = [int(lens[f:f + c].sum()) if 0 <= f and c >= 1 and f + c <= self.batch else 0 for f, c in zip(first, count)]
         labels, fnode = (np.empty(max(sum(frames), 1), np.int32) for _ in range(2))
         nt = int(nn.sum())
         path, begin, end, peak = (np.empty(nt, np.int32) for _ in range(4))
@@ -506,16 +514,11 @@ class Engine:
         seqs = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in phrases]
         if not seqs:
             raise RvbError("find: at least one phrase")
-        if chunk_ranges is None:
-            chunk_ranges = [(0, self.batch)]
-        lens = self.encoder_lens()
-        first = np.array([r[0] for r in chunk_ranges], np.int32)
-        count = np.array([r[1] for r in chunk_ranges], np.int32)
-        tok = np.ascontiguousarray(np.concatenate(seqs) if sum(map(len, seqs)) else np.zeros(1, np.int32), np.int32)
-        tl = np.array([len(t) for t in seqs], np.int32)
+        lens, first, count, _ = self._chunk_spans(None, chunk_ranges, [(0, self.batch)])
+        tok, tl = self._pack_tokens(seqs)
         thr = np.array([np.float32(min_score * len(t)) for t in seqs], np.float32)
         thr[np.isnan(thr) & (tl == 0)] = 0.0                 # -inf * 0: the empty phrase is refused below, by its own name
-        n_p, n_s, max_hits = len(seqs), len(chunk_ranges), int(max_hits)
+        n_p, n_s, max_hits = len(seqs), len(first), int(max_hits)
         cap = int(max_candidates) if max_candidates is not None else max(4 * max_hits, 256)
         n_hits = np.zeros(max(n_p * n_s, 1), np.int32)
         start, end = (np.zeros(max(n_p * n_s * max(max_hits, 1), 1), np.int32) for _ in range(2))
@@ -560,16 +563,9 @@ class Engine:
         (left decoder, log p of each target, <eos> last).  lsm_weight, ctc_weight and reverse_weight
         default to the config's model_conf.  The decoder's memory is ONE chunk: a sequence over several chunks is refused."""
         seqs = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in token_seqs]
-        if chunk_ranges is None:
-            chunk_ranges = [(i, 1) for i in range(len(seqs))]
-        if len(chunk_ranges) != len(seqs) or not seqs:
-            raise RvbError("score: one chunk range per token sequence, at least one sequence")
-        lens = self.encoder_lens()
-        first = np.array([r[0] for r in chunk_ranges], np.int32)
-        count = np.array([r[1] for r in chunk_ranges], np.int32)
-        tok = np.ascontiguousarray(np.concatenate(seqs) if sum(map(len, seqs)) else np.zeros(1, np.int32), np.int32)
-        tl = np.array([len(t) for t in seqs], np.int32)
-        frames = [int(lens[f:f + c].sum()) if 0 <= f and c >= 1 and f + c <= self.batch else 0 for f, c in zip(first, count)]
+        _, first, count, frames = self._chunk_spans(len(seqs), chunk_ranges, [(i, 1) for i in range(len(seqs))],
+                                                    "score: one chunk range per token sequence, at least one sequence")
+        tok, tl = self._pack_tokens(seqs)
         nt = max(int(tl.sum()), 1)
         loglik = np.empty(len(seqs), np.float64)
         occ, mean, peak = (np.empty(nt, np.float32) for _ in range(3))
@@ -600,8 +596,7 @@ class Engine:
         if np.any(count != 1):
             raise RvbError("score(attention=True) failed (-5): RVB_E_UNSUPPORTED: a sequence spans several chunks; the attention "
                            "decoder's memory is one chunk (score each chunk's transcript against its own chunk)")
-        tok = np.ascontiguousarray(np.concatenate(seqs) if sum(map(len, seqs)) else np.zeros(1, np.int32), np.int32)
-        tl = np.array([len(t) for t in seqs], np.int32)
+        tok, tl = self._pack_tokens(seqs)
         n, npos = len(seqs), int(tl.sum()) + len(seqs)
         loss_l, loss_r = np.zeros(n, np.float64), np.zeros(n, np.float64)
         ncor, nposn = np.zeros(n, np.int32), np.zeros(n, np.int32)
@@ -627,8 +622,7 @@ class Engine:
         seqs = [np.ascontiguousarray(t, np.int32).reshape(-1) for t in token_seqs]
         if not seqs or len(chunk_of) != len(seqs):
             raise RvbError("attention_score: one chunk per token sequence, at least one sequence")
-        tok = np.ascontiguousarray(np.concatenate(seqs) if sum(map(len, seqs)) else np.zeros(1, np.int32), np.int32)
-        tl = np.array([len(t) for t in seqs], np.int32)
+        tok, tl = self._pack_tokens(seqs)
         ch = np.ascontiguousarray(chunk_of, np.int32)
         n, npos = len(seqs), max(int(np.maximum(tl, 0).sum()) + len(seqs), 1)
         loss_l, loss_r = np.zeros(n, np.float64), np.zeros(n, np.float64)
