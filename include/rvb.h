@@ -288,6 +288,32 @@ int rvb_ctc_align_graph_limits(int32_t* max_nodes, int32_t* max_in_degree, int32
 int rvb_ctc_score(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,
                   const int32_t* n_chunks, double* loglik, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame);
 
+/* rvb_ctc_score for a transcript with ALTERNATIVES and OPTIONAL words: the full-sum score over a token GRAPH, in one pass
+ * (csrc/ctc_graph_score.hip).  Graph, labels, predecessor lists, finals, states and chunk ranges are exactly those of
+ * rvb_ctc_align_graph, with log-sum-exp where that call takes the maximum:
+ *   frame 0:  a(B_start) = lp[0][blank];  a(T_j) = lp[0][tok_j] if -1 is a predecessor of j, else -inf;  a(B_j) = -inf
+ *   frame t:  a(B_start) = a'(B_start) + lp[t][blank];  a(B_j) = lse(a'(B_j), a'(T_j)) + lp[t][blank];
+ *             a(T_j) = lse(a'(T_j), per predecessor p: a'(B_p) (a'(B_start) for -1), and a'(T_p) if tok_p != tok_j) + lp[t][tok_j]
+ *   loglik  = lse over the final nodes f of a_{T-1}(B_f), a_{T-1}(T_f)
+ * so loglik [n_seq] (fp64, normalised as rvb_ctc_score's) = log of the sum over the graph's node paths pi of p_CTC(labels(pi) | frames).
+ * Two node paths that spell the same tokens are two paths and both count: the graph {a|a} scores loglik(a) + log 2.  Nothing is
+ * deduplicated.
+ * Per-node outputs (each nullable, concatenated like node_tokens), from the posteriors gamma_t(T_j) of a backward sweep: occupancy,
+ * mean_frame (-1 where the occupancy is exactly 0), peak_post and peak_frame (first on ties) as rvb_ctc_score defines them per token,
+ * and visit = the probability that the path passes through node j, i.e. the summed posterior of the readings that contain it
+ * (sum over frames of the mass that enters T_j).  With all five null only the forward sweep runs and nothing is stored per frame;
+ * otherwise the forward sweep keeps a(T_j) of every frame, 4 bytes per frame and node (nodes padded to a multiple of 64) of device
+ * memory: RVB_E_NOMEM naming the byte count if they do not fit.
+ * Refusals and caps are those of rvb_ctc_align_graph, in the same words after this call's name, all before any device work and with
+ * every output untouched; in addition RVB_CTC_WILDCARD is refused (RVB_E_ARG, naming sequence and node: the maximum over the
+ * vocabulary is no probability), a graph whose shortest reading needs more frames than there are is refused as infeasible
+ * (RVB_E_ARG), and, only when a per-node output is asked for, a node with more than RVB_CTC_GRAPH_MAX_IN_DEGREE SUCCESSORS
+ * (RVB_E_UNSUPPORTED, naming sequence and node).  A graph that the frames cannot emit with a finite score is refused (RVB_E_ARG) after
+ * the forward sweep. */
+int rvb_ctc_score_graph(rvb_engine* e, const int32_t* node_tokens, const int32_t* n_nodes, const int32_t* pred_off,
+                        const int32_t* preds, const uint8_t* is_final, int n_seq, const int32_t* first_chunk, const int32_t* n_chunks,
+                        double* loglik, float* visit, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame);
+
 /* Phrase search: EVERY occurrence of given short phrases (names, terms) in the audio of the last rvb_encode / rvb_stream_finish, on
  * the device (csrc/ctc_find.hip, one wave per phrase and sequence).  n_phrases phrases, concatenated in `tokens`, tok_lens[p] ids
  * each (1 .. RVB_CTC_FIND_MAX_TOKENS, in [0, vocab), none the blank); n_seq sequences of frames given by first_chunk / n_chunks as
@@ -456,7 +482,7 @@ int rvb_comm_destroy(rvb_engine* e);
 /* Stage timing (HIP events on the engine stream).  level 1: every kernel family is bracketed;
  * names: "fbank","subsample","gemm","attention","rownorm","glu_dwconv","ctc_topk","embed",
  * "lse_gather" (the row kernel after the decoders' output layer: rescoring and rvb_attention_score),"search_host","ctc_align_lp" (rvb_ctc_align: CTC head + log-softmax),"ctc_viterbi" (its
- * forward pass + back-trace),"ctc_forward" / "ctc_backward" (rvb_ctc_score: the two sweeps),"ctc_find" (rvb_ctc_find: the search kernel),"ctc_graph" (rvb_ctc_align_graph:
+ * forward pass + back-trace),"ctc_forward" / "ctc_backward" (rvb_ctc_score: the two sweeps),"ctc_graph_forward" / "ctc_graph_backward" (rvb_ctc_score_graph: the two sweeps),"ctc_find" (rvb_ctc_find: the search kernel),"ctc_graph" (rvb_ctc_align_graph:
  * forward pass + back-trace).  level 2: only the GEMM launches (the dominant kernel; half the
  * events, ~1 % less perturbation of the step).  level 0: off.
  * flops: algorithmic FLOPs launched (gemm/attention only). */

@@ -97,6 +97,8 @@ SIGNATURES = {
                                       _i32p, _i32p, _i32p, _f32p, _f32p]),
     "rvb_ctc_align_graph_limits": (C.c_int, [_i32p, _i32p, _i32p, _i32p]),
     "rvb_ctc_score": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, _i32p, _f64p, _f32p, _f32p, _f32p, _i32p]),
+    "rvb_ctc_score_graph": (C.c_int, [_eng, _i32p, _i32p, _i32p, _i32p, _u8p, C.c_int, _i32p, _i32p, _f64p, _f32p, _f32p, _f32p, _f32p,
+                                      _i32p]),
     "rvb_ctc_find": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _f32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f32p,
                                _i64p]),
     "rvb_ctc_prefix_beam": (C.c_int, [_eng, C.c_int]),
@@ -201,6 +203,8 @@ TEST_SIGNATURES = {
     "rvb_test_ctc_viterbi_graph": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, _f32p, C.c_float, _i32p, _i32p, _i32p, _i32p, _u8p, C.c_int,
                                              C.c_int, _i32p, _i32p, _f32p]),
     "rvb_test_ctc_score": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, _f64p, _f32p, _f32p, _f32p, _i32p]),
+    "rvb_test_ctc_score_graph": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, _u8p, C.c_int, C.c_int, _f64p, _f32p,
+                                           _f32p, _f32p, _f32p, _i32p]),
     "rvb_test_ctc_score_batch": (C.c_int, [_f32p, _i32p, C.c_int, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _f64p, _f32p, _f32p, _f32p,
                                            _i32p]),
     "rvb_test_ctc_find": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, _f32p, _i32p, _i32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_int,

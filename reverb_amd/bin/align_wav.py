@@ -5,7 +5,8 @@ the transcript (the reference's bin/get_loss.py reports its negative as loss_ctc
 attention decoders' loss_att and acc_att and the combined loss.  --wildcard TOKEN marks, in the transcript, audio that nobody
 transcribed: the aligner gives each marker the frames the rest of the transcript does not explain (at least one), and the marker
 shows up in the result as a word / label / token of its own.  --alternatives reads choices and optional words in the transcript,
-`it is {twenty|two zero} [um] goodbye`, and aligns the reading that was spoken.  Praat .lab / TextGrid output (--gen_praat there) is not written."""
+`it is {twenty|two zero} [um] goodbye`, and aligns the reading that was spoken; with --graph_score, `<audio>.score.json` holds the
+full-sum log-likelihood over ALL readings and the probability of every word run of the transcript.  Praat .lab / TextGrid output (--gen_praat there) is not written."""
 from __future__ import annotations
 
 import argparse
@@ -42,12 +43,21 @@ def get_args(argv=None):
                    help="penalty (<= 0, nats per frame) on wildcard frames: the misfit above which a marker is preferred to the transcript")
     p.add_argument("--alternatives", action="store_true",
                    help="the transcript holds choices {a|b c|} and optional words [x]: align the reading that was spoken")
+    p.add_argument("--graph_score", action="store_true",
+                   help="with --alternatives (no --wildcard): also write <audio>.score.json, the full-sum score over all readings and "
+                        "the probability, occupancy and mean_time of every word run")
     p.add_argument("--reverse_weight", type=float, default=None, help="weight of the right-to-left decoder in loss_att (default: the config's)")
     args = p.parse_args(argv)
     if args.wildcard is not None and (args.score or args.posteriors):
         p.error("--wildcard: the full-sum score (--score, --posteriors) is not defined for a transcript with gaps")
     if args.alternatives and (args.score or args.posteriors):
         p.error("--alternatives: the full-sum score (--score, --posteriors) is not defined for a transcript with alternatives")
+    if args.graph_score and not args.alternatives:
+        p.error("--graph_score scores a transcript with alternatives: it needs --alternatives")
+    if args.graph_score and args.wildcard is not None:
+        p.error("--graph_score: the full-sum score is not defined for a transcript with gaps (--wildcard)")
+    if args.graph_score and args.attention:
+        p.error("--graph_score: the attention decoders' loss (--attention) is defined for one token sequence, not for alternatives")
     if not args.wildcard_bias <= 0:
         p.error("--wildcard_bias must be <= 0")
     return args
@@ -77,9 +87,10 @@ def main(argv=None):
     with open(path, "w", encoding="utf-8") as f:
         f.write(out)
     logging.info("wrote %s", path)
-    if args.score:
+    if args.score or args.graph_score:
         sc = reverb.score(args.audio_file, transcript=transcript, verbatimicity=args.verbatimicity, chunk_size=args.chunk_size,
-                          posteriors=args.posteriors, attention=args.attention, reverse_weight=args.reverse_weight)
+                          posteriors=args.posteriors or args.graph_score, attention=args.attention, reverse_weight=args.reverse_weight,
+                          alternatives=args.graph_score)
         path = os.path.join(args.result_dir, Path(args.audio_file).with_suffix(".score.json").name)
         with open(path, "w", encoding="utf-8") as f:
             f.write(json.dumps(sc, ensure_ascii=False, indent=1))

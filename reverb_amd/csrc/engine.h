@@ -145,7 +145,7 @@ struct TrieBatch {
 // whose rows lie in the slab just computed (slabs in row order), finish() back-traces and returns states and scores.
 // With allow_wild, plan() accepts RVB_CTC_WILDCARD as a token (a label of its own: it counts towards the caps and, next to another
 // wildcard, as a repeat); advance() then needs wmax[nrows], the maximum of each row of the slab, and the per-frame bias <= 0.
-// The four drivers below share their slab feed (row checks, frame windows per slab, coverage, descriptor upload): ctc_slabs.h.
+// The five drivers below share their slab feed (row checks, frame windows per slab, coverage, descriptor upload): ctc_slabs.h.
 struct CtcAligner {
   std::vector<VitSeq> seq;
   std::vector<int32_t> h_tokens, h_rows;
@@ -203,6 +203,27 @@ struct CtcScorer {
   void release();
 };
 
+
+// ---- full-sum scoring over a token graph (ctc_graph_score.hip): the host side shared by rvb_ctc_score_graph and the lab hook, as
+// CtcScorer is for chains.  plan() is CtcGraphAligner::plan (same checks, refusals and layout), then refuses wildcards, with
+// posteriors an out-degree above the in-degree cap, and a graph no path of which fits the frames; it computes every state's fewest
+// frames to a final end (the normaliser's live set) and the transposed arcs.  The sweeps are CtcScorer's.
+struct CtcGraphScorer {
+  CtcGraphAligner lat;
+  bool post = false;
+  std::vector<uint32_t> h_rem, h_succs;
+  std::vector<int32_t> h_succ_off;
+  std::vector<uint8_t> h_fin;
+  DevBuf d_rem, d_csum, d_loglik, d_llhat, d_coff, d_arows, d_beta, d_acc, d_succ_off, d_succs, d_fin;
+  int plan(const char* who, const int32_t* node_tokens, const int32_t* n_nodes, const int32_t* pred_off, const int32_t* preds,
+           const uint8_t* is_final, int n_seq, const std::vector<std::vector<int32_t>>& seq_rows, int V, int blank_id, bool posteriors);
+  int begin(hipStream_t s);
+  int advance(hipStream_t s, const float* lp, int ld, int r0, int nrows);
+  int finish_forward(hipStream_t s, double* loglik /* [n_seq] */);
+  int advance_backward(hipStream_t s, const float* lp, int ld, int r0, int nrows);
+  int finish_backward(hipStream_t s, float* visit, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame /* per node, nullable */);
+  void release();
+};
 
 // ---- phrase search (ctc_find.hip): the host side shared by rvb_ctc_find and the lab hook.  plan() validates and lays out the
 // (phrase, sequence) pairs (no device work; E_NOMEM if the candidate buffers cannot fit any device), begin() allocates and uploads
@@ -323,6 +344,7 @@ struct rvb_engine {
   rvb::CtcScorer scorer;           // rvb_ctc_score
   rvb::CtcFinder finder;           // rvb_ctc_find
   rvb::CtcGraphAligner graph_aligner;   // rvb_ctc_align_graph
+  rvb::CtcGraphScorer graph_scorer;     // rvb_ctc_score_graph
   rvb::DevBuf align_lp, align_tv, align_ti, align_row, align_col, align_out;   // fp32 [LOGIT_SLAB][V] log-softmax slab; gather scratch
 
   // ---- RCCL communicator of the C-ABI collectives (comm.hip; optional) ----

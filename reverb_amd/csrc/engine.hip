@@ -2018,6 +2018,7 @@ void rvb_destroy(rvb_engine* e) {
   for (DevBuf* b : bufs) b->release();
   e->aligner.release();
   e->graph_aligner.release();
+  e->graph_scorer.release();
   e->finder.release();
   e->scorer.release();
   for (DevBuf* b : {&e->align_lp, &e->align_tv, &e->align_ti, &e->align_row, &e->align_col, &e->align_out}) b->release();
@@ -2624,6 +2625,43 @@ int rvb_ctc_score(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens,
                       [&](int r0, int rows) { return sc.advance_backward(e->stream, e->align_lp.as<float>(), V, r0, rows); }));
   Scope t(e, "ctc_backward");
   return sc.finish_backward(e->stream, occupancy, mean_frame, peak_post, peak_frame);
+}
+
+// Full-sum score over token graphs (ctc_graph_score.hip): rvb_ctc_score's two sweeps on the lattices of rvb_ctc_align_graph.  Nothing
+// is written before the last step has succeeded: a refusal leaves every output untouched.
+int rvb_ctc_score_graph(rvb_engine* e, const int32_t* node_tokens, const int32_t* n_nodes, const int32_t* pred_off, const int32_t* preds,
+                        const uint8_t* is_final, int n_seq, const int32_t* first_chunk, const int32_t* n_chunks, double* loglik,
+                        float* visit, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame) {
+  const char* who = "rvb_ctc_score_graph";
+  if (!e) { set_error("rvb_ctc_score_graph: null engine"); return E_ARG; }
+  if (!node_tokens || !n_nodes || !pred_off || !preds || !is_final || !first_chunk || !n_chunks || !loglik || n_seq <= 0) {
+    set_error("rvb_ctc_score_graph: null argument or n_seq <= 0");
+    return E_ARG;
+  }
+  const int V = e->cfg.vocab;
+  CtcGraphScorer& sc = e->graph_scorer;
+  const bool post = visit || occupancy || mean_frame || peak_post || peak_frame;
+  std::vector<std::vector<int32_t>> seq_rows;
+  RVB_TRY(align_seq_rows(e, who, first_chunk, n_chunks, n_seq, &seq_rows));
+  RVB_TRY(sc.plan(who, node_tokens, n_nodes, pred_off, preds, is_final, n_seq, seq_rows, V, e->cfg.blank_id, post));
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
+  RVB_TRY(sc.begin(e->stream));
+  RVB_TRY(sweep_slabs(e, slabs, false, "ctc_graph_forward", sc.lat,
+                      [&](int r0, int rows) { return sc.advance(e->stream, e->align_lp.as<float>(), V, r0, rows); }));
+  std::vector<double> ll((size_t)n_seq);
+  {
+    Scope t(e, "ctc_graph_forward");
+    RVB_TRY(sc.finish_forward(e->stream, ll.data()));
+  }
+  if (post) {
+    RVB_TRY(sweep_slabs(e, slabs, true, "ctc_graph_backward", sc.lat,
+                        [&](int r0, int rows) { return sc.advance_backward(e->stream, e->align_lp.as<float>(), V, r0, rows); }));
+    Scope t(e, "ctc_graph_backward");
+    RVB_TRY(sc.finish_backward(e->stream, visit, occupancy, mean_frame, peak_post, peak_frame));
+  }
+  memcpy(loglik, ll.data(), (size_t)n_seq * 8);
+  return OK;
 }
 
 // Phrase search (csrc/ctc_find.hip) over the same slabs: align_slab leaves the log-probs in align_lp and each row's maximum in

@@ -223,6 +223,25 @@ int ctc_graph_forward(hipStream_t s, const GraphSeq* seqs, int n_seq, int max_N,
 int ctc_graph_backtrace(hipStream_t s, const GraphSeq* seqs, int n_seq, const int* arc_off, const unsigned* arcs, const int* finals,
                         const float* alpha, const uint8_t* bp, int* states, float* score);
 
+// ---------------------------------------------------------------- ctc_graph_score.hip
+// CTC full-sum score over a token graph and per-node posteriors: the lattices, caps and slab feed of ctc_graph.hip, the normalised
+// sweeps of ctc_forward_backward.hip.  rem: N + 1 words per lattice (at node_off + index, as arc_off): the fewest frames to a final
+// end from T_j | from B_j << 16 (0xffff: never), the last word B_start's.  The T rows of a lattice start bp_off floats into arows and
+// take bp_stride floats (N padded to 64) per frame.  alpha / beta: the aligner's {T, B} per slot at alpha_off, in fp64.
+int ctc_graph_sum_forward(hipStream_t s, const GraphSeq* seqs, int n_seq, int max_N, const float* lp, int ld, int r0, const int* rows,
+                          const int* node_tok, const int* arc_off, const unsigned* arcs, const unsigned* rem, int blank, double* alpha,
+                          double* csum, float* coff, float* arows);
+// loglik[i] (fp64; -inf: no path) and llhat[i] = its part above the summed offsets, from alpha after the last frame
+int ctc_graph_sum_loglik(hipStream_t s, const GraphSeq* seqs, int n_seq, const int* finals, const double* alpha, const double* csum,
+                         double* loglik, float* llhat);
+// backward: frames [f0, f1) in descending order (f1 == T starts the sweep) over the transposed arcs (succ_off as arc_off; a word is
+// successor | 0x8000 when its label differs, from the lattice's arc_off); per node (index node_off + j) the reductions accumulate
+// across launches.
+int ctc_graph_sum_backward(hipStream_t s, const GraphSeq* seqs, int n_seq, int max_N, const float* lp, int ld, int r0, const int* rows,
+                           const int* node_tok, const int* succ_off, const unsigned* succs, const uint8_t* fin, int blank, double* beta,
+                           const float* coff, const float* arows, const float* llhat, float* occ, float* tsum, float* peak, int* peak_frame,
+                           float* visit);
+
 // ---------------------------------------------------------------- ctc_find.hip
 // CTC phrase search: every occurrence of short phrases (z = [y0, b, y1, ..., y(L-1)], free start and end, emission lp - row maximum)
 // in the log-probs, one WAVE per (phrase, sequence) pair.  Pair ph * n_seq + sq owns 64 floats of h, 64 ints of st, one count and

@@ -173,6 +173,14 @@ int rvb_test_ctc_score(const float* lp, int T, int V, const int32_t* tokens, int
 int rvb_test_ctc_score_batch(const float* lp, const int32_t* T, int V, const int32_t* tokens, const int32_t* L, int n_seq, int blank,
                              int slab_rows, double* loglik_out, float* occupancy, float* mean_frame, float* peak_post,
                              int32_t* peak_frame);
+/* ctc_graph_score.hip: full-sum score of n_seq token graphs (arguments as rvb_ctc_score_graph) over host log-probs with the kernels
+ * and the driver rvb_ctc_score_graph runs: lp is the lattices' frames concatenated ([sum T][V]), slab_rows frames per launch in both
+ * sweeps.  loglik_out [n_seq] is fp64; the five per-node outputs are nullable and concatenated like node_tokens, and with all five
+ * null only the forward sweep runs.  Refuses what rvb_ctc_score_graph refuses, in the same words, before any device work; outputs
+ * untouched. */
+int rvb_test_ctc_score_graph(const float* lp, const int32_t* T, int n_seq, int V, const int32_t* node_tokens, const int32_t* n_nodes,
+                             const int32_t* pred_off, const int32_t* preds, const uint8_t* is_final, int blank, int slab_rows,
+                             double* loglik_out, float* visit, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame);
 /* ctc_find.hip: phrase search over host log-probs with exactly the kernel and the host code rvb_ctc_find runs.  lp holds the frames
  * of n_seq sequences concatenated ([sum T][V]; T[i] >= 0), w [sum T] each row's maximum (null: computed on the host from lp);
  * n_phrases phrases concatenated in `tokens`; threshold [n_phrases]; slab_rows rows per launch (h, st and the counts carried in HBM).

@@ -696,6 +696,37 @@ int rvb_test_ctc_score_batch(const float* lp, const int32_t* T, int V, const int
                        peak_post, peak_frame);
 }
 
+int rvb_test_ctc_score_graph(const float* lp, const int32_t* T, int n_seq, int V, const int32_t* node_tokens, const int32_t* n_nodes,
+                             const int32_t* pred_off, const int32_t* preds, const uint8_t* is_final, int blank, int slab_rows,
+                             double* loglik_out, float* visit, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame) {
+  const char* who = "rvb_test_ctc_score_graph";
+  const std::string w(who);
+  if (!lp || !T || !node_tokens || !n_nodes || !pred_off || !preds || !is_final || !loglik_out) { set_error(w + ": null argument"); return E_ARG; }
+  if (n_seq < 1 || slab_rows < 1) { set_error(w + ": need n_seq >= 1 and slab_rows >= 1"); return E_ARG; }
+  for (int i = 0; i < n_seq; ++i)
+    if (T[i] < 1) { set_error(w + ": sequence " + std::to_string(i) + ": need T >= 1"); return E_ARG; }
+  CtcGraphScorer sc;
+  std::vector<std::vector<int32_t>> rows;
+  const int64_t M = lab_rows(T, n_seq, &rows);
+  const bool post = visit || occupancy || mean_frame || peak_post || peak_frame;
+  RVB_TRY(sc.plan(who, node_tokens, n_nodes, pred_off, preds, is_final, n_seq, rows, V, blank, post));
+  RVB_TRY(need_gpu());
+  Dev dlp;
+  std::vector<double> ll((size_t)n_seq);
+  int r = up_raw(dlp, lp, (size_t)M * V * 4);
+  if (r == OK) r = sc.begin(nullptr);
+  r = feed_slabs(r, M, slab_rows, false, [&](int r0, int n) { return sc.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, n); });
+  if (r == OK) r = sc.finish_forward(nullptr, ll.data());
+  if (r == OK && post) {
+    r = feed_slabs(r, M, slab_rows, true, [&](int r0, int n) { return sc.advance_backward(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, n); });
+    if (r == OK) r = sc.finish_backward(nullptr, visit, occupancy, mean_frame, peak_post, peak_frame);
+  }
+  if (r == OK) memcpy(loglik_out, ll.data(), (size_t)n_seq * 8);
+  if (r != OK) (void)hipDeviceSynchronize();
+  sc.release();
+  return r;
+}
+
 int rvb_test_ctc_find(const float* lp, const int32_t* T, int n_seq, int V, const float* w, const int32_t* tokens, const int32_t* tok_lens,
                       int n_phrases, const float* threshold, int blank, int slab_rows, int max_candidates, int max_hits,
                       int64_t* raw_count, int32_t* raw_end, int32_t* raw_start, float* raw_score, int32_t* n_hits, int32_t* hit_start,

@@ -587,6 +587,40 @@ class Engine:
             self._attention_score(seqs, first, count, out, reverse_weight, lsm_weight, ctc_weight)
         return out
 
+    def score_graph(self, graphs, chunk_ranges=None, posteriors=False):
+        """score() for transcripts with alternatives and optional words (rvb_ctc_score_graph, csrc/ctc_graph_score.hip): each sequence
+        is a token_graph.TokenGraph without wildcards, graphs and chunk_ranges as in align_graph().  loglik is the log of the SUM
+        over the graph's node paths of the CTC likelihood of the path's labels; two paths that spell the same tokens are two paths
+        and both count ({a|a} scores loglik(a) + log 2), nothing is deduplicated.  -> List[dict]: loglik (fp64), n_nodes, n_frames
+        and, with posteriors=True, per node visit (the probability that the path passes through the node = the posterior of the
+        readings that contain it), occupancy, mean_frame (-1 where no mass), peak_posterior, peak_frame.  On TokenGraph.chain(ids)
+        loglik and the per-node outputs are those of score(ids) within rounding, and every visit is 1."""
+        from ._lib import u8ptr
+        graphs = list(graphs)
+        _, first, count, frames = self._chunk_spans(len(graphs), chunk_ranges, [(i, 1) for i in range(len(graphs))],
+                                                    "score_graph: one chunk range per graph, at least one graph")
+        arrs = [g.arrays() for g in graphs]
+        tok, off, prd, fin = (np.ascontiguousarray(np.concatenate([a[k] for a in arrs])) for k in range(4))
+        nn = np.array([len(g) for g in graphs], np.int32)
+        nt = max(int(nn.sum()), 1)
+        loglik = np.empty(len(graphs), np.float64)
+        vis, occ, mean, peak = (np.empty(nt, np.float32) for _ in range(4))
+        pkf = np.empty(nt, np.int32)
+        none_f, none_i = C.POINTER(C.c_float)(), C.POINTER(C.c_int32)()
+        check(self.lib.rvb_ctc_score_graph(self.handle, iptr(tok), iptr(nn), iptr(off), iptr(prd), u8ptr(fin), len(graphs), iptr(first),
+                                           iptr(count), dptr(loglik), *[fptr(a) if posteriors else none_f for a in (vis, occ, mean, peak)],
+                                           iptr(pkf) if posteriors else none_i), "rvb_ctc_score_graph")
+        out, t0 = [], 0
+        for i, g in enumerate(graphs):
+            n = len(g)
+            r = {"loglik": float(loglik[i]), "n_nodes": n, "n_frames": frames[i]}
+            if posteriors:
+                r.update(visit=vis[t0:t0 + n].tolist(), occupancy=occ[t0:t0 + n].tolist(), mean_frame=mean[t0:t0 + n].tolist(),
+                         peak_posterior=peak[t0:t0 + n].tolist(), peak_frame=pkf[t0:t0 + n].tolist())
+            out.append(r)
+            t0 += n
+        return out
+
     def _attention_score(self, seqs, first, count, out, reverse_weight, lsm_weight, ctc_weight):
         """rvb_attention_score of the sequences of score(); fills the attention keys into the dicts of `out`."""
         mc = self.configs.get("model_conf", {})

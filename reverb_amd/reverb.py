@@ -291,9 +291,11 @@ class ReverbASR:
         alternatives=True: `transcript` holds choices and optional words in the syntax of token_graph.parse_alternatives --
         "it is {twenty|two zero} [um] [<star>] goodbye" -- and ONE pass over the graph of all readings (Engine.align_graph) picks the
         reading that was spoken and aligns it.  [<star>] (with wildcard="<star>") is a gap marker that may be empty.  Every format
-        shows the chosen reading; json adds "text" (that reading) and "node" (the graph node) per token.  tokens= and posteriors=True
-        are refused: a graph is written as text, and the full-sum score has no graphs."""
-        from .ctc_align import DecodeLike, align_to_ali, align_to_json, posteriors_to_json, split_by_chunk, split_transcript
+        shows the chosen reading; json adds "text" (that reading) and "node" (the graph node) per token.  tokens= is refused: a
+        graph is written as text.  With posteriors=True (json, no wildcard in the text: the full-sum score has none) each token of the
+        chosen path also carries its node's probability (Engine.score_graph's visit: the posterior of the readings through that
+        node), occupancy, mean_time and peak_posterior of the full sum over ALL readings."""
+        from .ctc_align import WILDCARD, DecodeLike, align_to_ali, align_to_json, posteriors_to_json, split_by_chunk, split_transcript
         if (transcript is None) == (tokens is None):
             raise ValueError("align: give exactly one of transcript= (text) or tokens= (ids)")
         if format not in ("ctm", "txt", "ali", "json"):
@@ -306,9 +308,11 @@ class ReverbASR:
         graph = None
         if alternatives:
             from .token_graph import parse_alternatives
-            if tokens is not None or posteriors:
-                raise ValueError("align: alternatives=True takes transcript= (text) and has no posteriors")
+            if tokens is not None:
+                raise ValueError("align: alternatives=True takes transcript= (text)")
             graph = parse_alternatives(transcript, lambda text: self.tokenizer.tokenize(text)[1], wildcard)
+            if posteriors and WILDCARD in graph.tokens:
+                raise ValueError("align: alternatives=True with a wildcard has no posteriors: the full-sum score has no wildcards")
             tokens = []                                       # nothing to tokenise below
         elif wildcard is not None:
             if posteriors:
@@ -329,7 +333,13 @@ class ReverbASR:
             out = align_to_json(res, self.tokenizer, chunk_size, self.input_frame_length, self.output_frame_length, wildcard)
             if graph is not None:
                 out["text"] = graph.text_of(res.nodes)
-            if posteriors:
+            if posteriors and graph is not None:
+                sg = eng.score_graph([graph], [(0, n_chunks)], posteriors=True)[0]
+                on_path = {key: [sg[key][j] for j in res.nodes] for key in ("visit", "occupancy", "mean_frame", "peak_posterior")}
+                for tok, extra, p in zip(out["tokens"], posteriors_to_json(res, on_path, chunk_size, self.input_frame_length,
+                                                                           self.output_frame_length), on_path["visit"]):
+                    tok.update(extra, probability=float(p))
+            elif posteriors:
                 post = eng.score([ids], [(0, n_chunks)], posteriors=True)[0]
                 for tok, extra in zip(out["tokens"], posteriors_to_json(res, post, chunk_size, self.input_frame_length,
                                                                         self.output_frame_length)):
@@ -357,7 +367,7 @@ class ReverbASR:
         return eng, ids, n_chunks
 
     def score(self, audio_file, transcript: Optional[str] = None, tokens=None, verbatimicity: float = 1.0, chunk_size: int = 2051,
-              posteriors: bool = False, attention: bool = False, reverse_weight: Optional[float] = None):
+              posteriors: bool = False, attention: bool = False, reverse_weight: Optional[float] = None, alternatives: bool = False):
         """How likely a KNOWN transcript is under the model: the full-sum CTC log-likelihood, the negative of what the reference
         calls loss_ctc (CTC.forward, transformer/ctc.py:65-104; bin/get_loss.py), of the transcript as ONE sequence over the whole
         file, tokenised and encoded exactly as align() does.  -> dict: loglik, n_tokens, n_frames, loglik_per_token, viterbi_score
@@ -367,8 +377,17 @@ class ReverbASR:
         attention=True adds the other half of the reference's bin/get_loss.py: loss_ctc (= -loglik), loss_att and acc_att of the
         attention decoders (ASRModel._calc_att_loss, asr_model.py:248-286; reverse_weight defaults to the config's), loss =
         ctc_weight loss_ctc + (1 - ctc_weight) loss_att and att_logp (left decoder, per target, <eos> last) -- see Engine.score.  The
-        decoder attends to ONE chunk's frames: audio that encodes to more than one chunk raises ValueError."""
+        decoder attends to ONE chunk's frames: audio that encodes to more than one chunk raises ValueError.
+        alternatives=True: `transcript` holds choices and optional words in the syntax of token_graph.parse_alternatives (no wildcard)
+        and ONE pass scores the graph of all readings (Engine.score_graph): loglik is the log of the summed likelihood of the
+        readings -- "how well does this transcript fit, whichever way the numerals were read" -- where two readings that spell the
+        same tokens both count.  -> dict: loglik, n_frames, viterbi_score and text (the best reading, from align(alternatives=True))
+        and, with posteriors=True, words: one entry per node that opens a run of text, with text, node, probability (the posterior of
+        the readings through that node; the branches of a choice, plus the skip of an optional one, sum to 1), occupancy and
+        mean_time (None where the node holds no mass).  tokens= and attention=True are refused."""
         from .ctc_align import posteriors_to_json
+        if alternatives and (tokens is not None or attention):
+            raise ValueError("score: alternatives=True takes transcript= (text) and has no attention loss")
         if (transcript is None) == (tokens is None):
             raise ValueError("score: give exactly one of transcript= (text) or tokens= (ids)")
         fc = self.test_conf["fbank_conf"]
@@ -376,6 +395,20 @@ class ReverbASR:
             raise NotImplementedError("the device fbank is built for 80 bins / 25 ms / 10 ms")
         if chunk_size < 7:
             raise ValueError("chunk_size must be at least 7 frames (Conv2dSubsampling4 needs 7 input frames, subsampling.py:201-226)")
+        if alternatives:
+            from .token_graph import parse_alternatives
+            graph = parse_alternatives(transcript, lambda text: self.tokenizer.tokenize(text)[1], None)
+            eng, _, n_chunks = self._encode_for_align("score", audio_file, transcript, [], verbatimicity, chunk_size)
+            res = eng.align_graph([graph], [(0, n_chunks)])[0]
+            sg = eng.score_graph([graph], [(0, n_chunks)], posteriors=posteriors)[0]
+            out = {"loglik": sg["loglik"], "n_frames": sg["n_frames"], "viterbi_score": float(res.score), "text": graph.text_of(res.nodes)}
+            if posteriors:
+                opens = [j for j in range(len(graph)) if graph.words[j] != ""]
+                picked = {key: [sg[key][j] for j in opens] for key in ("occupancy", "mean_frame", "peak_posterior")}
+                per = posteriors_to_json(res, picked, chunk_size, self.input_frame_length, self.output_frame_length)
+                out["words"] = [{"text": graph.words[j], "node": j, "probability": float(sg["visit"][j]), "occupancy": p["occupancy"],
+                                 "mean_time": p["mean_time"] if p["occupancy"] > 0 else None} for j, p in zip(opens, per)]
+            return out
         eng, ids, n_chunks = self._encode_for_align("score", audio_file, transcript, tokens, verbatimicity, chunk_size)
         res = eng.align([ids], [(0, n_chunks)])[0]
         sc = eng.score([ids], [(0, n_chunks)], posteriors=posteriors)[0]

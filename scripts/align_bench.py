@@ -2,10 +2,14 @@
 ONE lattice over all chunks.  Prints one JSON line: wall time of Engine.align per repetition (host clock around a call that ends in a
 device synchronise) and the "ctc_align_lp" / "ctc_viterbi" device times of rvb_get_timing (HIP events; a profiled run of its own).
 
-    python scripts/align_bench.py [--model r640] [--dtype bf16] [--seconds 3600] [--reps 5] [--warmup 2] [--score [--attention]] [--graph]
+    python scripts/align_bench.py [--model r640] [--dtype bf16] [--seconds 3600] [--reps 5] [--warmup 2] [--score [--attention]] [--graph] [--graph_score]
 
 --graph also times Engine.align_graph on the same transcript as a chain graph (csrc/ctc_graph.hip against csrc/ctc_viterbi.hip on the
 same log-probs; the "ctc_graph" device time).  A graph holds at most 8192 nodes: choose --seconds so that the tokens fit.
+
+--graph_score times Engine.score_graph on the same transcript as a chain graph (csrc/ctc_graph_score.hip against
+csrc/ctc_forward_backward.hip on the same log-probs): the "ctc_graph_forward" / "ctc_graph_backward" device times beside
+"ctc_forward" / "ctc_backward" of Engine.score, both with posteriors.  The same cap of 8192 nodes holds.
 
 --score --attention also times Engine.attention_score: every chunk's own greedy tokens against that chunk, all chunks in one call,
 both decoders (reverse_weight 0.3): the wall time per call and the "lse_gather" device time, which is the row_xent kernel there.
@@ -30,6 +34,8 @@ def main():
     p.add_argument("--warmup", type=int, default=2)
     p.add_argument("--score", action="store_true", help="also time Engine.score of the same lattice: ctc_forward / ctc_backward")
     p.add_argument("--graph", action="store_true", help="also time Engine.align_graph of the transcript as a chain graph: ctc_graph")
+    p.add_argument("--graph_score", action="store_true",
+                   help="also time Engine.score_graph of the transcript as a chain graph against Engine.score: ctc_graph_forward / _backward")
     p.add_argument("--attention", action="store_true", help="with --score: also time Engine.attention_score, one sequence per chunk")
     a = p.parse_args()
     from reverb_amd import synth
@@ -118,6 +124,29 @@ def main():
         extra.update({"align_graph_wall_ms_median": round(float(np.median(gwall)), 2), "ctc_graph_ms": round(gr["ms"] / a.reps, 3),
                       "graph_us_per_frame": round(gr["ms"] / a.reps * 1e3 / T, 3),
                       "graph_equals_chain": gres.labels == res.labels and gres.score == res.score})
+    if a.graph_score:
+        from reverb_amd.token_graph import TokenGraph
+        chain = TokenGraph.chain(tokens)
+        for _ in range(a.warmup):
+            gs = eng.score_graph([chain], [(0, n_chunks)], posteriors=True)[0]
+            cs = eng.score([tokens], [(0, n_chunks)], posteriors=True)[0]
+        eng.set_profiling(False)
+        gswall = []
+        for _ in range(a.reps):
+            t0 = time.perf_counter()
+            eng.score_graph([chain], [(0, n_chunks)])
+            gswall.append((time.perf_counter() - t0) * 1e3)
+        eng.set_profiling(True)
+        eng.reset_timings()
+        for _ in range(a.reps):
+            gs = eng.score_graph([chain], [(0, n_chunks)], posteriors=True)[0]
+            cs = eng.score([tokens], [(0, n_chunks)], posteriors=True)[0]
+        t = {k: eng.timing(k)["ms"] / a.reps for k in ("ctc_graph_forward", "ctc_graph_backward", "ctc_forward", "ctc_backward")}
+        extra.update({"score_graph_forward_wall_ms_median": round(float(np.median(gswall)), 2),
+                      **{k + "_ms": round(v, 3) for k, v in t.items()},
+                      **{k + "_us_per_frame": round(v * 1e3 / T, 3) for k, v in t.items()},
+                      "graph_loglik": gs["loglik"], "chain_loglik": cs["loglik"],
+                      "graph_alpha_rows_bytes": 4 * T * ((len(tokens) + 63) // 64 * 64)})
     print(json.dumps({"model": a.model, "dtype": a.dtype, "frames": T, "tokens": len(tokens), "states": 2 * len(tokens) + 1,
                       "align_wall_ms": [round(w, 2) for w in wall], "align_wall_ms_median": round(float(np.median(wall)), 2),
                       "ctc_align_lp_ms": round(lp["ms"] / a.reps, 3), "ctc_viterbi_ms": round(vit["ms"] / a.reps, 3),
