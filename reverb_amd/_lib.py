@@ -198,6 +198,9 @@ TEST_SIGNATURES = {
     "rvb_test_attention_pos_bias": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_float, _f32p]),
     "rvb_test_logsoftmax_topk": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _f32p, _i32p, _f32p]),
     "rvb_test_lse_gather": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, _f32p]),
+    "rvb_test_logsoftmax_topk_ex": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _f32p, _i32p, _f32p]),
+    "rvb_test_lse_gather_ex": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, _i32p, C.c_float, C.c_int, _f32p]),
+    "rvb_test_lse_gather_multi_ex": (C.c_int, [_f32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _f32p]),
     "rvb_test_ctc_viterbi": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _f32p]),
     "rvb_test_ctc_viterbi_wild": (C.c_int, [_f32p, C.c_int, C.c_int, _f32p, C.c_float, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _f32p]),
     "rvb_test_ctc_viterbi_graph": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, _f32p, C.c_float, _i32p, _i32p, _i32p, _i32p, _u8p, C.c_int,
@@ -227,6 +230,7 @@ TEST_SIGNATURES = {
     "rvb_test_build_trie": (C.c_int, [_i32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
                                       _i32p, _i32p, _i32p, _i32p, _i32p]),
     "rvb_test_fbank": (C.c_int, [_i16p, C.c_int64, _f32p]),
+    "rvb_test_fbank_ex": (C.c_int, [_i16p, _f32p, C.c_int64, _f32p]),
     "rvb_test_set_gemm_variant": (C.c_int, [C.c_int]),
     "rvb_test_set_gemm2_opts": (C.c_int, [C.c_int, C.c_int]),
     "rvb_test_gemm_timeline": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_longlong), C.c_int, _i32p]),

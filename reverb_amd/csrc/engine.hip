@@ -3098,23 +3098,36 @@ extern "C" int rvb_test_host_pool(int n_threads, int items, int rounds) {
   return OK;
 }
 
-extern "C" int rvb_test_fbank(const int16_t* pcm, int64_t n_samples, float* feats) {
+extern "C" int rvb_test_fbank_ex(const int16_t* pcm, const float* wave, int64_t n_samples, float* feats) {
+  if ((pcm == nullptr) == (wave == nullptr) || !feats || n_samples < 0) { set_error("rvb_test_fbank_ex: one of pcm / wave, feats and n_samples >= 0 are needed"); return E_ARG; }
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: librvb has no CPU fallback"); return E_HIP; }
-  if (!pcm || !feats) { set_error("rvb_test_fbank: null argument"); return E_ARG; }
   rvb_engine e;   // default stream, only the fbank tables are used
   RVB_TRY(make_fbank_tables(&e));
   const int64_t nf = rvb_num_frames(n_samples);
-  DevBuf dp, df;
-  RVB_TRY(dp.ensure((size_t)n_samples * 2 + 16));
-  RVB_TRY(df.ensure((size_t)std::max<int64_t>(nf, 1) * 80 * 4));
-  RVB_HIP_CHECK(hipMemcpy(dp.p, pcm, (size_t)n_samples * 2, hipMemcpyHostToDevice));
+  const size_t in_bytes = (size_t)n_samples * (pcm ? 2 : 4), out_bytes = (size_t)(nf + 4) * 80 * 4;
+  void* din = nullptr;     // not a DevBuf: exactly the waveform's bytes, so that a read past its end is a read past the allocation
+  DevBuf df;
+  int r = df.ensure(out_bytes);
+  if (r == OK && in_bytes && hipMalloc(&din, in_bytes) != hipSuccess) { set_error("rvb_test_fbank_ex: hipMalloc failed"); r = E_NOMEM; }
+  if (r == OK && in_bytes && hipMemcpy(din, pcm ? (const void*)pcm : (const void*)wave, in_bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("rvb_test_fbank_ex: upload failed"); r = E_HIP; }
+  if (r == OK && hipMemset(df.p, 0xff, out_bytes) != hipSuccess) { set_error("rvb_test_fbank_ex: memset failed"); r = E_HIP; }
   FbankTables t{e.fb_window.as<float>(), e.fb_twiddle.as<float>(), e.fb_melw.as<float>(), e.fb_lo.as<int>(), e.fb_hi.as<int>()};
-  int r = fbank(nullptr, dp.as<int16_t>(), nf, df.as<float>(), t);
+  if (r == OK) r = pcm ? fbank(nullptr, (const int16_t*)din, nf, df.as<float>(), t) : fbank_f32(nullptr, (const float*)din, nf, df.as<float>(), t);
   if (r == OK && hipDeviceSynchronize() != hipSuccess) { set_error("fbank kernel failed"); r = E_HIP; }
-  if (r == OK && nf && hipMemcpy(feats, df.p, (size_t)nf * 80 * 4, hipMemcpyDeviceToHost) != hipSuccess) r = E_HIP;
-  dp.release(); df.release();
+  if (r == OK && hipMemcpy(feats, df.p, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) { set_error("rvb_test_fbank_ex: download failed"); r = E_HIP; }
+  if (din) (void)hipFree(din);
+  df.release();
   for (DevBuf* b : {&e.fb_window, &e.fb_twiddle, &e.fb_melw, &e.fb_lo, &e.fb_hi}) b->release();
   return r;
+}
+
+extern "C" int rvb_test_fbank(const int16_t* pcm, int64_t n_samples, float* feats) {
+  if (!pcm || !feats || n_samples < 0) { set_error("rvb_test_fbank: null argument"); return E_ARG; }
+  const int64_t nf = rvb_num_frames(n_samples);
+  std::vector<float> all((size_t)(nf + 4) * 80);
+  RVB_TRY(rvb_test_fbank_ex(pcm, nullptr, n_samples, all.data()));
+  memcpy(feats, all.data(), (size_t)nf * 80 * 4);
+  return OK;
 }
 #endif   // RVB_TEST_API

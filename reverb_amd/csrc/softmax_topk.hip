@@ -194,6 +194,7 @@ __global__ __launch_bounds__(256) void row_lse_kernel(const float* __restrict__ 
 int logsoftmax_topk(hipStream_t s, const float* logits, int M, int V, int ld, int k, float blank_penalty,
                     int blank_id, float* topk_val, int* topk_idx, float* logp_out) {
   if (M <= 0) return OK;
+  if (V < 1 || ld < V) { set_error("logsoftmax_topk: need 1 <= V <= ld"); return E_ARG; }
   if (k < 1 || k > TOPK_MAX || k > V) { set_error("logsoftmax_topk: beam must be in [1,64] and <= vocab"); return E_ARG; }
   hipLaunchKernelGGL(row_lse_kernel<true>, dim3(cdiv(M, 4)), dim3(256), 0, s, logits, M, V, ld, k, blank_penalty,
                      blank_id, topk_val, topk_idx, logp_out, (const int*)nullptr, (float*)nullptr);
@@ -203,6 +204,7 @@ int logsoftmax_topk(hipStream_t s, const float* logits, int M, int V, int ld, in
 
 int lse_gather(hipStream_t s, const float* logits, int R, int V, int ld, const int* target, float* out, float blank_penalty, int blank_id) {
   if (R <= 0) return OK;
+  if (V < 1 || ld < V) { set_error("lse_gather: need 1 <= V <= ld"); return E_ARG; }
   hipLaunchKernelGGL(row_lse_kernel<false>, dim3(cdiv(R, 4)), dim3(256), 0, s, logits, R, V, ld, 0, blank_penalty, blank_penalty != 0.f ? blank_id : -1,
                      (float*)nullptr, (int*)nullptr, (float*)nullptr, target, out);
   RVB_HIP_CHECK(hipGetLastError());
@@ -213,6 +215,7 @@ int lse_gather(hipStream_t s, const float* logits, int R, int V, int ld, const i
 // out[p] = logits[r][target[p]] - logsumexp(logits[r][:V]) for each of them
 int lse_gather_multi(hipStream_t s, const float* logits, int R, int V, int ld, const int* ptr, const int* target, float* out) {
   if (R <= 0) return OK;
+  if (V < 1 || ld < V) { set_error("lse_gather_multi: need 1 <= V <= ld"); return E_ARG; }
   hipLaunchKernelGGL(row_lse_kernel<false>, dim3(cdiv(R, 4)), dim3(256), 0, s, logits, R, V, ld, -1, 0.f, -1,
                      (float*)nullptr, const_cast<int*>(ptr), (float*)nullptr, target, out);
   RVB_HIP_CHECK(hipGetLastError());

@@ -78,6 +78,18 @@ int rvb_test_attention_pos_bias(const float* p, int p_rows, int p_stride, int p_
 int rvb_test_logsoftmax_topk(const float* logits, int M, int V, int k, float blank_penalty, int blank_id,
                              float* topk_val, int32_t* topk_idx, float* logp);
 int rvb_test_lse_gather(const float* logits, int R, int V, const int32_t* target, float* out);
+/* the three entry points of softmax_topk.hip's row_lse_kernel as the engine calls them: host logits [M][ld] with the pad columns
+ * V .. ld - 1 as the caller filled them (the kernel must not read them), the blank penalty and blank id of kernels.h (lse_gather_multi
+ * has none).  logp [M][V] stays nullable.  The device outputs start as all-ones bytes (NaN / -1), so an element the kernel did not
+ * write comes back as that.  Refused by name before any device work: V < 1, ld < V, a target outside [0, V), a ptr that does not
+ * ascend from 0; what the launcher refuses (k outside [1, 64], k > V) leaves the outputs as the caller filled them.  The three hooks
+ * without a stride are the ld = V, no-penalty calls of these. */
+int rvb_test_logsoftmax_topk_ex(const float* logits, int M, int V, int ld, int k, float blank_penalty, int blank_id,
+                                float* topk_val /* [M][k] */, int32_t* topk_idx /* [M][k] */, float* logp);
+int rvb_test_lse_gather_ex(const float* logits, int R, int V, int ld, const int32_t* target /* [R] */, float blank_penalty, int blank_id,
+                           float* out /* [R] */);
+int rvb_test_lse_gather_multi_ex(const float* logits, int R, int V, int ld, const int32_t* ptr /* [R+1] */, const int32_t* target,
+                                 float* out /* [ptr[R]] */);
 /* fp8 (e4m3) GEMM / LayerNorm-to-fp8 of the RVB_FP8 mode on host floats (operands quantised as the engine does) */
 /* bf16 GEMM with bf16 output and the row-periodic addend of GemmArgs::rowadd (round 6): C[m][n] = A.W^T + bias (+ add[m % add_rows][n - add_col0]
  * for add_col0 <= n < add_col0 + add_cols); add is fp32 on the host, rounded to bf16 on the way up (what the engine's positional keys are) */
@@ -202,6 +214,11 @@ int rvb_test_slab_windows(const char* who, const int32_t* rows, const int32_t* T
                           int descending, int32_t* windows_out, int32_t* any_out, int32_t* touches_out, int32_t* fed_out,
                           int32_t* covered_out);
 int rvb_test_fbank(const int16_t* pcm, int64_t n_samples, float* feats /* [frames,80] */);
+/* fbank (pcm non-null) or fbank_f32 (wave non-null: a float waveform at int16 scale, as the resampler leaves it) with the engine's
+ * tables; exactly one of the two is given.  The device waveform holds exactly n_samples elements.  feats [frames + 4][80]: the device
+ * buffer starts as all-ones bytes and comes back whole, so the four rows after the last frame show whether anything was written
+ * past it (n_samples < 400: no frame, no launch, four sentinel rows). */
+int rvb_test_fbank_ex(const int16_t* pcm, const float* wave, int64_t n_samples, float* feats /* [frames + 4][80] */);
 /* native prefix beam search on host arrays: top-k log-probs/indices [T,beam] of one utterance */
 int rvb_test_prefix_beam(const float* topk_val, const int32_t* topk_idx, int T, int beam, int blank,
                          int32_t* n_hyps, int32_t* tokens /* [beam][T] */, int32_t* lens, int32_t* times,

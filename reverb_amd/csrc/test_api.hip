@@ -578,21 +578,38 @@ int rvb_test_attention_pos_bias(const float* p, int p_rows, int p_stride, int p_
   return OK;
 }
 
-int rvb_test_logsoftmax_topk(const float* logits, int M, int V, int k, float blank_penalty, int blank_id,
-                             float* topk_val, int32_t* topk_idx, float* logp) {
+// the three row_lse_kernel entry points on host logits [M][ld] (test_api.h): outputs start as all-ones bytes on the device
+static int rowlse_args(const char* who, const float* logits, int M, int V, int ld) {
+  const std::string me(who);
+  if (!logits || M < 1) { set_error(me + ": null logits or fewer than one row"); return E_ARG; }
+  if (V < 1) { set_error(me + ": V < 1"); return E_ARG; }
+  if (ld < V) { set_error(me + ": ld < V"); return E_ARG; }
+  return OK;
+}
+
+int rvb_test_logsoftmax_topk_ex(const float* logits, int M, int V, int ld, int k, float blank_penalty, int blank_id,
+                                float* topk_val, int32_t* topk_idx, float* logp) {
+  RVB_TRY(rowlse_args("rvb_test_logsoftmax_topk_ex", logits, M, V, ld));
+  if (!topk_val || !topk_idx) { set_error("rvb_test_logsoftmax_topk_ex: null output"); return E_ARG; }
   RVB_TRY(need_gpu());
   Dev dl, dv, di, dp;
-  RVB_TRY(up_raw(dl, logits, (size_t)M * V * 4));
-  RVB_TRY(dv.alloc((size_t)M * k * 4));
-  RVB_TRY(di.alloc((size_t)M * k * 4));
-  if (logp) RVB_TRY(dp.alloc((size_t)M * V * 4));
-  RVB_TRY(logsoftmax_topk(nullptr, (const float*)dl.p, M, V, V, k, blank_penalty, blank_id, (float*)dv.p, (int*)di.p,
+  const size_t nk = (size_t)M * (size_t)std::max(k, 1) * 4, nlp = (size_t)M * V * 4;    // a k the launcher is going to refuse still gets buffers
+  RVB_TRY(up_raw(dl, logits, (size_t)M * ld * 4));
+  RVB_TRY(dv.alloc(nk)); RVB_HIP_CHECK(hipMemset(dv.p, 0xff, nk));
+  RVB_TRY(di.alloc(nk)); RVB_HIP_CHECK(hipMemset(di.p, 0xff, nk));
+  if (logp) { RVB_TRY(dp.alloc(nlp)); RVB_HIP_CHECK(hipMemset(dp.p, 0xff, nlp)); }
+  RVB_TRY(logsoftmax_topk(nullptr, (const float*)dl.p, M, V, ld, k, blank_penalty, blank_id, (float*)dv.p, (int*)di.p,
                         (float*)dp.p));
   RVB_HIP_CHECK(hipDeviceSynchronize());
-  RVB_HIP_CHECK(hipMemcpy(topk_val, dv.p, (size_t)M * k * 4, hipMemcpyDeviceToHost));
-  RVB_HIP_CHECK(hipMemcpy(topk_idx, di.p, (size_t)M * k * 4, hipMemcpyDeviceToHost));
-  if (logp) RVB_HIP_CHECK(hipMemcpy(logp, dp.p, (size_t)M * V * 4, hipMemcpyDeviceToHost));
+  RVB_HIP_CHECK(hipMemcpy(topk_val, dv.p, nk, hipMemcpyDeviceToHost));
+  RVB_HIP_CHECK(hipMemcpy(topk_idx, di.p, nk, hipMemcpyDeviceToHost));
+  if (logp) RVB_HIP_CHECK(hipMemcpy(logp, dp.p, nlp, hipMemcpyDeviceToHost));
   return OK;
+}
+
+int rvb_test_logsoftmax_topk(const float* logits, int M, int V, int k, float blank_penalty, int blank_id,
+                             float* topk_val, int32_t* topk_idx, float* logp) {
+  return rvb_test_logsoftmax_topk_ex(logits, M, V, V, k, blank_penalty, blank_id, topk_val, topk_idx, logp);
 }
 
 static int ctc_viterbi_lab(const char* who, bool wild, const float* lp, int T, int V, const float* w, float bias, const int32_t* tokens,
@@ -798,29 +815,50 @@ int rvb_test_slab_windows(const char* who, const int32_t* rows, const int32_t* T
   return OK;
 }
 
-int rvb_test_lse_gather(const float* logits, int R, int V, const int32_t* target, float* out) {
+int rvb_test_lse_gather_ex(const float* logits, int R, int V, int ld, const int32_t* target, float blank_penalty, int blank_id,
+                           float* out) {
+  RVB_TRY(rowlse_args("rvb_test_lse_gather_ex", logits, R, V, ld));
+  if (!target || !out) { set_error("rvb_test_lse_gather_ex: null target / out"); return E_ARG; }
+  for (int r = 0; r < R; ++r) if (target[r] < 0 || target[r] >= V) { set_error("rvb_test_lse_gather_ex: target outside [0, V)"); return E_ARG; }
   RVB_TRY(need_gpu());
   Dev dl, dt, dout;
-  RVB_TRY(up_raw(dl, logits, (size_t)R * V * 4));
+  RVB_TRY(up_raw(dl, logits, (size_t)R * ld * 4));
   RVB_TRY(up_raw(dt, target, (size_t)R * 4));
-  RVB_TRY(dout.alloc((size_t)R * 4));
-  RVB_TRY(lse_gather(nullptr, (const float*)dl.p, R, V, V, (const int*)dt.p, (float*)dout.p));
+  RVB_TRY(dout.alloc((size_t)R * 4)); RVB_HIP_CHECK(hipMemset(dout.p, 0xff, (size_t)R * 4));
+  RVB_TRY(lse_gather(nullptr, (const float*)dl.p, R, V, ld, (const int*)dt.p, (float*)dout.p, blank_penalty, blank_id));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   RVB_HIP_CHECK(hipMemcpy(out, dout.p, (size_t)R * 4, hipMemcpyDeviceToHost));
   return OK;
 }
 
-int rvb_test_lse_gather_multi(const float* logits, int R, int V, const int32_t* ptr, const int32_t* target, int P, float* out) {
+int rvb_test_lse_gather(const float* logits, int R, int V, const int32_t* target, float* out) {
+  return rvb_test_lse_gather_ex(logits, R, V, V, target, 0.f, -1, out);
+}
+
+int rvb_test_lse_gather_multi_ex(const float* logits, int R, int V, int ld, const int32_t* ptr, const int32_t* target, float* out) {
+  RVB_TRY(rowlse_args("rvb_test_lse_gather_multi_ex", logits, R, V, ld));
+  if (!ptr) { set_error("rvb_test_lse_gather_multi_ex: null ptr"); return E_ARG; }
+  if (ptr[0] != 0) { set_error("rvb_test_lse_gather_multi_ex: ptr[0] must be 0"); return E_ARG; }
+  for (int r = 0; r < R; ++r) if (ptr[r + 1] < ptr[r]) { set_error("rvb_test_lse_gather_multi_ex: ptr decreases"); return E_ARG; }
+  const int P = ptr[R];
+  if (P > 0 && (!target || !out)) { set_error("rvb_test_lse_gather_multi_ex: targets without target / out arrays"); return E_ARG; }
+  for (int p = 0; p < P; ++p) if (target[p] < 0 || target[p] >= V) { set_error("rvb_test_lse_gather_multi_ex: target outside [0, V)"); return E_ARG; }
   RVB_TRY(need_gpu());
   Dev dl, dp, dt, dout;
-  RVB_TRY(up_raw(dl, logits, (size_t)R * V * 4));
+  const size_t nout = (size_t)(P > 0 ? P : 1) * 4;
+  RVB_TRY(up_raw(dl, logits, (size_t)R * ld * 4));
   RVB_TRY(up_raw(dp, ptr, (size_t)(R + 1) * 4));
-  RVB_TRY(up_raw(dt, target, (size_t)P * 4));
-  RVB_TRY(dout.alloc((size_t)(P > 0 ? P : 1) * 4));
-  RVB_TRY(lse_gather_multi(nullptr, (const float*)dl.p, R, V, V, (const int*)dp.p, (const int*)dt.p, (float*)dout.p));
+  if (P > 0) { RVB_TRY(up_raw(dt, target, (size_t)P * 4)); } else { RVB_TRY(dt.alloc(4)); }
+  RVB_TRY(dout.alloc(nout)); RVB_HIP_CHECK(hipMemset(dout.p, 0xff, nout));
+  RVB_TRY(lse_gather_multi(nullptr, (const float*)dl.p, R, V, ld, (const int*)dp.p, (const int*)dt.p, (float*)dout.p));
   RVB_HIP_CHECK(hipDeviceSynchronize());
   if (P > 0) RVB_HIP_CHECK(hipMemcpy(out, dout.p, (size_t)P * 4, hipMemcpyDeviceToHost));
   return OK;
+}
+
+int rvb_test_lse_gather_multi(const float* logits, int R, int V, const int32_t* ptr, const int32_t* target, int P, float* out) {
+  if (ptr && R >= 1 && ptr[R] != P) { set_error("rvb_test_lse_gather_multi: P is not ptr[R]"); return E_ARG; }
+  return rvb_test_lse_gather_multi_ex(logits, R, V, V, ptr, target, out);
 }
 
 int rvb_test_row_xent(const float* logits, int R, int V, int ld, const int32_t* ptr, const int32_t* target, float* logp, float* lse,

@@ -8,7 +8,8 @@ has more targets than lanes.  Row 1 has its maximum planted at index 0, row 4 at
 (the lower index wins, as torch.argmax on the CPU), row 7 is scaled by 20.
 
 Bounds.  logp: 3e-6 against fp64 log_softmax on the N(0, 2) rows, the bound tests/test_kernels_gpu.py applies to the sibling; and the
-SAME BITS as the sibling where ld = V (the hook of the sibling has no stride).  sum_x: V max|x| 2^-23.  The loss of a pair is
+SAME BITS as the sibling where ld = V (this hook of the sibling has no stride; tests/test_rowlse_kernels_gpu.py holds the two to the
+same bits at (10001, 10004) through the strided one).  sum_x: V max|x| 2^-23.  The loss of a pair is
     kl = const - (c - u) logp_t - u sum_x + u V lse,      c = 1 - smoothing, u = smoothing / (V - 1)
 so its error is at most |c - u| 3e-6 <= 3e-6 from the target term, plus u V 3e-6 = smoothing V / (V - 1) 3e-6 from V lse (lse is held
 to the bound of logp, whose error it is), plus u times the error of sum_x, u V max|x| 2^-23 = smoothing V / (V - 1) max|x| 2^-23 < 1.2e-7
