@@ -5,8 +5,10 @@ Objects are cached under reverb_amd/csrc/_build and rebuilt when a source or hea
 
 Two shared objects come out:
   librvb.so        the PRODUCT: exports include/rvb.h + include/rvd.h and nothing else of the C ABI
-  librvb_test.so   the same objects + csrc/test_api.hip (rvb_test_*: raw kernel / host-search hooks, csrc/test_api.h) and
-                   engine.hip compiled with -DRVB_TEST_API; loaded by tests/ and scripts/ only (reverb_amd._lib.load_test)
+  librvb_test.so   the same objects + csrc/test_api.hip (rvb_test_*: raw kernel / host-search hooks, csrc/test_api.h); loaded by
+                   tests/ and scripts/ only (reverb_amd._lib.load_test)
+Every object of SOURCES is built once and linked into both.  The libraries differ in one function: lab_env(), which reads the tuning
+switches from the environment in test_api.hip and answers nullptr in lab_env_off.cpp (PRODUCT_ONLY).
 """
 import os
 import subprocess
@@ -17,8 +19,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librvb.so")
 OUT_TEST = os.path.join(HERE, "librvb_test.so")
-SOURCES = ["gemm.hip", "gemm2.hip", "attention.hip", "elementwise.hip", "softmax_topk.hip", "ctc_viterbi.hip", "ctc_graph.hip", "ctc_graph_score.hip", "ctc_forward_backward.hip", "ctc_find.hip", "fbank.hip", "engine.hip", "diar.hip", "resnet.hip", "conv_gemm.hip", "conv_stream.hip", "conv_block.hip", "conv_row64.hip", "conv_s2.hip", "linkage.hip", "diar_engine.hip", "comm.hip", "search.cpp", "audio.cpp", "mp3.cpp"]
-TEST_SOURCES = ["test_api.hip", ("engine.hip", "engine_testapi", ["-DRVB_TEST_API"])]      # (source, object stem, extra flags)
+SOURCES = ["gemm.hip", "gemm2.hip", "attention.hip", "elementwise.hip", "softmax_topk.hip", "ctc_viterbi.hip", "ctc_graph.hip", "ctc_graph_score.hip", "ctc_forward_backward.hip", "ctc_find.hip", "fbank.hip", "engine.hip", "engine_weights.hip", "engine_encode.hip", "engine_decode.hip", "engine_ctc.hip", "diar.hip", "resnet.hip", "conv_gemm.hip", "conv_stream.hip", "conv_block.hip", "conv_row64.hip", "conv_s2.hip", "linkage.hip", "diar_engine.hip", "comm.hip", "search.cpp", "audio.cpp", "mp3.cpp"]
+PRODUCT_ONLY = ["lab_env_off.cpp"]
+TEST_SOURCES = ["test_api.hip"]
+LINK = {OUT: SOURCES + PRODUCT_ONLY, OUT_TEST: SOURCES + TEST_SOURCES}      # library -> the sources whose objects it is linked from
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result", "-Wno-unused-value", "-Wno-unused-variable"]
@@ -56,15 +60,14 @@ def _stale(target, deps):
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def _compile(item):
-    src, stem, extra = item if isinstance(item, tuple) else (item, os.path.splitext(item)[0], [])
+def _compile(src):
     bdir = os.path.join(CSRC, "_build")
     os.makedirs(bdir, exist_ok=True)
-    obj = os.path.join(bdir, stem + ".o")
+    obj = os.path.join(bdir, os.path.splitext(src)[0] + ".o")
     path = os.path.join(CSRC, src)
     if _stale(obj, [path] + _headers(path)):
         lang = ["-x", "hip"] if src.endswith(".hip") else []
-        cmd = [HIPCC] + FLAGS + extra + lang + ["-c", path, "-o", obj]
+        cmd = [HIPCC] + FLAGS + lang + ["-c", path, "-o", obj]
         r = subprocess.run(cmd, capture_output=True, text=True)
         if r.returncode != 0:
             raise RuntimeError("hipcc failed for %s:\n%s\n%s" % (src, r.stdout, r.stderr))
@@ -77,11 +80,11 @@ def build(force=False, verbose=True):
     if force:
         for f in os.listdir(os.path.join(CSRC, "_build")) if os.path.isdir(os.path.join(CSRC, "_build")) else []:
             os.remove(os.path.join(CSRC, "_build", f))
-    with ThreadPoolExecutor(max_workers=min(8, len(SOURCES) + len(TEST_SOURCES))) as ex:
-        all_objs = list(ex.map(_compile, SOURCES + TEST_SOURCES))
-    objs, test_objs = all_objs[:len(SOURCES)], all_objs[len(SOURCES):]
-    engine_obj = objs[SOURCES.index("engine.hip")]
-    for out, members in ((OUT, objs), (OUT_TEST, [o for o in objs if o != engine_obj] + test_objs)):
+    every = SOURCES + PRODUCT_ONLY + TEST_SOURCES
+    with ThreadPoolExecutor(max_workers=8) as ex:
+        obj = dict(zip(every, ex.map(_compile, every)))
+    for out, sources in LINK.items():
+        members = [obj[s] for s in sources]
         if _stale(out, members):
             cmd = [HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", out] + members + ["-lpthread", "-ldl"]
             r = subprocess.run(cmd, capture_output=True, text=True)

@@ -190,7 +190,7 @@ namespace rvb {
 void set_error(const std::string& msg);  // thread-local last error (engine.hip)
 const char* last_error();
 // Tuning / diagnosis switches (kernel variants, A/B legs of scripts/, the measured-slower alternatives the tuning log keeps):
-// the PRODUCT library never reads them -- lab_env() returns nullptr there and every switch takes its default.  Only
-// librvb_test.so (engine.hip compiled with -DRVB_TEST_API; reverb_amd._lib: RVB_LAB=1) consults the environment.
+// the PRODUCT library never reads them -- its lab_env() (lab_env_off.cpp) returns nullptr and every switch takes its default.  Only
+// librvb_test.so (the same objects with test_api.hip's lab_env(); reverb_amd._lib: RVB_LAB=1) consults the environment.
 const char* lab_env(const char* name);
 }

@@ -126,7 +126,7 @@ class HostPool {
   bool stop_ = false;
 };
 
-// ---- rescoring: every DISTINCT prefix of a chunk's n-best list is one decoder row (engine.hip, "rescoring")
+// ---- rescoring: every DISTINCT prefix of a chunk's n-best list is one decoder row (trie.h, engine_decode.hip "rescoring")
 struct HypRef { int chunk, idx, len, row0; };      // row0: first of the hypothesis' len+1 (hyp, j) pairs
 
 struct TrieBatch {

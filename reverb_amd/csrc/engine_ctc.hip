@@ -1,0 +1,376 @@
+// librvb engine, CTC lattices: forced alignment (chain, wildcard, graph), full-sum scoring (chain, graph) and phrase search over the
+// log-prob slabs of the encoded batch.
+#include "engine_impl.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+namespace rvb {
+
+// Forced alignment (ctc_utils.py:105-161 / bin/alignment.py:233-242).  The log-probs exist one LOGIT_SLAB of rows at a time, exactly as
+// rvb_encode produces them (run_gemm on the CTC head + logsoftmax_topk with its lp output, no blank penalty); the Viterbi kernel
+// consumes a slab before the next one overwrites it and carries alpha in HBM.  Token confidences need lp[t][label[t]] along the path,
+// which is known only after the back-trace: a second sweep of the slabs gathers those T values.
+static int align_slab(rvb_engine* e, int r0, int rows) {
+  const int d = e->cfg.d_model, V = e->cfg.vocab, Vld = (V + 3) & ~3;
+  Scope sc(e, "ctc_align_lp");
+  RVB_TRY(run_gemm(e, (const char*)e->enc_out.p + (size_t)r0 * d * dt_size(e->dtype), d, e->ctc, e->logits.p, Vld, rows, true));
+  return logsoftmax_topk(e->stream, e->logits.as<float>(), rows, V, Vld, 1, 0.f, e->cfg.blank_id, e->align_tv.as<float>(),
+                         e->align_ti.as<int>(), e->align_lp.as<float>());
+}
+
+// The lattice entry points (rvb_ctc_align, _align_wild, _align_graph, _score, _find) begin alike once their own arguments are checked:
+// align_seq_rows, the driver's plan() (so every refusal comes before any device work), align_workspace, the driver's begin().
+// the log-prob rows of each sequence: the valid encoder frames of its chunks, in order
+static int align_seq_rows(rvb_engine* e, const char* who, const int32_t* first_chunk, const int32_t* n_chunks, int n_seq,
+                          std::vector<std::vector<int32_t>>* seq_rows) {
+  if (e->B <= 0) { set_error(std::string(who) + " before rvb_encode"); return E_STATE; }
+  seq_rows->assign(n_seq, {});
+  for (int i = 0; i < n_seq; ++i) {
+    if (first_chunk[i] < 0 || n_chunks[i] < 1 || (int64_t)first_chunk[i] + n_chunks[i] > e->B) {
+      set_error(std::string(who) + ": sequence " + std::to_string(i) + ": chunk range outside the encoded batch of " + std::to_string(e->B) + " chunks");
+      return E_ARG;
+    }
+    for (int c = first_chunk[i]; c < first_chunk[i] + n_chunks[i]; ++c)
+      for (int t = 0; t < e->enc_lens[c]; ++t) (*seq_rows)[i].push_back(c * e->T2 + t);
+  }
+  return OK;
+}
+// the slabs rvb_encode computed its log-probs in (per slice of the batch, LOGIT_SLAB rows at a time): the same GEMM launches, so
+// the same bits as the top-k the searches saw
+static std::vector<std::pair<int, int>> align_slabs(const rvb_engine* e) {
+  std::vector<std::pair<int, int>> slabs;
+  auto add_range = [&](int row0, int m) { for (int r0 = 0; r0 < m; r0 += LOGIT_SLAB) slabs.push_back({row0 + r0, std::min(LOGIT_SLAB, m - r0)}); };
+  if (e->slices.empty()) add_range(0, e->B * e->T2);
+  for (const auto& sl : e->slices) add_range(sl.c0 * e->T2, sl.nb * e->T2);
+  return slabs;
+}
+// the device side of the beginning: the encoded batch is waited for, the slab buffers exist, *slabs = the slabs to sweep
+static int align_workspace(rvb_engine* e, std::vector<std::pair<int, int>>* slabs) {
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(wait_slices(e, -1));
+  const int V = e->cfg.vocab, Vld = (V + 3) & ~3, slab = std::min(LOGIT_SLAB, e->B * e->T2);
+  RVB_TRY(e->logits.ensure((size_t)LOGIT_SLAB * Vld * 4));
+  RVB_TRY(e->align_lp.ensure((size_t)slab * V * 4));
+  RVB_TRY(e->align_tv.ensure((size_t)slab * 4));
+  RVB_TRY(e->align_ti.ensure((size_t)slab * 4));
+  *slabs = align_slabs(e);
+  return OK;
+}
+
+// lp[t][label[t]] of every frame of every lattice (seq: frame_off and T into rows / lab): the slabs once more, one gather_pairs per
+// slab.  A wildcard frame's emission is the row maximum, what it emitted less the bias.
+template <typename Seq>
+static int align_emissions(rvb_engine* e, const std::vector<std::pair<int, int>>& slabs, const std::vector<Seq>& seq,
+                           const std::vector<int32_t>& h_rows, const std::vector<int32_t>& lab, bool has_wild, std::vector<float>* emit_out) {
+  const int V = e->cfg.vocab, blank = e->cfg.blank_id;
+  std::vector<float>& emit = *emit_out;
+  emit.resize(lab.size());
+  std::vector<int32_t> grow, gcol, gidx;
+  std::vector<float> gout, wrow;
+  for (const auto& [r0, rows] : slabs) {
+    grow.clear(); gcol.clear(); gidx.clear();
+    for (const Seq& q : seq) {
+      const int frame_off = q.frame_off, T = q.T;
+      const int32_t* rw = h_rows.data() + frame_off;
+      for (int f = (int)(std::lower_bound(rw, rw + T, r0) - rw); f < T && rw[f] < r0 + rows; ++f) {
+        const int32_t l = lab[frame_off + f];
+        grow.push_back(rw[f] - r0); gcol.push_back(l == RVB_CTC_WILDCARD ? blank : l); gidx.push_back(frame_off + f);
+      }
+    }
+    if (grow.empty()) continue;
+    RVB_TRY(align_slab(e, r0, rows));
+    RVB_TRY(upload_i32(e, e->align_row, grow.data(), grow.size()));
+    RVB_TRY(upload_i32(e, e->align_col, gcol.data(), gcol.size()));
+    RVB_TRY(e->align_out.ensure(grow.size() * 4));
+    RVB_TRY(gather_pairs(e->stream, e->align_lp.as<float>(), (size_t)V, e->align_row.as<int>(), e->align_col.as<int>(), (int)grow.size(),
+                         e->align_out.as<float>()));
+    gout.resize(grow.size());
+    RVB_HIP_CHECK(hipMemcpyAsync(gout.data(), e->align_out.p, grow.size() * 4, hipMemcpyDeviceToHost, e->stream));
+    if (has_wild) {
+      wrow.resize(rows);
+      RVB_HIP_CHECK(hipMemcpyAsync(wrow.data(), e->align_tv.p, (size_t)rows * 4, hipMemcpyDeviceToHost, e->stream));
+    }
+    RVB_HIP_CHECK(hipStreamSynchronize(e->stream));     // also: grow / gcol may be rewritten
+    for (size_t k = 0; k < gidx.size(); ++k) emit[gidx[k]] = lab[gidx[k]] == RVB_CTC_WILDCARD ? wrow[grow[k]] : gout[k];
+  }
+  return OK;
+}
+
+// One sweep over the slabs, in row order or backwards.  A slab that holds a frame of the driver's sequences is computed (align_slab:
+// one GEMM, one log-softmax) and handed to advance(r0, rows) under the profile name `name`; a slab that holds none costs nothing.
+template <typename Driver, typename Advance>
+static int sweep_slabs(rvb_engine* e, const std::vector<std::pair<int, int>>& slabs, bool descending, const char* name, const Driver& d,
+                       Advance advance) {
+  for (size_t i = 0; i < slabs.size(); ++i) {
+    const auto& [r0, rows] = slabs[descending ? slabs.size() - 1 - i : i];
+    if (!d.touches(r0, rows)) continue;
+    RVB_TRY(align_slab(e, r0, rows));
+    Scope sc(e, name);
+    RVB_TRY(advance(r0, rows));
+  }
+  return OK;
+}
+
+// The forward sweep and the back-trace of either aligner (align_tv: the row maxima a wildcard emits): the state of every frame and
+// the score of every lattice.
+template <typename Aligner>
+static int align_sweep(rvb_engine* e, const std::vector<std::pair<int, int>>& slabs, const char* name, Aligner& al, float bias,
+                       std::vector<int32_t>* states, std::vector<float>* score) {
+  RVB_TRY(sweep_slabs(e, slabs, false, name, al, [&](int r0, int rows) {
+    return al.advance(e->stream, e->align_lp.as<float>(), e->cfg.vocab, r0, rows, e->align_tv.as<float>(), bias);
+  }));
+  states->resize((size_t)al.total_frames);
+  score->resize(al.seq.size());
+  Scope sc(e, name);
+  return al.finish(e->stream, states->data(), score->data());
+}
+
+// The runs of equal values in id[frame_off .. frame_off + T): the state, or the node, of each frame of one lattice's best path.
+// slot(value) says where the outputs of a run go (< 0: a blank's run, which has none).  A run yields its first and last frame and,
+// from emit (lp[t][label[t]]; filled when peak or confidence is asked for), the frame of its largest emission and that probability.
+template <typename Slot>
+static void run_outputs(const std::vector<int32_t>& id, const std::vector<float>& emit, int frame_off, int T, Slot slot, int32_t* begin,
+                        int32_t* end, int32_t* peak, float* confidence) {
+  for (int t = 0; t < T;) {
+    const int v = id[frame_off + t];
+    int t1 = t;
+    while (t1 + 1 < T && id[frame_off + t1 + 1] == v) ++t1;
+    const int k = slot(v);
+    if (k >= 0) {
+      if (begin) begin[k] = t;
+      if (end) end[k] = t1;
+      if (peak || confidence) {
+        int pk = t;
+        for (int u = t + 1; u <= t1; ++u) if (emit[frame_off + u] > emit[frame_off + pk]) pk = u;
+        if (peak) peak[k] = pk;
+        if (confidence) confidence[k] = std::exp(emit[frame_off + pk]);
+      }
+    }
+    t = t1 + 1;
+  }
+}
+
+// rvb_ctc_align (wild = false: RVB_CTC_WILDCARD is an id outside the vocabulary) and rvb_ctc_align_wild.  A wildcard emits the row's
+// top-1 log-prob, which align_slab already produces: align_tv[r] = max logit - lse and lp[r][v] = logit[v] - lse are the same fp32
+// subtraction (softmax_topk.hip), so align_tv[r] IS the maximum of the lp row the aligner reads, bit for bit.
+static int ctc_align_impl(const char* who, bool wild, float bias, rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq,
+                          const int32_t* first_chunk, const int32_t* n_chunks, int32_t* labels, int32_t* begin, int32_t* end,
+                          int32_t* peak, float* confidence, float* score) {
+  static_assert(CTC_ALIGN_MAX_TOKENS == RVB_CTC_ALIGN_MAX_TOKENS && CTC_ALIGN_MAX_FRAMES == RVB_CTC_ALIGN_MAX_FRAMES, "caps of rvb.h");
+  const std::string w(who);
+  if (!e) { set_error(w + ": null engine"); return E_ARG; }
+  if (!tokens || !tok_lens || !first_chunk || !n_chunks || n_seq <= 0) { set_error(w + ": null argument or n_seq <= 0"); return E_ARG; }
+  if (wild && !(std::isfinite(bias) && bias <= 0.f)) { set_error(w + ": wildcard_bias must be finite and <= 0"); return E_ARG; }
+  const int V = e->cfg.vocab, blank = e->cfg.blank_id;
+  CtcAligner& al = e->aligner;
+  std::vector<std::vector<int32_t>> seq_rows;
+  RVB_TRY(align_seq_rows(e, who, first_chunk, n_chunks, n_seq, &seq_rows));
+  RVB_TRY(al.plan(who, tokens, tok_lens, n_seq, seq_rows, V, blank, wild));
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
+  RVB_TRY(al.begin(e->stream));
+  std::vector<int32_t> states;
+  std::vector<float> sc_host;
+  RVB_TRY(align_sweep(e, slabs, "ctc_viterbi", al, bias, &states, &sc_host));
+  if (score) memcpy(score, sc_host.data(), (size_t)n_seq * 4);
+  std::vector<int32_t> lab(states.size());
+  for (int i = 0; i < n_seq; ++i) {
+    const VitSeq& q = al.seq[i];
+    for (int t = 0; t < q.T; ++t) {
+      const int st = states[q.frame_off + t];
+      lab[q.frame_off + t] = (st & 1) ? tokens[q.tok_off + (st >> 1)] : blank;   // a wildcard's state: RVB_CTC_WILDCARD
+    }
+  }
+  if (labels) memcpy(labels, lab.data(), lab.size() * 4);
+  if (!begin && !end && !peak && !confidence) return OK;
+  std::vector<float> emit;
+  if (peak || confidence) RVB_TRY(align_emissions(e, slabs, al.seq, al.h_rows, lab, al.has_wild, &emit));
+  for (const VitSeq& q : al.seq)                   // a run is a state; a token state's outputs go to its token
+    run_outputs(states, emit, q.frame_off, q.T, [&](int st) { return (st & 1) ? q.tok_off + (st >> 1) : -1; }, begin, end, peak, confidence);
+  return OK;
+}
+
+}  // namespace rvb
+
+using namespace rvb;
+
+extern "C" {
+
+int rvb_ctc_align_limits(int32_t* max_tokens, int32_t* max_frames) {
+  if (max_tokens) *max_tokens = CTC_ALIGN_MAX_TOKENS;
+  if (max_frames) *max_frames = CTC_ALIGN_MAX_FRAMES;
+  return OK;
+}
+
+int rvb_ctc_align(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,
+                  const int32_t* n_chunks, int32_t* labels, int32_t* begin, int32_t* end, int32_t* peak, float* confidence, float* score) {
+  return ctc_align_impl("rvb_ctc_align", false, 0.f, e, tokens, tok_lens, n_seq, first_chunk, n_chunks, labels, begin, end, peak,
+                        confidence, score);
+}
+int rvb_ctc_align_wild(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,
+                       const int32_t* n_chunks, float wildcard_bias, int32_t* labels, int32_t* begin, int32_t* end, int32_t* peak,
+                       float* confidence, float* score) {
+  return ctc_align_impl("rvb_ctc_align_wild", true, wildcard_bias, e, tokens, tok_lens, n_seq, first_chunk, n_chunks, labels, begin,
+                        end, peak, confidence, score);
+}
+
+// Alignment over token graphs (ctc_graph.hip): the slabs, the wildcard's emission and the second sweep for the confidences are those
+// of ctc_align_impl; what differs is the lattice and that the per-token outputs follow the chosen path.
+int rvb_ctc_align_graph_limits(int32_t* max_nodes, int32_t* max_in_degree, int32_t* max_arcs, int32_t* max_frames) {
+  if (max_nodes) *max_nodes = CTC_GRAPH_MAX_NODES;
+  if (max_in_degree) *max_in_degree = CTC_GRAPH_MAX_IN_DEGREE;
+  if (max_arcs) *max_arcs = CTC_GRAPH_MAX_ARCS;
+  if (max_frames) *max_frames = CTC_ALIGN_MAX_FRAMES;
+  return OK;
+}
+
+int rvb_ctc_align_graph(rvb_engine* e, const int32_t* node_tokens, const int32_t* n_nodes, const int32_t* pred_off, const int32_t* preds,
+                        const uint8_t* is_final, int n_seq, const int32_t* first_chunk, const int32_t* n_chunks, float wildcard_bias,
+                        int32_t* labels, int32_t* frame_node, int32_t* path_len, int32_t* path_nodes, int32_t* begin, int32_t* end,
+                        int32_t* peak, float* confidence, float* score) {
+  static_assert(CTC_GRAPH_MAX_NODES == RVB_CTC_GRAPH_MAX_NODES && CTC_GRAPH_MAX_IN_DEGREE == RVB_CTC_GRAPH_MAX_IN_DEGREE &&
+                CTC_GRAPH_MAX_ARCS == RVB_CTC_GRAPH_MAX_ARCS, "caps of rvb.h");
+  const std::string w("rvb_ctc_align_graph");
+  if (!e) { set_error(w + ": null engine"); return E_ARG; }
+  if (!node_tokens || !n_nodes || !pred_off || !preds || !is_final || !first_chunk || !n_chunks || n_seq <= 0) {
+    set_error(w + ": null argument or n_seq <= 0");
+    return E_ARG;
+  }
+  if (!(std::isfinite(wildcard_bias) && wildcard_bias <= 0.f)) { set_error(w + ": wildcard_bias must be finite and <= 0"); return E_ARG; }
+  const int V = e->cfg.vocab, blank = e->cfg.blank_id;
+  CtcGraphAligner& al = e->graph_aligner;
+  std::vector<std::vector<int32_t>> seq_rows;
+  RVB_TRY(align_seq_rows(e, w.c_str(), first_chunk, n_chunks, n_seq, &seq_rows));
+  RVB_TRY(al.plan(w.c_str(), node_tokens, n_nodes, pred_off, preds, is_final, n_seq, seq_rows, V, blank));
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
+  RVB_TRY(al.begin(e->stream));
+  std::vector<int32_t> states;
+  std::vector<float> sc_host;
+  RVB_TRY(align_sweep(e, slabs, "ctc_graph", al, wildcard_bias, &states, &sc_host));
+  std::vector<int32_t> lab(states.size()), node(states.size());
+  for (int i = 0; i < n_seq; ++i) {
+    const GraphSeq& q = al.seq[i];
+    for (int t = 0; t < q.T; ++t) {
+      const int st = states[q.frame_off + t], j = (st >> 1) - 1;
+      node[q.frame_off + t] = (st & 1) ? j : -1;
+      lab[q.frame_off + t] = (st & 1) ? node_tokens[q.node_off + j] : blank;
+    }
+  }
+  std::vector<float> emit;
+  if (peak || confidence) RVB_TRY(align_emissions(e, slabs, al.seq, al.h_rows, lab, al.has_wild, &emit));
+  // nothing was written so far: a refusal leaves every output untouched
+  if (score) memcpy(score, sc_host.data(), (size_t)n_seq * 4);
+  if (labels) memcpy(labels, lab.data(), lab.size() * 4);
+  if (frame_node) memcpy(frame_node, node.data(), node.size() * 4);
+  for (int i = 0; i < n_seq; ++i) {
+    const GraphSeq& q = al.seq[i];
+    int n_path = 0;
+    auto next_on_path = [&](int j) {               // a run is a node; its outputs go to the next position of the chosen path
+      if (j < 0) return -1;
+      const int k = q.node_off + n_path++;
+      if (path_nodes) path_nodes[k] = j;
+      return k;
+    };
+    run_outputs(node, emit, q.frame_off, q.T, next_on_path, begin, end, peak, confidence);
+    if (path_len) path_len[i] = n_path;
+  }
+  return OK;
+}
+
+// Full-sum score (CTC.forward, transformer/ctc.py:65-104) over the same slabs: a forward sweep, and for per-token outputs the slabs
+// once more in descending order for the backward sweep (the CTC head is recomputed, as for the alignment's confidences).
+int rvb_ctc_score(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,
+                  const int32_t* n_chunks, double* loglik, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame) {
+  if (!e) { set_error("rvb_ctc_score: null engine"); return E_ARG; }
+  if (!tokens || !tok_lens || !first_chunk || !n_chunks || !loglik || n_seq <= 0) { set_error("rvb_ctc_score: null argument or n_seq <= 0"); return E_ARG; }
+  const char* who = "rvb_ctc_score";
+  const int V = e->cfg.vocab;
+  CtcScorer& sc = e->scorer;
+  const bool post = occupancy || mean_frame || peak_post || peak_frame;
+  std::vector<std::vector<int32_t>> seq_rows;
+  RVB_TRY(align_seq_rows(e, who, first_chunk, n_chunks, n_seq, &seq_rows));
+  RVB_TRY(sc.plan(who, tokens, tok_lens, n_seq, seq_rows, V, e->cfg.blank_id));
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
+  RVB_TRY(sc.begin(e->stream, post));
+  RVB_TRY(sweep_slabs(e, slabs, false, "ctc_forward", sc.lat,
+                      [&](int r0, int rows) { return sc.advance(e->stream, e->align_lp.as<float>(), V, r0, rows); }));
+  {
+    Scope t(e, "ctc_forward");
+    RVB_TRY(sc.finish_forward(e->stream, loglik));
+  }
+  if (!post) return OK;
+  RVB_TRY(sweep_slabs(e, slabs, true, "ctc_backward", sc.lat,
+                      [&](int r0, int rows) { return sc.advance_backward(e->stream, e->align_lp.as<float>(), V, r0, rows); }));
+  Scope t(e, "ctc_backward");
+  return sc.finish_backward(e->stream, occupancy, mean_frame, peak_post, peak_frame);
+}
+
+// Full-sum score over token graphs (ctc_graph_score.hip): rvb_ctc_score's two sweeps on the lattices of rvb_ctc_align_graph.  Nothing
+// is written before the last step has succeeded: a refusal leaves every output untouched.
+int rvb_ctc_score_graph(rvb_engine* e, const int32_t* node_tokens, const int32_t* n_nodes, const int32_t* pred_off, const int32_t* preds,
+                        const uint8_t* is_final, int n_seq, const int32_t* first_chunk, const int32_t* n_chunks, double* loglik,
+                        float* visit, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame) {
+  const char* who = "rvb_ctc_score_graph";
+  if (!e) { set_error("rvb_ctc_score_graph: null engine"); return E_ARG; }
+  if (!node_tokens || !n_nodes || !pred_off || !preds || !is_final || !first_chunk || !n_chunks || !loglik || n_seq <= 0) {
+    set_error("rvb_ctc_score_graph: null argument or n_seq <= 0");
+    return E_ARG;
+  }
+  const int V = e->cfg.vocab;
+  CtcGraphScorer& sc = e->graph_scorer;
+  const bool post = visit || occupancy || mean_frame || peak_post || peak_frame;
+  std::vector<std::vector<int32_t>> seq_rows;
+  RVB_TRY(align_seq_rows(e, who, first_chunk, n_chunks, n_seq, &seq_rows));
+  RVB_TRY(sc.plan(who, node_tokens, n_nodes, pred_off, preds, is_final, n_seq, seq_rows, V, e->cfg.blank_id, post));
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
+  RVB_TRY(sc.begin(e->stream));
+  RVB_TRY(sweep_slabs(e, slabs, false, "ctc_graph_forward", sc.lat,
+                      [&](int r0, int rows) { return sc.advance(e->stream, e->align_lp.as<float>(), V, r0, rows); }));
+  std::vector<double> ll((size_t)n_seq);
+  {
+    Scope t(e, "ctc_graph_forward");
+    RVB_TRY(sc.finish_forward(e->stream, ll.data()));
+  }
+  if (post) {
+    RVB_TRY(sweep_slabs(e, slabs, true, "ctc_graph_backward", sc.lat,
+                        [&](int r0, int rows) { return sc.advance_backward(e->stream, e->align_lp.as<float>(), V, r0, rows); }));
+    Scope t(e, "ctc_graph_backward");
+    RVB_TRY(sc.finish_backward(e->stream, visit, occupancy, mean_frame, peak_post, peak_frame));
+  }
+  memcpy(loglik, ll.data(), (size_t)n_seq * 8);
+  return OK;
+}
+
+// Phrase search (csrc/ctc_find.hip) over the same slabs: align_slab leaves the log-probs in align_lp and each row's maximum in
+// align_tv (the same fp32 subtraction, see ctc_align_impl), which is all the kernel reads.  Everything is checked before any device work.
+int rvb_ctc_find(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_phrases, const float* threshold,
+                 const int32_t* first_chunk, const int32_t* n_chunks, int n_seq, int max_candidates, int max_hits, int32_t* n_hits,
+                 int32_t* start, int32_t* end, float* score, int64_t* n_candidates) {
+  static_assert(CTC_FIND_MAX_TOKENS == RVB_CTC_FIND_MAX_TOKENS, "cap of rvb.h");
+  const char* who = "rvb_ctc_find";
+  if (!e) { set_error("rvb_ctc_find: null engine"); return E_ARG; }
+  if (!tokens || !tok_lens || !threshold || !first_chunk || !n_chunks || !n_hits || !start || !end || !score) {
+    set_error("rvb_ctc_find: null argument"); return E_ARG;
+  }
+  if (n_phrases < 1 || n_seq < 1) { set_error("rvb_ctc_find: need n_phrases >= 1 and n_seq >= 1"); return E_ARG; }
+  if (max_candidates < 1 || max_hits < 1) { set_error("rvb_ctc_find: need max_candidates >= 1 and max_hits >= 1"); return E_ARG; }
+  const int V = e->cfg.vocab;
+  CtcFinder& fd = e->finder;
+  std::vector<std::vector<int32_t>> seq_rows;
+  RVB_TRY(align_seq_rows(e, who, first_chunk, n_chunks, n_seq, &seq_rows));
+  RVB_TRY(fd.plan(who, tokens, tok_lens, n_phrases, threshold, seq_rows, V, e->cfg.blank_id, max_candidates));
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
+  RVB_TRY(fd.begin(e->stream));
+  RVB_TRY(sweep_slabs(e, slabs, false, "ctc_find", fd, [&](int r0, int rows) {
+    return fd.advance(e->stream, e->align_lp.as<float>(), V, r0, rows, e->align_tv.as<float>());
+  }));
+  return fd.finish(e->stream, max_hits, n_hits, start, end, score, n_candidates);
+}
+
+}  // extern "C"

@@ -1,6 +1,6 @@
 /* test_api.h -- entry points of librvb_test.so: raw kernel / host-search hooks for the unit tests and the tuning scripts
  * (host buffers in, host buffers out).  NOT part of the product: librvb.so exports include/rvb.h and include/rvd.h only;
- * reverb_amd/build.py links the same objects plus csrc/test_api.hip (and engine.hip compiled with -DRVB_TEST_API) into
+ * reverb_amd/build.py links the same objects plus csrc/test_api.hip (in place of the product's csrc/lab_env_off.cpp) into
  * reverb_amd/librvb_test.so, which tests/ and scripts/ load through reverb_amd._lib.load_test(). */
 #ifndef RVB_TEST_API_H_
 #define RVB_TEST_API_H_
@@ -147,7 +147,7 @@ int rvb_test_lse_gather_multi(const float* logits, int R, int V, const int32_t* 
  * ld < V) before any device work. */
 int rvb_test_row_xent(const float* logits, int R, int V, int ld, const int32_t* ptr /* [R+1] */, const int32_t* target,
                       float* logp /* [ptr[R]] */, float* lse /* [R] */, double* sum_x /* [R] */, int32_t* top1 /* [R] */);
-/* host only: the trie of distinct hypothesis prefixes attention rescoring computes decoder rows for (engine.hip build_trie) */
+/* host only: the trie of distinct hypothesis prefixes attention rescoring computes decoder rows for (trie.h build_trie_range, merge_tries) */
 int rvb_test_build_trie(const int32_t* tokens, const int32_t* lens, const int32_t* chunk_of, int n_hyps, int n_chunks, int sos, int eos,
                         int reversed, int32_t* n_rows, int32_t* tok, int32_t* pos, int32_t* path, int32_t* hq_start, int32_t* hq_len,
                         int32_t* hq_pos0, int32_t* tgt_ptr, int32_t* tgt, int32_t* pair_slot, int32_t* n_work);

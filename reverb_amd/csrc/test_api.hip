@@ -3,16 +3,22 @@
 // uses), launches exactly the kernel the engine launches, and downloads the result as fp32.
 #include "mp3.h"
 #include <algorithm>
+#include <atomic>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
 #include "test_api.h"
-#include "engine.h"
+#include "engine_impl.h"
 #include "kernels.h"
 #include "search.h"
+#include "trie.h"
 
 using namespace rvb;
+
+namespace rvb {
+const char* lab_env(const char* name) { return getenv(name); }      // librvb_test.so: the lab build reads its switches (librvb.so: lab_env_off.cpp)
+}
 
 namespace {
 struct Dev {
@@ -1729,4 +1735,108 @@ extern "C" int rvb_test_emb_stem(int dtype, const float* fb, int64_t n_rows, con
   RVB_HIP_CHECK(hipDeviceSynchronize());
   RVB_HIP_CHECK(hipMemcpy(mean, dmean.p, (size_t)n_windows * 80 * 4, hipMemcpyDeviceToHost));
   return down_bordered(dout, dtype, out, B, F, nfr, C, kSlack, "rvb_test_emb_stem");
+}
+
+// ---- hooks into the engine's host code (engine_impl.h, trie.h)
+// host only: the rescoring trie of given hypotheses (tests/test_search_native.py checks it against a Python trie).
+// tokens: the hypotheses back to back; lens / chunk_of: per hypothesis (chunk ids ascending).  Outputs sized by the caller:
+// rows <= P = sum(len + 1); tok, pos [rows]; path, tgt, pair_slot [P]; hq_start, hq_len, hq_pos0 [n_hyps]; tgt_ptr [rows + 1].
+extern "C" int rvb_test_build_trie(const int32_t* tokens, const int32_t* lens, const int32_t* chunk_of, int n_hyps, int n_chunks, int sos,
+                                   int eos, int reversed, int32_t* n_rows, int32_t* tok, int32_t* pos, int32_t* path, int32_t* hq_start,
+                                   int32_t* hq_len, int32_t* hq_pos0, int32_t* tgt_ptr, int32_t* tgt, int32_t* pair_slot, int32_t* n_work) {
+  if (!tokens || !lens || !chunk_of || !n_rows || n_hyps < 0) { set_error("rvb_test_build_trie: bad argument"); return E_ARG; }
+  std::vector<HypRef> hyps;
+  std::vector<int> first(n_hyps);
+  int P = 0, off = 0;
+  for (int i = 0; i < n_hyps; ++i) { hyps.push_back({chunk_of[i], i, lens[i], P}); first[i] = off; P += lens[i] + 1; off += lens[i]; }
+  TrieBatch t;
+  auto seq = [&](const HypRef& h, int j) { return tokens[first[h.idx] + (reversed ? h.len - 1 - j : j)]; };
+  build_trie_range(hyps.data(), hyps.data() + hyps.size(), 0, n_chunks, sos, eos, seq, &t);
+  {   // the engine builds the same trie chunk by chunk and stitches the parts (merge_tries): both forms must agree exactly
+    std::vector<TrieBatch> part(std::max(n_chunks, 0));
+    size_t a = 0;
+    for (int b = 0; b < n_chunks; ++b) {
+      size_t z = a;
+      while (z < hyps.size() && hyps[z].chunk == b) ++z;
+      build_trie_range(hyps.data() + a, hyps.data() + z, b, 1, sos, eos, seq, &part[b]);
+      a = z;
+    }
+    TrieBatch m;
+    merge_tries(part, &m);
+    const bool same = m.R == t.R && m.P == t.P && m.max_chunk_rows == t.max_chunk_rows && m.tok == t.tok && m.pos == t.pos &&
+                      m.path == t.path && m.hq_start == t.hq_start && m.hq_len == t.hq_len && m.hq_pos0 == t.hq_pos0 &&
+                      m.hkv_start == t.hkv_start && m.hkv_len == t.hkv_len && m.crow_start == t.crow_start &&
+                      m.crow_len == t.crow_len && m.tgt_ptr == t.tgt_ptr && m.tgt == t.tgt && m.pair_slot == t.pair_slot &&
+                      m.work == t.work;
+    if (a != hyps.size() || !same) {
+      std::string which;
+#define RVB_DIFF(f) if (!(m.f == t.f)) which += std::string(" ") + #f;
+      RVB_DIFF(R) RVB_DIFF(P) RVB_DIFF(max_chunk_rows) RVB_DIFF(tok) RVB_DIFF(pos) RVB_DIFF(path) RVB_DIFF(hq_start) RVB_DIFF(hq_len)
+      RVB_DIFF(hq_pos0) RVB_DIFF(hkv_start) RVB_DIFF(hkv_len) RVB_DIFF(crow_start) RVB_DIFF(crow_len) RVB_DIFF(tgt_ptr) RVB_DIFF(tgt)
+      RVB_DIFF(pair_slot) RVB_DIFF(work)
+#undef RVB_DIFF
+      set_error("rvb_test_build_trie: the stitched per-chunk tries differ from the batch trie in:" + which);
+      return E_STATE;
+    }
+  }
+  *n_rows = t.R;
+  if (n_work) *n_work = (int32_t)t.work.size() / 2;
+  auto cp = [](int32_t* dst, const std::vector<int32_t>& v) { if (dst) memcpy(dst, v.data(), v.size() * 4); };
+  cp(tok, t.tok); cp(pos, t.pos); cp(path, t.path); cp(hq_start, t.hq_start); cp(hq_len, t.hq_len); cp(hq_pos0, t.hq_pos0);
+  cp(tgt_ptr, t.tgt_ptr); cp(tgt, t.tgt); cp(pair_slot, t.pair_slot);
+  return OK;
+}
+
+// host only: HostPool runs `rounds` jobs of `n_threads` threads each; every job hands out `items` work items through an atomic
+// counter (the pattern of the CTC search) and the call checks that each item was executed exactly once in every round.
+extern "C" int rvb_test_host_pool(int n_threads, int items, int rounds) {
+  if (n_threads < 1 || items < 0 || rounds < 1) { set_error("rvb_test_host_pool: bad argument"); return E_ARG; }
+  HostPool pool;
+  std::vector<std::atomic<int>> hits(items);
+  for (int r = 0; r < rounds; ++r) {
+    for (auto& h : hits) h.store(0);
+    std::atomic<int> next(0), entered(0);
+    const unsigned n = (unsigned)std::max(1, n_threads - (r % 3));     // the pool grows and is reused with fewer threads
+    pool.run(n, [&] {
+      entered.fetch_add(1);
+      for (int i = next.fetch_add(1); i < items; i = next.fetch_add(1)) hits[i].fetch_add(1);
+    });
+    if (entered.load() != (int)n) { set_error("rvb_test_host_pool: a job was not run by the requested number of threads"); return E_STATE; }
+    for (int i = 0; i < items; ++i)
+      if (hits[i].load() != 1) { set_error("rvb_test_host_pool: work item executed " + std::to_string(hits[i].load()) + " times"); return E_STATE; }
+  }
+  return OK;
+}
+
+extern "C" int rvb_test_fbank_ex(const int16_t* pcm, const float* wave, int64_t n_samples, float* feats) {
+  if ((pcm == nullptr) == (wave == nullptr) || !feats || n_samples < 0) { set_error("rvb_test_fbank_ex: one of pcm / wave, feats and n_samples >= 0 are needed"); return E_ARG; }
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: librvb has no CPU fallback"); return E_HIP; }
+  rvb_engine e;   // default stream, only the fbank tables are used
+  RVB_TRY(make_fbank_tables(&e));
+  const int64_t nf = rvb_num_frames(n_samples);
+  const size_t in_bytes = (size_t)n_samples * (pcm ? 2 : 4), out_bytes = (size_t)(nf + 4) * 80 * 4;
+  void* din = nullptr;     // not a DevBuf: exactly the waveform's bytes, so that a read past its end is a read past the allocation
+  DevBuf df;
+  int r = df.ensure(out_bytes);
+  if (r == OK && in_bytes && hipMalloc(&din, in_bytes) != hipSuccess) { set_error("rvb_test_fbank_ex: hipMalloc failed"); r = E_NOMEM; }
+  if (r == OK && in_bytes && hipMemcpy(din, pcm ? (const void*)pcm : (const void*)wave, in_bytes, hipMemcpyHostToDevice) != hipSuccess) { set_error("rvb_test_fbank_ex: upload failed"); r = E_HIP; }
+  if (r == OK && hipMemset(df.p, 0xff, out_bytes) != hipSuccess) { set_error("rvb_test_fbank_ex: memset failed"); r = E_HIP; }
+  FbankTables t{e.fb_window.as<float>(), e.fb_twiddle.as<float>(), e.fb_melw.as<float>(), e.fb_lo.as<int>(), e.fb_hi.as<int>()};
+  if (r == OK) r = pcm ? fbank(nullptr, (const int16_t*)din, nf, df.as<float>(), t) : fbank_f32(nullptr, (const float*)din, nf, df.as<float>(), t);
+  if (r == OK && hipDeviceSynchronize() != hipSuccess) { set_error("fbank kernel failed"); r = E_HIP; }
+  if (r == OK && hipMemcpy(feats, df.p, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) { set_error("rvb_test_fbank_ex: download failed"); r = E_HIP; }
+  if (din) (void)hipFree(din);
+  df.release();
+  for (DevBuf* b : {&e.fb_window, &e.fb_twiddle, &e.fb_melw, &e.fb_lo, &e.fb_hi}) b->release();
+  return r;
+}
+
+extern "C" int rvb_test_fbank(const int16_t* pcm, int64_t n_samples, float* feats) {
+  if (!pcm || !feats || n_samples < 0) { set_error("rvb_test_fbank: null argument"); return E_ARG; }
+  const int64_t nf = rvb_num_frames(n_samples);
+  std::vector<float> all((size_t)(nf + 4) * 80);
+  RVB_TRY(rvb_test_fbank_ex(pcm, nullptr, n_samples, all.data()));
+  memcpy(feats, all.data(), (size_t)nf * 80 * 4);
+  return OK;
 }
