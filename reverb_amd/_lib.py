@@ -160,10 +160,20 @@ class NormTestArgs(C.Structure):
                 [("sat", C.c_uint32), ("sat2", C.c_uint32)])
 
 
+class GemmTestArgs(C.Structure):
+    """rvb_test_gemm_args of csrc/test_api.h (rvb_test_gemm_ex): one gemm() call on host floats."""
+    _fields_ = ([(n, C.c_int32) for n in ("dtype", "M", "N", "K", "lda", "ldw", "ldc", "ldres", "act", "out_f32", "out_fp8", "in_fp8",
+                                          "inplace", "a_row0", "c_rows", "conv", "cT1", "cF1", "cC", "cB")] +
+                [(n, C.c_float) for n in ("alpha", "a_scale", "out_scale")] +
+                [("path", C.c_int32), ("a_elems", C.c_int64)] +
+                [(n, _f32p) for n in ("A", "W", "bias", "res", "C", "a_deq", "w_deq")])
+
+
 _u32p = C.POINTER(C.c_uint32)
 
 # librvb_test.so (csrc/test_api.h): raw kernel / host-search hooks for tests/ and scripts/ -- not in the product library
 TEST_SIGNATURES = {
+    "rvb_test_gemm_ex": (C.c_int, [C.POINTER(GemmTestArgs)]),
     "rvb_test_rownorm_ex": (C.c_int, [C.POINTER(NormTestArgs)]),
     "rvb_test_conv1_ex": (C.c_int, [C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                     _f32p, _u32p]),

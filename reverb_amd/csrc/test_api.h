@@ -108,6 +108,29 @@ int rvb_test_mp3_window(float* out512);
 int rvb_test_mp3_huffman(int t, uint16_t* codes, uint8_t* lens, int32_t* linbits32);
 int rvb_test_gemm_fp8(const float* A, const float* W, const float* bias, const float* res, float* C, int M, int N, int K,
                       float a_scale, float alpha, int act, int out_kind, float out_scale, float* a_deq, float* w_deq);
+/* gemm() with everything GemmArgs carries but the row-periodic addend, on host floats, so that a test can build any call the engines
+ * build (run_gemm: strides, a null bias, the residual in the output buffer, A offset into its allocation, overlapping rows).
+ * A: a_elems values, rounded to the compute dtype (or quantised to e4m3 at a_scale when in_fp8); the kernel's A starts a_row0 * lda
+ * elements in, so a_elems >= (a_row0 + M - 1) * lda + K (lda < K: overlapping rows); conv != 0: the NHWC activation of rvb_test_gemm
+ * (lda = cC, a_row0 = 0, a_elems ignored).  W [N][ldw] (in_fp8: one scale per row, as rvb_test_gemm_fp8 quantises).  bias [N] and
+ * res [M][ldres] are nullable.  C [c_rows][ldc] (c_rows 0 = M, else >= M) goes up as the caller filled it and comes back whole:
+ * pad columns and rows past M keep their canaries.  The output is fp32 (f32 engine, out_f32), e4m3 of value / out_scale (out_fp8;
+ * a NaN of the caller's goes up as the NaN code and comes back NaN) or bf16.  inplace: the fp32 output buffer IS the residual (res
+ * null, ldres ignored in favour of ldc).  a_deq [a_elems] / w_deq [N][ldw] (nullable, in_fp8 only): the values the quantised operands
+ * stand for.  path (out): 2 when gemm() hands this problem to gemm2.hip (gemm2_applicable and the variant switch), else 1.
+ * Refused by name before any device work (E_ARG): a buffer smaller than the strides need, inplace without an fp32 output.  What gemm()
+ * itself refuses comes back with its code and its words, C as the caller filled it. */
+typedef struct rvb_test_gemm_args {
+  int32_t dtype, M, N, K, lda, ldw, ldc, ldres;
+  int32_t act, out_f32, out_fp8, in_fp8, inplace, a_row0, c_rows, conv;
+  int32_t cT1, cF1, cC, cB;
+  float alpha, a_scale, out_scale;
+  int32_t path;
+  int64_t a_elems;
+  const float* A; const float* W; const float* bias; const float* res;
+  float* C; float* a_deq; float* w_deq;
+} rvb_test_gemm_args;
+int rvb_test_gemm_ex(rvb_test_gemm_args* a);
 int rvb_test_rownorm_fp8(const float* x, const float* gamma, const float* beta, float eps, int silu, int M, int d, float scale,
                          float* out, const float* gamma2, const float* beta2, float eps2, float scale2, float* out1_f32, float* out2);
 /* rownorm() with everything NormArgs carries, on host floats.  x goes up as fp32, or as bf16 when x_bf16; add in the compute dtype.

@@ -1052,6 +1052,89 @@ static int down_fp8(const Dev& d, float* dst, size_t n, float scale) {
   return OK;
 }
 
+// gemm() with the whole of GemmArgs but the row-periodic addend (test_api.h): the GemmArgs are filled as run_gemm fills them
+int rvb_test_gemm_ex(rvb_test_gemm_args* t) {
+  auto bad = [](const char* m) { set_error(std::string("rvb_test_gemm_ex: ") + m); return E_ARG; };
+  if (!t) return bad("null");
+  t->path = 0;
+  const int dtype = t->dtype;
+  if (!t->A || !t->W || !t->C || (dtype != DT_F32 && dtype != DT_BF16)) return bad("null A, W or C, or an unknown dtype");
+  const int M = t->M, N = t->N, K = t->K;
+  if (M < 0 || N < 1 || K < 1 || t->a_row0 < 0) return bad("M < 0, N < 1, K < 1 or a negative a_row0");
+  const int lda = t->conv ? t->cC : t->lda;
+  const int c_rows = t->c_rows ? t->c_rows : M;
+  if (lda < 1 || t->ldw < K || t->ldc < N || c_rows < M) return bad("lda < 1, ldw < K, ldc < N or c_rows < M");
+  if (t->in_fp8 && (dtype != DT_BF16 || !(t->a_scale > 0.f) || t->conv)) return bad("fp8 operands: bf16 engine, a positive a_scale, no convolution gather");
+  if (t->out_fp8 && (!t->in_fp8 || !(t->out_scale > 0.f))) return bad("an fp8 output needs fp8 operands and a positive scale");
+  const bool f32out = !t->out_fp8 && (dtype == DT_F32 || t->out_f32);
+  if (t->inplace && (t->res || !f32out)) return bad("inplace: the fp32 output buffer is the residual (res must be null)");
+  if (t->res && t->ldres < N) return bad("ldres < N");
+  size_t a_elems = (size_t)(t->a_elems > 0 ? t->a_elems : 0);
+  if (t->conv) {
+    const int T2 = (t->cT1 - 3) / 2 + 1, F2 = (t->cF1 - 3) / 2 + 1;
+    if (t->cT1 < 3 || t->cF1 < 3 || t->cC < 1 || t->cB < 1 || M != t->cB * T2 * F2 || K != 9 * t->cC || t->a_row0 != 0) return bad("conv shape mismatch");
+    a_elems = (size_t)t->cB * t->cT1 * t->cF1 * t->cC;
+  } else if (M > 0 && (int64_t)a_elems < ((int64_t)t->a_row0 + M - 1) * lda + K) {
+    return bad("a_elems < (a_row0 + M - 1) * lda + K");
+  }
+  RVB_TRY(need_gpu());
+  const size_t w_elems = (size_t)N * t->ldw, c_elems = (size_t)c_rows * t->ldc;
+  Dev dA, dW, dS, dB, dR, dC;
+  if (t->in_fp8) {      // A per tensor, W per output channel over its K columns (rvb_test_gemm_fp8); pad columns of W are zero bytes
+    std::vector<uint8_t> qa(a_elems), qw(w_elems, 0);
+    std::vector<float> ws(N);
+    for (size_t i = 0; i < a_elems; ++i) { qa[i] = f32_to_fp8_host(t->A[i] / t->a_scale); if (t->a_deq) t->a_deq[i] = fp8_to_f32_host(qa[i]) * t->a_scale; }
+    for (int n = 0; n < N; ++n) {
+      const float* w = t->W + (size_t)n * t->ldw;
+      float am = 0.f;
+      for (int k = 0; k < K; ++k) am = fmaxf(am, fabsf(w[k]));
+      ws[n] = am > 0.f ? am / 448.f : 1.f;
+      for (int k = 0; k < t->ldw; ++k) {
+        const uint8_t q = k < K ? f32_to_fp8_host(w[k] / ws[n]) : 0;
+        qw[(size_t)n * t->ldw + k] = q;
+        if (t->w_deq) t->w_deq[(size_t)n * t->ldw + k] = fp8_to_f32_host(q) * ws[n];
+      }
+    }
+    if (a_elems > 0) RVB_TRY(up_raw(dA, qa.data(), a_elems)); else RVB_TRY(dA.alloc(16));
+    RVB_TRY(up_raw(dW, qw.data(), qw.size()));
+    RVB_TRY(up_raw(dS, ws.data(), (size_t)N * 4));
+  } else {
+    if (a_elems > 0) RVB_TRY(up_T(dA, dtype, t->A, a_elems)); else RVB_TRY(dA.alloc(16));
+    RVB_TRY(up_T(dW, dtype, t->W, w_elems));
+  }
+  RVB_TRY(up_raw(dB, t->bias, (size_t)N * 4));
+  if (M > 0) RVB_TRY(up_raw(dR, t->res, (size_t)M * t->ldres * 4));
+  // the caller's C in the output's own format: canaries and an in-place residual survive the way up
+  if (t->out_fp8) {
+    std::vector<uint8_t> q(c_elems);
+    for (size_t i = 0; i < c_elems; ++i) q[i] = t->C[i] != t->C[i] ? 0x7f : f32_to_fp8_host(t->C[i] / t->out_scale);
+    if (c_elems > 0) RVB_TRY(up_raw(dC, q.data(), c_elems)); else RVB_TRY(dC.alloc(16));
+  } else if (c_elems > 0) {
+    RVB_TRY(up_T(dC, f32out ? DT_F32 : DT_BF16, t->C, c_elems));
+  } else {
+    RVB_TRY(dC.alloc(16));
+  }
+  const size_t a_esz = t->in_fp8 ? 1 : dt_size(dtype);
+  GemmArgs g;
+  memset(&g, 0, sizeof(g));
+  g.A = (const char*)dA.p + (size_t)t->a_row0 * lda * a_esz; g.W = dW.p; g.bias = (const float*)dB.p; g.C = dC.p;
+  g.res = t->inplace ? (const float*)dC.p : (const float*)dR.p;
+  g.M = M; g.N = N; g.K = K; g.lda = lda; g.ldw = t->ldw; g.ldc = t->ldc; g.ldres = t->inplace ? t->ldc : t->ldres;
+  g.alpha = t->alpha; g.act = t->act; g.out_f32 = t->out_f32 ? 1 : 0;
+  if (t->conv) {
+    g.conv = 1; g.cT1 = t->cT1; g.cF1 = t->cF1; g.cT2 = (t->cT1 - 3) / 2 + 1; g.cF2 = (t->cF1 - 3) / 2 + 1; g.cC = t->cC;
+  }
+  if (t->in_fp8) { g.in_fp8 = 1; g.a_scale = t->a_scale; g.w_scale = (const float*)dS.p; }
+  if (t->out_fp8) { g.out_fp8 = 1; g.out_inv_scale = 1.f / t->out_scale; }
+  // where gemm() sends it (gemm.hip: ACT_GLU and fp8 operands exist on gemm2.hip only; otherwise the variant switch and gemm2_applicable)
+  t->path = (t->act == ACT_GLU || t->in_fp8 || (g_gemm_variant != 1 && (dtype == DT_BF16 || g_gemm_variant == 2) && gemm2_applicable(dtype, g))) ? 2 : 1;
+  RVB_TRY(gemm(nullptr, dtype, g));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  if (c_elems == 0) return OK;
+  if (t->out_fp8) return down_fp8(dC, t->C, c_elems, t->out_scale);
+  return down_T(dC, f32out ? DT_F32 : DT_BF16, f32out, t->C, c_elems);
+}
+
 // rownorm() with the whole of NormArgs (test_api.h)
 int rvb_test_rownorm_ex(rvb_test_norm_args* t) {
   if (!t || !t->x || !t->gamma || !t->beta || !t->out || t->M < 1 || t->d < 1 || (t->dtype != DT_F32 && t->dtype != DT_BF16)) {
