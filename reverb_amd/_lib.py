@@ -264,6 +264,8 @@ TEST_SIGNATURES = {
                                   C.c_int, C.c_int, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p]),
     "rvb_test_emb_stem": (C.c_int, [C.c_int, _f32p, C.c_int64, _i64p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _f32p, _f32p,
                                     _f32p, _f32p]),
+    "rvb_test_pdist_nn": (C.c_int, [_f64p, C.c_int, C.c_int, _f64p, _i32p, _f64p]),
+    "rvb_test_centroid_linkage": (C.c_int, [_f64p, C.c_int, C.c_int, C.c_int, _f64p, _i32p, _f64p]),
 }
 
 

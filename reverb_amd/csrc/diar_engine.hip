@@ -1032,16 +1032,7 @@ int rvd_centroid_linkage(rvd_engine* e, const double* X, int n, int d, double* Z
       (void)hipMemcpy(&retries, dM.as<double>() + (n - 1), 8, hipMemcpyDeviceToHost);
       if (retries < 0.0) { set_error("rvd_centroid_linkage: the merge loop found no candidate pair (non-finite embeddings?)"); rc = E_ARG; break; }
       e->prof["linkage"].flops += retries; }      // reported through rvd_get_timing("linkage").flops
-    // slots -> scipy cluster ids: the merged cluster lives on in slot y under the new id n + k
-    std::vector<int> cid(n);
-    for (int i = 0; i < n; ++i) cid[i] = i;
-    for (int k = 0; k < n - 1; ++k) {
-      const int x = (int)Z[4 * (size_t)k], y = (int)Z[4 * (size_t)k + 1];
-      const int ix = cid[x], iy = cid[y];
-      Z[4 * (size_t)k] = ix < iy ? ix : iy;
-      Z[4 * (size_t)k + 1] = ix < iy ? iy : ix;
-      cid[y] = n + k;
-    }
+    linkage_slots_to_ids(Z, n);      // slots -> scipy cluster ids
   } while (0);
   dX.release(); dD.release(); dI.release(); dM.release(); dZ.release(); dC.release();
   return rc;

@@ -495,7 +495,19 @@ int tstp_pool(hipStream_t s, int dtype, const void* x, const int* item_b, const 
 // returns after the loop has finished (it checks the loop's status and falls back to the one-workgroup loop if needed).
 // `workgroups`: 0 = default (16), 1 = the one-workgroup loop, 2 / 4 / 8 / 16 = that many workgroups (fewer disturb a concurrent
 // kernel less: the joint pipeline clusters underneath the ASR encoder).
+// `ran` (nullable, tests): {loop, G, exchange form, fell_back} of the merge loop whose result Z holds -- loop 1 = LDS state with slot
+// compaction, 2 = LDS state without it, 3 = state in global memory, 4 = the multi-workgroup loop; G = its workgroups (1 for loops
+// 1-3); exchange form 0 = A, 1 = B, 2 = C (0 for loops 1-3); fell_back = 1 when the multi-workgroup loop gave up and the
+// one-workgroup loop produced the result.  Zeros when nothing was launched.
 int centroid_linkage(hipStream_t s, const double* X, int n, int d, double* D, uint16_t* size, int* cluster_id, int* neighbor,
-                     double* min_dist, double* Z, void* scratch, int workgroups = 0);
+                     double* min_dist, double* Z, void* scratch, int workgroups = 0, int* ran = nullptr);
+// the first two launches of centroid_linkage() on their own: D [n][n] = the full symmetric fp64 distance matrix of X [n][d], then
+// the nearest neighbour of every row x < n - 1 among the columns above x (first index on ties) into neighbor[x] / min_dist[x]; slot
+// n - 1 of both is not written
+int pdist(hipStream_t s, const double* X, int n, int d, double* D);
+int nn_init(hipStream_t s, const double* D, int n, int* neighbor, double* min_dist);
+// host: the merge loops write a dendrogram row as (slot x, slot y, distance, size); this turns the slots into scipy's cluster ids in
+// place (the merged cluster lives on in slot y under the new id n + k; the smaller id first)
+void linkage_slots_to_ids(double* Z, int n);
 
 }  // namespace rvb

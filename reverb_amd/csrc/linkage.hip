@@ -10,6 +10,7 @@
 // argmin over the candidate distances plus one fused pass over the two merged rows.
 #include <cstdio>
 #include <cstdlib>
+#include <vector>
 
 #include "kernels.h"
 
@@ -305,7 +306,9 @@ __global__ __launch_bounds__(NTH) void linkage_kernel(int getenv_prof, double* _
       // date where D changes (the merge pass below), encoded in the sign of the neighbour: nb >= 0 valid,
       // nb <= -2 stale (neighbour -2-nb), -1 none -- no global read on the critical path
       x = p.i; dist = p.v;
-      if (x >= n - 1) break;                  // no candidate at all: cannot happen while two clusters are alive
+      // no candidate at all (a non-finite row has no distance to anybody): dropped rows hold +inf too and tie with the empty
+      // minimum on the value, so the value decides, not the index
+      if (x >= n - 1 || !(dist < INFINITY)) break;
       const int nbx = NB(x);
       if (prof) { const long long t1 = wall_clock64(); t_arg += t1 - t0c; t0c = t1; }
       if (nbx >= 0) { y = nbx; break; }
@@ -858,10 +861,35 @@ __global__ __launch_bounds__(MB_NT) void linkage_mb_kernel(double* __restrict__ 
   if (b == 0 && tid == 0) g_min_dist[n - 1] = (double)rescans;       // statistics (workgroup 0's rescans; slot n-1 is unused)
 }
 
-int centroid_linkage(hipStream_t s, const double* X, int n, int d, double* D, uint16_t* size, int* cluster_id, int* neighbor,
-                     double* min_dist, double* Z, void* scratch, int workgroups) {
-  if (n < 2) return OK;
+int pdist(hipStream_t s, const double* X, int n, int d, double* D) {
   const int t = cdiv(n, 64);
+  hipLaunchKernelGGL(pdist_kernel, dim3(t, t), dim3(256), 0, s, X, n, d, D);
+  RVB_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
+int nn_init(hipStream_t s, const double* D, int n, int* neighbor, double* min_dist) {
+  hipLaunchKernelGGL(nn_init_kernel, dim3(n - 1), dim3(256), 0, s, D, n, neighbor, min_dist);
+  RVB_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
+void linkage_slots_to_ids(double* Z, int n) {
+  std::vector<int> cid(n);
+  for (int i = 0; i < n; ++i) cid[i] = i;
+  for (int k = 0; k < n - 1; ++k) {
+    const int x = (int)Z[4 * (size_t)k], y = (int)Z[4 * (size_t)k + 1];
+    const int ix = cid[x], iy = cid[y];
+    Z[4 * (size_t)k] = ix < iy ? ix : iy;
+    Z[4 * (size_t)k + 1] = ix < iy ? iy : ix;
+    cid[y] = n + k;
+  }
+}
+
+int centroid_linkage(hipStream_t s, const double* X, int n, int d, double* D, uint16_t* size, int* cluster_id, int* neighbor,
+                     double* min_dist, double* Z, void* scratch, int workgroups, int* ran) {
+  if (ran) ran[0] = ran[1] = ran[2] = ran[3] = 0;
+  if (n < 2) return OK;
   const size_t lds = (size_t)n * 14 + 16, lds_c = (size_t)n * 16 + 16;      // + the sorted slot list of the compacting variant
   const bool force_global = lab_env("RVD_LINKAGE_GLOBAL") != nullptr;      // test hook: exercise the large-n variant on small inputs
   const bool no_compact = lab_env("RVD_LINKAGE_COMPACT") && atoi(lab_env("RVD_LINKAGE_COMPACT")) == 0;
@@ -888,10 +916,8 @@ int centroid_linkage(hipStream_t s, const double* X, int n, int d, double* D, ui
     attr_set = true;
   }
   for (int attempt = 0; attempt < 2; ++attempt) {
-    hipLaunchKernelGGL(pdist_kernel, dim3(t, t), dim3(256), 0, s, X, n, d, D);
-    RVB_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(nn_init_kernel, dim3(n - 1), dim3(256), 0, s, D, n, neighbor, min_dist);
-    RVB_HIP_CHECK(hipGetLastError());
+    RVB_TRY(pdist(s, X, n, d, D));
+    RVB_TRY(nn_init(s, D, n, neighbor, min_dist));
     if (use_mb && attempt == 0) {
       RVB_HIP_CHECK(hipMemsetAsync(scratch, 0, sizeof(LkCtl), s));
       // at least 64 KiB of LDS per workgroup so that a CU holds one of them (the MB_G participants sit on MB_G different CUs)
@@ -901,6 +927,7 @@ int centroid_linkage(hipStream_t s, const double* X, int n, int d, double* D, ui
       double status = 0.0;
       RVB_HIP_CHECK(hipMemcpyAsync(&status, min_dist + (n - 1), 8, hipMemcpyDeviceToHost, s));
       RVB_HIP_CHECK(hipStreamSynchronize(s));
+      if (ran) { ran[0] = 4; ran[1] = G; ran[2] = (flags & 4) ? 2 : (flags & 2) ? 1 : 0; }
       if (status != -2.0) return OK;               // done (or -1: no candidate pair, reported by the caller)
       // a barrier gave up (the workgroups did not all become resident on one XCD): start over on the one-workgroup loop --
       // unless the multi-workgroup loop was asked for by name (tests): then this is an error, never a silent fall-back
@@ -909,15 +936,21 @@ int centroid_linkage(hipStream_t s, const double* X, int n, int d, double* D, ui
       const double inf = INFINITY;
       RVB_HIP_CHECK(hipMemcpyAsync(min_dist + (n - 1), &inf, 8, hipMemcpyHostToDevice, s));
       RVB_HIP_CHECK(hipStreamSynchronize(s));
+      if (ran) ran[3] = 1;
       continue;
     }
+    int loop;
     if (!force_global && !no_compact && lds_c <= 158 * 1024 && n <= LK_E * 1024) {
+      loop = 1;
       hipLaunchKernelGGL((linkage_kernel<true, 1024, true>), dim3(1), dim3(1024), lds_c, s, flags, D, n, size, cluster_id, neighbor, min_dist, Z);
     } else if (lds <= 158 * 1024 && !force_global) {
+      loop = 2;
       hipLaunchKernelGGL((linkage_kernel<true, 1024, false>), dim3(1), dim3(1024), lds, s, flags, D, n, size, cluster_id, neighbor, min_dist, Z);
     } else {
+      loop = 3;
       hipLaunchKernelGGL((linkage_kernel<false, 1024, false>), dim3(1), dim3(1024), 0, s, flags, D, n, size, cluster_id, neighbor, min_dist, Z);
     }
+    if (ran) { ran[0] = loop; ran[1] = 1; ran[2] = 0; }
     RVB_HIP_CHECK(hipGetLastError());
     break;
   }

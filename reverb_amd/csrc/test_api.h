@@ -283,6 +283,20 @@ int rvb_test_conv2d(int dtype, int path, const float* x, const float* w, const f
                     int stride2, int32_t* ran);
 int rvb_test_emb_stem(int dtype, const float* fb, int64_t n_rows, const int64_t* win, int B, int n_windows, int frames_per_step, int nfr,
                       int F, int C, const float* w, const float* bias, float* mean, float* out);
+/* clustering (linkage.hip).  pdist_nn: the two launches centroid_linkage() starts with, on host X [n][d] (n >= 2): the device D [n][n],
+ * neighbor [n] and min_dist [n] start as all-ones bytes and come back whole, so an element no kernel wrote comes back NaN / -1 (slot
+ * n - 1 of neighbor and min_dist always does: nn_init's grid is n - 1).
+ * centroid_linkage: centroid_linkage() on the allocations, the initial state and the 4096-byte control block rvd_centroid_linkage
+ * makes, then its status check and its slot-to-id conversion: Z [n-1][4] as scipy.cluster.hierarchy.linkage(X, "centroid") lays it
+ * out, written only on success.  workgroups as rvd_set_linkage_workgroups takes it.  ran[4] = {loop, G, exchange form, fell_back}:
+ * loop 1 = LDS state + slot compaction, 2 = LDS state, 3 = state in global memory, 4 = multi-workgroup; G = workgroups of the loop
+ * (1 for loops 1-3); exchange form 0 = A, 1 = B, 2 = C (0 for loops 1-3); fell_back = 1 when the multi-workgroup loop gave up and
+ * the one-workgroup loop produced Z.  retries (nullable) = stale candidates the loop re-evaluated (workgroup 0's, in loop 4).
+ * Refuses what rvd_centroid_linkage refuses (n < 1, d < 1, n > 46000, no candidate pair) in its words.  The lab switches
+ * RVD_LINKAGE_MB / _G / _XCHG / _COMPACT / _GLOBAL apply. */
+int rvb_test_pdist_nn(const double* X, int n, int d, double* D /* [n][n] */, int32_t* neighbor /* [n] */, double* min_dist /* [n] */);
+int rvb_test_centroid_linkage(const double* X, int n, int d, int workgroups, double* Z /* [n-1][4] */, int32_t* ran /* [4] */,
+                              double* retries);
 
 /* GEMM kernel selection / micro-benchmark hooks (tests and tuning only) */
 int rvb_test_set_gemm_variant(int variant /* 0 auto, 1 gemm.hip 128x128, 2 gemm2.hip 256x256 LDS-DMA */);

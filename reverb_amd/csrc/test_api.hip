@@ -1820,6 +1820,70 @@ extern "C" int rvb_test_emb_stem(int dtype, const float* fb, int64_t n_rows, con
   return down_bordered(dout, dtype, out, B, F, nfr, C, kSlack, "rvb_test_emb_stem");
 }
 
+// ---------------------------------------------------------------------------------------------- clustering (linkage.hip)
+// pdist + nn_init as centroid_linkage() launches them: X [n][d] fp64 -> D [n][n], neighbor [n], min_dist [n].  The three device
+// outputs start as all-ones bytes (NaN / -1) and come back whole, so an element no kernel wrote comes back as that (slot n - 1 of
+// neighbor and min_dist always does: nn_init's grid is n - 1).
+extern "C" int rvb_test_pdist_nn(const double* X, int n, int d, double* D, int32_t* neighbor, double* min_dist) {
+  if (!X || !D || !neighbor || !min_dist || n < 2 || d < 1 || n > 46000) { set_error("rvb_test_pdist_nn: bad argument"); return E_ARG; }
+  RVB_TRY(need_gpu());
+  Dev dX, dD, dN, dM;
+  RVB_TRY(up_raw(dX, X, (size_t)n * d * 8));
+  RVB_TRY(dD.alloc((size_t)n * n * 8));
+  RVB_TRY(dN.alloc((size_t)n * 4));
+  RVB_TRY(dM.alloc((size_t)n * 8));
+  RVB_HIP_CHECK(hipMemset(dD.p, 0xff, (size_t)n * n * 8));
+  RVB_HIP_CHECK(hipMemset(dN.p, 0xff, (size_t)n * 4));
+  RVB_HIP_CHECK(hipMemset(dM.p, 0xff, (size_t)n * 8));
+  RVB_TRY(pdist(nullptr, (const double*)dX.p, n, d, (double*)dD.p));
+  RVB_TRY(nn_init(nullptr, (const double*)dD.p, n, (int*)dN.p, (double*)dM.p));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  RVB_HIP_CHECK(hipMemcpy(D, dD.p, (size_t)n * n * 8, hipMemcpyDeviceToHost));
+  RVB_HIP_CHECK(hipMemcpy(neighbor, dN.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  RVB_HIP_CHECK(hipMemcpy(min_dist, dM.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+  return OK;
+}
+
+// centroid_linkage() without an engine: the allocations, the initial state and the 4096-byte control block of rvd_centroid_linkage
+// (diar_engine.hip), the status check and the slot-to-id conversion; `workgroups` as rvd_set_linkage_workgroups takes it.  ran [4] =
+// what centroid_linkage() reports (kernels.h); retries (nullable) = the merge loop's count of stale candidates it re-evaluated.  Z is
+// written only when the call succeeds.  The RVD_LINKAGE_* switches apply (this library reads them).
+extern "C" int rvb_test_centroid_linkage(const double* X, int n, int d, int workgroups, double* Z, int32_t* ran, double* retries) {
+  if (!X || !Z || !ran || n < 1 || d < 1) { set_error("rvb_test_centroid_linkage: bad argument"); return E_ARG; }
+  if (n > 46000) { set_error("rvb_test_centroid_linkage: more than 46000 points"); return E_UNSUPPORTED; }
+  if (!(workgroups == 0 || workgroups == 1 || workgroups == 2 || workgroups == 4 || workgroups == 8 || workgroups == 16)) {
+    set_error("rvb_test_centroid_linkage: workgroups: 0 (default), 1, 2, 4, 8 or 16");
+    return E_ARG;
+  }
+  ran[0] = ran[1] = ran[2] = ran[3] = 0;
+  if (retries) *retries = 0.0;
+  if (n == 1) return OK;
+  RVB_TRY(need_gpu());
+  Dev dX, dD, dI, dM, dZ, dC;
+  RVB_TRY(dC.alloc(4096));
+  RVB_TRY(up_raw(dX, X, (size_t)n * d * 8));
+  RVB_TRY(dD.alloc((size_t)n * n * 8));
+  std::vector<int> init((size_t)3 * n);     // [cluster_id | neighbor | size as uint16]
+  for (int i = 0; i < n; ++i) { init[i] = i; init[n + i] = -1; ((uint16_t*)&init[2 * (size_t)n])[i] = 1; }
+  std::vector<double> inf(n, INFINITY);
+  RVB_TRY(up_raw(dI, init.data(), init.size() * 4));
+  RVB_TRY(up_raw(dM, inf.data(), (size_t)n * 8));
+  RVB_TRY(dZ.alloc((size_t)(n - 1) * 4 * 8));
+  int r4[4] = {0, 0, 0, 0};
+  const int rc = centroid_linkage(nullptr, (const double*)dX.p, n, d, (double*)dD.p, (uint16_t*)((int*)dI.p + 2 * n), (int*)dI.p,
+                                  (int*)dI.p + n, (double*)dM.p, (double*)dZ.p, dC.p, workgroups, r4);
+  for (int i = 0; i < 4; ++i) ran[i] = r4[i];
+  if (rc != OK) { (void)hipDeviceSynchronize(); return rc; }
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  double status = 0.0;
+  RVB_HIP_CHECK(hipMemcpy(&status, (double*)dM.p + (n - 1), 8, hipMemcpyDeviceToHost));
+  if (status < 0.0) { set_error("rvb_test_centroid_linkage: the merge loop found no candidate pair (non-finite embeddings?)"); return E_ARG; }
+  if (retries) *retries = status;
+  RVB_HIP_CHECK(hipMemcpy(Z, dZ.p, (size_t)(n - 1) * 4 * 8, hipMemcpyDeviceToHost));
+  linkage_slots_to_ids(Z, n);
+  return OK;
+}
+
 // ---- hooks into the engine's host code (engine_impl.h, trie.h)
 // host only: the rescoring trie of given hypotheses (tests/test_search_native.py checks it against a Python trie).
 // tokens: the hypotheses back to back; lens / chunk_of: per hypothesis (chunk ids ascending).  Outputs sized by the caller:

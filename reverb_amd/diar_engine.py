@@ -143,7 +143,9 @@ class DiarEngine:
         return out[:n.value].copy()
 
     def set_linkage_workgroups(self, workgroups: int = 0):
-        """Workgroups the clustering's merge loop may take (0 default = 16, 1, 2, 4, 8, 16); the dendrogram does not depend on it."""
+        """Workgroups the clustering's merge loop may take (0 default = 16, 1, 2, 4, 8, 16).  The dendrogram does not depend on the count
+        from 2 up; 1 selects another loop, which gives the same dendrogram bit for bit on input without tied distances and an equally
+        valid one (every merge joins a closest pair) when distances tie -- there the two loops may take tied merges in another order."""
         _check(self.lib.rvd_set_linkage_workgroups(self._h, int(workgroups)), "rvd_set_linkage_workgroups")
 
     def emb_windows_per_pass(self) -> int:
