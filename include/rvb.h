@@ -159,6 +159,39 @@ int64_t rvb_audio_decode_i16(const void* data, int64_t nbytes, int channel, int1
  * resampled on the device when sample_rate != 16000; the fbank reads the float values as they are. */
 int rvb_upload_wave_f32(rvb_engine* e, const float* wave, int64_t n_samples, int sample_rate);
 
+/* Several recordings resident together: what the reference's bin/recognize.py does with a data set -- batches through the same
+ * model.decode -- for the users who transcribe thousands of short recordings.  N recordings cost one upload call, ONE fbank launch
+ * and ceil(chunks / max_chunks) rvb_encode calls, and each recording keeps the frames (snip_edges per recording: no frame reads a
+ * neighbour's samples), the chunks and the zero padding it has when uploaded alone, so its results are those of the single calls.
+ *
+ * rvb_batch_plan: host only, no engine.  The layout the other calls use, from the 16 kHz lengths n_samples [n_rec]: n_frames [n_rec],
+ * first_chunk [n_rec + 1] = the chunk row each recording starts at (first_chunk[n_rec] = all chunks; a recording under 400 samples
+ * has no frame and no chunk: equal neighbours) and, when asked for, lens [first_chunk[n_rec]] = the valid frames of every chunk
+ * (chunk_size, the recording's last chunk its remainder: feats_batcher, cli/reverb.py:148-180).  Call it once with lens = NULL to
+ * size lens.  chunk_size >= 7 (RVB_E_ARG); 1 <= n_rec <= 65 536 (more: RVB_E_UNSUPPORTED naming the cap).
+ *
+ * rvb_upload_batch: data[r] holds n_samples[r] mono samples, int16 (sample_format[r] == RVB_SAMPLE_I16) or float at int16 scale
+ * (RVB_SAMPLE_F32), at sample_rate[r] (1000 .. 384000; other than 16000: resampled on the device as rvb_upload_pcm_rate /
+ * rvb_upload_wave_f32 do, one launch per such recording).  16 kHz int16 recordings are packed into one int16 device buffer, float
+ * recordings and the resampler's outputs into one float buffer.  Returns when the copies have landed.  Every argument is checked
+ * before any device work (RVB_E_ARG naming the recording; the cap on n_rec as above).  A batch upload replaces a single upload
+ * and the other way round; while an rvb_upload_pcm_async upload is pending the call is refused (RVB_E_STATE).
+ * rvb_batch_n_samples: the 16 kHz lengths [n_rec] after resampling, which rvb_batch_plan needs.
+ *
+ * rvb_fbank_batch: one launch of the segmented fbank kernel over the live frames of all recordings; recording r's frame j goes to
+ * row first_chunk[r] * chunk_size + j of the resident features, every other row of its chunks is zero, and
+ * rvb_encode(e, NULL, first_chunk, lens, B, chunk_size, ...) then reads any chunk range, also one that crosses recordings.
+ * 7 <= chunk_size <= cfg.chunk_frames.  n_frames [n_rec] and first_chunk [n_rec + 1] are filled as by rvb_batch_plan; feats_out
+ * (nullable) receives all first_chunk[n_rec] * chunk_size rows of 80.  RVB_E_STATE, naming the right call: rvb_fbank_batch
+ * without rvb_upload_batch, and rvb_fbank or rvb_get_waveform on a batch. */
+int rvb_batch_plan(const int64_t* n_samples, int n_rec, int chunk_size, int64_t* n_frames /* [n_rec] */,
+                   int64_t* first_chunk /* [n_rec+1] */, int32_t* lens /* nullable [first_chunk[n_rec]] */);
+int rvb_upload_batch(rvb_engine* e, const void* const* data, const int32_t* sample_format, const int64_t* n_samples,
+                     const int32_t* sample_rate, int n_rec);
+int rvb_batch_n_samples(rvb_engine* e, int64_t* out /* [n_rec] */);
+int rvb_fbank_batch(rvb_engine* e, int chunk_size, float* feats_out /* nullable [total_chunks*chunk_size*80] */, int64_t* n_frames,
+                    int64_t* first_chunk);
+
 /* Chunk-masked encoder attention for the following rvb_encode calls: query frame i attends the encoder frames
  * [max((i/chunk - left)*chunk, 0), (i/chunk + 1)*chunk) -- what `decoding_chunk_size` / `num_decoding_left_chunks`
  * select in BaseEncoder.forward via add_optional_chunk_mask (encoder.py:140-145, utils/mask.py:86-197) for models

@@ -75,6 +75,10 @@ SIGNATURES = {
     "rvb_upload_pcm_rate": (C.c_int, [_eng, _i16p, C.c_int64, C.c_int]),
     "rvb_get_waveform": (C.c_int, [_eng, _f32p, _i64p]),
     "rvb_upload_wave_f32": (C.c_int, [_eng, _f32p, C.c_int64, C.c_int]),
+    "rvb_batch_plan": (C.c_int, [_i64p, C.c_int, C.c_int, _i64p, _i64p, _i32p]),
+    "rvb_upload_batch": (C.c_int, [_eng, C.POINTER(C.c_void_p), _i32p, _i64p, _i32p, C.c_int]),
+    "rvb_batch_n_samples": (C.c_int, [_eng, _i64p]),
+    "rvb_fbank_batch": (C.c_int, [_eng, C.c_int, _f32p, _i64p, _i64p]),
     "rvb_audio_probe": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(AudioInfo)]),
     "rvb_audio_decode_f32": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(AudioInfo)]),
     "rvb_audio_decode_i16": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int, _i16p, C.c_int64, C.c_int, C.POINTER(AudioInfo)]),
@@ -241,6 +245,7 @@ TEST_SIGNATURES = {
                                       _i32p, _i32p, _i32p, _i32p, _i32p]),
     "rvb_test_fbank": (C.c_int, [_i16p, C.c_int64, _f32p]),
     "rvb_test_fbank_ex": (C.c_int, [_i16p, _f32p, C.c_int64, _f32p]),
+    "rvb_test_fbank_batch": (C.c_int, [C.POINTER(C.c_void_p), _i32p, _i64p, _i64p, C.c_int, C.c_int, _f32p]),
     "rvb_test_set_gemm_variant": (C.c_int, [C.c_int]),
     "rvb_test_set_gemm2_opts": (C.c_int, [C.c_int, C.c_int]),
     "rvb_test_gemm_timeline": (C.c_int, [C.c_int] * 6 + [C.POINTER(C.c_longlong), C.c_int, _i32p]),

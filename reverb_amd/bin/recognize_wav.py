@@ -1,6 +1,7 @@
 """`reverb` console script: same flags and output files as the reference's
 `asr/wenet/bin/recognize_wav.py` (:29-147 flags, :150-208 main): one `<result_dir>/<mode>/<audio>.ctm`
-per decoding mode.  Extra flags: --dtype, --max_chunks."""
+per decoding mode.  Extra flags: --dtype, --max_chunks, and --audio_list FILE (one path per line) in place of --audio_file: every listed
+recording in one pass (ReverbASR.transcribe_modes_many), one `<result_dir>/<mode>/<stem>.ctm` each."""
 from __future__ import annotations
 
 import argparse
@@ -16,7 +17,9 @@ def get_args(argv=None):
     p.add_argument("--model", default=None, help="reverb model name or a directory with config.yaml and a .pt file")
     p.add_argument("--config", default=None, help="config file")
     p.add_argument("--checkpoint", default=None, help="checkpoint model")
-    p.add_argument("--audio_file", required=True, help="audio to transcribe")
+    p.add_argument("--audio_file", default=None, help="audio to transcribe")
+    p.add_argument("--audio_list", default=None, help="file with one audio path per line (blank lines and # comments skipped): "
+                   "all of them in one pass; exactly one of --audio_file / --audio_list")
     p.add_argument("--gpu", type=int, default=-1, help="gpu id for this rank, -1 means device 0")
     p.add_argument("--tokenizer-symbols", help="Path to tk.units.txt. Overrides the config path.")
     p.add_argument("--bpe-path", help="Path to tk.model. Overrides the config path.")
@@ -42,7 +45,31 @@ def get_args(argv=None):
     p.add_argument("--max_chunks", type=int, default=64, help="chunks per device batch")
     p.add_argument("--context_list_path", default=None, help="hot words to bias ctc_prefix_beam_search / attention_rescoring towards, one per line")
     p.add_argument("--context_graph_score", type=float, default=6.0, help="bonus per matched hot-word token")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if (args.audio_file is None) == (args.audio_list is None):
+        p.error("exactly one of --audio_file and --audio_list is required")
+    args.audio_files = None
+    if args.audio_list is not None:
+        try:
+            args.audio_files = read_audio_list(args.audio_list)
+        except (OSError, ValueError) as e:
+            p.error(str(e))
+    return args
+
+
+def read_audio_list(path):
+    """The paths of an --audio_list file.  Two entries with the same stem would write the same <stem>.ctm: refused."""
+    with open(path, encoding="utf-8") as f:
+        files = [line.strip() for line in f if line.strip() and not line.strip().startswith("#")]
+    if not files:
+        raise ValueError(f"{path}: no audio path listed")
+    seen = {}
+    for a in files:
+        stem = Path(a).with_suffix(".ctm").name
+        if stem in seen:
+            raise ValueError(f"{path}: {seen[stem]} and {a} would both be written to {stem}")
+        seen[stem] = a
+    return files
 
 
 def main(argv=None):
@@ -62,21 +89,24 @@ def main(argv=None):
                            tokenizer_symbols=args.tokenizer_symbols, bpe_path=args.bpe_path, gpu=args.gpu,
                            overwrite_cmvn=args.overwrite_cmvn, dtype=args.dtype, max_chunks=args.max_chunks,
                            context_path=args.context_list_path, context_score=args.context_graph_score)
-    outputs = reverb.transcribe_modes(
-        args.audio_file, args.modes, format="ctm", verbatimicity=args.verbatimicity, chunk_size=args.chunk_size,
-        batch_size=args.batch_size, beam_size=args.beam_size, decoding_chunk_size=args.decoding_chunk_size,
-        num_decoding_left_chunks=args.num_decoding_left_chunks, ctc_weight=args.ctc_weight,
-        simulate_streaming=args.simulate_streaming, reverse_weight=args.reverse_weight,
-        blank_penalty=args.blank_penalty, length_penalty=args.length_penalty,
-        timings_adjustment=args.timings_adjustment)
-    stem = Path(args.audio_file).with_suffix(".ctm").name
-    for mode, text in zip(args.modes, outputs):
-        out_dir = os.path.join(args.result_dir, mode)
-        os.makedirs(out_dir, exist_ok=True)
-        with open(os.path.join(out_dir, stem), "w", encoding="utf-8") as f:
-            f.write(text)
-        logging.info("wrote %s", os.path.join(out_dir, stem))
-
+    kw = dict(format="ctm", verbatimicity=args.verbatimicity, chunk_size=args.chunk_size,
+              batch_size=args.batch_size, beam_size=args.beam_size, decoding_chunk_size=args.decoding_chunk_size,
+              num_decoding_left_chunks=args.num_decoding_left_chunks, ctc_weight=args.ctc_weight,
+              simulate_streaming=args.simulate_streaming, reverse_weight=args.reverse_weight,
+              blank_penalty=args.blank_penalty, length_penalty=args.length_penalty,
+              timings_adjustment=args.timings_adjustment)
+    if args.audio_files is not None:
+        files, per_file = args.audio_files, reverb.transcribe_modes_many(args.audio_files, args.modes, **kw)
+    else:
+        files, per_file = [args.audio_file], [reverb.transcribe_modes(args.audio_file, args.modes, **kw)]
+    for audio_file, outputs in zip(files, per_file):
+        stem = Path(audio_file).with_suffix(".ctm").name
+        for mode, text in zip(args.modes, outputs):
+            out_dir = os.path.join(args.result_dir, mode)
+            os.makedirs(out_dir, exist_ok=True)
+            with open(os.path.join(out_dir, stem), "w", encoding="utf-8") as f:
+                f.write(text)
+            logging.info("wrote %s", os.path.join(out_dir, stem))
 
 if __name__ == "__main__":
     main()

@@ -293,6 +293,14 @@ struct rvb_engine {
   bool pcm_is_float = false;
   int dec_chunk = 0, dec_left = -1;   // encoder chunk mask (decoding_chunk_size / num_decoding_left_chunks), 0 = full context
   int64_t n_samples = 0, n_frames = 0, feat_rows = 0;
+  // rvb_upload_batch: several recordings resident together.  16 kHz int16 recordings are packed in `pcm`, float ones and the
+  // resampler's outputs in `wave_f32` (resampler inputs: `pcm` / `wave_in`); a single upload clears `batch` and vice versa
+  bool batch = false;
+  std::vector<int64_t> batch_n, batch_src;       // per recording: 16 kHz samples; element offset in the buffer the fbank reads
+  std::vector<int32_t> batch_is_float;
+  std::vector<int64_t> h_frame0;                 // host images of the descriptors of the last rvb_fbank_batch
+  std::vector<rvb::FbankRec> h_rec;
+  rvb::DevBuf d_frame0, d_rec;
 
   // ---- batch state ----
   int B = 0, T0 = 0, T1 = 0, F1 = 0, T2 = 0, F2 = 0, beam = 0;

@@ -161,6 +161,7 @@ static int resample_uploaded(rvb_engine* e, bool src_float, int64_t n, int sampl
   RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
   e->n_samples = n_out;
   e->pcm_is_float = true;
+  e->batch = false;
   return OK;
 }
 
@@ -252,7 +253,7 @@ void rvb_destroy(rvb_engine* e) {
   for (DevBuf* b : {&e->align_lp, &e->align_tv, &e->align_ti, &e->align_row, &e->align_col, &e->align_out}) b->release();
   e->d_xlse.release(); e->d_xsum.release(); e->d_xtop.release();
   e->atopv.release(); e->atopi.release(); e->d_stream_i32.release(); e->d_amax.release(); e->d_f8sat.release();
-  e->wave_f32.release(); e->wave_in.release(); e->rs_kernel.release();
+  e->wave_f32.release(); e->wave_in.release(); e->rs_kernel.release(); e->d_frame0.release(); e->d_rec.release();
   e->jlogp.release(); e->jpair_row.release(); e->jpair_tok.release(); e->jpair_out.release();
   for (auto& b : e->jkv) b.release();
   for (auto* v : {&e->stream_st.kv, &e->stream_st.kv2, &e->stream_st.cnn, &e->stream_st.cnn2}) for (auto& b : *v) b.release();
@@ -312,6 +313,7 @@ int rvb_upload_pcm(rvb_engine* e, const int16_t* pcm, int64_t n) {
   RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
   e->n_samples = n;
   e->pcm_is_float = false;
+  e->batch = false;
   return OK;
 }
 
@@ -385,11 +387,13 @@ int rvb_upload_wave_f32(rvb_engine* e, const float* wave, int64_t n, int sample_
   RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
   e->n_samples = n;
   e->pcm_is_float = true;
+  e->batch = false;
   return OK;
 }
 
 int rvb_get_waveform(rvb_engine* e, float* out, int64_t* n) {
   if (!e) { set_error("rvb_get_waveform: null engine"); return E_ARG; }
+  if (e->batch) { set_error("rvb_get_waveform: the engine holds a batch of recordings (rvb_upload_batch); rvb_batch_n_samples gives their lengths"); return E_STATE; }
   RVB_HIP_CHECK(hipSetDevice(e->device));
   if (n) *n = e->n_samples;
   if (!out || e->n_samples == 0) return OK;
@@ -413,7 +417,9 @@ int rvb_fbank(rvb_engine* e, float* feats_out, int64_t* n_frames) {
     e->n_samples = e->n_samples_next;
     e->pcm_is_float = false;
     e->pcm_pending = false;
+    e->batch = false;
   }
+  if (e->batch) { set_error("rvb_fbank: the engine holds a batch of recordings (rvb_upload_batch): call rvb_fbank_batch"); return E_STATE; }
   const int64_t nf = rvb_num_frames(e->n_samples);
   const int64_t T0 = e->cfg.chunk_frames;
   // zero padded so that ANY chunking with chunk_size <= chunk_frames finds whole chunks (feats_batcher pads the last

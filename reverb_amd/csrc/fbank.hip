@@ -21,28 +21,15 @@ namespace rvb {
 
 static constexpr int WIN = 400, SHIFT = 160, NFFT = 512, NBIN = 257, NMEL = 80;
 
-template <typename In>
-__global__ __launch_bounds__(256) void fbank_kernel(const In* __restrict__ pcm, int64_t n_frames,
-                                                    float* __restrict__ feats, FbankTables t) {
-  __shared__ float s_re[4][NFFT];
-  __shared__ float s_im[4][NFFT];
-  const int lane = threadIdx.x & 63;
-  const int w = threadIdx.x >> 6;
-  const int64_t frame = (int64_t)blockIdx.x * 4 + w;
-  const bool live = frame < n_frames;
-  float* re = s_re[w];
-  float* im = s_im[w];
-
-  // 1. load window, remove DC
-  float x[7];
+// One frame on one wave64: `x` holds the wave's 400 samples (lane + 64 i, zero past the window and in a wave without a frame), `re` /
+// `im` are the wave's own 512-float LDS rows, `out` the frame's 80 features.  Shared by fbank_kernel and fbank_batch_kernel, so
+// that both run the same arithmetic on the same samples.  Every wave of the block must call it: it holds the __syncthreads().
+__device__ __forceinline__ void fbank_frame(const float (&x)[7], bool live, int lane, float* re, float* im, float* out,
+                                            const FbankTables& t) {
+  // 1. remove DC
   float sum = 0.f;
-  const In* src = pcm + frame * SHIFT;
 #pragma unroll
-  for (int i = 0; i < 7; ++i) {
-    const int j = lane + 64 * i;
-    x[i] = (live && j < WIN) ? (float)src[j] : 0.f;
-    sum += x[i];
-  }
+  for (int i = 0; i < 7; ++i) sum += x[i];
   const float mean = wave_sum(sum) / (float)WIN;
 #pragma unroll
   for (int i = 0; i < 7; ++i) {
@@ -115,10 +102,69 @@ __global__ __launch_bounds__(256) void fbank_kernel(const In* __restrict__ pcm, 
         const float* wrow = t.mel_w + (size_t)m * NBIN;
         float acc = 0.f;
         for (int b = lo; b < hi; ++b) acc += re[b] * wrow[b];
-        feats[frame * NMEL + m] = logf(fmaxf(acc, 1.1920928955078125e-07f));
+        out[m] = logf(fmaxf(acc, 1.1920928955078125e-07f));
       }
     }
   }
+}
+
+// the wave's window: sample lane + 64 i of the 400 at `src`, read coalesced
+template <typename In>
+__device__ __forceinline__ void fbank_load(const In* __restrict__ src, bool live, int lane, float (&x)[7]) {
+#pragma unroll
+  for (int i = 0; i < 7; ++i) {
+    const int j = lane + 64 * i;
+    x[i] = (live && j < WIN) ? (float)src[j] : 0.f;
+  }
+}
+
+template <typename In>
+__global__ __launch_bounds__(256) void fbank_kernel(const In* __restrict__ pcm, int64_t n_frames,
+                                                    float* __restrict__ feats, FbankTables t) {
+  __shared__ float s_re[4][NFFT];
+  __shared__ float s_im[4][NFFT];
+  const int lane = threadIdx.x & 63;
+  const int w = threadIdx.x >> 6;
+  const int64_t frame = (int64_t)blockIdx.x * 4 + w;
+  const bool live = frame < n_frames;
+  float x[7];
+  fbank_load(pcm + frame * SHIFT, live, lane, x);
+  fbank_frame(x, live, lane, s_re[w], s_im[w], feats + frame * NMEL, t);
+}
+
+// Segmented form: the grid runs over the concatenated live frames of n_rec recordings.  frame0 [n_rec + 1] are the cumulative frame
+// counts (a recording under 400 samples has none: equal neighbours); each wave finds its recording by binary search -- the frame
+// index, hence the search and the descriptor reads, are the same in every lane of the wave, while the four waves of a block may
+// land in different recordings -- and reads its window from that recording's samples only: frames stop at recording boundaries
+// (Kaldi's snip_edges count per recording).  Rows that no frame writes (the tail of a recording's last chunk) are zeroed by the
+// launcher's memset ahead of the kernel.
+__global__ __launch_bounds__(256) void fbank_batch_kernel(const int16_t* __restrict__ pcm, const float* __restrict__ wave,
+                                                          const int64_t* __restrict__ frame0, const FbankRec* __restrict__ rec,
+                                                          int n_rec, float* __restrict__ feats, FbankTables t) {
+  __shared__ float s_re[4][NFFT];
+  __shared__ float s_im[4][NFFT];
+  const int lane = threadIdx.x & 63;
+  const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int64_t frame = (int64_t)blockIdx.x * 4 + w;
+  const bool live = frame < frame0[n_rec];
+  float x[7];
+  float* out = feats;
+  if (live) {                      // wave-uniform; no barrier inside
+    int lo = 0, hi = n_rec;        // frame0[lo] <= frame < frame0[hi]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (frame0[mid] <= frame) lo = mid; else hi = mid;
+    }
+    const FbankRec r = rec[lo];
+    const int64_t local = frame - frame0[lo];
+    out = feats + (r.row0 + local) * NMEL;
+    if (r.is_float) fbank_load(wave + r.src + local * SHIFT, true, lane, x);
+    else fbank_load(pcm + r.src + local * SHIFT, true, lane, x);
+  } else {
+#pragma unroll
+    for (int i = 0; i < 7; ++i) x[i] = 0.f;
+  }
+  fbank_frame(x, live, lane, s_re[w], s_im[w], out, t);
 }
 
 int fbank(hipStream_t s, const int16_t* pcm, int64_t n_frames, float* feats, const FbankTables& t) {
@@ -133,6 +179,17 @@ int fbank(hipStream_t s, const int16_t* pcm, int64_t n_frames, float* feats, con
 int fbank_f32(hipStream_t s, const float* wave, int64_t n_frames, float* feats, const FbankTables& t) {
   if (n_frames <= 0) return OK;
   hipLaunchKernelGGL(fbank_kernel<float>, dim3(cdiv(n_frames, 4)), dim3(256), 0, s, wave, n_frames, feats, t);
+  RVB_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
+// rows [0, n_rows) of feats are zeroed first (the padding rows lie scattered between the recordings; the live rows are written twice),
+// then one launch over the total_frames live frames
+int fbank_batch(hipStream_t s, const int16_t* pcm, const float* wave, const int64_t* frame0, const FbankRec* rec, int n_rec,
+                int64_t total_frames, float* feats, int64_t n_rows, const FbankTables& t) {
+  if (n_rows > 0) RVB_HIP_CHECK(hipMemsetAsync(feats, 0, (size_t)n_rows * NMEL * 4, s));
+  if (total_frames <= 0 || n_rec <= 0) return OK;
+  hipLaunchKernelGGL(fbank_batch_kernel, dim3(cdiv(total_frames, 4)), dim3(256), 0, s, pcm, wave, frame0, rec, n_rec, feats, t);
   RVB_HIP_CHECK(hipGetLastError());
   return OK;
 }

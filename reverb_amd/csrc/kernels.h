@@ -68,6 +68,18 @@ struct FbankTables {
 // pcm: int16 mono (device).  feats: fp32 [n_frames, 80] raw log-mel.
 int fbank(hipStream_t s, const int16_t* pcm, int64_t n_frames, float* feats, const FbankTables& t);
 int fbank_f32(hipStream_t s, const float* wave, int64_t n_frames, float* feats, const FbankTables& t);
+// The same for several recordings in one launch (rvb_fbank_batch).  Recording r has frames [frame0[r], frame0[r + 1]) of the launch;
+// its samples start at element rec[r].src of `pcm` (int16) or, with rec[r].is_float, of `wave` (float at int16 scale); its frame j
+// goes to row rec[r].row0 + j of feats.  frame0 [n_rec + 1] and rec [n_rec] are device arrays.  Rows [0, n_rows) of feats that no
+// frame writes are zero afterwards.
+struct FbankRec {
+  int64_t src;
+  int64_t row0;
+  int32_t is_float;
+  int32_t reserved;
+};
+int fbank_batch(hipStream_t s, const int16_t* pcm, const float* wave, const int64_t* frame0, const FbankRec* rec, int n_rec,
+                int64_t total_frames, float* feats, int64_t n_rows, const FbankTables& t);
 // torchaudio.functional.resample's kernel (sinc_interp_hann, lowpass_filter_width 6, rolloff 0.99) for sample_rate -> target,
 // built in fp64 on the host: ker [new][K], K = 2 * width + orig, with orig / new the rates divided by their gcd
 void resample_taps(int sample_rate, int target, std::vector<float>* ker, int* orig, int* new_, int* width, int* K);

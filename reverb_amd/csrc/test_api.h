@@ -242,6 +242,13 @@ int rvb_test_fbank(const int16_t* pcm, int64_t n_samples, float* feats /* [frame
  * buffer starts as all-ones bytes and comes back whole, so the four rows after the last frame show whether anything was written
  * past it (n_samples < 400: no frame, no launch, four sentinel rows). */
 int rvb_test_fbank_ex(const int16_t* pcm, const float* wave, int64_t n_samples, float* feats /* [frames + 4][80] */);
+/* fbank_batch (the segmented kernel behind rvb_fbank_batch, with its memset) on caller-given recordings: data[r] holds n_samples[r]
+ * int16 (sample_format RVB_SAMPLE_I16) or float (RVB_SAMPLE_F32) samples at 16 kHz, placed at element offset[r] of the packed device
+ * buffer of its format (NULL: packed back to back; each buffer is allocated to exactly the last sample any recording covers).  feats
+ * [total_chunks * chunk_size + 4][80] in the layout of rvb_batch_plan; the four rows behind the last chunk are sentinels (all-ones
+ * bytes) that the launch must leave alone.  Overlapping or negative offsets are refused (RVB_E_ARG) before any device work. */
+int rvb_test_fbank_batch(const void* const* data, const int32_t* sample_format, const int64_t* n_samples, const int64_t* offset, int n_rec,
+                         int chunk_size, float* feats);
 /* native prefix beam search on host arrays: top-k log-probs/indices [T,beam] of one utterance */
 int rvb_test_prefix_beam(const float* topk_val, const int32_t* topk_idx, int T, int beam, int blank,
                          int32_t* n_hyps, int32_t* tokens /* [beam][T] */, int32_t* lens, int32_t* times,

@@ -1979,6 +1979,60 @@ extern "C" int rvb_test_fbank_ex(const int16_t* pcm, const float* wave, int64_t 
   return r;
 }
 
+extern "C" int rvb_test_fbank_batch(const void* const* data, const int32_t* sample_format, const int64_t* n_samples, const int64_t* offset,
+                                    int n_rec, int chunk_size, float* feats) {
+  if (!data || !sample_format || !n_samples || !feats || n_rec <= 0 || n_rec > 65536 || chunk_size < 7) { set_error("rvb_test_fbank_batch: bad argument"); return E_ARG; }
+  std::vector<int64_t> off(n_rec), nfr(n_rec), first(n_rec + 1), frame0(n_rec + 1);
+  std::vector<FbankRec> rec(n_rec);
+  int64_t end[2] = {0, 0};               // elements of the int16 / the float buffer
+  for (int r = 0; r < n_rec; ++r) {
+    if ((sample_format[r] != RVB_SAMPLE_I16 && sample_format[r] != RVB_SAMPLE_F32) || n_samples[r] < 0 || (!data[r] && n_samples[r] > 0)) {
+      set_error("rvb_test_fbank_batch: bad recording " + std::to_string(r)); return E_ARG;
+    }
+    const int k = sample_format[r] == RVB_SAMPLE_F32;
+    off[r] = offset ? offset[r] : end[k];
+    if (off[r] < end[k]) { set_error("rvb_test_fbank_batch: offsets must not be negative, overlap or go backwards (recording " + std::to_string(r) + ")"); return E_ARG; }
+    end[k] = off[r] + n_samples[r];
+  }
+  RVB_TRY(rvb_batch_plan(n_samples, n_rec, chunk_size, nfr.data(), first.data(), nullptr));
+  for (int r = 0; r < n_rec; ++r) {
+    frame0[r] = r ? frame0[r - 1] + nfr[r - 1] : 0;
+    rec[r] = FbankRec{off[r], first[r] * chunk_size, sample_format[r] == RVB_SAMPLE_F32 ? 1 : 0, 0};
+  }
+  frame0[n_rec] = frame0[n_rec - 1] + nfr[n_rec - 1];
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: librvb has no CPU fallback"); return E_HIP; }
+  rvb_engine e;   // default stream, only the fbank tables are used
+  RVB_TRY(make_fbank_tables(&e));
+  const int64_t rows = first[n_rec] * chunk_size;
+  const size_t out_bytes = (size_t)(rows + 4) * 80 * 4;
+  void *d16 = nullptr, *d32 = nullptr, *dfr = nullptr, *drec = nullptr;     // exactly the bytes: a read past the end is a read past the allocation
+  DevBuf df;
+  int r = df.ensure(out_bytes);
+  auto fail = [&](const char* what) { set_error(std::string("rvb_test_fbank_batch: ") + what); return E_HIP; };
+  if (r == OK && end[0] && hipMalloc(&d16, (size_t)end[0] * 2) != hipSuccess) r = fail("hipMalloc failed");
+  if (r == OK && end[1] && hipMalloc(&d32, (size_t)end[1] * 4) != hipSuccess) r = fail("hipMalloc failed");
+  if (r == OK && (hipMalloc(&dfr, frame0.size() * 8) != hipSuccess || hipMalloc(&drec, rec.size() * sizeof(FbankRec)) != hipSuccess)) r = fail("hipMalloc failed");
+  for (int i = 0; r == OK && i < n_rec; ++i) {
+    if (!n_samples[i]) continue;
+    const bool f32 = sample_format[i] == RVB_SAMPLE_F32;
+    void* dst = f32 ? (void*)((float*)d32 + off[i]) : (void*)((int16_t*)d16 + off[i]);
+    if (hipMemcpy(dst, data[i], (size_t)n_samples[i] * (f32 ? 4 : 2), hipMemcpyHostToDevice) != hipSuccess) r = fail("upload failed");
+  }
+  if (r == OK && (hipMemcpy(dfr, frame0.data(), frame0.size() * 8, hipMemcpyHostToDevice) != hipSuccess ||
+                  hipMemcpy(drec, rec.data(), rec.size() * sizeof(FbankRec), hipMemcpyHostToDevice) != hipSuccess)) r = fail("upload failed");
+  if (r == OK && hipMemset(df.p, 0xff, out_bytes) != hipSuccess) r = fail("memset failed");
+  FbankTables t{e.fb_window.as<float>(), e.fb_twiddle.as<float>(), e.fb_melw.as<float>(), e.fb_lo.as<int>(), e.fb_hi.as<int>()};
+  if (r == OK) r = fbank_batch(nullptr, (const int16_t*)d16, (const float*)d32, (const int64_t*)dfr, (const FbankRec*)drec, n_rec, frame0[n_rec],
+                               df.as<float>(), rows, t);
+  if (r == OK && hipDeviceSynchronize() != hipSuccess) r = fail("fbank_batch kernel failed");
+  if (r == OK && hipMemcpy(feats, df.p, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) r = fail("download failed");
+  for (void* q : {d16, d32, dfr, drec}) if (q) (void)hipFree(q);
+  df.release();
+  for (DevBuf* b : {&e.fb_window, &e.fb_twiddle, &e.fb_melw, &e.fb_lo, &e.fb_hi}) b->release();
+  return r;
+}
+
 extern "C" int rvb_test_fbank(const int16_t* pcm, int64_t n_samples, float* feats) {
   if (!pcm || !feats || n_samples < 0) { set_error("rvb_test_fbank: null argument"); return E_ARG; }
   const int64_t nf = rvb_num_frames(n_samples);

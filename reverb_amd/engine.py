@@ -174,6 +174,7 @@ class Engine:
         """Mono waveform -> HBM; other rates than 16 kHz are resampled on the device (reverb.py:128-134).  int16 PCM stays
         int16; a float32 array (the `.to(torch.float)` of a source whose native format is not int16) is uploaded as it is."""
         self._n_samples_next = None             # a synchronous upload replaces a pending upload_pcm_async
+        self._batch_n = self._batch_plan = None # ... and a batch
         if isinstance(pcm, np.ndarray) and pcm.dtype.kind == "f":
             wave = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
             check(self.lib.rvb_upload_wave_f32(self.handle, wave.ctypes.data_as(_lib._f32p), len(wave), int(sample_rate)),
@@ -295,6 +296,75 @@ class Engine:
         check(self.lib.rvb_fbank(self.handle, fptr(out), C.byref(n)), "rvb_fbank")
         self.n_frames = int(n.value)
         return (self.n_frames, out) if return_feats else self.n_frames
+
+    # -------------------------------------------------------------------------------- several recordings at once
+    def upload_batch(self, items):
+        """Several recordings resident together (rvb_upload_batch): items = [(waveform, sample_rate)], each mono int16 PCM or float32
+        at int16 scale, at any rate upload_pcm takes.  Replaces whatever was uploaded before; fbank_batch() / decode_batch() follow.
+        -> the 16 kHz lengths (after resampling)."""
+        items = list(items)
+        if not items:
+            raise RvbError("upload_batch: at least one recording")
+        waves = []
+        for w, _ in items:
+            w = np.asarray(w)
+            waves.append(np.ascontiguousarray(w, np.float32 if w.dtype.kind == "f" else np.int16).reshape(-1))
+        n = len(waves)
+        data = (C.c_void_p * n)(*[w.ctypes.data for w in waves])
+        fmt = np.array([4 if w.dtype == np.float32 else 2 for w in waves], np.int32)          # RVB_SAMPLE_F32 / RVB_SAMPLE_I16
+        ns = np.array([len(w) for w in waves], np.int64)
+        rate = np.array([int(r) for _, r in items], np.int32)
+        self._n_samples_next = None
+        self._batch_n = self._batch_plan = None
+        check(self.lib.rvb_upload_batch(self.handle, data, iptr(fmt), ns.ctypes.data_as(_lib._i64p), iptr(rate), n), "rvb_upload_batch")
+        out = np.empty(n, np.int64)
+        check(self.lib.rvb_batch_n_samples(self.handle, out.ctypes.data_as(_lib._i64p)), "rvb_batch_n_samples")
+        self._batch_n = out
+        return out
+
+    def batch_plan(self, n_samples, chunk_size: int):
+        """rvb_batch_plan (host only): 16 kHz lengths -> (n_frames [n], first_chunk [n + 1], lens [chunks])."""
+        ns = np.ascontiguousarray(n_samples, np.int64).reshape(-1)
+        p64 = lambda a: a.ctypes.data_as(_lib._i64p)
+        nf, first = np.empty(len(ns), np.int64), np.empty(len(ns) + 1, np.int64)
+        check(self.lib.rvb_batch_plan(p64(ns), len(ns), int(chunk_size), p64(nf), p64(first), None), "rvb_batch_plan")
+        lens = np.empty(int(first[-1]), np.int32)
+        check(self.lib.rvb_batch_plan(p64(ns), len(ns), int(chunk_size), p64(nf), p64(first), iptr(lens)), "rvb_batch_plan")
+        return nf, first, lens
+
+    def fbank_batch(self, chunk_size: int, return_feats: bool = False):
+        """Kaldi fbank of every recording of upload_batch() in one launch; recording r's frames start at row first_chunk[r] *
+        chunk_size of the resident features and stop at its own last sample, the rest of its last chunk is zero.  -> (n_frames [n],
+        first_chunk [n + 1]) and, when asked, the (first_chunk[n] * chunk_size, 80) float32 rows."""
+        if getattr(self, "_batch_n", None) is None:
+            n, ff = C.c_int64(0), C.c_int64(0)              # no batch: the library says which call is missing
+            check(self.lib.rvb_fbank_batch(self.handle, int(chunk_size), None, C.byref(n), C.byref(ff)), "rvb_fbank_batch")
+        p64 = lambda a: a.ctypes.data_as(_lib._i64p)
+        nf, first, lens = self.batch_plan(self._batch_n, chunk_size)
+        out = np.empty((int(first[-1]) * int(chunk_size), 80), np.float32) if return_feats else None
+        check(self.lib.rvb_fbank_batch(self.handle, int(chunk_size), fptr(out), p64(nf), p64(first)), "rvb_fbank_batch")
+        self._batch_plan = (int(chunk_size), nf, first, lens)
+        return (nf, first, out) if return_feats else (nf, first)
+
+    def decode_batch(self, modes, chunk_size: int, beam_size: int, ctc_weight: float, reverse_weight: float,
+                     blank_penalty: float = 0.0, length_penalty: float = 0.0) -> List[Dict[str, List[DecodeResult]]]:
+        """decode_resident() over every chunk of the batch, `max_chunks` chunks per encode whichever recordings they belong to (a
+        recording whose chunks fall into two encodes is the normal case) -> per recording {mode: [DecodeResult per chunk]}."""
+        if not 7 <= chunk_size <= self.cfg.chunk_frames:
+            raise RvbError(f"resident decoding needs 7 <= chunk_size <= engine chunk_frames ({self.cfg.chunk_frames}); "
+                           "ReverbASR rebuilds the engine for larger chunks")
+        plan = getattr(self, "_batch_plan", None)
+        if plan is None or plan[0] != int(chunk_size):
+            self.fbank_batch(chunk_size)
+        _, _, first, lens = self._batch_plan
+        flat: Dict[str, List[DecodeResult]] = {m: [] for m in modes}
+        for s in range(0, len(lens), self.cfg.max_chunks):
+            e = min(len(lens), s + self.cfg.max_chunks)
+            self.encode(None, lens[s:e], beam_size, blank_penalty, first_chunk=s, T0=chunk_size, topk=joint_topk(modes, beam_size))
+            part = self.search(modes, ctc_weight, reverse_weight, length_penalty)
+            for m in modes:
+                flat[m].extend(part[m])
+        return [{m: flat[m][int(first[r]):int(first[r + 1])] for m in modes} for r in range(len(first) - 1)]
 
     # -------------------------------------------------------------------------------- decode
     def encode(self, feats: Optional[np.ndarray], lens, beam: int, blank_penalty: float = 0.0, first_chunk: int = 0,

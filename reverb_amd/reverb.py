@@ -510,6 +510,99 @@ class ReverbASR:
         return self.engine.decode_resident(n_frames, modes, chunk_size, beam_size, ctc_weight, reverse_weight,
                                            blank_penalty, length_penalty)
 
+    def _item_duration(self, item) -> float:
+        """seconds of one transcribe_modes_many item, from the file's header or the waveform's length"""
+        if isinstance(item, (tuple, list)):
+            return np.asarray(item[0]).size / float(item[1])
+        with open(item, "rb") as f:                       # the whole file: a clipped image would probe as a shorter recording
+            info = audio.probe_bytes(f.read())
+        return info.frames / float(max(info.sample_rate, 1))
+
+    def _load_item(self, item):
+        if isinstance(item, (tuple, list)):
+            wave = np.asarray(item[0])
+            return (wave[0] if wave.ndim == 2 else wave), int(item[1])
+        return self._load_pcm(item, 16000)
+
+    def transcribe_modes_many(self, audio_files, modes: List[str], format: str = "txt", verbatimicity: float = 1.0,
+                              chunk_size: int = 2051, batch_size: int = 1, beam_size: int = 10, decoding_chunk_size: int = -1,
+                              num_decoding_left_chunks: int = -1, ctc_weight: float = 0.1, simulate_streaming: bool = False,
+                              reverse_weight: float = 0.0, blank_penalty: float = 0.0, length_penalty: float = 0.0,
+                              timings_adjustment: float = 230, group_seconds: float = 3600.0, load_threads: int = 8,
+                              errors: str = "raise") -> list:
+        """transcribe_modes for many recordings in one pass (the reference's bin/recognize.py decodes a data set in batches through
+        the same model.decode): -> list[list[str]] indexed [recording][mode].  Items are paths or (waveform, sample_rate) pairs
+        (mono int16, or float32 at int16 scale; the CTM name of a pair is its index in the list).  Output i is string-equal to
+        transcribe_modes(audio_files[i], ...): every recording keeps its own frames, chunks and padding, so a recording without a
+        frame gives "".  verbatimicity, the context graph and decoding_chunk_size apply to the whole call.
+        Recordings are taken in order into groups of at most group_seconds of audio (plan_groups); a group costs one upload, one
+        fbank launch and ceil(chunks / max_chunks) encodes, and while it decodes the next group's files are read and decoded on
+        load_threads host threads (at most 16).  errors="raise": a file that cannot be read raises, naming it, before any decode of
+        its group; "skip": its place in the result holds None and its name is logged.
+        fp8 engines are allowed but outside the identity promise: their activation scales come from the first batch they see."""
+        from concurrent.futures import ThreadPoolExecutor
+        if simulate_streaming:
+            raise NotImplementedError("transcribe_modes_many does not simulate streaming: use transcribe / transcribe_modes per file")
+        if errors not in ("raise", "skip"):
+            raise ValueError("errors must be 'raise' or 'skip'")
+        fc = self.test_conf["fbank_conf"]
+        if (fc["num_mel_bins"], fc["frame_length"], fc["frame_shift"]) != (80, 25, 10):
+            raise NotImplementedError("the device fbank is built for 80 bins / 25 ms / 10 ms")
+        if chunk_size < 7:
+            raise ValueError("chunk_size must be at least 7 frames (Conv2dSubsampling4 needs 7 input frames, subsampling.py:201-226)")
+        items = list(audio_files)
+        out: list = [None] * len(items)
+        if not items:
+            return out
+        eng = self._engine_for_chunk(chunk_size)
+        eng.set_cat_embs([verbatimicity, 1.0 - verbatimicity])
+        eng.set_context_graph(self.context_graph)
+        eng.apply_decoding_chunk(decoding_chunk_size, num_decoding_left_chunks)
+
+        def duration(item):
+            try:
+                return self._item_duration(item)
+            except (OSError, ValueError, NotImplementedError) as e:
+                return e
+        with ThreadPoolExecutor(max_workers=max(1, min(int(load_threads), 16))) as pool:
+            durations, bad = list(pool.map(duration, items)), set()
+            for i, d in enumerate(durations):
+                if isinstance(d, Exception):
+                    if errors == "raise":
+                        raise type(d)(f"{items[i]}: {d}") from None
+                    logging.warning("skipping %s: %s", items[i], d)
+                    bad.add(i)
+                    durations[i] = 0.0
+            groups = [[i for i in g if i not in bad] for g in plan_groups(durations, group_seconds)]
+            groups = [g for g in groups if g]
+            submit = lambda g: [pool.submit(self._load_item, items[i]) for i in g]
+            pending = submit(groups[0]) if groups else []
+            for k, g in enumerate(groups):
+                futures, pending = pending, (submit(groups[k + 1]) if k + 1 < len(groups) else [])
+                loaded = []
+                for i, fut in zip(g, futures):
+                    try:
+                        loaded.append((i, fut.result()))
+                    except (OSError, ValueError, NotImplementedError) as e:
+                        if errors == "raise":
+                            for p in pending:
+                                p.cancel()
+                            raise type(e)(f"{items[i]}: {e}") from None
+                        logging.warning("skipping %s: %s", items[i], e)
+                if not loaded:
+                    continue
+                eng.upload_batch([w for _, w in loaded])
+                hyps = eng.decode_batch(modes, chunk_size, beam_size, ctc_weight, reverse_weight, blank_penalty, length_penalty)
+                for (i, _), h in zip(loaded, hyps):
+                    name = str(i) if isinstance(items[i], (tuple, list)) else Path(items[i]).name
+                    out[i] = [get_output(format, self.tokenizer, name, h[mode], timings_adjustment, chunk_size,
+                                         self.input_frame_length, self.output_frame_length) for mode in modes]
+        return out
+
+    def transcribe_many(self, audio_files, mode: str = "ctc_prefix_beam_search", **kwargs) -> list:
+        """transcribe for many recordings in one pass -> list[str] (None for a skipped file): transcribe_modes_many with one mode."""
+        return [None if r is None else r[0] for r in self.transcribe_modes_many(audio_files, [mode], **kwargs)]
+
     def transcribe(self, audio_file, mode: str = "ctc_prefix_beam_search", format: str = "txt",
                    verbatimicity: float = 1.0, chunk_size: int = 2051, batch_size: int = 1, beam_size: int = 10,
                    decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1, ctc_weight: float = 0.1,
@@ -521,6 +614,22 @@ class ReverbASR:
             num_decoding_left_chunks=num_decoding_left_chunks, ctc_weight=ctc_weight,
             simulate_streaming=simulate_streaming, reverse_weight=reverse_weight, blank_penalty=blank_penalty,
             length_penalty=length_penalty, timings_adjustment=timings_adjustment)[0]
+
+
+def plan_groups(durations, group_seconds: float) -> List[List[int]]:
+    """Recordings, in order, into groups of at most group_seconds of audio: -> lists of indices, each index exactly once, order kept.
+    A recording longer than the budget is a group of its own."""
+    groups, cur, total = [], [], 0.0
+    for i, d in enumerate(durations):
+        d = float(d)
+        if cur and total + d > group_seconds:
+            groups.append(cur)
+            cur, total = [], 0.0
+        cur.append(i)
+        total += d
+    if cur:
+        groups.append(cur)
+    return groups
 
 
 def load_cmvn(cmvn_file: str, is_json: bool):
