@@ -68,6 +68,17 @@ int rvd_frames_per_window(const rvd_engine* e);
 
 /* 16-bit mono PCM at cfg.sample_rate -> HBM; evaluates the sinc filter bank once for all windows */
 int rvd_upload_pcm(rvd_engine* e, const int16_t* pcm, int64_t n_samples);
+/* n_rec recordings in one upload and one front-end pass, packed so that the kernels see one long recording.  Recording r has
+ * W_r = rvd_num_windows(n_samples[r]) windows and takes (W_r + window_samples / step_samples - 1) * step_samples samples (its own
+ * zero-padded length) from sample first_window[r] * step_samples on: its window w is GLOBAL window first_window[r] + w, which is
+ * the index rvd_segment_windows, rvd_embed and rvd_get_emb_fbank take, and every such window sees exactly the samples and zeros it
+ * sees after rvd_upload_pcm of that recording alone (results are bit-identical).  The window_samples / step_samples - 1 global
+ * indices between two recordings straddle a boundary: never list them.  *total_windows = one past the last valid global index.  A
+ * recording of 0 samples has no windows and takes no space (its first_window is that of the next recording).  n_rec < 1, a null
+ * pointer for a non-empty recording or a negative length: RVB_E_ARG.  rvd_rerun_resident afterwards reruns the packed front end;
+ * rvd_upload_pcm returns the engine to a single recording. */
+int rvd_upload_pcm_many(rvd_engine* e, const int16_t* const* pcm, const int64_t* n_samples, int n_rec,
+                        int64_t* first_window /* [n_rec] */, int64_t* total_windows);
 /* the recording of the last rvd_upload_pcm is still resident in HBM: run its front end again (everything rvd_upload_pcm does
  * behind the copy -- waveform, sinc filter bank, embedding fbank).  For callers that keep a recording on the device and for
  * bench_diar.py, whose timed step starts from HBM-resident samples as the ASR bench's does (the reference has no counterpart:
@@ -81,6 +92,10 @@ int rvd_resample_pcm(rvd_engine* e, const int16_t* pcm, int64_t n_samples, int s
 /* segmentation model on windows [first, first+n): logp_out host fp32 [n][frames][num_classes] (NULL: keep the
  * result on the device only) */
 int rvd_segment(rvd_engine* e, int64_t first_window, int n_windows, float* logp_out);
+/* rvd_segment over a window LIST: row i of the result (and of what rvd_get_classes / rvd_get_tap return afterwards) is window
+ * windows[i] (after rvd_upload_pcm_many: a global index).  An index outside the uploaded audio is refused before anything runs.
+ * A window's result does not depend on the call or the row it is computed in. */
+int rvd_segment_windows(rvd_engine* e, const int64_t* windows, int n, float* logp_out);
 /* argmax powerset class of every frame of the last rvd_segment (what Powerset.to_multilabel(soft=False) needs):
  * out host uint8 [n][frames] */
 int rvd_get_classes(rvd_engine* e, uint8_t* out);
@@ -97,6 +112,13 @@ int rvd_get_emb_fbank(rvd_engine* e, int64_t window, float* out, int32_t* n_fram
  * metric="euclidean") returns for X host fp64 [n][d] -- Z host fp64 [n-1][4] (id_a, id_b, distance, size),
  * rows in merge order, cluster n+k created by row k.  fp64 throughout. */
 int rvd_centroid_linkage(rvd_engine* e, const double* X, int n, int d, double* Z);
+/* rvd_centroid_linkage for many point sets at once: X host fp64 [sum n][d], the problems back to back; n [n_problems]; Z host fp64
+ * [sum max(n - 1, 0)][4], back to back, cluster ids per problem (0 .. 2 n[p] - 2).  Problems of fewer than 3 000 points share one
+ * device allocation, one distance-matrix launch, one nearest-neighbour launch and one merge-loop launch in which every problem
+ * has a workgroup of its own; each dendrogram is what rvd_centroid_linkage gives for that problem with one workgroup
+ * (rvd_set_linkage_workgroups(e, 1)), bit for bit.  Larger problems go through rvd_centroid_linkage one by one.  n[p] < 2 gives no
+ * rows.  A problem in which no pair can be merged (non-finite points) fails the call with RVB_E_ARG; the message names its index. */
+int rvd_centroid_linkage_many(rvd_engine* e, const double* X, const int32_t* n, int n_problems, int d, double* Z);
 /* How many workgroups the merge loop of rvd_centroid_linkage may take (it is persistent: its workgroups keep their CUs for the
  * whole clustering): 0 = default (16 workgroups of one XCD from 3 000 points on), 1 = one workgroup, 2 / 4 / 8 / 16.  The
  * dendrogram does not depend on it.  A pipeline that clusters UNDERNEATH another engine's kernels (transcribe_diarize: the ASR

@@ -271,6 +271,7 @@ TEST_SIGNATURES = {
                                     _f32p, _f32p]),
     "rvb_test_pdist_nn": (C.c_int, [_f64p, C.c_int, C.c_int, _f64p, _i32p, _f64p]),
     "rvb_test_centroid_linkage": (C.c_int, [_f64p, C.c_int, C.c_int, C.c_int, _f64p, _i32p, _f64p]),
+    "rvb_test_centroid_linkage_many": (C.c_int, [_f64p, _i32p, C.c_int, C.c_int, _f64p, _i32p]),
 }
 
 
@@ -294,14 +295,17 @@ DIAR_SIGNATURES = {
     "rvd_num_windows": (C.c_int64, [_eng, C.c_int64]),
     "rvd_frames_per_window": (C.c_int, [_eng]),
     "rvd_upload_pcm": (C.c_int, [_eng, _i16p, C.c_int64]),
+    "rvd_upload_pcm_many": (C.c_int, [_eng, C.POINTER(_i16p), _i64p, C.c_int, _i64p, _i64p]),
     "rvd_rerun_resident": (C.c_int, [_eng]),
     "rvd_resample_pcm": (C.c_int, [_eng, _i16p, C.c_int64, C.c_int, _i16p, _i64p]),
     "rvd_segment": (C.c_int, [_eng, C.c_int64, C.c_int, _f32p]),
+    "rvd_segment_windows": (C.c_int, [_eng, _i64p, C.c_int, _f32p]),
     "rvd_get_classes": (C.c_int, [_eng, C.POINTER(C.c_uint8)]),
     "rvd_get_tap": (C.c_int, [_eng, C.c_char_p, _f32p]),
     "rvd_embed": (C.c_int, [_eng, _i64p, _f32p, C.c_int, _f32p]),
     "rvd_get_emb_fbank": (C.c_int, [_eng, C.c_int64, _f32p, _i32p]),
     "rvd_centroid_linkage": (C.c_int, [_eng, _f64p, C.c_int, C.c_int, _f64p]),
+    "rvd_centroid_linkage_many": (C.c_int, [_eng, _f64p, _i32p, C.c_int, C.c_int, _f64p]),
     "rvd_set_linkage_workgroups": (C.c_int, [_eng, C.c_int]),
     "rvd_get_emb_fp8": (C.c_int, [_eng, _i32p, _f32p, _i32p, C.POINTER(C.c_uint32)]),
     "rvd_set_emb_fp8_scales": (C.c_int, [_eng, _f32p, C.c_int32]),

@@ -198,9 +198,9 @@ __device__ inline double block_sum_d(double v, double* red) {
 }
 
 __global__ __launch_bounds__(256) void window_stats_kernel(const float* __restrict__ wave, int64_t first, int64_t step, int len,
-                                                           float eps, float* __restrict__ stats) {
+                                                           float eps, float* __restrict__ stats, const int64_t* __restrict__ win) {
   __shared__ double red[4];
-  const float* x = wave + (first + blockIdx.x) * step;
+  const float* x = wave + (win ? win[blockIdx.x] : first + blockIdx.x) * step;      // win: block b is window win[b] (rvd_segment_windows)
   double s = 0.0, ss = 0.0;
   for (int i = threadIdx.x * 4; i < len; i += 256 * 4) {
     if (i + 4 <= len) {
@@ -221,10 +221,11 @@ __global__ __launch_bounds__(256) void window_stats_kernel(const float* __restri
     stats[2 * blockIdx.x + 1] = (float)(1.0 / sqrt(var + (double)eps));
   }
 }
-int window_stats(hipStream_t s, const float* wave, int64_t first, int nwin, int64_t step, int len, float eps, float* stats) {
+int window_stats(hipStream_t s, const float* wave, int64_t first, int nwin, int64_t step, int len, float eps, float* stats,
+                 const int64_t* win) {
   if (nwin <= 0) return OK;
   if (step % 4) { set_error("window_stats: step must be a multiple of 4 samples"); return E_ARG; }
-  hipLaunchKernelGGL(window_stats_kernel, dim3(nwin), dim3(256), 0, s, wave, first, step, len, eps, stats);
+  hipLaunchKernelGGL(window_stats_kernel, dim3(nwin), dim3(256), 0, s, wave, first, step, len, eps, stats, win);
   RVB_HIP_CHECK(hipGetLastError());
   return OK;
 }
@@ -251,7 +252,7 @@ __global__ __launch_bounds__(256) void pool_norm_kernel(PoolNormArgs p) {
     const float mean = p.stats[2 * w], rstd = p.stats[2 * w + 1];
     a = p.wn_gamma * rstd;
     if (active) off = (p.wn_beta - a * mean) * p.fsum[c];
-    cr = (const T*)p.craw + (p.craw_frame0 + (int64_t)w * p.craw_frames_per_step) * p.C + c;
+    cr = (const T*)p.craw + (p.craw_frame0 + (p.win ? p.win[w] : (int64_t)w) * p.craw_frames_per_step) * p.C + c;
   } else {
     x = (const T*)p.x + (size_t)w * p.rows_in * p.ld_in + c;
   }
@@ -328,7 +329,7 @@ __global__ __launch_bounds__(256) void pool_norm_vec_kernel(PoolNormArgs p) {
     a = p.wn_gamma * rstd;
 #pragma unroll
     for (int e = 0; e < 8; ++e) off[e] = (c0 + e < p.C) ? (p.wn_beta - a * mean) * p.fsum[c0 + e] : 0.f;
-    src = (const bf16_t*)p.craw + (p.craw_frame0 + (int64_t)w * p.craw_frames_per_step) * p.C + c0;
+    src = (const bf16_t*)p.craw + (p.craw_frame0 + (p.win ? p.win[w] : (int64_t)w) * p.craw_frames_per_step) * p.C + c0;
   } else {
     src = (const bf16_t*)p.x + (size_t)w * p.rows_in * p.ld_in + c0;
   }

@@ -55,6 +55,8 @@ struct rvd_engine {
   // audio
   DevBuf pcm, wave, craw;
   int64_t n_samples = 0, n_pad = 0, n_windows = 0, craw_frames = 0;
+  std::vector<int16_t> pack_host;      // rvd_upload_pcm_many: the packed layout, assembled here and uploaded with one copy
+  DevBuf seg_win;                      // rvd_segment_windows: the window list of the call
 
   // workspace of rvd_segment
   DevBuf stats, a1, c2, a2, c3, a3, xproj, hA, hB, l0, l1, logp, cls;
@@ -289,10 +291,12 @@ int finalize_impl(rvd_engine* e) {
   return OK;
 }
 
-int segment_impl(rvd_engine* e, int64_t first, int W, float* logp_out) {
+// d_win (device, nullable): row w of every activation tensor is window d_win[w] (rvd_segment_windows; indices checked by the
+// caller); null: window first + w
+int segment_impl(rvd_engine* e, int64_t first, int W, float* logp_out, const int64_t* d_win = nullptr) {
   const rvd_model_cfg& c = e->cfg;
   if (!e->finalized || e->n_windows == 0) { set_error("rvd_segment: finalize the model and upload audio first"); return E_STATE; }
-  if (first < 0 || W <= 0 || first + W > e->n_windows) { set_error("rvd_segment: window range outside the uploaded audio"); return E_ARG; }
+  if (!d_win && (first < 0 || W <= 0 || first + W > e->n_windows)) { set_error("rvd_segment: window range outside the uploaded audio"); return E_ARG; }
   const size_t ts = dt_size(e->dtype);
   const int H = c.lstm_hidden, CP = e->cpad, NF = c.sinc_filters;
   const int64_t R1 = (int64_t)W * e->p1, R2 = (int64_t)W * e->p2, R3 = (int64_t)W * e->p3;
@@ -312,13 +316,13 @@ int segment_impl(rvd_engine* e, int64_t first, int W, float* logp_out) {
   RVB_TRY(e->cls.ensure((size_t)R3));
 
   { DScope sc(e, "window_stats");
-    RVB_TRY(window_stats(e->stream, e->wave.as<float>(), first, W, c.step_samples, c.window_samples, 1e-5f, e->stats.as<float>())); }
+    RVB_TRY(window_stats(e->stream, e->wave.as<float>(), first, W, c.step_samples, c.window_samples, 1e-5f, e->stats.as<float>(), d_win)); }
   PoolNormArgs pn{};
   pn.W = W; pn.eps = 1e-5f;
   { DScope sc(e, "pool_norm");
     pn.x = nullptr; pn.frames_in = e->f1; pn.C = NF; pn.ld_out = NF;
     pn.gamma = e->norm[0].g.as<float>(); pn.beta = e->norm[0].b.as<float>(); pn.out = e->a1.p;
-    pn.craw = e->craw.p; pn.craw_frame0 = first * (c.step_samples / SINC_STRIDE);
+    pn.craw = e->craw.p; pn.craw_frame0 = first * (c.step_samples / SINC_STRIDE); pn.win = d_win;
     pn.craw_frames_per_step = c.step_samples / SINC_STRIDE;
     pn.stats = e->stats.as<float>(); pn.fsum = e->fsum.as<float>(); pn.wn_gamma = e->wn_gamma; pn.wn_beta = e->wn_beta;
     RVB_TRY(pool_norm(e->stream, e->dtype, pn)); }
@@ -828,7 +832,7 @@ void rvd_destroy(rvd_engine* e) {
   drain(e);
   for (auto ev : e->event_pool) (void)hipEventDestroy(ev);
   DevBuf* bufs[] = {&e->filt, &e->fsum, &e->cls_w, &e->cls_b, &e->stage, &e->pcm, &e->wave, &e->craw, &e->stats, &e->a1, &e->c2,
-                    &e->a2, &e->c3, &e->a3, &e->xproj, &e->hA, &e->hB, &e->l0, &e->l1, &e->logp, &e->cls, &e->conv2.w, &e->conv2.b,
+                    &e->a2, &e->c3, &e->a3, &e->xproj, &e->hA, &e->hB, &e->l0, &e->l1, &e->logp, &e->cls, &e->seg_win, &e->conv2.w, &e->conv2.b,
                     &e->conv3.w, &e->conv3.b};
   for (auto* b : bufs) b->release();
   for (auto& n : e->norm) { n.g.release(); n.b.release(); }
@@ -882,6 +886,47 @@ int rvd_upload_pcm(rvd_engine* e, const int16_t* pcm, int64_t n) {
   { DScope sc(e, "h2d");
     RVB_HIP_CHECK(hipMemcpyAsync(e->pcm.p, pcm, (size_t)n * 2, hipMemcpyHostToDevice, e->stream)); }
   return prepare_audio(e, n);
+}
+
+// Several recordings behind each other so that the kernels see ONE long recording: recording r has W_r = rvd_num_windows(n_r)
+// windows and takes (W_r + window / step - 1) * step samples -- its own zero-padded length, what prepare_audio gives it alone --
+// from sample first_window[r] * step on.  Its window w is global window first_window[r] + w and reads nothing but the recording's
+// samples and zeros; the window / step - 1 global indices between two recordings straddle a boundary and belong to nobody.
+int rvd_upload_pcm_many(rvd_engine* e, const int16_t* const* pcm, const int64_t* n_samples, int n_rec, int64_t* first_window,
+                        int64_t* total_windows) {
+  if (n_rec < 1) { set_error("rvd_upload_pcm_many: n_rec must be at least 1"); return E_ARG; }
+  if (!e) { set_error("rvd_upload_pcm_many: null engine"); return E_ARG; }
+  if (!pcm || !n_samples || !first_window || !total_windows) { set_error("rvd_upload_pcm_many: null argument"); return E_ARG; }
+  for (int r = 0; r < n_rec; ++r) {
+    if (n_samples[r] < 0) { set_error("rvd_upload_pcm_many: recording " + std::to_string(r) + " has a negative length"); return E_ARG; }
+    if (n_samples[r] > 0 && !pcm[r]) { set_error("rvd_upload_pcm_many: recording " + std::to_string(r) + " is null"); return E_ARG; }
+  }
+  if (!e->finalized) { set_error("rvd_upload_pcm_many: finalize the model first"); return E_STATE; }
+  const int64_t step = e->cfg.step_samples, gap = e->cfg.window_samples / step - 1;
+  int64_t next = 0, total = 0;
+  for (int r = 0; r < n_rec; ++r) {
+    const int64_t W = rvd_num_windows(e, n_samples[r]);
+    first_window[r] = next;
+    if (W > 0) { total = next + W; next = total + gap; }
+  }
+  *total_windows = total;
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  if (total == 0) {                      // nothing but empty recordings: no audio is resident afterwards
+    RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
+    e->n_samples = e->n_pad = e->n_windows = e->craw_frames = 0;
+    return OK;
+  }
+  // the padded length of the whole layout is that of a single recording with `total` windows and no tail: prepare_audio, and
+  // rvd_rerun_resident after it, take the packed samples for one recording of exactly that length
+  const int64_t n_total = (total - 1) * step + e->cfg.window_samples;
+  RVB_HIP_CHECK(hipStreamSynchronize(e->stream));      // the staging buffer may still be the source of an earlier copy
+  e->pack_host.assign((size_t)n_total, 0);
+  for (int r = 0; r < n_rec; ++r)
+    if (n_samples[r] > 0) memcpy(e->pack_host.data() + first_window[r] * step, pcm[r], (size_t)n_samples[r] * 2);
+  RVB_TRY(e->pcm.ensure((size_t)n_total * 2));
+  { DScope sc(e, "h2d");
+    RVB_HIP_CHECK(hipMemcpyAsync(e->pcm.p, e->pack_host.data(), (size_t)n_total * 2, hipMemcpyHostToDevice, e->stream)); }
+  return prepare_audio(e, n_total);
 }
 
 int rvd_rerun_resident(rvd_engine* e) {
@@ -960,6 +1005,21 @@ int rvd_segment(rvd_engine* e, int64_t first_window, int n_windows, float* logp_
   return segment_impl(e, first_window, n_windows, logp_out);
 }
 
+int rvd_segment_windows(rvd_engine* e, const int64_t* windows, int n, float* logp_out) {
+  if (!e || !windows || n < 1) { set_error("rvd_segment_windows: null engine, null or empty window list"); return E_ARG; }
+  if (!e->finalized || e->n_windows == 0) { set_error("rvd_segment_windows: finalize the model and upload audio first"); return E_STATE; }
+  for (int i = 0; i < n; ++i)
+    if (windows[i] < 0 || windows[i] >= e->n_windows) {
+      set_error("rvd_segment_windows: window " + std::to_string(windows[i]) + " (entry " + std::to_string(i) + ") outside the uploaded audio");
+      return E_ARG;
+    }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(e->seg_win.ensure((size_t)n * 8));
+  RVB_HIP_CHECK(hipMemcpyAsync(e->seg_win.p, windows, (size_t)n * 8, hipMemcpyHostToDevice, e->stream));
+  RVB_HIP_CHECK(hipStreamSynchronize(e->stream));      // the caller's list may go away
+  return segment_impl(e, 0, n, logp_out, e->seg_win.as<int64_t>());
+}
+
 int rvd_get_classes(rvd_engine* e, uint8_t* out) {
   if (!e || !out) { set_error("rvd_get_classes: null argument"); return E_ARG; }
   if (e->last_W <= 0) { set_error("rvd_get_classes: no rvd_segment call yet"); return E_STATE; }
@@ -1036,6 +1096,40 @@ int rvd_centroid_linkage(rvd_engine* e, const double* X, int n, int d, double* Z
   } while (0);
   dX.release(); dD.release(); dI.release(); dM.release(); dZ.release(); dC.release();
   return rc;
+}
+
+int rvd_centroid_linkage_many(rvd_engine* e, const double* X, const int32_t* n, int n_problems, int d, double* Z) {
+  if (!e || !n || n_problems < 1 || d < 1) { set_error("rvd_centroid_linkage_many: bad argument"); return E_ARG; }
+  int64_t points = 0, rows = 0;
+  for (int p = 0; p < n_problems; ++p) {
+    if (n[p] < 0) { set_error("rvd_centroid_linkage_many: problem " + std::to_string(p) + " has a negative size"); return E_ARG; }
+    if (n[p] > 46000) { set_error("rvd_centroid_linkage_many: problem " + std::to_string(p) + " has more than 46000 points"); return E_UNSUPPORTED; }
+    points += n[p]; rows += n[p] > 1 ? n[p] - 1 : 0;
+  }
+  if ((points > 0 && !X) || (rows > 0 && !Z)) { set_error("rvd_centroid_linkage_many: null X or Z"); return E_ARG; }
+  if (rows == 0) return OK;
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  std::vector<int> route(n_problems);
+  {
+    double retries = 0.0;
+    int rc;
+    { DScope sc(e, "linkage");
+      rc = centroid_linkage_many(e->stream, X, n, n_problems, d, Z, route.data(), &retries); }
+    if (rc != OK) {
+      if (rc == E_ARG) set_error(std::string("rvd_") + rvb::last_error());
+      return rc;
+    }
+    e->prof["linkage"].flops += retries;      // reported through rvd_get_timing("linkage").flops, as the single call's
+  }
+  int64_t ox = 0, oz = 0;
+  for (int p = 0; p < n_problems; ++p) {       // what the batched loop does not take: the single call, one by one
+    if (route[p] == 0) {
+      const int rc = rvd_centroid_linkage(e, X + ox * d, n[p], d, Z + oz * 4);
+      if (rc != OK) { set_error("rvd_centroid_linkage_many: problem " + std::to_string(p) + ": " + rvb::last_error()); return rc; }
+    }
+    ox += n[p]; oz += n[p] > 1 ? n[p] - 1 : 0;
+  }
+  return OK;
 }
 
 int rvd_get_emb_fp8(rvd_engine* e, int32_t* state, float* scales, int32_t* n, uint32_t* clipped) {

@@ -354,9 +354,10 @@ int pcm_to_float(hipStream_t s, const int16_t* pcm, int64_t n, float* out, int64
 int sinc_conv(hipStream_t s, int dtype, const float* wave, const float* filt, void* craw, int64_t n_frames, int nf,
               int ksize, int stride);
 
-// per window (start = (first+w)*step samples, `len` samples): stats[w] = {mean, 1/sqrt(var+eps)} (biased var)
+// per window (start = (first+w)*step samples, `len` samples): stats[w] = {mean, 1/sqrt(var+eps)} (biased var).
+// win (device, nullable): window w of the call is window win[w] of the waveform instead of first + w (rvd_segment_windows)
 int window_stats(hipStream_t s, const float* wave, int64_t first, int nwin, int64_t step, int len, float eps,
-                 float* stats);
+                 float* stats, const int64_t* win = nullptr);
 
 // MaxPool1d(3,3) + InstanceNorm1d(affine) + LeakyReLU over the frames of each window (SincNet block tail).
 struct PoolNormArgs {
@@ -371,6 +372,8 @@ struct PoolNormArgs {
   // i.e. the sinc conv of the instance-normalised window, from the shared raw conv
   const void* craw /* T */; int64_t craw_frame0; int craw_frames_per_step;
   const float* stats; const float* fsum; float wn_gamma, wn_beta;
+  const int64_t* win;   // first block, device, nullable: window w reads craw from frame craw_frame0 + win[w] * craw_frames_per_step
+                        // (null: craw_frame0 + w * craw_frames_per_step)
 };
 int pool_norm(hipStream_t s, int dtype, const PoolNormArgs& a);
 // SincNet conv layers 2 / 3 (Conv1d kernel 5, 64 padded filters) straight from the [rows + 8][cin] activation tensor (bf16; cin 80 or 64):
@@ -521,5 +524,14 @@ int nn_init(hipStream_t s, const double* D, int n, int* neighbor, double* min_di
 // host: the merge loops write a dendrogram row as (slot x, slot y, distance, size); this turns the slots into scipy's cluster ids in
 // place (the merged cluster lives on in slot y under the new id n + k; the smaller id first)
 void linkage_slots_to_ids(double* Z, int n);
+// Many clusterings in one launch per stage (rvd_centroid_linkage_many).  HOST X [sum n][d], problems back to back; n [n_problems];
+// HOST Z [sum max(n - 1, 0)][4], back to back, scipy ids per problem.  Problems of 2 .. 2 999 points whose state fits LDS run the
+// one-workgroup merge loop, one workgroup each, behind one batched pdist and one batched nn_init launch (at most 2 GiB of distance
+// matrices per launch: a larger batch is split; lab: RVD_LINKAGE_MANY_CAP, bytes): route[p] = 1 (loop 1) or 2 (loop 2, RVD_LINKAGE_COMPACT=0), and Z holds the
+// dendrogram the single call gives with one workgroup, bit for bit.  route[p] = -1: fewer than 2 points, no rows.  route[p] = 0: not
+// run here (3 000 points or more, state too large for LDS, RVD_LINKAGE_GLOBAL) -- the caller runs the single call on it.
+// *retries (nullable) grows by the stale candidates the loops re-evaluated.  A problem without a candidate pair: E_ARG, its index
+// in the message.  Synchronises the stream.
+int centroid_linkage_many(hipStream_t s, const double* X, const int* n, int n_problems, int d, double* Z, int* route, double* retries);
 
 }  // namespace rvb

@@ -10,6 +10,8 @@
 // argmin over the candidate distances plus one fused pass over the two merged rows.
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
+#include <string>
 #include <vector>
 
 #include "kernels.h"
@@ -18,10 +20,12 @@ namespace rvb {
 
 // ------------------------------------------------------------------------------------ pairwise distances (fp64)
 // D[i][j] = sqrt(sum_k (X[i][k] - X[j][k])^2), full symmetric n x n.  64x64 tile per block, 4x4 per thread.
-__global__ __launch_bounds__(256) void pdist_kernel(const double* __restrict__ X, int n, int d, double* __restrict__ D) {
+// One definition for the single call's kernel (grid = tiles of one problem) and the batched one (grid = tiles of every problem):
+// a problem's distance matrix is the same bits either way.
+__device__ __forceinline__ void pdist_tile(const double* __restrict__ X, int n, int d, double* __restrict__ D, int tile_i, int tile_j) {
   __shared__ double sa[16][65], sb[16][65];
   const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
-  const int i0 = blockIdx.y * 64, j0 = blockIdx.x * 64;
+  const int i0 = tile_i * 64, j0 = tile_j * 64;
   if (j0 + 63 < i0) return;     // strictly-lower tiles are filled by symmetry
   double acc[4][4];
 #pragma unroll
@@ -61,6 +65,31 @@ __global__ __launch_bounds__(256) void pdist_kernel(const double* __restrict__ X
         D[(size_t)j * n + i] = v;
       }
     }
+}
+__global__ __launch_bounds__(256) void pdist_kernel(const double* __restrict__ X, int n, int d, double* __restrict__ D) {
+  pdist_tile(X, n, d, D, blockIdx.y, blockIdx.x);
+}
+
+// ------------------------------------------------------------------------------------ problem table of a batch
+// rvd_centroid_linkage_many: many small clusterings in one launch per stage.  Row p describes problem p (n >= 2 points; smaller
+// ones never get a row): where its points, its distance matrix, its per-slot state and its dendrogram start in the batch's arrays,
+// and the first block of each flattened grid that works on it.
+struct LkProblem {
+  int n, tile0;                 // points; first block of the pdist grid (the problem has cdiv(n, 64)^2 tiles)
+  long long x0, d0, s0, z0;     // offsets in elements: X [n][d], D [n][n], per-slot state [n], Z [n-1][4]
+};
+// the problem block `b` of a flattened grid belongs to: the last row whose first block is <= b (first(p) ascending, first(0) = 0)
+template <typename F> __device__ inline int lk_find_problem(int n_problems, int b, F first) {
+  int lo = 0, hi = n_problems - 1;
+  while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (first(mid) <= b) lo = mid; else hi = mid - 1; }
+  return lo;
+}
+__global__ __launch_bounds__(256) void pdist_many_kernel(const LkProblem* __restrict__ tab, int n_problems, const double* __restrict__ X,
+                                                         int d, double* __restrict__ D) {
+  const int p = lk_find_problem(n_problems, (int)blockIdx.x, [&](int q) { return tab[q].tile0; });
+  const LkProblem pr = tab[p];
+  const int t = (pr.n + 63) >> 6, q = (int)blockIdx.x - pr.tile0;
+  pdist_tile(X + pr.x0, pr.n, d, D + pr.d0, q / t, q % t);
 }
 
 // ------------------------------------------------------------------------------------ block-wide (value, index) argmin
@@ -180,14 +209,27 @@ __device__ inline void block_argmin3_alt(MinPair& a, MinPair& b, MinPair& c, Min
 }
 
 // nearest neighbour of every x among y > x (scipy find_min_dist: first index on ties); one block per row
-__global__ __launch_bounds__(256) void nn_init_kernel(const double* __restrict__ D, int n, int* __restrict__ neighbor,
-                                                      double* __restrict__ min_dist) {
+__device__ __forceinline__ void nn_init_row(const double* __restrict__ D, int n, int x, int* __restrict__ neighbor,
+                                            double* __restrict__ min_dist) {
   __shared__ MinPair red[4];
-  const int x = blockIdx.x;
   MinPair p{INFINITY, 0x7fffffff};
   for (int j = x + 1 + threadIdx.x; j < n; j += 256) p = min_pair(p, MinPair{D[(size_t)x * n + j], j});
   p = block_argmin(p, red);
   if (threadIdx.x == 0) { neighbor[x] = p.v < INFINITY ? p.i : -1; min_dist[x] = p.v; }
+}
+__global__ __launch_bounds__(256) void nn_init_kernel(const double* __restrict__ D, int n, int* __restrict__ neighbor,
+                                                      double* __restrict__ min_dist) {
+  nn_init_row(D, n, blockIdx.x, neighbor, min_dist);
+}
+// batch: one block per slot of every problem (grid = sum n); the block of a problem's last slot has nothing to do, as in the
+// single call, whose grid is n - 1
+__global__ __launch_bounds__(256) void nn_init_many_kernel(const LkProblem* __restrict__ tab, int n_problems, const double* __restrict__ D,
+                                                           int* __restrict__ neighbor, double* __restrict__ min_dist) {
+  const int p = lk_find_problem(n_problems, (int)blockIdx.x, [&](int q) { return (int)tab[q].s0; });
+  const LkProblem pr = tab[p];
+  const int x = (int)blockIdx.x - (int)pr.s0;
+  if (x >= pr.n - 1) return;                  // uniform across the block
+  nn_init_row(D + pr.d0, pr.n, x, neighbor + pr.s0, min_dist + pr.s0);
 }
 
 // Lance-Williams centroid update, scipy's `_centroid` with the two divisions of a merge hoisted: sub = nx ny d(x,y)^2 / (nx + ny)
@@ -210,15 +252,18 @@ __device__ inline double lw_centroid(double fx, double fy, double dxi, double dy
 // merged row).  Every thread derives (x, y, dist) from the same reduction result, so nothing is broadcast through
 // shared variables, and state writes sit right after a reduction's barrier: 1 barrier per candidate round, per row
 // rescan and per merge.
+static constexpr int LK_MANY_MAX_N = 3000;      // rvd_centroid_linkage_many: from here on a problem goes through the single call (which takes the multi-workgroup loop there)
 static constexpr int LK_E = 10;      // elements per thread and batch (registers: 2 x LK_E doubles in the merge pass)
 // COMPACT (LDS_STATE, n <= LK_E * NTH): the slots a thread owns are re-dealt from the sorted list of live slots every 256
 // merges (registers `myz`), so that the passes walk ~the live clusters instead of all n slots -- dead slots are skipped per
 // lane anyway, but a wave instruction costs the same whether 64 or 20 of its lanes are alive, and the merge pass is
 // VALU-issue-bound.  Order is preserved (ascending slots per list position), so ties break as before.
+// The loop is a device function with two kernels around it: linkage_kernel (the single call: one workgroup, one problem) and
+// linkage_many_kernel (rvd_centroid_linkage_many: workgroup b runs problem b of the table, on its own -- no word passes between
+// workgroups).  Both run this one body, so a problem's dendrogram does not depend on which of them produced it.
 template <bool LDS_STATE, int NTH, bool COMPACT>
-__global__ __launch_bounds__(NTH) void linkage_kernel(int getenv_prof, double* __restrict__ D, int n, uint16_t* __restrict__ g_size,
-                                                       int* __restrict__ cluster_id, int* __restrict__ g_neighbor,
-                                                       double* __restrict__ g_min_dist, double* __restrict__ Z) {
+__device__ __forceinline__ void linkage_loop(int getenv_prof, double* __restrict__ D, int n, uint16_t* __restrict__ g_size,
+                                             int* __restrict__ g_neighbor, double* __restrict__ g_min_dist, double* __restrict__ Z) {
   extern __shared__ __attribute__((aligned(16))) char lk_smem[];
   __shared__ MinPair red[2][16];
   int rphase = 0;
@@ -405,6 +450,21 @@ __global__ __launch_bounds__(NTH) void linkage_kernel(int getenv_prof, double* _
   if (tid == 0 && prof) printf("linkage n=%d: argmin+validate %.1f ms, row rescans %.1f ms, merge pass %.1f ms (100 MHz wall clock), retries %lld\n", n, t_arg * 1e-5, t_scan * 1e-5, t_merge * 1e-5, retries);
   __syncthreads();
   if (tid == 0) g_min_dist[n - 1] = (double)retries;     // statistics: invalid candidates re-evaluated (slot n-1 is unused)
+}
+template <bool LDS_STATE, int NTH, bool COMPACT>
+__global__ __launch_bounds__(NTH) void linkage_kernel(int getenv_prof, double* __restrict__ D, int n, uint16_t* __restrict__ g_size,
+                                                       int* __restrict__ cluster_id, int* __restrict__ g_neighbor,
+                                                       double* __restrict__ g_min_dist, double* __restrict__ Z) {
+  (void)cluster_id;
+  linkage_loop<LDS_STATE, NTH, COMPACT>(getenv_prof, D, n, g_size, g_neighbor, g_min_dist, Z);
+}
+// batch: dynamic LDS is sized for the largest problem of the launch; every problem lays its state out from its own n
+template <int NTH, bool COMPACT>
+__global__ __launch_bounds__(NTH) void linkage_many_kernel(int getenv_prof, const LkProblem* __restrict__ tab, double* __restrict__ D,
+                                                            uint16_t* __restrict__ g_size, int* __restrict__ g_neighbor,
+                                                            double* __restrict__ g_min_dist, double* __restrict__ Z) {
+  const LkProblem pr = tab[blockIdx.x];
+  linkage_loop<true, NTH, COMPACT>(getenv_prof, D + pr.d0, pr.n, g_size + pr.s0, g_neighbor + pr.s0, g_min_dist + pr.s0, Z + pr.z0);
 }
 
 // ------------------------------------------------------------------------------------ merge loop (MB_G workgroups of ONE XCD)
@@ -954,6 +1014,120 @@ int centroid_linkage(hipStream_t s, const double* X, int n, int d, double* D, ui
     RVB_HIP_CHECK(hipGetLastError());
     break;
   }
+  return OK;
+}
+
+// ------------------------------------------------------------------------------------ many small problems, one launch per stage
+namespace {
+struct LkFree { void* p = nullptr; ~LkFree() { if (p) (void)hipFree(p); } };
+inline size_t lk_align16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// the problems `list` (indices into n[]; all routed to the batched loop `loop`): one allocation, one upload, three launches, one download
+int linkage_many_launch(hipStream_t s, const double* X, const int* n, const std::vector<long long>& hx, const std::vector<long long>& hz,
+                        const std::vector<int>& list, int d, int loop, int flags, double* Z, double* retries) {
+  const int P = (int)list.size();
+  std::vector<LkProblem> tab(P);
+  long long sumN = 0, sumD = 0, sumZ = 0, tiles = 0;
+  int nmax = 0;
+  for (int i = 0; i < P; ++i) {
+    const int np = n[list[i]], t = cdiv(np, 64);
+    tab[i].n = np; tab[i].tile0 = (int)tiles;
+    tab[i].x0 = sumN * d; tab[i].d0 = sumD; tab[i].s0 = sumN; tab[i].z0 = sumZ;
+    sumN += np; sumD += (long long)np * np; sumZ += (long long)(np - 1) * 4; tiles += (long long)t * t;
+    nmax = np > nmax ? np : nmax;
+  }
+  if (tiles > 0x7fffffffLL || sumN > 0x7fffffffLL) { set_error("centroid_linkage_many: too many problems for one launch"); return E_UNSUPPORTED; }
+  // [table | X | neighbor | size | min_dist] go up in one copy, [min_dist | Z] come back in one; D is written by pdist
+  const size_t o_x = lk_align16((size_t)P * sizeof(LkProblem)), o_nb = lk_align16(o_x + (size_t)sumN * d * 8),
+               o_sz = lk_align16(o_nb + (size_t)sumN * 4), o_md = lk_align16(o_sz + (size_t)sumN * 2), o_z = o_md + (size_t)sumN * 8,
+               o_d = lk_align16(o_z + (size_t)sumZ * 8), total = o_d + (size_t)sumD * 8;
+  std::vector<char> up(o_z, 0);
+  memcpy(up.data(), tab.data(), (size_t)P * sizeof(LkProblem));
+  for (int i = 0; i < P; ++i)
+    memcpy(up.data() + o_x + (size_t)tab[i].x0 * 8, X + hx[list[i]], (size_t)tab[i].n * d * 8);
+  for (long long i = 0; i < sumN; ++i) {
+    ((int*)(up.data() + o_nb))[i] = -1;
+    ((uint16_t*)(up.data() + o_sz))[i] = 1;
+    ((double*)(up.data() + o_md))[i] = INFINITY;
+  }
+  LkFree dev;
+  if (hipMalloc(&dev.p, total) != hipSuccess) {
+    (void)hipGetLastError();
+    set_error("centroid_linkage_many: out of device memory (" + std::to_string(total >> 20) + " MiB)");
+    return E_NOMEM;
+  }
+  char* base = (char*)dev.p;
+  const LkProblem* d_tab = (const LkProblem*)base;
+  double* d_D = (double*)(base + o_d);
+  int* d_nb = (int*)(base + o_nb);
+  uint16_t* d_sz = (uint16_t*)(base + o_sz);
+  double* d_md = (double*)(base + o_md);
+  double* d_Z = (double*)(base + o_z);
+  RVB_HIP_CHECK(hipMemcpyAsync(base, up.data(), o_z, hipMemcpyHostToDevice, s));
+  hipLaunchKernelGGL(pdist_many_kernel, dim3((unsigned)tiles), dim3(256), 0, s, d_tab, P, (const double*)(base + o_x), d, d_D);
+  RVB_HIP_CHECK(hipGetLastError());
+  hipLaunchKernelGGL(nn_init_many_kernel, dim3((unsigned)sumN), dim3(256), 0, s, d_tab, P, (const double*)d_D, d_nb, d_md);
+  RVB_HIP_CHECK(hipGetLastError());
+  static bool attr_set = false;
+  if (!attr_set) {
+    RVB_HIP_CHECK(hipFuncSetAttribute((const void*)linkage_many_kernel<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
+    RVB_HIP_CHECK(hipFuncSetAttribute((const void*)linkage_many_kernel<1024, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024));
+    attr_set = true;
+  }
+  if (loop == 1)
+    hipLaunchKernelGGL((linkage_many_kernel<1024, true>), dim3(P), dim3(1024), (size_t)nmax * 16 + 16, s, flags, d_tab, d_D, d_sz, d_nb, d_md, d_Z);
+  else
+    hipLaunchKernelGGL((linkage_many_kernel<1024, false>), dim3(P), dim3(1024), (size_t)nmax * 14 + 16, s, flags, d_tab, d_D, d_sz, d_nb, d_md, d_Z);
+  RVB_HIP_CHECK(hipGetLastError());
+  std::vector<double> down((size_t)sumN + (size_t)sumZ);
+  RVB_HIP_CHECK(hipMemcpyAsync(down.data(), d_md, down.size() * 8, hipMemcpyDeviceToHost, s));
+  RVB_HIP_CHECK(hipStreamSynchronize(s));
+  for (int i = 0; i < P; ++i) {                    // a problem's status sits in its unused slot n - 1, as after the single call
+    const double status = down[(size_t)tab[i].s0 + tab[i].n - 1];
+    if (status < 0.0) {
+      set_error("centroid_linkage_many: problem " + std::to_string(list[i]) + ": the merge loop found no candidate pair (non-finite embeddings?)");
+      return E_ARG;
+    }
+    if (retries) *retries += status;
+  }
+  for (int i = 0; i < P; ++i) {
+    double* zp = Z + hz[list[i]];
+    memcpy(zp, down.data() + sumN + tab[i].z0, (size_t)(tab[i].n - 1) * 4 * 8);
+    linkage_slots_to_ids(zp, tab[i].n);
+  }
+  return OK;
+}
+}  // namespace
+
+int centroid_linkage_many(hipStream_t s, const double* X, const int* n, int n_problems, int d, double* Z, int* route, double* retries) {
+  const bool force_global = lab_env("RVD_LINKAGE_GLOBAL") != nullptr;
+  const bool no_compact = lab_env("RVD_LINKAGE_COMPACT") && atoi(lab_env("RVD_LINKAGE_COMPACT")) == 0;
+  const int flags = lab_env("RVD_LINKAGE_PROF") ? 1 : 0;
+  const int loop = no_compact ? 2 : 1;
+  std::vector<long long> hx(n_problems), hz(n_problems);
+  long long ox = 0, oz = 0;
+  for (int p = 0; p < n_problems; ++p) {
+    const int np = n[p];
+    hx[p] = ox; hz[p] = oz;
+    ox += (long long)np * d; oz += np > 1 ? (long long)(np - 1) * 4 : 0;
+    // LDS of the loop that would run: 16 bytes per point with the sorted slot list of the compacting loop, 14 without it
+    const bool fits = loop == 1 ? ((size_t)np * 16 + 16 <= 158 * 1024 && np <= LK_E * 1024) : ((size_t)np * 14 + 16 <= 158 * 1024);
+    route[p] = np < 2 ? -1 : (force_global || np >= LK_MANY_MAX_N || !fits) ? 0 : loop;
+  }
+  size_t cap = (size_t)2 << 30;                  // distance matrices of one launch
+  if (const char* ce = lab_env("RVD_LINKAGE_MANY_CAP")) { const long long v = atoll(ce); if (v > 0) cap = (size_t)v; }      // lab, bytes: tests split a small batch
+  std::vector<int> list;
+  size_t bytes = 0;
+  for (int p = 0; p < n_problems; ++p) {
+    if (route[p] < 1) continue;
+    const size_t b = (size_t)n[p] * n[p] * 8;
+    if (!list.empty() && bytes + b > cap) {
+      RVB_TRY(linkage_many_launch(s, X, n, hx, hz, list, d, loop, flags, Z, retries));
+      list.clear(); bytes = 0;
+    }
+    list.push_back(p); bytes += b;
+  }
+  if (!list.empty()) RVB_TRY(linkage_many_launch(s, X, n, hx, hz, list, d, loop, flags, Z, retries));
   return OK;
 }
 

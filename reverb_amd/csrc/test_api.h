@@ -304,6 +304,11 @@ int rvb_test_emb_stem(int dtype, const float* fb, int64_t n_rows, const int64_t*
 int rvb_test_pdist_nn(const double* X, int n, int d, double* D /* [n][n] */, int32_t* neighbor /* [n] */, double* min_dist /* [n] */);
 int rvb_test_centroid_linkage(const double* X, int n, int d, int workgroups, double* Z /* [n-1][4] */, int32_t* ran /* [4] */,
                               double* retries);
+/* rvd_centroid_linkage_many without an engine: X [sum n][d] and Z [sum max(n-1,0)][4], problems back to back.  route[p]: 1 or 2 =
+ * the batched one-workgroup loop that ran (2 under RVD_LINKAGE_COMPACT=0), 0 = routed to the single call (3 000 points or more, or
+ * RVD_LINKAGE_GLOBAL), -1 = fewer than 2 points, nothing to do.  A problem without a candidate pair fails the call, its index in
+ * the message. */
+int rvb_test_centroid_linkage_many(const double* X, const int32_t* n, int n_problems, int d, double* Z, int32_t* route);
 
 /* GEMM kernel selection / micro-benchmark hooks (tests and tuning only) */
 int rvb_test_set_gemm_variant(int variant /* 0 auto, 1 gemm.hip 128x128, 2 gemm2.hip 256x256 LDS-DMA */);

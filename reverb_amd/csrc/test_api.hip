@@ -1884,6 +1884,33 @@ extern "C" int rvb_test_centroid_linkage(const double* X, int n, int d, int work
   return OK;
 }
 
+// centroid_linkage_many() without an engine, then -- as rvd_centroid_linkage_many does -- the single call (the hook above, default
+// workgroups) on every problem it routed away.  route [n_problems]: 1 / 2 = the batched loop that ran, 0 = the single call,
+// -1 = fewer than 2 points.  Z as rvd_centroid_linkage_many lays it out; on failure its contents are unspecified.
+extern "C" int rvb_test_centroid_linkage_many(const double* X, const int32_t* n, int n_problems, int d, double* Z, int32_t* route) {
+  if (!n || !route || n_problems < 1 || d < 1) { set_error("rvb_test_centroid_linkage_many: bad argument"); return E_ARG; }
+  int64_t points = 0, rows = 0;
+  for (int p = 0; p < n_problems; ++p) {
+    if (n[p] < 0 || n[p] > 46000) { set_error("rvb_test_centroid_linkage_many: problem " + std::to_string(p) + ": size outside 0 .. 46000"); return E_ARG; }
+    points += n[p]; rows += n[p] > 1 ? n[p] - 1 : 0;
+  }
+  if ((points > 0 && !X) || (rows > 0 && !Z)) { set_error("rvb_test_centroid_linkage_many: null X or Z"); return E_ARG; }
+  for (int p = 0; p < n_problems; ++p) route[p] = -1;
+  if (rows == 0) return OK;
+  RVB_TRY(need_gpu());
+  RVB_TRY(centroid_linkage_many(nullptr, X, n, n_problems, d, Z, route, nullptr));
+  int64_t ox = 0, oz = 0;
+  for (int p = 0; p < n_problems; ++p) {
+    if (route[p] == 0) {
+      int32_t ran[4];
+      const int rc = rvb_test_centroid_linkage(X + ox * d, n[p], d, 0, Z + oz * 4, ran, nullptr);
+      if (rc != OK) { set_error("rvb_test_centroid_linkage_many: problem " + std::to_string(p) + ": " + rvb::last_error()); return rc; }
+    }
+    ox += n[p]; oz += n[p] > 1 ? n[p] - 1 : 0;
+  }
+  return OK;
+}
+
 // ---- hooks into the engine's host code (engine_impl.h, trie.h)
 // host only: the rescoring trie of given hypotheses (tests/test_search_native.py checks it against a Python trie).
 // tokens: the hypotheses back to back; lens / chunk_of: per hypothesis (chunk ids ascending).  Outputs sized by the caller:

@@ -31,6 +31,34 @@ def _np32(v) -> Optional[np.ndarray]:
     return np.ascontiguousarray(v, dtype=np.float32)
 
 
+def window_count(n_samples: int, window: int, step: int) -> int:
+    """rvd_num_windows without the library: the full windows of n_samples samples plus one zero-padded tail."""
+    n, window, step = int(n_samples), int(window), int(step)
+    if n <= 0:
+        return 0
+    full = (n - window) // step + 1 if n >= window else 0
+    tail = n < window or (n - window) % step > 0
+    return full + (1 if tail else 0)
+
+
+def window_layout(n_samples, window: int, step: int) -> np.ndarray:
+    """The packed layout of rvd_upload_pcm_many, stated once more without the library: -> first_window int64 [n_rec].
+    Recording r of n_samples[r] samples has W_r = window_count(n_samples[r]) windows and takes (W_r + window // step - 1) * step
+    samples -- its own zero-padded length -- from sample first_window[r] * step on, so that its window w is global window
+    first_window[r] + w and the window // step - 1 global indices between two recordings belong to nobody.  A recording of
+    0 samples has no windows and takes no space (its entry is where the next recording starts).  One past the last valid global
+    index -- the `total` of DiarEngine.upload_many -- is max(first_window[r] + W_r) over the recordings that have windows, else 0."""
+    first, nxt = [], 0
+    for n in n_samples:
+        if int(n) < 0:
+            raise ValueError("window_layout: negative length")
+        W = window_count(n, window, step)
+        first.append(nxt)
+        if W > 0:
+            nxt += W + int(window) // int(step) - 1
+    return np.array(first, np.int64)
+
+
 class DiarEngine:
     """segmentation (PyanNet) + embedding (WeSpeaker ResNet34) networks resident on one GPU."""
 
@@ -92,6 +120,21 @@ class DiarEngine:
         self.n_windows = self.num_windows(pcm.shape[0])
         return self.n_windows
 
+    def upload_many(self, pcms):
+        """Several recordings (int16 at the model's rate) in one upload and one front-end pass, packed as window_layout() states:
+        -> (first_window int64 [n_rec], total).  Window w of recording r is global window first_window[r] + w for segment_windows,
+        embed and emb_fbank; self.n_windows becomes `total`.  upload() afterwards returns to a single recording."""
+        pcms = [np.ascontiguousarray(p, dtype=np.int16).reshape(-1) for p in pcms]
+        n = len(pcms)
+        ptrs = (C.POINTER(C.c_int16) * max(n, 1))(*[p.ctypes.data_as(C.POINTER(C.c_int16)) for p in pcms])
+        lens = (C.c_int64 * max(n, 1))(*[p.shape[0] for p in pcms])
+        first = np.zeros(max(n, 1), np.int64)
+        total = C.c_int64(0)
+        _check(self.lib.rvd_upload_pcm_many(self._h, ptrs, lens, n, first.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(total)),
+               "rvd_upload_pcm_many")
+        self.n_windows = int(total.value)
+        return first[:n], self.n_windows
+
     def rerun_resident(self) -> int:
         """The recording of the last upload() is still in HBM: its front end again (what upload() does behind the copy)."""
         _check(self.lib.rvd_rerun_resident(self._h), "rvd_rerun_resident")
@@ -114,6 +157,28 @@ class DiarEngine:
         for b0 in range(0, n, batch):
             nb = min(batch, n - b0)
             _check(self.lib.rvd_segment(self._h, first + b0, nb, None), "rvd_segment")
+            _check(self.lib.rvd_get_classes(self._h, out[b0:b0 + nb].ctypes.data_as(C.POINTER(C.c_uint8))), "rvd_get_classes")
+        return out
+
+    def segment_windows(self, windows, batch: int = 4096) -> np.ndarray:
+        """segment() over a window list (after upload_many: global indices): [len(windows), frames, classes]."""
+        windows = np.ascontiguousarray(windows, dtype=np.int64).reshape(-1)
+        n = windows.shape[0]
+        out = np.empty((n, self.frames, self.num_classes), np.float32)
+        for b0 in range(0, n, batch):
+            nb = min(batch, n - b0)
+            _check(self.lib.rvd_segment_windows(self._h, windows[b0:].ctypes.data_as(C.POINTER(C.c_int64)), nb, fptr(out[b0:b0 + nb])),
+                   "rvd_segment_windows")
+        return out
+
+    def segment_classes_windows(self, windows, batch: int = 4096) -> np.ndarray:
+        """segment_classes() over a window list: uint8 [len(windows), frames]."""
+        windows = np.ascontiguousarray(windows, dtype=np.int64).reshape(-1)
+        n = windows.shape[0]
+        out = np.empty((n, self.frames), np.uint8)
+        for b0 in range(0, n, batch):
+            nb = min(batch, n - b0)
+            _check(self.lib.rvd_segment_windows(self._h, windows[b0:].ctypes.data_as(C.POINTER(C.c_int64)), nb, None), "rvd_segment_windows")
             _check(self.lib.rvd_get_classes(self._h, out[b0:b0 + nb].ctypes.data_as(C.POINTER(C.c_uint8))), "rvd_get_classes")
         return out
 
@@ -176,6 +241,30 @@ class DiarEngine:
         f64 = C.POINTER(C.c_double)
         _check(self.lib.rvd_centroid_linkage(self._h, X.ctypes.data_as(f64), n, d, Z.ctypes.data_as(f64)), "rvd_centroid_linkage")
         return Z
+
+    def centroid_linkage_many(self, Xs):
+        """centroid_linkage for a list of point sets [n_p, d] in one call (rvd_centroid_linkage_many): -> list of Z [max(n_p - 1, 0), 4].
+        Sets of fewer than 3 000 points are clustered together, one workgroup each, in one launch per stage; every dendrogram equals
+        centroid_linkage's with set_linkage_workgroups(1), bit for bit."""
+        Xs = [np.ascontiguousarray(X, dtype=np.float64) for X in Xs]
+        if not Xs:
+            return []
+        for X in Xs:
+            if X.ndim != 2:
+                raise ValueError("centroid_linkage_many: every point set is [n, d]")
+        ds = {X.shape[1] for X in Xs if X.shape[0] > 0}
+        if len(ds) > 1:
+            raise ValueError(f"centroid_linkage_many: point sets of different dimensions {sorted(ds)}")
+        d = ds.pop() if ds else max(Xs[0].shape[1], 1)
+        ns = np.array([X.shape[0] for X in Xs], np.int32)
+        rows = np.maximum(ns.astype(np.int64) - 1, 0)
+        allX = np.ascontiguousarray(np.concatenate([X.reshape(-1, d) for X in Xs], axis=0)) if ns.sum() else np.zeros((0, d))
+        Z = np.zeros((int(rows.sum()), 4), np.float64)
+        f64 = C.POINTER(C.c_double)
+        _check(self.lib.rvd_centroid_linkage_many(self._h, allX.ctypes.data_as(f64), ns.ctypes.data_as(C.POINTER(C.c_int32)), len(Xs), int(d),
+                                                  Z.ctypes.data_as(f64)), "rvd_centroid_linkage_many")
+        ends = np.cumsum(rows)
+        return [Z[e - r:e] for r, e in zip(rows, ends)]
 
     # ------------------------------------------------------------------ profiling
     def set_profiling(self, on: bool):

@@ -368,6 +368,21 @@ def _fcluster_distance(dendrogram: np.ndarray, t: float) -> np.ndarray:
         return fcluster(dendrogram, t, criterion="distance")
 
 
+def clustering_points(embeddings: np.ndarray, active: np.ndarray):
+    """The embeddings the clustering trains on: those of the active (chunk, speaker) pairs without a NaN entry.
+    -> (chunk_idx, speaker_idx, train float32 [n, dim] as pyannote holds them, valid bool (chunks, speakers))."""
+    valid = ~np.isnan(embeddings.sum(axis=2))            # an embedding is valid iff none of its entries is NaN
+    chunk_idx, speaker_idx = np.where(active * valid)
+    train = np.ascontiguousarray(embeddings[chunk_idx, speaker_idx], dtype=np.float32)
+    return chunk_idx, speaker_idx, train, valid
+
+
+def unit_vectors(train: np.ndarray) -> np.ndarray:
+    """The points the dendrogram is built on: pyannote normalises the float32 embeddings in place, scipy then works in fp64.
+    One definition for cluster_embeddings and for SpeakerDiarization.diarize_many, which clusters many recordings in one call."""
+    return (train / np.linalg.norm(train, axis=-1, keepdims=True)).astype(np.float64)
+
+
 def cluster_embeddings(embeddings: np.ndarray, binarized: np.ndarray, threshold: float, min_cluster_size: int,
                        method: str = "centroid", num_clusters: Optional[int] = None, min_clusters: Optional[int] = None,
                        max_clusters: Optional[int] = None, linkage_fn=None, active: Optional[np.ndarray] = None):
@@ -381,9 +396,7 @@ def cluster_embeddings(embeddings: np.ndarray, binarized: np.ndarray, threshold:
     num_chunks, nspk, dim = embeddings.shape
     if active is None:                                   # (chunks, speakers): speaker active in at least one frame
         active = np.any(binarized > 0, axis=1)
-    valid = ~np.isnan(embeddings.sum(axis=2))            # an embedding is valid iff none of its entries is NaN
-    chunk_idx, speaker_idx = np.where(active * valid)
-    train = np.ascontiguousarray(embeddings[chunk_idx, speaker_idx], dtype=np.float32)     # float32, as pyannote holds them
+    chunk_idx, speaker_idx, train, valid = clustering_points(embeddings, active)
     n = train.shape[0]
     if n == 0:
         return np.zeros((num_chunks, nspk), np.int64), np.zeros((1, dim))
@@ -398,8 +411,7 @@ def cluster_embeddings(embeddings: np.ndarray, binarized: np.ndarray, threshold:
     if n == 1:
         clusters = np.zeros((1,), np.int64)
     else:
-        # pyannote normalises the float32 embeddings in place, scipy then works in fp64
-        unit = (train / np.linalg.norm(train, axis=-1, keepdims=True)).astype(np.float64)
+        unit = unit_vectors(train)
         if linkage_fn is not None and method == "centroid":
             dendrogram = linkage_fn(unit)
         else:
@@ -652,8 +664,11 @@ class SpeakerDiarization:
         return self._pool
 
     def finish(self, classes: np.ndarray, emb: np.ndarray, uri: Optional[str], num_speakers: Optional[int] = None,
-               min_speakers: Optional[int] = None, max_speakers: Optional[int] = None, return_embeddings: bool = False):
-        """The host part: speaker count, clustering (linkage on the GPU), reconstruction, RTTM turns."""
+               min_speakers: Optional[int] = None, max_speakers: Optional[int] = None, return_embeddings: bool = False,
+               linkage_fn=None):
+        """The host part: speaker count, clustering (linkage on the GPU), reconstruction, RTTM turns.
+        `linkage_fn(unit_vectors) -> Z` (default: the engine's centroid_linkage): diarize_many hands back the dendrogram it
+        computed for this recording together with the other recordings' in one call."""
         import time
         t0 = time.perf_counter()
         step = self.cfg["step_samples"] / self.cfg["sample_rate"]
@@ -674,7 +689,7 @@ class SpeakerDiarization:
         cp = self.params["clustering"]
         ms = max_speakers if max_speakers is not None else np.inf
         hard, centroids = cluster_embeddings(emb, None, float(cp["threshold"]), int(cp["min_cluster_size"]), cp.get("method", "centroid"),
-                                             num_speakers, min_speakers, max_speakers, linkage_fn=self.engine.centroid_linkage,
+                                             num_speakers, min_speakers, max_speakers, linkage_fn=linkage_fn or self.engine.centroid_linkage,
                                              active=active)
         t1 = time.perf_counter()
         count = np.minimum(count, ms).astype(np.int8)
@@ -701,6 +716,130 @@ class SpeakerDiarization:
         return out
 
     apply = __call__
+
+    def diarize_many(self, files, num_speakers=None, min_speakers=None, max_speakers=None, return_embeddings: bool = False,
+                     group_seconds: float = 7200.0) -> list:
+        """`[pipeline(f) for f in files]` in one pass over the GPU per group of recordings: the same annotations (the networks'
+        outputs are bit-identical to the single-recording path, the dendrograms equal), without the per-recording fixed costs.
+        The files are loaded as __call__ loads them, grouped in order so that a group holds at most `group_seconds` of audio
+        (reverb.plan_groups; a longer recording is a group of its own), and per group there is one packed upload and front-end
+        pass (DiarEngine.upload_many), one segmentation call over all windows, one embedding call over all (window, speaker)
+        items and one clustering call over all recordings (DiarEngine.centroid_linkage_many); finish() then runs per recording on
+        its precomputed dendrogram.  num_speakers / min_speakers / max_speakers: a scalar for all files, or a sequence with one
+        entry per file.  A file of zero samples yields Annotation(uri) without turns (with return_embeddings: and a [0, dim]
+        centroid array) instead of failing the batch.  -> list, one entry per file, of what __call__ returns.
+        self.timings holds the batch's stage times (seconds, summed over the groups) and the counts of windows and embeddings."""
+        import time
+        from .reverb import plan_groups
+        t_start = time.perf_counter()
+        files = list(files)
+        nf = len(files)
+
+        def per_file(v, name):
+            if v is None or np.isscalar(v):
+                return [v] * nf
+            v = list(v)
+            if len(v) != nf:
+                raise ValueError(f"diarize_many: {name} has {len(v)} entries for {nf} files")
+            return v
+        ns_, mins_, maxs_ = per_file(num_speakers, "num_speakers"), per_file(min_speakers, "min_speakers"), per_file(max_speakers, "max_speakers")
+        eng = self.engine
+        loaded = [self._load(f) for f in files]
+        rate = float(self.cfg["sample_rate"])
+        step = self.cfg["step_samples"] / self.cfg["sample_rate"]
+        dur = self.cfg["window_samples"] / self.cfg["sample_rate"]
+        excl = bool(self.params["embedding_exclude_overlap"])
+        dim = int(self.cfg["emb_dim"])
+        tm = dict(load=time.perf_counter() - t_start, upload=0.0, segmentation=0.0, host_masks=0.0, embedding=0.0, linkage=0.0,
+                  clustering=0.0, reconstruction=0.0, windows=0, embeddings=0, recordings=nf, groups=0)
+        out = [None] * nf
+
+        class _Ready:                       # what networks() hands finish() as a future: count, activity table, run-length view
+            def __init__(self, v):
+                self.v = v
+
+            def result(self):
+                return self.v
+
+        for group in plan_groups([p.shape[0] / rate for p, _ in loaded], group_seconds):
+            tm["groups"] += 1
+            t0 = time.perf_counter()
+            pcms = [loaded[i][0] for i in group]
+            first, total = eng.upload_many(pcms)
+            counts = [eng.num_windows(p.shape[0]) for p in pcms]
+            t1 = time.perf_counter()
+            tm["upload"] += t1 - t0
+            offs = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            W = int(offs[-1])
+            recs = []
+            if W:
+                windows = np.concatenate([first[r] + np.arange(counts[r], dtype=np.int64) for r in range(len(group))])
+                classes_all = eng.segment_classes_windows(windows)
+                t2 = time.perf_counter()
+                tm["segmentation"] += t2 - t1
+                gw, gm = [], []
+                for r in range(len(group)):
+                    classes = classes_all[offs[r]:offs[r + 1]]
+                    runs = self._runs(classes) if counts[r] else None
+                    wi, si, masks = embedding_items_from_classes(classes, excl, 400, self.cfg["window_samples"], runs) if counts[r] else \
+                        (np.zeros(0, np.int64), np.zeros(0, np.int64), np.zeros((0, eng.frames), np.float32))
+                    recs.append((classes, runs, wi, si))
+                    gw.append(first[r] + wi.astype(np.int64))           # items of one window stay adjacent (wi ascends)
+                    gm.append(masks)
+                gw, gm = np.concatenate(gw), np.concatenate(gm)
+                t3 = time.perf_counter()
+                tm["host_masks"] += t3 - t2
+                emb_all = eng.embed(gw, gm) if gw.size else np.zeros((0, dim), np.float32)
+                t4 = time.perf_counter()
+                tm["embedding"] += t4 - t3
+                tm["windows"] += W
+                tm["embeddings"] += int(gw.size)
+            else:
+                recs = [(np.zeros((0, eng.frames), np.uint8), None, np.zeros(0, np.int64), np.zeros(0, np.int64)) for _ in group]
+                emb_all = np.zeros((0, dim), np.float32)
+                t4 = time.perf_counter()
+            # per recording: the embeddings tensor networks() would return, finish()'s precomputed inputs, and the points to cluster
+            prepared, Xs, e0 = [], [], 0
+            for r, (classes, runs, wi, si) in enumerate(recs):
+                if counts[r] == 0:
+                    prepared.append(None)
+                    continue
+                emb = np.full((counts[r], 3, dim), np.nan, np.float32)
+                emb[wi, si] = emb_all[e0:e0 + wi.size]
+                e0 += wi.size
+                count, active = speaker_count_from_classes(classes, step, dur, runs), active_from_classes(classes, runs)
+                x = None
+                if count.size and np.max(count) > 0:
+                    train = clustering_points(emb, active)[2]
+                    if train.shape[0] >= 2:
+                        x = unit_vectors(train)
+                        Xs.append(x)
+                prepared.append((classes, emb, count, active, runs, x))
+            t5 = time.perf_counter()
+            Zs = iter(eng.centroid_linkage_many(Xs) if Xs else [])
+            t6 = time.perf_counter()
+            tm["clustering"] += t5 - t4
+            tm["linkage"] += t6 - t5
+            for r, i in enumerate(group):
+                uri = loaded[i][1]
+                if prepared[r] is None:                                 # a file of zero samples
+                    out[i] = (Annotation(uri), np.zeros((0, dim))) if return_embeddings else Annotation(uri)
+                    continue
+                classes, emb, count, active, runs, x = prepared[r]
+                Z = next(Zs) if x is not None else None
+
+                def handed_back(unit, Z=Z, x=x):
+                    if Z is None or unit.shape != x.shape:
+                        raise RuntimeError("diarize_many: finish() asked for a dendrogram that was not prepared")
+                    return Z
+                self._pre = (classes, _Ready((count, active, runs)))
+                self.timings = {}
+                out[i] = self.finish(classes, emb, uri, ns_[i], mins_[i], maxs_[i], return_embeddings, linkage_fn=handed_back)
+                tm["clustering"] += self.timings.get("clustering", 0.0)
+                tm["reconstruction"] += self.timings.get("reconstruction", 0.0)
+        tm["total"] = time.perf_counter() - t_start
+        self.timings = tm
+        return out
 
 
 class Pipeline:
