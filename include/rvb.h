@@ -192,6 +192,40 @@ int rvb_batch_n_samples(rvb_engine* e, int64_t* out /* [n_rec] */);
 int rvb_fbank_batch(rvb_engine* e, int chunk_size, float* feats_out /* nullable [total_chunks*chunk_size*80] */, int64_t* n_frames,
                     int64_t* first_chunk);
 
+/* Chunks cut at pauses, chosen on the device (csrc/pause_chunks.hip).  The calls above cut a recording every chunk_size frames, as
+ * the reference's feats_batcher does, which usually lands inside a word.  rvb_pause_chunks moves each cut to the quietest place of
+ * the `search` frames before that boundary.  THE DEFINITION, per recording, over its own n fbank frames f = 0 .. n-1 (nothing reads
+ * a neighbour recording's rows):
+ *   loudness  e[f] = the fp32 sum of the 80 log-mel values of frame f.  s[c], for a cut position c in 0 .. n (the cut lies between
+ *             frames c-1 and c), = the fp32 sum of e[clamp(c+j, 0, n-1)] for j = -h .. h-1; h = the smoothing half-width, 1 <= h <= 64
+ *             (10 = 200 ms is the default of the Python layers).  e is formed as ONE sum of 80 terms and s as ONE sum of 2h values
+ *             of e, in any order within each sum; no running or prefix sums across frames.
+ *   pieces    start_0 = 0.  While n - start_k > chunk_size: lo = start_k + chunk_size - search, hi = min(start_k + chunk_size, n - 7),
+ *             start_{k+1} = the LAST c in [lo, hi] that attains the minimum of s; a NaN s is never chosen, and if every candidate is
+ *             NaN the cut is hi.  The final piece runs to n.  lens[k] = start_{k+1} - start_k.
+ *   search    the frames before the fixed boundary in which a cut may fall, 7 <= search <= chunk_size - 7 (the Python layers default
+ *             to chunk_size / 4).  Then every piece but a recording's only one has at least 7 frames, none exceeds chunk_size, and
+ *             lo <= hi always.  A recording with n <= chunk_size is one piece, identical to the fixed chunk; n = 0 gives no piece.
+ *   ties      the last minimum cuts as late as possible (fewer chunks); exact ties are common: digital silence gives every bin the
+ *             floor value -15.942385.
+ * Valid after rvb_fbank (one recording) or rvb_fbank_batch (n_rec recordings; the chunk_size here need not be that call's).  Three
+ * kernels (frame loudness, cut search: one workgroup per recording, gather) and one copy of the small start table to the host.
+ * Piece k's rows go to chunk row k * chunk_size of a SECOND feature buffer, the rest of the slot zero; pieces of all recordings are
+ * numbered consecutively in recording order.  Outputs: first_chunk [n_rec + 1] = each recording's first piece (first_chunk[n_rec] =
+ * *n_chunks = all pieces), starts [*n_chunks] = each piece's first frame within its recording, lens [*n_chunks]; feats_out
+ * (nullable) receives the *n_chunks * chunk_size packed rows of 80.  From then on rvb_encode(e, NULL, first_chunk, lens, B,
+ * chunk_size, ...) reads the packed buffer.  The frame-ordered features are kept: a second call with other parameters works from
+ * them.  The next upload or fbank call restores the fixed layout.
+ * Checked before any device work, by name: RVB_E_ARG for h or search out of range and for chunk_size outside [7, cfg.chunk_frames];
+ * RVB_E_STATE when no features are resident; RVB_E_NOMEM naming the bytes.  capacity = the entries of starts and lens: if the cuts
+ * give more pieces (at most ceil(n / (chunk_size - search)) per recording) the call returns RVB_E_ARG naming the count, *n_chunks
+ * holds it, nothing else is written and the layout stays as it was.  Timed under "pause_chunks" in rvb_get_timing, one launch group
+ * per call (the bracket holds the three kernels and the table copy between them). */
+int rvb_pause_chunks(rvb_engine* e, int chunk_size, int search, int h, int64_t* first_chunk /* [n_rec+1] */, int32_t* starts,
+                     int32_t* lens, int64_t capacity, int64_t* n_chunks, float* feats_out /* nullable */);
+/* Back to the fixed layout without a new fbank call: rvb_encode(e, NULL, ...) reads the frame-ordered features again (host only). */
+int rvb_fixed_chunks(rvb_engine* e);
+
 /* Chunk-masked encoder attention for the following rvb_encode calls: query frame i attends the encoder frames
  * [max((i/chunk - left)*chunk, 0), (i/chunk + 1)*chunk) -- what `decoding_chunk_size` / `num_decoding_left_chunks`
  * select in BaseEncoder.forward via add_optional_chunk_mask (encoder.py:140-145, utils/mask.py:86-197) for models

@@ -79,6 +79,8 @@ SIGNATURES = {
     "rvb_upload_batch": (C.c_int, [_eng, C.POINTER(C.c_void_p), _i32p, _i64p, _i32p, C.c_int]),
     "rvb_batch_n_samples": (C.c_int, [_eng, _i64p]),
     "rvb_fbank_batch": (C.c_int, [_eng, C.c_int, _f32p, _i64p, _i64p]),
+    "rvb_pause_chunks": (C.c_int, [_eng, C.c_int, C.c_int, C.c_int, _i64p, _i32p, _i32p, C.c_int64, _i64p, _f32p]),
+    "rvb_fixed_chunks": (C.c_int, [_eng]),
     "rvb_audio_probe": (C.c_int, [C.c_void_p, C.c_int64, C.POINTER(AudioInfo)]),
     "rvb_audio_decode_f32": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int, _f32p, C.c_int64, C.c_int, C.POINTER(AudioInfo)]),
     "rvb_audio_decode_i16": (C.c_int64, [C.c_void_p, C.c_int64, C.c_int, _i16p, C.c_int64, C.c_int, C.POINTER(AudioInfo)]),
@@ -272,6 +274,8 @@ TEST_SIGNATURES = {
     "rvb_test_pdist_nn": (C.c_int, [_f64p, C.c_int, C.c_int, _f64p, _i32p, _f64p]),
     "rvb_test_centroid_linkage": (C.c_int, [_f64p, C.c_int, C.c_int, C.c_int, _f64p, _i32p, _f64p]),
     "rvb_test_centroid_linkage_many": (C.c_int, [_f64p, _i32p, C.c_int, C.c_int, _f64p, _i32p]),
+    "rvb_test_pause_cuts": (C.c_int, [_f32p, C.c_int64, _i64p, _i64p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, C.c_int64, _i32p]),
+    "rvb_test_gather_chunks": (C.c_int, [_f32p, C.c_int64, _i64p, _i32p, C.c_int64, C.c_int, _f32p]),
 }
 
 

@@ -1,6 +1,7 @@
 """`reverb` console script: same flags and output files as the reference's
 `asr/wenet/bin/recognize_wav.py` (:29-147 flags, :150-208 main): one `<result_dir>/<mode>/<audio>.ctm`
-per decoding mode.  Extra flags: --dtype, --max_chunks, and --audio_list FILE (one path per line) in place of --audio_file: every listed
+per decoding mode.  Extra flags: --dtype, --max_chunks, --chunking {fixed,pauses} [--pause_search_frames N] [--pause_smooth_frames H] (cut
+the chunks at pauses instead of every --chunk_size frames: ReverbASR.transcribe_modes), and --audio_list FILE (one path per line) in place of --audio_file: every listed
 recording in one pass (ReverbASR.transcribe_modes_many), one `<result_dir>/<mode>/<stem>.ctm` each."""
 from __future__ import annotations
 
@@ -43,6 +44,12 @@ def get_args(argv=None):
     p.add_argument("--log_level", default="INFO", help="log level")
     p.add_argument("--dtype", default="bf16", choices=["bf16", "f32"], help="device compute mode")
     p.add_argument("--max_chunks", type=int, default=64, help="chunks per device batch")
+    p.add_argument("--chunking", default="fixed", choices=["fixed", "pauses"],
+                   help="fixed: a chunk every --chunk_size frames; pauses: each cut moved to the quietest place shortly before")
+    p.add_argument("--pause_search_frames", type=int, default=None,
+                   help="--chunking pauses: frames before the fixed boundary in which a cut may fall (default chunk_size // 4)")
+    p.add_argument("--pause_smooth_frames", type=int, default=10,
+                   help="--chunking pauses: half-width in frames of the loudness smoothing, 1 .. 64")
     p.add_argument("--context_list_path", default=None, help="hot words to bias ctc_prefix_beam_search / attention_rescoring towards, one per line")
     p.add_argument("--context_graph_score", type=float, default=6.0, help="bonus per matched hot-word token")
     args = p.parse_args(argv)
@@ -94,7 +101,8 @@ def main(argv=None):
               num_decoding_left_chunks=args.num_decoding_left_chunks, ctc_weight=args.ctc_weight,
               simulate_streaming=args.simulate_streaming, reverse_weight=args.reverse_weight,
               blank_penalty=args.blank_penalty, length_penalty=args.length_penalty,
-              timings_adjustment=args.timings_adjustment)
+              timings_adjustment=args.timings_adjustment, chunking=args.chunking, pause_search=args.pause_search_frames,
+              pause_smooth=args.pause_smooth_frames)
     if args.audio_files is not None:
         files, per_file = args.audio_files, reverb.transcribe_modes_many(args.audio_files, args.modes, **kw)
     else:

@@ -301,6 +301,12 @@ struct rvb_engine {
   std::vector<int64_t> h_frame0;                 // host images of the descriptors of the last rvb_fbank_batch
   std::vector<rvb::FbankRec> h_rec;
   rvb::DevBuf d_frame0, d_rec;
+  // rvb_pause_chunks (pause_chunks.hip): `feats` keeps the frame-ordered rows; while `packed` is set rvb_encode reads the pieces from
+  // `feats_packed` instead (packed_rows rows).  Every upload and every fbank call clears `packed`.
+  int feat_kind = 0;                             // what `feats` holds: 0 nothing, 1 rvb_fbank's rows, 2 rvb_fbank_batch's
+  bool packed = false;
+  int64_t packed_rows = 0;
+  rvb::DevBuf feats_packed, pc_loud, pc_rec, pc_frame0, pc_table, pc_count, pc_pieces;
 
   // ---- batch state ----
   int B = 0, T0 = 0, T1 = 0, F1 = 0, T2 = 0, F2 = 0, beam = 0;

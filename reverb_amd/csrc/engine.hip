@@ -254,6 +254,7 @@ void rvb_destroy(rvb_engine* e) {
   e->d_xlse.release(); e->d_xsum.release(); e->d_xtop.release();
   e->atopv.release(); e->atopi.release(); e->d_stream_i32.release(); e->d_amax.release(); e->d_f8sat.release();
   e->wave_f32.release(); e->wave_in.release(); e->rs_kernel.release(); e->d_frame0.release(); e->d_rec.release();
+  for (DevBuf* b : {&e->feats_packed, &e->pc_loud, &e->pc_rec, &e->pc_frame0, &e->pc_table, &e->pc_count, &e->pc_pieces}) b->release();
   e->jlogp.release(); e->jpair_row.release(); e->jpair_tok.release(); e->jpair_out.release();
   for (auto& b : e->jkv) b.release();
   for (auto* v : {&e->stream_st.kv, &e->stream_st.kv2, &e->stream_st.cnn, &e->stream_st.cnn2}) for (auto& b : *v) b.release();
@@ -308,6 +309,7 @@ int rvb_upload_pcm(rvb_engine* e, const int16_t* pcm, int64_t n) {
   if (!e || (!pcm && n > 0) || n < 0) { set_error("rvb_upload_pcm: bad argument"); return E_ARG; }
   RVB_HIP_CHECK(hipSetDevice(e->device));
   RVB_TRY(drop_pending_upload(e));
+  e->packed = false;             // rvb_pause_chunks: an upload restores the fixed layout
   RVB_TRY(e->pcm.ensure((size_t)n * 2 + 16));
   if (n) RVB_HIP_CHECK(hipMemcpyAsync(e->pcm.p, pcm, (size_t)n * 2, hipMemcpyHostToDevice, e->stream));
   RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
@@ -371,6 +373,7 @@ int rvb_upload_pcm_rate(rvb_engine* e, const int16_t* pcm, int64_t n, int sample
   if (!e || (!pcm && n > 0) || n < 0 || sample_rate < 1000 || sample_rate > 384000) { set_error("rvb_upload_pcm_rate: bad argument"); return E_ARG; }
   RVB_HIP_CHECK(hipSetDevice(e->device));
   RVB_TRY(drop_pending_upload(e));
+  e->packed = false;
   RVB_TRY(e->pcm.ensure((size_t)n * 2 + 16));
   if (n) RVB_HIP_CHECK(hipMemcpyAsync(e->pcm.p, pcm, (size_t)n * 2, hipMemcpyHostToDevice, e->stream));
   return resample_uploaded(e, false, n, sample_rate);
@@ -380,6 +383,7 @@ int rvb_upload_wave_f32(rvb_engine* e, const float* wave, int64_t n, int sample_
   if (!e || (!wave && n > 0) || n < 0 || sample_rate < 1000 || sample_rate > 384000) { set_error("rvb_upload_wave_f32: bad argument"); return E_ARG; }
   RVB_HIP_CHECK(hipSetDevice(e->device));
   RVB_TRY(drop_pending_upload(e));
+  e->packed = false;
   rvb::DevBuf& dst = sample_rate == 16000 ? e->wave_f32 : e->wave_in;
   RVB_TRY(dst.ensure((size_t)std::max<int64_t>(n, 1) * 4));
   if (n) RVB_HIP_CHECK(hipMemcpyAsync(dst.p, wave, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
@@ -420,6 +424,7 @@ int rvb_fbank(rvb_engine* e, float* feats_out, int64_t* n_frames) {
     e->batch = false;
   }
   if (e->batch) { set_error("rvb_fbank: the engine holds a batch of recordings (rvb_upload_batch): call rvb_fbank_batch"); return E_STATE; }
+  e->packed = false;             // rvb_pause_chunks: an fbank call restores the fixed layout
   const int64_t nf = rvb_num_frames(e->n_samples);
   const int64_t T0 = e->cfg.chunk_frames;
   // zero padded so that ANY chunking with chunk_size <= chunk_frames finds whole chunks (feats_batcher pads the last
@@ -440,7 +445,7 @@ int rvb_fbank(rvb_engine* e, float* feats_out, int64_t* n_frames) {
     RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
   }
   // features that stay in HBM: nothing to wait for, rvb_encode is ordered behind the kernel on the engine's stream
-  e->n_frames = nf; e->feat_rows = rows;
+  e->n_frames = nf; e->feat_rows = rows; e->feat_kind = 1;
   if (n_frames) *n_frames = nf;
   return OK;
 }

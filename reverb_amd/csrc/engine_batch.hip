@@ -98,6 +98,7 @@ int rvb_upload_batch(rvb_engine* e, const void* const* data, const int32_t* samp
     else src[r] = in_off[r];
   }
   e->batch = false;                     // whatever fails below leaves no half-made batch behind
+  e->packed = false; e->feat_kind = 0;  // ... and no features of an earlier upload (rvb_pause_chunks)
   RVB_TRY(e->pcm.ensure((size_t)n_i16 * 2 + 16));
   RVB_TRY(e->wave_in.ensure((size_t)std::max<int64_t>(n_fin, 1) * 4));
   RVB_TRY(e->wave_f32.ensure((size_t)std::max<int64_t>(n_f16, 1) * 4));
@@ -159,6 +160,7 @@ int rvb_fbank_batch(rvb_engine* e, int chunk_size, float* feats_out, int64_t* n_
   if (!e->fb_window.p) { set_error("rvb_fbank_batch before rvb_finalize"); return E_STATE; }
   if (!e->batch) { set_error("rvb_fbank_batch: no batch of recordings: call rvb_upload_batch first (rvb_fbank serves a single upload)"); return E_STATE; }
   RVB_HIP_CHECK(hipSetDevice(e->device));
+  e->packed = false; e->feat_kind = 0;  // rvb_pause_chunks: an fbank call restores the fixed layout
   const int n_rec = (int)e->batch_n.size();
   plan(e->batch_n.data(), n_rec, chunk_size, n_frames, first_chunk, nullptr);
   e->h_frame0.resize(n_rec + 1);
@@ -187,7 +189,7 @@ int rvb_fbank_batch(rvb_engine* e, int chunk_size, float* feats_out, int64_t* n_
     RVB_HIP_CHECK(hipMemcpyAsync(feats_out, e->feats.p, (size_t)rows * 80 * 4, hipMemcpyDeviceToHost, e->stream));
     RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
   }
-  e->n_frames = f; e->feat_rows = rows;
+  e->n_frames = f; e->feat_rows = rows; e->feat_kind = 2;
   return OK;
 }
 

@@ -242,10 +242,11 @@ int encode_impl(rvb_engine* e, const float* feats, int64_t first_chunk, const in
     RVB_TRY(upload_f32(e, e->d_feats_in, feats, (size_t)B * T0 * F0));
     d_feats = e->d_feats_in.as<float>();
   } else {
-    if (!e->feats.p || (first_chunk + B) * (int64_t)T0 > e->feat_rows) {
+    const DevBuf& fb = e->packed ? e->feats_packed : e->feats;       // rvb_pause_chunks: the pieces, one per chunk slot
+    if (!fb.p || first_chunk < 0 || (first_chunk + B) * (int64_t)T0 > (e->packed ? e->packed_rows : e->feat_rows)) {
       set_error("rvb_encode: device features missing or too short (call rvb_fbank first)"); return E_STATE;
     }
-    d_feats = e->feats.as<float>() + (size_t)first_chunk * T0 * F0;
+    d_feats = fb.as<float>() + (size_t)first_chunk * T0 * F0;
   }
   // Sub-batch pipeline: the batch is encoded in up to 2 slices on the engine stream; each slice ends with
   // an async D2H copy of its per-frame top-k into pinned memory and an event.  rvb_encode returns once

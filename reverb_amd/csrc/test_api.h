@@ -320,6 +320,18 @@ int rvb_test_gemm_timeline(int M, int N, int K, int act, int out_f32, int with_r
 int rvb_test_gemm_bench(int dtype, int M, int N, int K, int variant, int iters, int act, int out_f32, int with_res,
                         double* ms_out, double* max_abs_diff_vs_variant1);
 
+/* pause_chunks.hip: the loudness and cut-search kernels behind rvb_pause_chunks on host feature rows feats [n_rows][80]: recording r
+ * owns the rows [row0[r], row0[r] + n_frames[r]); the rows between recordings may hold anything.  starts: every recording's piece
+ * starts, concatenated in recording order (at most `capacity` entries: RVB_E_ARG naming the count if more); counts [n_rec].  The
+ * parameters are refused as by rvb_pause_chunks, before any device work, in this hook's name. */
+int rvb_test_pause_cuts(const float* feats, int64_t n_rows, const int64_t* row0, const int64_t* n_frames, int n_rec, int chunk_size,
+                        int search, int h, int32_t* starts, int64_t capacity, int32_t* counts);
+/* pause_chunks.hip: the gather kernel alone: lens[k] rows from row src[k] of feats [n_rows][80] to rows [k * chunk_size ..) of out
+ * [n_pieces * chunk_size + 1][80], the rest of each slot zero; the device buffer starts as all-ones bytes and comes back whole, so
+ * the row behind the last slot shows whether anything was written past it. */
+int rvb_test_gather_chunks(const float* feats, int64_t n_rows, const int64_t* src, const int32_t* lens, int64_t n_pieces,
+                           int chunk_size, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2068,3 +2068,99 @@ extern "C" int rvb_test_fbank(const int16_t* pcm, int64_t n_samples, float* feat
   memcpy(feats, all.data(), (size_t)nf * 80 * 4);
   return OK;
 }
+
+// ---- pause_chunks.hip
+#include "pause_chunks.h"
+
+namespace {
+struct HipMem {      // a device allocation of exactly the bytes asked for, freed on every way out
+  void* p = nullptr;
+  ~HipMem() { if (p) (void)hipFree(p); }
+  int alloc(const char* who, size_t bytes) {
+    if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) { p = nullptr; (void)hipGetLastError(); set_error(std::string(who) + ": hipMalloc of " + std::to_string(bytes) + " bytes failed"); return E_NOMEM; }
+    return OK;
+  }
+};
+int need_device(const char* who) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error(std::string(who) + ": no HIP device available: librvb has no CPU fallback"); return E_HIP; }
+  return OK;
+}
+}  // namespace
+
+extern "C" int rvb_test_pause_cuts(const float* feats, int64_t n_rows, const int64_t* row0, const int64_t* n_frames, int n_rec, int chunk_size,
+                                   int search, int h, int32_t* starts, int64_t capacity, int32_t* counts) {
+  const char* who = "rvb_test_pause_cuts";
+  RVB_TRY(pause_check_args(who, chunk_size, search, h));
+  if (!feats || !row0 || !n_frames || !starts || !counts || n_rows < 1 || n_rec < 1 || n_rec > 65536 || capacity < 0) { set_error(std::string(who) + ": bad argument"); return E_ARG; }
+  std::vector<PauseRec> rec(n_rec);
+  std::vector<int64_t> frame0(n_rec + 1, 0);
+  int64_t tab = 0;
+  for (int r = 0; r < n_rec; ++r) {
+    if (row0[r] < 0 || n_frames[r] < 0 || n_frames[r] > (1 << 30) || row0[r] + n_frames[r] > n_rows) {
+      set_error(std::string(who) + ": recording " + std::to_string(r) + " lies outside the " + std::to_string(n_rows) + " rows"); return E_ARG;
+    }
+    const int64_t cap = pause_max_pieces(n_frames[r], chunk_size, search);
+    rec[r] = PauseRec{row0[r], tab, (int32_t)n_frames[r], (int32_t)cap};
+    frame0[r + 1] = frame0[r] + n_frames[r];
+    tab += cap;
+  }
+  RVB_TRY(need_device(who));
+  HipMem df, dl, dr, d0, dt, dc;
+  RVB_TRY(df.alloc(who, (size_t)n_rows * 80 * 4));
+  RVB_TRY(dl.alloc(who, (size_t)n_rows * 4));
+  RVB_TRY(dr.alloc(who, rec.size() * sizeof(PauseRec)));
+  RVB_TRY(d0.alloc(who, frame0.size() * 8));
+  RVB_TRY(dt.alloc(who, (size_t)std::max<int64_t>(tab, 1) * 4));
+  RVB_TRY(dc.alloc(who, (size_t)n_rec * 4));
+  RVB_HIP_CHECK(hipMemcpy(df.p, feats, (size_t)n_rows * 80 * 4, hipMemcpyHostToDevice));
+  RVB_HIP_CHECK(hipMemset(dl.p, 0xff, (size_t)n_rows * 4));            // e of a row nobody owns: NaN
+  RVB_HIP_CHECK(hipMemcpy(dr.p, rec.data(), rec.size() * sizeof(PauseRec), hipMemcpyHostToDevice));
+  RVB_HIP_CHECK(hipMemcpy(d0.p, frame0.data(), frame0.size() * 8, hipMemcpyHostToDevice));
+  RVB_TRY(pause_loudness(nullptr, (const float*)df.p, (const int64_t*)d0.p, (const PauseRec*)dr.p, n_rec, frame0[n_rec], (float*)dl.p));
+  RVB_TRY(pause_cuts(nullptr, (const float*)dl.p, (const PauseRec*)dr.p, n_rec, chunk_size, search, h, (int32_t*)dt.p, (int32_t*)dc.p));
+  if (hipDeviceSynchronize() != hipSuccess) { set_error(std::string(who) + ": a kernel failed"); return E_HIP; }
+  std::vector<int32_t> table((size_t)std::max<int64_t>(tab, 1)), cnt(n_rec);
+  if (tab) RVB_HIP_CHECK(hipMemcpy(table.data(), dt.p, (size_t)tab * 4, hipMemcpyDeviceToHost));
+  RVB_HIP_CHECK(hipMemcpy(cnt.data(), dc.p, (size_t)n_rec * 4, hipMemcpyDeviceToHost));
+  int64_t total = 0;
+  for (int r = 0; r < n_rec; ++r) {
+    if (cnt[r] < 0 || cnt[r] > rec[r].tab_cap) { set_error(std::string(who) + ": the cut search left its table"); return E_HIP; }
+    total += cnt[r];
+  }
+  if (total > capacity) { set_error(std::string(who) + ": capacity " + std::to_string(capacity) + " is too small: " + std::to_string(total) + " pieces"); return E_ARG; }
+  int64_t k = 0;
+  for (int r = 0; r < n_rec; ++r) {
+    counts[r] = cnt[r];
+    for (int j = 0; j < cnt[r]; ++j) starts[k++] = table[rec[r].tab0 + j];
+  }
+  return OK;
+}
+
+extern "C" int rvb_test_gather_chunks(const float* feats, int64_t n_rows, const int64_t* src, const int32_t* lens, int64_t n_pieces,
+                                      int chunk_size, float* out) {
+  const char* who = "rvb_test_gather_chunks";
+  if (!feats || !src || !lens || !out || n_rows < 1 || n_pieces < 1 || n_pieces > (1 << 20) || chunk_size < 7 || chunk_size > (1 << 20)) {
+    set_error(std::string(who) + ": bad argument"); return E_ARG;
+  }
+  std::vector<PausePiece> pieces((size_t)n_pieces);
+  for (int64_t k = 0; k < n_pieces; ++k) {
+    if (src[k] < 0 || lens[k] < 0 || lens[k] > chunk_size || src[k] + lens[k] > n_rows) {
+      set_error(std::string(who) + ": piece " + std::to_string(k) + " lies outside the " + std::to_string(n_rows) + " rows or exceeds chunk_size"); return E_ARG;
+    }
+    pieces[k] = PausePiece{src[k], lens[k], 0};
+  }
+  RVB_TRY(need_device(who));
+  const size_t out_bytes = (size_t)(n_pieces * chunk_size + 1) * 80 * 4;       // one sentinel row behind the last slot
+  HipMem df, dp, dout;
+  RVB_TRY(df.alloc(who, (size_t)n_rows * 80 * 4));
+  RVB_TRY(dp.alloc(who, pieces.size() * sizeof(PausePiece)));
+  RVB_TRY(dout.alloc(who, out_bytes));
+  RVB_HIP_CHECK(hipMemcpy(df.p, feats, (size_t)n_rows * 80 * 4, hipMemcpyHostToDevice));
+  RVB_HIP_CHECK(hipMemcpy(dp.p, pieces.data(), pieces.size() * sizeof(PausePiece), hipMemcpyHostToDevice));
+  RVB_HIP_CHECK(hipMemset(dout.p, 0xff, out_bytes));
+  RVB_TRY(pause_gather(nullptr, (const float*)df.p, (const PausePiece*)dp.p, n_pieces, chunk_size, (float*)dout.p));
+  if (hipDeviceSynchronize() != hipSuccess) { set_error(std::string(who) + ": the kernel failed"); return E_HIP; }
+  RVB_HIP_CHECK(hipMemcpy(out, dout.p, out_bytes, hipMemcpyDeviceToHost));
+  return OK;
+}

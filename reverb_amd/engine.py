@@ -63,6 +63,11 @@ def model_cfg_from_configs(configs: dict, dtype: str, max_chunks: int, chunk_fra
     return cfg
 
 
+def _check_chunking(chunking: str):
+    if chunking not in ("fixed", "pauses"):
+        raise ValueError(f"chunking must be 'fixed' or 'pauses', not {chunking!r}")
+
+
 def joint_topk(methods, beam_size: int) -> Optional[int]:
     """CTC log-probs to keep per frame when `joint_decoding` is among the modes (its pre-beam), else None."""
     if "joint_decoding" not in methods:
@@ -175,6 +180,7 @@ class Engine:
         int16; a float32 array (the `.to(torch.float)` of a source whose native format is not int16) is uploaded as it is."""
         self._n_samples_next = None             # a synchronous upload replaces a pending upload_pcm_async
         self._batch_n = self._batch_plan = None # ... and a batch
+        self._packed = False                    # ... and the pieces of pause_chunks
         if isinstance(pcm, np.ndarray) and pcm.dtype.kind == "f":
             wave = np.ascontiguousarray(pcm, dtype=np.float32).reshape(-1)
             check(self.lib.rvb_upload_wave_f32(self.handle, wave.ctypes.data_as(_lib._f32p), len(wave), int(sample_rate)),
@@ -295,6 +301,8 @@ class Engine:
             out = np.empty((int(self.lib.rvb_num_frames(self._n_samples)), 80), np.float32)
         check(self.lib.rvb_fbank(self.handle, fptr(out), C.byref(n)), "rvb_fbank")
         self.n_frames = int(n.value)
+        self._resident = [self.n_frames]        # frames per recording of the resident features (pause_chunks)
+        self._packed = False
         return (self.n_frames, out) if return_feats else self.n_frames
 
     # -------------------------------------------------------------------------------- several recordings at once
@@ -316,6 +324,7 @@ class Engine:
         rate = np.array([int(r) for _, r in items], np.int32)
         self._n_samples_next = None
         self._batch_n = self._batch_plan = None
+        self._packed = False
         check(self.lib.rvb_upload_batch(self.handle, data, iptr(fmt), ns.ctypes.data_as(_lib._i64p), iptr(rate), n), "rvb_upload_batch")
         out = np.empty(n, np.int64)
         check(self.lib.rvb_batch_n_samples(self.handle, out.ctypes.data_as(_lib._i64p)), "rvb_batch_n_samples")
@@ -344,19 +353,61 @@ class Engine:
         out = np.empty((int(first[-1]) * int(chunk_size), 80), np.float32) if return_feats else None
         check(self.lib.rvb_fbank_batch(self.handle, int(chunk_size), fptr(out), p64(nf), p64(first)), "rvb_fbank_batch")
         self._batch_plan = (int(chunk_size), nf, first, lens)
+        self._resident = [int(x) for x in nf]
+        self._packed = False
         return (nf, first, out) if return_feats else (nf, first)
 
+    def pause_chunks(self, chunk_size: int, search: Optional[int] = None, smooth: int = 10, return_feats: bool = False):
+        """Cut the resident features (after fbank() or fbank_batch()) at pauses instead of every chunk_size frames (rvb_pause_chunks;
+        the definition is in include/rvb.h): each cut falls in the `search` frames before the fixed boundary (default chunk_size // 4),
+        where the loudness summed over 2 * smooth frames is smallest.  -> (first_chunk [n_rec + 1], starts [chunks], lens [chunks])
+        and, when asked, the packed (chunks * chunk_size, 80) rows: piece k of recording r is chunk first_chunk[r] + k, starts at
+        frame starts[k] of its recording and has lens[k] frames.  encode(None, lens[a:b], ..., first_chunk=a, T0=chunk_size) reads the
+        pieces until the next upload or fbank call.  Both defaults are unmeasured (docs/tuning-log.md)."""
+        search = int(chunk_size) // 4 if search is None else int(search)
+        res = getattr(self, "_resident", None) or [0]
+        gap = max(int(chunk_size) - search, 1)
+        cap = sum(-(-n // gap) for n in res) + 1
+        first = np.zeros(len(res) + 1, np.int64)
+        starts, lens = np.zeros(cap, np.int32), np.zeros(cap, np.int32)
+        n = C.c_int64(0)
+        p64 = lambda a: a.ctypes.data_as(_lib._i64p)
+        out = None
+        if return_feats:        # sized by a first call: the piece count is not known before the cuts are
+            check(self.lib.rvb_pause_chunks(self.handle, int(chunk_size), search, int(smooth), p64(first), iptr(starts), iptr(lens), cap,
+                                            C.byref(n), None), "rvb_pause_chunks")
+            out = np.empty((int(n.value) * int(chunk_size), 80), np.float32)
+        check(self.lib.rvb_pause_chunks(self.handle, int(chunk_size), search, int(smooth), p64(first), iptr(starts), iptr(lens), cap,
+                                        C.byref(n), fptr(out)), "rvb_pause_chunks")
+        k = int(n.value)
+        self._packed = True
+        return (first, starts[:k].copy(), lens[:k].copy()) + ((out,) if return_feats else ())
+
+    def fixed_chunks(self):
+        """Undo pause_chunks(): encode(None, ...) reads the frame-ordered features again (every upload and fbank call does the same)."""
+        if getattr(self, "_packed", False):
+            check(self.lib.rvb_fixed_chunks(self.handle), "rvb_fixed_chunks")
+            self._packed = False
+
     def decode_batch(self, modes, chunk_size: int, beam_size: int, ctc_weight: float, reverse_weight: float,
-                     blank_penalty: float = 0.0, length_penalty: float = 0.0) -> List[Dict[str, List[DecodeResult]]]:
+                     blank_penalty: float = 0.0, length_penalty: float = 0.0, chunking: str = "fixed",
+                     pause_search: Optional[int] = None, pause_smooth: int = 10):
         """decode_resident() over every chunk of the batch, `max_chunks` chunks per encode whichever recordings they belong to (a
-        recording whose chunks fall into two encodes is the normal case) -> per recording {mode: [DecodeResult per chunk]}."""
+        recording whose chunks fall into two encodes is the normal case) -> per recording {mode: [DecodeResult per chunk]}.
+        chunking="pauses": the chunks are the pieces of pause_chunks(chunk_size, pause_search, pause_smooth), and the result is
+        (that list, per recording the start frame of each of its pieces)."""
         if not 7 <= chunk_size <= self.cfg.chunk_frames:
             raise RvbError(f"resident decoding needs 7 <= chunk_size <= engine chunk_frames ({self.cfg.chunk_frames}); "
                            "ReverbASR rebuilds the engine for larger chunks")
+        _check_chunking(chunking)
         plan = getattr(self, "_batch_plan", None)
         if plan is None or plan[0] != int(chunk_size):
             self.fbank_batch(chunk_size)
+        self.fixed_chunks()
         _, _, first, lens = self._batch_plan
+        starts = None
+        if chunking == "pauses":
+            first, starts, lens = self.pause_chunks(chunk_size, pause_search, pause_smooth)
         flat: Dict[str, List[DecodeResult]] = {m: [] for m in modes}
         for s in range(0, len(lens), self.cfg.max_chunks):
             e = min(len(lens), s + self.cfg.max_chunks)
@@ -364,7 +415,10 @@ class Engine:
             part = self.search(modes, ctc_weight, reverse_weight, length_penalty)
             for m in modes:
                 flat[m].extend(part[m])
-        return [{m: flat[m][int(first[r]):int(first[r + 1])] for m in modes} for r in range(len(first) - 1)]
+        per_rec = [{m: flat[m][int(first[r]):int(first[r + 1])] for m in modes} for r in range(len(first) - 1)]
+        if starts is None:
+            return per_rec
+        return per_rec, [starts[int(first[r]):int(first[r + 1])].tolist() for r in range(len(first) - 1)]
 
     # -------------------------------------------------------------------------------- decode
     def encode(self, feats: Optional[np.ndarray], lens, beam: int, blank_penalty: float = 0.0, first_chunk: int = 0,
@@ -878,18 +932,29 @@ class Engine:
         return results
 
     def decode_resident(self, n_frames: int, modes, chunk_size: int, beam_size: int, ctc_weight: float,
-                        reverse_weight: float, blank_penalty: float = 0.0, length_penalty: float = 0.0
-                        ) -> Dict[str, List[DecodeResult]]:
+                        reverse_weight: float, blank_penalty: float = 0.0, length_penalty: float = 0.0, chunking: str = "fixed",
+                        pause_search: Optional[int] = None, pause_smooth: int = 10):
         """Decode the device-resident features of the last fbank() call: fixed, non-overlapping
         chunks with a length-masked zero-padded tail (feats_batcher, cli/reverb.py:148-180),
-        `max_chunks` chunks per launch, results concatenated in chunk order."""
+        `max_chunks` chunks per launch, results concatenated in chunk order -> {mode: [DecodeResult per chunk]}.
+        chunking="pauses": the chunks are the pieces of pause_chunks(chunk_size, pause_search, pause_smooth), of at most chunk_size
+        frames each, and the result is (that dict, the start frame of each piece)."""
         if not 7 <= chunk_size <= self.cfg.chunk_frames:
             raise RvbError(f"resident decoding needs 7 <= chunk_size <= engine chunk_frames ({self.cfg.chunk_frames}); "
                            "ReverbASR rebuilds the engine for larger chunks")
-        n_chunks = -(-n_frames // chunk_size)
-        lens = np.full(n_chunks, chunk_size, np.int32)
-        if n_chunks:
-            lens[-1] = n_frames - (n_chunks - 1) * chunk_size
+        _check_chunking(chunking)
+        starts = None
+        if chunking == "pauses":
+            _, starts, lens = self.pause_chunks(chunk_size, pause_search, pause_smooth)
+            if int(lens.sum()) != int(n_frames):
+                raise RvbError(f"decode_resident: n_frames = {n_frames}, the resident features hold {int(lens.sum())}")
+            n_chunks = len(lens)
+        else:
+            self.fixed_chunks()
+            n_chunks = -(-n_frames // chunk_size)
+            lens = np.full(n_chunks, chunk_size, np.int32)
+            if n_chunks:
+                lens[-1] = n_frames - (n_chunks - 1) * chunk_size
         out: Dict[str, List[DecodeResult]] = {m: [] for m in modes}
         for s in range(0, n_chunks, self.cfg.max_chunks):
             e = min(n_chunks, s + self.cfg.max_chunks)
@@ -897,7 +962,7 @@ class Engine:
             part = self.search(modes, ctc_weight, reverse_weight, length_penalty)
             for m in modes:
                 out[m].extend(part[m])
-        return out
+        return out if starts is None else (out, starts.tolist())
 
     # -------------------------------------------------------------------------------- timings
     def set_profiling(self, on, gemm_only: bool = False):

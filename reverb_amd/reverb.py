@@ -246,7 +246,12 @@ class ReverbASR:
                          chunk_size: int = 2051, batch_size: int = 1, beam_size: int = 10,
                          decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1, ctc_weight: float = 0.1,
                          simulate_streaming: bool = False, reverse_weight: float = 0.0, blank_penalty: float = 0.0,
-                         length_penalty: float = 0.0, timings_adjustment: float = 230) -> list[str]:
+                         length_penalty: float = 0.0, timings_adjustment: float = 230, chunking: str = "fixed",
+                         pause_search: Optional[int] = None, pause_smooth: int = 10) -> list[str]:
+        """chunking="pauses": instead of every chunk_size frames the recording is cut where it is quietest within the pause_search
+        frames (default chunk_size // 4) before each such boundary, the loudness smoothed over 2 * pause_smooth frames
+        (Engine.pause_chunks; both defaults are unmeasured), and CTM times follow the pieces' own start frames."""
+        _check_pause_args(chunking, simulate_streaming)
         fc = self.test_conf["fbank_conf"]
         if (fc["num_mel_bins"], fc["frame_length"], fc["frame_shift"]) != (80, 25, 10):
             raise NotImplementedError("the device fbank is built for 80 bins / 25 ms / 10 ms")
@@ -270,9 +275,11 @@ class ReverbASR:
                                self.input_frame_length, self.output_frame_length) for mode in modes]
         eng.apply_decoding_chunk(decoding_chunk_size, num_decoding_left_chunks)
         n_frames = eng.fbank()
-        hyps = self.decode_resident(n_frames, modes, chunk_size, beam_size, ctc_weight, reverse_weight, blank_penalty, length_penalty)
+        hyps = self.decode_resident(n_frames, modes, chunk_size, beam_size, ctc_weight, reverse_weight, blank_penalty, length_penalty,
+                                    chunking, pause_search, pause_smooth)
+        hyps, starts = hyps if chunking == "pauses" else (hyps, None)
         return [get_output(format, self.tokenizer, Path(audio_file).name, hyps[mode], timings_adjustment, chunk_size,
-                           self.input_frame_length, self.output_frame_length) for mode in modes]
+                           self.input_frame_length, self.output_frame_length, chunk_starts=starts) for mode in modes]
 
     def align(self, audio_file, transcript: Optional[str] = None, tokens=None, format: str = "ctm", verbatimicity: float = 1.0,
               chunk_size: int = 2051, timings_adjustment: float = 230, posteriors: bool = False, wildcard: Optional[str] = None,
@@ -506,9 +513,10 @@ class ReverbASR:
         return self.engine
 
     def decode_resident(self, n_frames: int, modes, chunk_size: int, beam_size: int, ctc_weight: float,
-                        reverse_weight: float, blank_penalty: float = 0.0, length_penalty: float = 0.0):
+                        reverse_weight: float, blank_penalty: float = 0.0, length_penalty: float = 0.0, chunking: str = "fixed",
+                        pause_search: Optional[int] = None, pause_smooth: int = 10):
         return self.engine.decode_resident(n_frames, modes, chunk_size, beam_size, ctc_weight, reverse_weight,
-                                           blank_penalty, length_penalty)
+                                           blank_penalty, length_penalty, chunking, pause_search, pause_smooth)
 
     def _item_duration(self, item) -> float:
         """seconds of one transcribe_modes_many item, from the file's header or the waveform's length"""
@@ -529,7 +537,8 @@ class ReverbASR:
                               num_decoding_left_chunks: int = -1, ctc_weight: float = 0.1, simulate_streaming: bool = False,
                               reverse_weight: float = 0.0, blank_penalty: float = 0.0, length_penalty: float = 0.0,
                               timings_adjustment: float = 230, group_seconds: float = 3600.0, load_threads: int = 8,
-                              errors: str = "raise") -> list:
+                              errors: str = "raise", chunking: str = "fixed", pause_search: Optional[int] = None,
+                              pause_smooth: int = 10) -> list:
         """transcribe_modes for many recordings in one pass (the reference's bin/recognize.py decodes a data set in batches through
         the same model.decode): -> list[list[str]] indexed [recording][mode].  Items are paths or (waveform, sample_rate) pairs
         (mono int16, or float32 at int16 scale; the CTM name of a pair is its index in the list).  Output i is string-equal to
@@ -539,8 +548,10 @@ class ReverbASR:
         fbank launch and ceil(chunks / max_chunks) encodes, and while it decodes the next group's files are read and decoded on
         load_threads host threads (at most 16).  errors="raise": a file that cannot be read raises, naming it, before any decode of
         its group; "skip": its place in the result holds None and its name is logged.
-        fp8 engines are allowed but outside the identity promise: their activation scales come from the first batch they see."""
+        fp8 engines are allowed but outside the identity promise: their activation scales come from the first batch they see.
+        chunking, pause_search, pause_smooth: as in transcribe_modes; every recording is cut on its own frames."""
         from concurrent.futures import ThreadPoolExecutor
+        _check_pause_args(chunking, simulate_streaming)
         if simulate_streaming:
             raise NotImplementedError("transcribe_modes_many does not simulate streaming: use transcribe / transcribe_modes per file")
         if errors not in ("raise", "skip"):
@@ -592,11 +603,13 @@ class ReverbASR:
                 if not loaded:
                     continue
                 eng.upload_batch([w for _, w in loaded])
-                hyps = eng.decode_batch(modes, chunk_size, beam_size, ctc_weight, reverse_weight, blank_penalty, length_penalty)
-                for (i, _), h in zip(loaded, hyps):
+                hyps = eng.decode_batch(modes, chunk_size, beam_size, ctc_weight, reverse_weight, blank_penalty, length_penalty,
+                                        chunking, pause_search, pause_smooth)
+                hyps, starts = hyps if chunking == "pauses" else (hyps, [None] * len(hyps))
+                for (i, _), h, st in zip(loaded, hyps, starts):
                     name = str(i) if isinstance(items[i], (tuple, list)) else Path(items[i]).name
                     out[i] = [get_output(format, self.tokenizer, name, h[mode], timings_adjustment, chunk_size,
-                                         self.input_frame_length, self.output_frame_length) for mode in modes]
+                                         self.input_frame_length, self.output_frame_length, chunk_starts=st) for mode in modes]
         return out
 
     def transcribe_many(self, audio_files, mode: str = "ctc_prefix_beam_search", **kwargs) -> list:
@@ -607,13 +620,22 @@ class ReverbASR:
                    verbatimicity: float = 1.0, chunk_size: int = 2051, batch_size: int = 1, beam_size: int = 10,
                    decoding_chunk_size: int = -1, num_decoding_left_chunks: int = -1, ctc_weight: float = 0.1,
                    simulate_streaming: bool = False, reverse_weight: float = 0.0, blank_penalty: float = 0.0,
-                   length_penalty: float = 0.0, timings_adjustment: float = 230) -> str:
+                   length_penalty: float = 0.0, timings_adjustment: float = 230, chunking: str = "fixed",
+                   pause_search: Optional[int] = None, pause_smooth: int = 10) -> str:
         return self.transcribe_modes(
             audio_file, modes=[mode], format=format, verbatimicity=verbatimicity, chunk_size=chunk_size,
             batch_size=batch_size, beam_size=beam_size, decoding_chunk_size=decoding_chunk_size,
             num_decoding_left_chunks=num_decoding_left_chunks, ctc_weight=ctc_weight,
             simulate_streaming=simulate_streaming, reverse_weight=reverse_weight, blank_penalty=blank_penalty,
-            length_penalty=length_penalty, timings_adjustment=timings_adjustment)[0]
+            length_penalty=length_penalty, timings_adjustment=timings_adjustment, chunking=chunking, pause_search=pause_search,
+            pause_smooth=pause_smooth)[0]
+
+
+def _check_pause_args(chunking: str, simulate_streaming: bool):
+    if chunking not in ("fixed", "pauses"):
+        raise ValueError(f"chunking must be 'fixed' or 'pauses', not {chunking!r}")
+    if chunking == "pauses" and simulate_streaming:
+        raise NotImplementedError("chunking='pauses' cuts the whole recording's features: it does not go with simulate_streaming")
 
 
 def plan_groups(durations, group_seconds: float) -> List[List[int]]:
@@ -658,9 +680,13 @@ def load_cmvn(cmvn_file: str, is_json: bool):
 
 
 def get_output(format: str, tokenizer, audio_name: str, hyps: List[DecodeResult], timings_adjustment_ms,
-               chunk_size: int, input_frame_length: int, output_frame_length: int, wildcard: Optional[str] = None) -> str:
+               chunk_size: int, input_frame_length: int, output_frame_length: int, wildcard: Optional[str] = None,
+               chunk_starts: Optional[List[int]] = None) -> str:
     """DecodeResults of consecutive chunks -> one TXT / CTM string (cli/reverb.py:298-327).  wildcard: the marker that the words of
-    wildcard tokens carry (forced alignment with gaps; such hyps also give `ends`)."""
+    wildcard tokens carry (forced alignment with gaps; such hyps also give `ends`).  chunk_starts: the first input frame of every
+    chunk (chunking="pauses"): chunk k is shifted by chunk_starts[k] * input_frame_length ms; None: by k * chunk_size frames."""
+    if chunk_starts is not None and len(chunk_starts) != len(hyps):
+        raise ValueError(f"get_output: {len(chunk_starts)} chunk starts for {len(hyps)} chunks")
     if format == "txt":
         render, sep = hyps_to_txt, " "
     elif format == "ctm":
@@ -668,7 +694,9 @@ def get_output(format: str, tokenizer, audio_name: str, hyps: List[DecodeResult]
     else:
         raise ValueError("Invalid output format.")
     lines, shift_ms = [], 0
-    for hyp in hyps:
+    for k, hyp in enumerate(hyps):
+        if chunk_starts is not None:
+            shift_ms = int(chunk_starts[k]) * input_frame_length
         times = hyp.times if hyp.times is not None else hyp.ctc_frames
         if times is None:
             # `attention` mode carries no timestamps (search.py:357-360: DecodeResult(hyp.tolist())); the reference's
