@@ -99,7 +99,23 @@ int rvd_segment_windows(rvd_engine* e, const int64_t* windows, int n, float* log
 /* argmax powerset class of every frame of the last rvd_segment (what Powerset.to_multilabel(soft=False) needs):
  * out host uint8 [n][frames] */
 int rvd_get_classes(rvd_engine* e, uint8_t* out);
-/* debug taps of the last rvd_segment: "sincnet" [n][frames][sinc_channels], "lstm" [n][frames][2*hidden] */
+/* debug taps of the last rvd_segment over n windows, as stored (fp32 copies; pad columns included).  Reads only: nothing
+ * rvd_segment computes depends on them.  Rows per window: p1 = ((window_samples - 251) / 10 + 1) / 3, p2 = (p1 - 4) / 3,
+ * frames = (p2 - 4) / 3; CP = 64, the padded width of the sinc_channels-wide tensors.
+ *   "sincnet"   [n][frames][sinc_channels]   the SincNet output without its pad columns
+ *   "lstm"      [n][frames][2*hidden]        the last LSTM layer's output
+ *   "a1"        [n][p1][sinc_filters]        block 1 output
+ *   "c2"        [n][p1][CP]                  conv 2 output; the last 4 rows of a window are never read and hold whatever the
+ *   "c3"        [n][p2][CP]                  convolution made of the next window's frames or of the buffer's slack: ignore them
+ *   "a2"        [n][p2][CP]   "a3" [n][frames][CP]      block 2 / 3 outputs
+ *   "lstm_prev" [n][frames][2*hidden]        the last LSTM layer's input (needs lstm_layers >= 2)
+ *   "linear0", "linear1" [n][frames][linear_dim]   outputs of linear layers 0 and 1, where no later layer reuses their buffer
+ *                                            (at most 2 / 3 linear layers)
+ *   "stats"     [n][2]                       every window's waveform mean and 1 / sqrt(var + eps), fp32 as the first block reads them
+ *   "fsum"      [sinc_filters]               the sums of the sinc filters' taps, fp32 as the first block reads them
+ *   "craw"      [(n_pad - 251) / 10 + 1][sinc_filters]   the sinc convolution of the whole upload,
+ *                                            n_pad = (windows - 1) * step_samples + window_samples
+ * n is the window count of that rvd_segment call: the caller's buffer must hold that many windows. */
 int rvd_get_tap(rvd_engine* e, const char* name, float* out);
 
 /* embedding model: for each of n items, window index win[i] and a frame mask[i][frames] (weights in [0,1],

@@ -62,6 +62,7 @@ struct rvd_engine {
   DevBuf stats, a1, c2, a2, c3, a3, xproj, hA, hB, l0, l1, logp, cls;
   int last_W = 0;
   const void* last_lstm = nullptr;
+  const void* prev_lstm = nullptr;     // rvd_get_tap "lstm_prev": the last LSTM layer's input when lstm_layers >= 2 (the other ping-pong buffer)
 
   // embedding model
   bool has_emb = false;
@@ -339,7 +340,9 @@ int segment_impl(rvd_engine* e, int64_t first, int W, float* logp_out, const int
 
   const void* x = e->a3.p;
   int ldx = CP;
+  e->prev_lstm = nullptr;
   for (int l = 0; l < c.lstm_layers; ++l) {
+    if (l > 0) e->prev_lstm = x;
     RVB_TRY(run_gemm(e, "lstm_inproj", x, ldx, e->lstm[l].ih, e->xproj.p, 8 * H, R3, ACT_NONE));
     void* out = (l & 1) ? e->hB.p : e->hA.p;
     { DScope sc(e, "lstm_recurrence", 2.0 * (double)R3 * 8 * H * H);
@@ -1032,9 +1035,31 @@ int rvd_get_tap(rvd_engine* e, const char* name, float* out) {
   if (!e || !name || !out) { set_error("rvd_get_tap: null argument"); return E_ARG; }
   if (e->last_W <= 0) { set_error("rvd_get_tap: no rvd_segment call yet"); return E_STATE; }
   RVB_HIP_CHECK(hipSetDevice(e->device));
-  const int64_t R3 = (int64_t)e->last_W * e->p3;
-  if (!strcmp(name, "sincnet")) return fetch_T(e, e->a3.p, R3, e->cpad, e->cfg.sinc_channels, out);
-  if (!strcmp(name, "lstm")) return fetch_T(e, e->last_lstm, R3, 2 * e->cfg.lstm_hidden, 2 * e->cfg.lstm_hidden, out);
+  const rvd_model_cfg& c = e->cfg;
+  const int64_t W = e->last_W, R3 = W * e->p3;
+  if (!strcmp(name, "sincnet")) return fetch_T(e, e->a3.p, R3, e->cpad, c.sinc_channels, out);
+  if (!strcmp(name, "lstm")) return fetch_T(e, e->last_lstm, R3, 2 * c.lstm_hidden, 2 * c.lstm_hidden, out);
+  // the tensors between the kernels, as stored, pad columns included (reads only: nothing rvd_segment computes depends on them)
+  // fp32 whatever the engine's dtype: the window statistics of the call {mean, rstd} and the sums of the sinc filters' taps
+  if (!strcmp(name, "stats")) { RVB_HIP_CHECK(hipMemcpy(out, e->stats.p, (size_t)W * 2 * 4, hipMemcpyDeviceToHost)); return OK; }
+  if (!strcmp(name, "fsum")) { RVB_HIP_CHECK(hipMemcpy(out, e->fsum.p, (size_t)c.sinc_filters * 4, hipMemcpyDeviceToHost)); return OK; }
+  if (!strcmp(name, "craw") && e->craw_frames <= 0) { set_error("rvd_get_tap: no audio resident"); return E_STATE; }
+  if (!strcmp(name, "craw")) return fetch_T(e, e->craw.p, e->craw_frames, c.sinc_filters, c.sinc_filters, out);
+  if (!strcmp(name, "a1")) return fetch_T(e, e->a1.p, W * e->p1, c.sinc_filters, c.sinc_filters, out);
+  if (!strcmp(name, "c2")) return fetch_T(e, e->c2.p, W * e->p1, e->cpad, e->cpad, out);
+  if (!strcmp(name, "a2")) return fetch_T(e, e->a2.p, W * e->p2, e->cpad, e->cpad, out);
+  if (!strcmp(name, "c3")) return fetch_T(e, e->c3.p, W * e->p2, e->cpad, e->cpad, out);
+  if (!strcmp(name, "a3")) return fetch_T(e, e->a3.p, R3, e->cpad, e->cpad, out);
+  if (!strcmp(name, "lstm_prev")) {
+    if (!e->prev_lstm) { set_error("rvd_get_tap: lstm_prev needs a model of at least two LSTM layers"); return E_STATE; }
+    return fetch_T(e, e->prev_lstm, R3, 2 * c.lstm_hidden, 2 * c.lstm_hidden, out);
+  }
+  if (!strcmp(name, "linear0") || !strcmp(name, "linear1")) {
+    const int i = name[6] - '0';
+    // layer i writes buffer i & 1: it survives the call when no later layer of the same parity follows
+    if (i >= c.linear_layers || i + 2 < c.linear_layers) { set_error(std::string("rvd_get_tap: ") + name + " does not survive this model's rvd_segment"); return E_STATE; }
+    return fetch_T(e, i ? e->l1.p : e->l0.p, R3, c.linear_dim, c.linear_dim, out);
+  }
   set_error(std::string("rvd_get_tap: unknown tap ") + name);
   return E_ARG;
 }

@@ -59,6 +59,9 @@ def window_layout(n_samples, window: int, step: int) -> np.ndarray:
     return np.array(first, np.int64)
 
 
+CPAD = 64            # padded width of the sinc_channels-wide activation tensors (csrc/diar_engine.hip rvd_create: cpad)
+
+
 class DiarEngine:
     """segmentation (PyanNet) + embedding (WeSpeaker ResNet34) networks resident on one GPU."""
 
@@ -87,6 +90,7 @@ class DiarEngine:
         self.frames = self.lib.rvd_frames_per_window(self._h)
         self.num_classes = int(cfg["num_classes"])
         self.n_windows = 0
+        self._last_W = 0                 # windows of the last rvd_segment / rvd_segment_windows call (what the taps hold)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -148,6 +152,7 @@ class DiarEngine:
         for b0 in range(0, n, batch):
             nb = min(batch, n - b0)
             _check(self.lib.rvd_segment(self._h, first + b0, nb, fptr(out[b0:b0 + nb])), "rvd_segment")
+            self._last_W = nb
         return out
 
     def segment_classes(self, first: int = 0, n: Optional[int] = None, batch: int = 4096) -> np.ndarray:
@@ -157,6 +162,7 @@ class DiarEngine:
         for b0 in range(0, n, batch):
             nb = min(batch, n - b0)
             _check(self.lib.rvd_segment(self._h, first + b0, nb, None), "rvd_segment")
+            self._last_W = nb
             _check(self.lib.rvd_get_classes(self._h, out[b0:b0 + nb].ctypes.data_as(C.POINTER(C.c_uint8))), "rvd_get_classes")
         return out
 
@@ -169,6 +175,7 @@ class DiarEngine:
             nb = min(batch, n - b0)
             _check(self.lib.rvd_segment_windows(self._h, windows[b0:].ctypes.data_as(C.POINTER(C.c_int64)), nb, fptr(out[b0:b0 + nb])),
                    "rvd_segment_windows")
+            self._last_W = nb
         return out
 
     def segment_classes_windows(self, windows, batch: int = 4096) -> np.ndarray:
@@ -179,12 +186,33 @@ class DiarEngine:
         for b0 in range(0, n, batch):
             nb = min(batch, n - b0)
             _check(self.lib.rvd_segment_windows(self._h, windows[b0:].ctypes.data_as(C.POINTER(C.c_int64)), nb, None), "rvd_segment_windows")
+            self._last_W = nb
             _check(self.lib.rvd_get_classes(self._h, out[b0:b0 + nb].ctypes.data_as(C.POINTER(C.c_uint8))), "rvd_get_classes")
         return out
 
     def tap(self, name: str, n: int) -> np.ndarray:
-        width = {"sincnet": self.cfg["sinc_channels"], "lstm": 2 * self.cfg["lstm_hidden"]}[name]
-        out = np.empty((n, self.frames, width), np.float32)
+        """debug taps of the last segment call (include/rvd.h rvd_get_tap): [n, rows per window, width] with the pad columns of the
+        stored tensor; "stats" [n, 2]; "fsum" [sinc_filters]; "craw" [frames of the whole upload, sinc_filters].  n must be the window
+        count of that call (its last batch): the engine copies that many windows."""
+        c = self.cfg
+        if self._last_W and n != self._last_W:
+            raise ValueError("tap: the last segment call ran %d windows, not %d" % (self._last_W, n))
+        p1 = ((c["window_samples"] - 251) // 10 + 1) // 3
+        p2 = (p1 - 4) // 3
+        H2, nf = 2 * c["lstm_hidden"], c["sinc_filters"]
+        if name == "craw":
+            n_pad = (self.n_windows - 1) * c["step_samples"] + c["window_samples"]
+            shape = ((n_pad - 251) // 10 + 1, nf)
+        elif name == "fsum":
+            shape = (nf,)
+        elif name == "stats":
+            shape = (n, 2)
+        else:
+            rows, width = {"sincnet": (self.frames, c["sinc_channels"]), "lstm": (self.frames, H2), "a1": (p1, nf), "c2": (p1, CPAD),
+                           "a2": (p2, CPAD), "c3": (p2, CPAD), "a3": (self.frames, CPAD), "lstm_prev": (self.frames, H2),
+                           "linear0": (self.frames, c["linear_dim"]), "linear1": (self.frames, c["linear_dim"])}[name]
+            shape = (n, rows, width)
+        out = np.empty(shape, np.float32)
         _check(self.lib.rvd_get_tap(self._h, name.encode(), fptr(out)), "rvd_get_tap")
         return out
 

@@ -15,25 +15,12 @@ import torch
 from reverb_amd import _lib
 from reverb_amd._lib import fptr, iptr
 from util import bf16_round, rnd, f32, i32
+# the fp64 references and derived bounds live in tests/diar_stage_ref.py, shared with the bf16-storage restatement of the network
+from diar_stage_ref import (U32, HB, LSTM_F32_MAX, LSTM_BF16_MAX, LSTM_BF16_MEAN, half_ulp as _half_ulp, check_within as _check_within,
+                            pool_norm_ref as _pool_norm_ref, conv1d5_ref, lstm_ref as _lstm_ref, classifier_ref)
 
 pytestmark = pytest.mark.gpu
 F32, BF16 = 0, 1
-U32 = 2.0 ** -24          # fp32 unit roundoff
-HB = 2.0 ** -8            # half a bf16 ulp, relative to the value: at most 2^-8 (8 significant bits)
-
-
-def _half_ulp(dtype, ref, tol=0.0):
-    """the output rounding of a value known to within tol of ref"""
-    return HB * (np.abs(ref) + tol) if dtype == BF16 else 0.0
-
-
-def _check_within(got, ref, tol, what):
-    err = np.abs(got.astype(np.float64) - ref)
-    bad = err > tol
-    assert not bad.any(), "%s: %d elements outside the bound, worst err %.3g at bound %.3g (max err %.3g)" % (
-        what, int(bad.sum()), float(err[bad].max()), float(np.asarray(tol * np.ones_like(err))[bad][np.argmax(err[bad])]),
-        float(err.max()))
-    return float(err.max())
 
 
 # ------------------------------------------------------------------------------------ window_stats
@@ -117,40 +104,6 @@ def test_sinc_conv_refuses_what_neither_form_covers(lib):
 
 
 # ------------------------------------------------------------------------------------ pool_norm
-def _pool_norm_ref(dtype, first, xin, W, frames_in, C, ld_out, gamma, beta, eps, craw=None, frame0=0, fstep=0, stats=None,
-                   fsum=None, wn_gamma=1.0, wn_beta=0.0, rows_in=0):
-    """fp64: max-pool 3 -> instance norm over the pooled frames -> leaky relu 0.01.  Returns (y [W][TP][C], bound)."""
-    TP = frames_in // 3
-    ys, tols = [], []
-    for w in range(W):
-        if first:
-            a = wn_gamma * float(stats[w, 1])
-            off = (wn_beta - a * float(stats[w, 0])) * fsum.astype(np.float64)
-            r0 = frame0 + w * fstep
-            raw = craw[r0:r0 + 3 * TP].astype(np.float64)               # [3TP][C]
-            v = np.abs(a * raw + off)
-            mag = np.abs(a * raw) + np.abs(off)
-        else:
-            raw = xin[w * rows_in:w * rows_in + 3 * TP, :C].astype(np.float64)
-            v = raw
-            mag = np.abs(raw)
-        pooled = v.reshape(TP, 3, C).max(1)
-        P = mag.reshape(TP, 3, C).max(1)
-        mean = pooled.mean(0)
-        var = ((pooled - mean) ** 2).mean(0)
-        g = gamma.astype(np.float64) / np.sqrt(var + eps)
-        y = (pooled - mean) * g + beta
-        y = np.where(y > 0, y, 0.01 * y)
-        # fp32 on the pooled value, the affine correction, scale / shift and the fma: 64 u |g| (P + |mean|) + 16 u |beta|
-        tol = 64 * U32 * np.abs(g) * (P + np.abs(mean)) + 16 * U32 * np.abs(beta)
-        ys.append(y)
-        tols.append(tol)
-    y, tol = np.stack(ys), np.stack(tols)
-    if dtype == BF16:
-        tol = tol + HB * (np.abs(y) + tol)
-    return y, tol + 1e-30
-
-
 POOL_FIRST = [  # frames_in, W, frame0, frames per step, C, ld_out
     (15975, 3, 1601, 1600, 80, 80),          # the product's shape (160 000 samples, stride 10), craw_frame0 != 0
     (601, 4, 0, 200, 80, 80),                # frames_in % 3 == 1
@@ -244,47 +197,12 @@ def test_conv1d5(lib, cin, M):
     bias = f32(rng.standard_normal(60) * 0.1)
     out = np.empty((M, 64), np.float32)
     _lib.check(lib.rvb_test_conv1d5(cin, fptr(A), M + 4, fptr(Wt), fptr(bias), fptr(out), M))
-    A64, W64 = A[:, :cr].astype(np.float64), Wt.astype(np.float64)
-    ref = np.tile(bias.astype(np.float64), (M, 1))
-    mag = np.tile(np.abs(bias.astype(np.float64)), (M, 1))
-    for k in range(5):
-        ref += A64[k:k + M] @ W64[:, :, k].T
-        mag += np.abs(A64[k:k + M]) @ np.abs(W64[:, :, k]).T
+    ref, tol = conv1d5_ref(A, Wt, bias, M, cin)
     assert np.all(out[:, 60:] == 0), "pad filters not zero"
-    tol = (5 * cin + 1) * U32 * mag
-    _check_within(out[:, :60], ref, tol + _half_ulp(BF16, ref, tol) + 1e-30, "conv1d5")
+    _check_within(out[:, :60], ref, tol, "conv1d5")
 
 
 # ------------------------------------------------------------------------------------ LSTM layer
-def _sig(x):
-    return 0.5 * (1.0 + np.tanh(0.5 * x))
-
-
-def _lstm_ref(dtype, x, W, T, w_ih, w_hh, b_ih, b_hh):
-    """fp64 bidirectional layer on the rounded operands; the projection rounded where the GEMM stores it and h_t rounded after
-    every step where the kernel stores it (bf16); the cell state stays unrounded (the kernel keeps it in fp32 registers)."""
-    H = 128
-    out = np.zeros((W, T, 2 * H))
-    xw = x.astype(np.float64).reshape(W, T, -1)
-    for d in range(2):
-        xp = xw @ w_ih[d].astype(np.float64).T + (b_ih[d].astype(np.float64) + b_hh[d].astype(np.float64))
-        if dtype == BF16:
-            xp = bf16_round(xp).astype(np.float64)
-        whh = w_hh[d].astype(np.float64)
-        h = np.zeros((W, H))
-        c = np.zeros((W, H))
-        for s in range(T):
-            t = T - 1 - s if d else s
-            g = xp[:, t] + h @ whh.T
-            i, f, gg, o = _sig(g[:, :H]), _sig(g[:, H:2 * H]), np.tanh(g[:, 2 * H:3 * H]), _sig(g[:, 3 * H:])
-            c = f * c + i * gg
-            h = o * np.tanh(c)
-            if dtype == BF16:
-                h = bf16_round(h).astype(np.float64)
-            out[:, t, d * H:(d + 1) * H] = h
-    return out.reshape(W * T, 2 * H)
-
-
 LSTM_CASES = [(1, 1, 64), (3, 2, 256), (15, 37, 64), (16, 37, 256), (17, 37, 64), (17, 2, 256), (33, 589, 64), (40, 589, 256),
               (1, 589, 256)]
 
@@ -322,9 +240,9 @@ def test_lstm_layer(lib, dtype, W, T, inp):
     for d, name in ((0, "forward"), (1, "reverse")):
         e = np.abs(out[:, d * H:(d + 1) * H] - ref[:, d * H:(d + 1) * H])
         if dtype == F32:
-            assert e.max() < 1e-4, (name, e.max())
+            assert e.max() < LSTM_F32_MAX, (name, e.max())
         else:
-            assert e.max() < 4e-2 and e.mean() < 5e-5, (name, e.max(), e.mean())
+            assert e.max() < LSTM_BF16_MAX and e.mean() < LSTM_BF16_MEAN, (name, e.max(), e.mean())
 
 
 # ------------------------------------------------------------------------------------ classifier + log-softmax
@@ -358,13 +276,7 @@ def test_classifier(lib, dtype, C, inp, ldx, M, offset):
     cls = np.full(M, 99, np.uint8)
     _lib.check(lib.rvb_test_classifier(dtype, fptr(x), ldx, fptr(w), fptr(b), fptr(logp), cls.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)),
                                        M, inp, C))
-    xx, w64, b64 = x[:, :inp].astype(np.float64), w.astype(np.float64), b.astype(np.float64)
-    z = xx @ w64.T + b64
-    mx = z.max(1, keepdims=True)
-    lse = mx + np.log(np.exp(z - mx).sum(1, keepdims=True))
-    ref = z - lse
-    mag = (np.abs(xx) @ np.abs(w64).T + np.abs(b64)).max(1, keepdims=True)
-    tol = 2 * (inp + 2) * U32 * mag + 8 * U32 * np.abs(lse) + 1e-6
+    ref, tol, z = classifier_ref(x[:, :inp], w, b)
     _check_within(logp, ref, tol, "classifier logp")
     if C == 1:
         assert np.all(logp == 0) and np.all(cls == 0)
