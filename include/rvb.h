@@ -266,6 +266,25 @@ int rvb_get_encoder_lens(rvb_engine* e, int32_t* lens /* [B] */);      /* encode
 int rvb_get_encoder_out(rvb_engine* e, float* out /* [B,T,d] */);      /* parity tap */
 int rvb_get_ctc_logprobs(rvb_engine* e, int chunk, float* out /* [T,V] */); /* parity tap */
 int rvb_get_ctc_topk(rvb_engine* e, float* vals, int32_t* idx /* [B,T,beam] each */);
+/* Parity taps of ONE position of the offline encoder (tests only; read-only: what rvb_encode computes does not change).  The encoder
+ * reuses its workspaces in every block, so nothing of a block survives the call; with a position selected -- block = 0 .. blocks - 1
+ * for a conformer block, block = blocks for the front end before block 0, -1 for off (the default) -- the following rvb_encode calls
+ * copy every stored tensor of that position, device to device on the engine's stream, into buffers the engine owns.  M = B * T rows:
+ *   block:     x_in x_ffm x_att x_conv x_ff x_out [M][d] fp32 (the residual stream on entry and after each module, the block's
+ *              output); xn_ffm xn_mha xn_conv xn_cnn xn_ff next [M][d], h_ffm h_ff [M][ff], qkv [M][3d], ao dconv [M][d],
+ *              glu [M][d] (GLU in the GEMM's epilogue) or [M][2d], y [M][d] (language-specific blocks only): the compute dtype;
+ *              pos_keys [T][d] (compute dtype) and pos_bias [heads][T] fp32 (bf16 engines) as loaded
+ *   front end: X1 [B][T1][F1][d], X2 [B][T][F2][d], xn0 [M][d] (compute dtype), x0 [M][d] fp32
+ *   forms:     forms[0] = n, then n small integers -- block: K' = k + p written by the qkv GEMM (1 / 0), GLU in the epilogue (1 / 0),
+ *              then for every GEMM in launch order (ffm1 ffm2 qkv att_out pw1 pw2 [lsl] ff1 ff2; front end: conv2 embed) 2 if
+ *              gemm() handed it to gemm2.hip, else 1
+ * rvb_get_encoder_tap copies one out: bf16 widened to fp32 bit for bit, fp32 as it is; `capacity` = floats `out` can take.
+ * Refused by name, with nothing written: rvb_set_encoder_tap on an fp8 engine (RVB_E_UNSUPPORTED) or with a stream open
+ * (RVB_E_STATE); rvb_encode of a batch that is encoded in two slices (B >= 16) and rvb_stream_chunk while a position is selected
+ * (RVB_E_UNSUPPORTED); a name the last rvb_encode did not keep (RVB_E_STATE).  Off, rvb_encode enqueues exactly what it does
+ * without this switch; switching off or to another position frees the kept copies. */
+int rvb_set_encoder_tap(rvb_engine* e, int block);
+int rvb_get_encoder_tap(rvb_engine* e, const char* name, float* out, int64_t capacity);
 
 /* ctc_greedy_search (search.py:106-121): tokens [B,T] (first ntok[b] valid) and the frame of each
  * token's first emission. */

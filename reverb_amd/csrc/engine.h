@@ -353,6 +353,13 @@ struct rvb_engine {
   } stream_st;
   rvb::DevBuf d_stream_i32;         // {kv_start = 0, kv_len = cache + chunk}
 
+  // ---- encoder taps (rvb_set_encoder_tap / rvb_get_encoder_tap: read-only, for the tests' stage-by-stage check) ----
+  int tap_block = -1;               // -1 off; 0 .. blocks - 1: that conformer block; blocks: the front end before block 0
+  bool tap_live = false;            // rvb_encode is inside the tapped position: tap_keep() copies, tap_note_gemm() notes
+  struct Tap { rvb::DevBuf buf; size_t elems = 0; bool bf16 = false; };
+  std::map<std::string, Tap> taps;  // what the last tapped rvb_encode kept, by name (device copies, made on the engine's stream)
+  std::vector<float> tap_forms;     // the forms that ran there: see rvb_get_encoder_tap "forms"
+
   // ---- forced alignment (rvb_ctc_align) ----
   rvb::CtcAligner aligner;
   rvb::CtcScorer scorer;           // rvb_ctc_score

@@ -91,7 +91,22 @@ int run_gemm(rvb_engine* e, const void* A, int lda, const Linear& L, void* C, in
   g.M = M; g.N = L.out; g.K = L.in; g.lda = lda; g.ldw = L.in; g.ldc = ldc; g.ldres = ldres;
   g.alpha = alpha; g.act = act; g.out_f32 = out_f32 ? 1 : 0;
   Scope sc(e, "gemm", 2.0 * M * (double)L.out * L.in, gemm_alg_bytes(e, g));
-  return gemm(e->stream, e->dtype, g);
+  const int rc = gemm(e->stream, e->dtype, g);
+  tap_note_gemm(e);
+  return rc;
+}
+// ---- encoder taps (rvb_set_encoder_tap): with the switch off, or outside the tapped position, neither does anything
+int tap_keep(rvb_engine* e, const char* name, const void* src, size_t elems, bool is_bf16) {
+  if (!e->tap_live) return OK;
+  auto& t = e->taps[name];
+  const size_t bytes = elems * (is_bf16 ? 2 : 4);
+  RVB_TRY(t.buf.ensure(bytes));
+  t.elems = elems; t.bf16 = is_bf16;
+  RVB_HIP_CHECK(hipMemcpyAsync(t.buf.p, src, bytes, hipMemcpyDeviceToDevice, e->stream));
+  return OK;
+}
+void tap_note_gemm(rvb_engine* e) {
+  if (e->tap_live) e->tap_forms.push_back((float)gemm_last_path());       // what gemm() itself reports of the call just made
 }
 // out8 / out2_8 > 0: that output is fp8 bytes of value / scale (the calibrated per-tensor scale of the GEMM that reads it)
 int run_norm(rvb_engine* e, const float* x, const LNorm& n, void* out, bool out_f32, int M, int d, int mode,
@@ -284,6 +299,7 @@ void rvb_destroy(rvb_engine* e) {
   if (e->pcm_ready) (void)hipEventDestroy(e->pcm_ready);
   if (e->pcm_free) (void)hipEventDestroy(e->pcm_free);
   e->pcm_next.release();
+  for (auto& t : e->taps) t.second.buf.release();
   (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -519,6 +535,54 @@ int rvb_get_ctc_topk(rvb_engine* e, float* vals, int32_t* idx) {
   RVB_TRY(wait_slices(e, -1));
   if (vals) memcpy(vals, e->h_topv, n * 4);
   if (idx) memcpy(idx, e->h_topi, n * 4);
+  return OK;
+}
+
+int rvb_set_encoder_tap(rvb_engine* e, int block) {
+  if (!e) { set_error("rvb_set_encoder_tap: null engine"); return E_ARG; }
+  if (!e->finalized) { set_error("rvb_set_encoder_tap before rvb_finalize"); return E_STATE; }
+  const int nb = (int)e->enc.size();
+  if (block < -1 || block > nb) { set_error("rvb_set_encoder_tap: block must be -1 (off), 0 .. blocks - 1, or blocks (the front end)"); return E_ARG; }
+  if (block >= 0 && e->fp8) { set_error("rvb_set_encoder_tap: not available on an fp8 engine (its calibration and fp8 passes store other tensors)"); return E_UNSUPPORTED; }
+  if (block >= 0 && e->stream_st.active) { set_error("rvb_set_encoder_tap: not available while a stream is open (the streaming encoder keeps caches instead)"); return E_STATE; }
+  if (block != e->tap_block) {       // another position, or off (rvb_encode is what it was): what the taps held is given back
+    RVB_HIP_CHECK(hipSetDevice(e->device));
+    RVB_TRY(wait_slices(e, -1));
+    RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
+    for (auto& t : e->taps) t.second.buf.release();
+    e->taps.clear(); e->tap_forms.clear();
+  }
+  e->tap_block = block; e->tap_live = false;
+  return OK;
+}
+int rvb_get_encoder_tap(rvb_engine* e, const char* name, float* out, int64_t capacity) {
+  if (!e || !name || !out) { set_error("rvb_get_encoder_tap: null argument"); return E_ARG; }
+  const bool forms = !strcmp(name, "forms");
+  auto it = e->taps.find(name);
+  if (!forms && it == e->taps.end()) {
+    set_error(std::string("rvb_get_encoder_tap: no tap named ") + name + " was kept by the last rvb_encode (see rvb_set_encoder_tap)");
+    return E_STATE;
+  }
+  const size_t n = forms ? e->tap_forms.size() + 1 : it->second.elems;
+  if (capacity < (int64_t)n) {
+    set_error(std::string("rvb_get_encoder_tap: ") + name + " holds " + std::to_string(n) + " values, the buffer " + std::to_string(capacity));
+    return E_ARG;
+  }
+  if (forms) {
+    out[0] = (float)e->tap_forms.size();
+    for (size_t i = 0; i < e->tap_forms.size(); ++i) out[1 + i] = e->tap_forms[i];
+    return OK;
+  }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(wait_slices(e, -1));
+  RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
+  if (!it->second.bf16) {
+    RVB_HIP_CHECK(hipMemcpy(out, it->second.buf.p, n * 4, hipMemcpyDeviceToHost));
+  } else {       // widened bit for bit
+    std::vector<bf16_t> tmp(n);
+    RVB_HIP_CHECK(hipMemcpy(tmp.data(), it->second.buf.p, n * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) out[i] = bf16_to_f32(tmp[i]);
+  }
   return OK;
 }
 

@@ -24,6 +24,14 @@ static int encoder_layer(rvb_engine* e, EncLayer& L, int lidx, int M, int B, int
   float* x = e->x.as<float>();
   const bool f8 = e->fp8 && e->f8_state == 2 && li < 0;
   const bool cal = e->fp8 && e->f8_state == 1 && li < 0;
+  // read-only taps of this block (rvb_set_encoder_tap; off: tap_keep / tap_note_gemm return at once): every stored tensor is copied
+  // out on the engine's stream behind the launch that wrote it, before the next block overwrites it
+  struct TapLive { rvb_engine* e; ~TapLive() { e->tap_live = false; } } tap_guard{e};
+  e->tap_live = e->tap_block == lidx && li < 0;
+  const bool t16 = e->dtype == DT_BF16;
+  const size_t Md = (size_t)M * d;
+  RVB_TRY(tap_keep(e, "x_in", x, Md, false));
+  RVB_TRY(tap_keep(e, "xn_ffm", e->xn.p, Md, t16));
   // which GEMM groups of this block run in fp8 (rvb_engine::f8_groups: bit 0 macaron feed-forward, 1 qkv, 2 pointwise conv 1,
   // 3 pointwise conv 2, 4 feed-forward); the others stay on the bf16 path, LayerNorm output included
   const unsigned grp = f8 ? e->f8_groups[lidx] : 0u;
@@ -37,6 +45,17 @@ static int encoder_layer(rvb_engine* e, EncLayer& L, int lidx, int M, int B, int
   const int prefold_on = prefold_env ? atoi(prefold_env) : 1;
   const bool prefold = prefold_on && e->dtype == DT_BF16 && li < 0 && !f8_qkv && L.pos_bias.p != nullptr && dk > 32 && dk <= 64 &&
                        T <= e->pe_rows && T <= 16384 && (d % 8) == 0;     // 16384: the keys whose constants the kernel holds in LDS
+  if (e->tap_live) {
+    e->tap_forms.assign(2, 0.f);
+    e->tap_forms[0] = prefold ? 1.f : 0.f;
+    RVB_TRY(tap_keep(e, "pos_keys", L.pos_keys.p, (size_t)T * d, t16));
+    if (L.pos_bias.p) {       // [heads][pe_rows] -> [heads][T]
+      auto& t = e->taps["pos_bias"];
+      RVB_TRY(t.buf.ensure((size_t)heads * T * 4));
+      t.elems = (size_t)heads * T; t.bf16 = false;
+      RVB_HIP_CHECK(hipMemcpy2DAsync(t.buf.p, (size_t)T * 4, L.pos_bias.p, (size_t)e->pe_rows * 4, (size_t)T * 4, heads, hipMemcpyDeviceToDevice, e->stream));
+    }
+  }
   auto note = [&](int slot, const void* t, size_t n) -> int {
     return cal ? amax_abs(e->stream, e->dtype, t, n, e->d_amax.as<float>() + (size_t)lidx * 8 + slot) : OK;
   };
@@ -51,8 +70,10 @@ static int encoder_layer(rvb_engine* e, EncLayer& L, int lidx, int M, int B, int
     RVB_TRY(note(0, e->xn.p, (size_t)M * d));
     RVB_TRY(run_gemm(e, e->xn.p, d, L.ffm1, e->h.p, ff, M, false, 1.f, ACT_SILU));
     RVB_TRY(note(1, e->h.p, (size_t)M * ff));
+    RVB_TRY(tap_keep(e, "h_ffm", e->h.p, (size_t)M * ff, t16));
     RVB_TRY(run_gemm(e, e->h.p, ff, L.ffm2, x, d, M, true, 0.5f, ACT_NONE, x, d));
   }
+  RVB_TRY(tap_keep(e, "x_ffm", x, Md, false));
   // rel-pos self attention: x += MHSA(LN(x))              encoder_layer.py:208-216
   if (f8_qkv) {
     RVB_TRY(run_norm(e, x, L.n_mha, e->xn.p, false, M, d, NORM_LN, 0, nullptr, nullptr, nullptr, sc8.in_qkv, 0.f, false, satp(2)));
@@ -68,10 +89,13 @@ static int encoder_layer(rvb_engine* e, EncLayer& L, int lidx, int M, int B, int
       g.rowadd = L.pos_keys.p; g.rowadd_rows = T; g.rowadd_ld = d; g.rowadd_col0 = d; g.rowadd_cols = d;
       Scope sc(e, "gemm", 2.0 * M * (double)g.N * g.K, gemm_alg_bytes(e, g));
       RVB_TRY(gemm(e->stream, e->dtype, g));
+      tap_note_gemm(e);
     } else {
       RVB_TRY(run_gemm(e, e->xn.p, d, L.qkv, e->h.p, 3 * d, M, false));
     }
   }
+  RVB_TRY(tap_keep(e, "xn_mha", e->xn.p, Md, t16));
+  RVB_TRY(tap_keep(e, "qkv", e->h.p, 3 * Md, t16));
   {
     AttnArgs a;
     memset(&a, 0, sizeof(a));
@@ -110,7 +134,9 @@ static int encoder_layer(rvb_engine* e, EncLayer& L, int lidx, int M, int B, int
     Scope sc(e, "attention", 6.0 * B * (double)T * keys * d);
     RVB_TRY(attention(e->stream, e->dtype, with_lab(a)));
   }
+  RVB_TRY(tap_keep(e, "ao", e->ao.p, Md, t16));
   RVB_TRY(run_gemm(e, e->ao.p, d, L.att_out, x, d, M, true, 1.f, ACT_NONE, x, d));
+  RVB_TRY(tap_keep(e, "x_att", x, Md, false));
   // convolution module: x += Conv(LN(x))                   encoder_layer.py:218-229, convolution.py:89-144
   bool glu_fused = false;
   if (f8_pw1) {
@@ -133,11 +159,15 @@ static int encoder_layer(rvb_engine* e, EncLayer& L, int lidx, int M, int B, int
       if (glu_fused) {
         Scope sc(e, "gemm", 2.0 * M * (double)t.N * t.K, gemm_alg_bytes(e, t));
         RVB_TRY(gemm(e->stream, e->dtype, t));
+        tap_note_gemm(e);
       } else {
         RVB_TRY(run_gemm(e, e->xn.p, d, L.pw1, e->h.p, 2 * d, M, false));
       }
     }
   }
+  if (e->tap_live) e->tap_forms[1] = glu_fused ? 1.f : 0.f;
+  RVB_TRY(tap_keep(e, "xn_conv", e->xn.p, Md, t16));
+  RVB_TRY(tap_keep(e, "glu", e->h.p, glu_fused ? Md : 2 * Md, t16));
   {
     GluDwArgs g;
     g.gated = glu_fused ? 1 : 0;
@@ -171,14 +201,17 @@ static int encoder_layer(rvb_engine* e, EncLayer& L, int lidx, int M, int B, int
   }
   const int cmode = e->cfg.cnn_norm == 0 ? NORM_LN : NORM_AFFINE;
   const bool dw16 = e->dtype == DT_BF16;
+  RVB_TRY(tap_keep(e, "dconv", e->dconv.p, Md, dw16));
   if (f8_pw2) {
     RVB_TRY(run_norm(e, e->dconv.as<float>(), L.n_cnn, e->xn.p, false, M, d, cmode, 1, nullptr, nullptr, nullptr, sc8.in_pw2, 0.f, dw16, satp(4)));
     RVB_TRY(run_gemm8(e, e->xn.p, d, L.pw2, x, d, M, sc8.in_pw2, 1, 1.f, 1.f, ACT_NONE, x, d));
   } else {
     RVB_TRY(run_norm(e, e->dconv.as<float>(), L.n_cnn, e->xn.p, false, M, d, cmode, 1, nullptr, nullptr, nullptr, 0.f, 0.f, dw16));
     RVB_TRY(note(4, e->xn.p, (size_t)M * d));
+    RVB_TRY(tap_keep(e, "xn_cnn", e->xn.p, Md, t16));
     RVB_TRY(run_gemm(e, e->xn.p, d, L.pw2, x, d, M, true, 1.f, ACT_NONE, x, d));
   }
+  RVB_TRY(tap_keep(e, "x_conv", x, Md, false));
   // feed-forward (+ language-specific mix), final norm     encoder_layer.py:231-244 / :372-402
   if (f8_ff) {
     RVB_TRY(run_norm(e, x, L.n_ff, e->xn.p, false, M, d, NORM_LN, 0, nullptr, nullptr, nullptr, sc8.in_ff1, 0.f, false, satp(5)));
@@ -186,22 +219,28 @@ static int encoder_layer(rvb_engine* e, EncLayer& L, int lidx, int M, int B, int
     RVB_TRY(run_gemm8(e, e->h.p, ff, L.ff2, x, d, M, sc8.h_ff, 1, 1.f, 0.5f, ACT_NONE, x, d));
   } else {
     RVB_TRY(run_norm(e, x, L.n_ff, e->xn.p, false, M, d));
+    RVB_TRY(tap_keep(e, "xn_ff", e->xn.p, Md, t16));
     const void* ffin = e->xn.p;
     if (L.is_lsl) {
       RVB_TRY(run_gemm(e, e->xn.p, d, L.lsl, e->y.p, d, M, false));
+      RVB_TRY(tap_keep(e, "y", e->y.p, Md, t16));
       ffin = e->y.p;
     } else {
       RVB_TRY(note(5, e->xn.p, (size_t)M * d));
     }
     RVB_TRY(run_gemm(e, ffin, d, L.ff1, e->h.p, ff, M, false, 1.f, ACT_SILU));
     if (!L.is_lsl) RVB_TRY(note(6, e->h.p, (size_t)M * ff));
+    RVB_TRY(tap_keep(e, "h_ff", e->h.p, (size_t)M * ff, t16));
     RVB_TRY(run_gemm(e, e->h.p, ff, L.ff2, x, d, M, true, 0.5f, ACT_NONE, x, d));
   }
+  RVB_TRY(tap_keep(e, "x_ff", x, Md, false));
   // x = norm_final(x) (+ y for the language-specific block, encoder_layer.py:400), and in the same pass the LayerNorm
   // that always reads it next: the following block's norm_ff_macaron, or the encoder's after_norm (encoder.py:147-148)
   // (the fp8 second output is the NEXT block's in_ffm1: slot 0 of block lidx + 1)
   RVB_TRY(run_norm(e, x, L.n_final, x, true, M, d, NORM_LN, 0, L.is_lsl ? e->y.p : nullptr, &next, next_out, 0.f, f8 ? next8 : 0.f, false,
                    nullptr, (f8 && next8 > 0.f && e->d_f8sat.p) ? e->d_f8sat.as<unsigned>() + (size_t)(lidx + 1) * 8 : nullptr));
+  RVB_TRY(tap_keep(e, "x_out", x, Md, false));
+  RVB_TRY(tap_keep(e, "next", next_out, Md, t16));
   return OK;
 }
 
@@ -213,6 +252,15 @@ int encode_impl(rvb_engine* e, const float* feats, int64_t first_chunk, const in
     set_error("rvb_encode: need 1 <= B <= max_chunks and 7 <= T0 <= chunk_frames"); return E_ARG;
   }
   if (beam < 1 || beam > 64 || beam > c.vocab) { set_error("rvb_encode: beam must be in [1,64]"); return E_ARG; }
+  // the slices of the sub-batch pipeline (see below)
+  int SB = B >= 16 ? (B * 7 + 9) / 10 : B;            // chunks in the first (largest) slice
+  if (B >= 64) SB = B - 32;
+  if (const char* ov = lab_env("RVB_SLICE0")) { const int v = atoi(ov); if (v > 0 && v <= B) SB = v; }   // tuning override
+  if (e->tap_block >= 0 && (SB < B || e->fp8)) {       // refused before anything is touched: the taps hold one slice of a bf16 / f32 pass
+    set_error(SB < B ? "rvb_encode: rvb_set_encoder_tap is on, and this batch is encoded in two slices (B >= 16): tap a smaller batch"
+                     : "rvb_encode: rvb_set_encoder_tap is on, and the engine runs its fp8 calibration / fp8 pass");
+    return E_UNSUPPORTED;
+  }
   RVB_HIP_CHECK(hipSetDevice(e->device));
   RVB_TRY(wait_slices(e, -1));      // a previous batch may still be in flight
   e->stream_st.active = false;      // the offline path reuses the stream's output buffer: an open stream ends here
@@ -258,9 +306,6 @@ int encode_impl(rvb_engine* e, const float* feats, int64_t first_chunk, const in
   // the first slice's search hides under the GPU time of the second.  For large batches the tail is exactly 32
   // chunks (32 x 512 frames = 64 row tiles = one full wave of 256x256 tiles over the 256 CUs for the N = 1024 GEMMs);
   // measured on the 176-chunk bench batch: first slice 96/112/128/144/160 -> 201.1/199.8/198.6/197.4/198.9 ms
-  int SB = B >= 16 ? (B * 7 + 9) / 10 : B;            // chunks in the first (largest) slice
-  if (B >= 64) SB = B - 32;
-  if (const char* ov = lab_env("RVB_SLICE0")) { const int v = atoi(ov); if (v > 0 && v <= B) SB = v; }   // tuning override
   const int Ms = SB * T2;
   RVB_TRY(e->X1.ensure((size_t)SB * T1 * F1 * d * es));
   RVB_TRY(e->X2.ensure((size_t)SB * T2 * F2 * d * es));
@@ -299,6 +344,10 @@ int encode_impl(rvb_engine* e, const float* feats, int64_t first_chunk, const in
     // fp8 mode with conv2 in the policy (bit 5): conv1 writes e4m3 at the calibrated scale and conv2 runs on the fp8 phase loop
     const bool f8c2 = e->fp8 && e->f8_state == 2 && e->f8_conv2 && e->f8_x1 > 0.f && e->conv2.w8.p && d % 128 == 0;
     const bool calx = e->fp8 && e->f8_state == 1;
+    struct TapLive { rvb_engine* e; ~TapLive() { e->tap_live = false; } } tap_guard{e};
+    e->tap_live = e->tap_block == (int)e->enc.size();       // the front end's taps (rvb_set_encoder_tap)
+    if (e->tap_live) e->tap_forms.clear();
+    const bool t16 = e->dtype == DT_BF16;
     {
       Scope sc(e, "subsample");
       RVB_TRY(subsample_conv1(e->stream, e->dtype, d_feats + (size_t)c0 * T0 * F0, e->cmvn_mean.as<float>(),
@@ -315,12 +364,18 @@ int encode_impl(rvb_engine* e, const float* feats, int64_t first_chunk, const in
       if (f8c2) { g.W = e->conv2.w8.p; g.in_fp8 = 1; g.a_scale = e->f8_x1; g.w_scale = e->conv2.wscale.as<float>(); }
       Scope sc(e, f8c2 ? "gemm_fp8" : "gemm", 2.0 * g.M * (double)g.N * g.K, gemm_alg_bytes(e, g));
       RVB_TRY(gemm(e->stream, e->dtype, g));
+      tap_note_gemm(e);
     }
+    RVB_TRY(tap_keep(e, "X1", e->X1.p, (size_t)nb * T1 * F1 * d, t16));
+    RVB_TRY(tap_keep(e, "X2", e->X2.p, (size_t)m * F2 * d, t16));
     RVB_TRY(run_gemm(e, e->X2.p, F2 * d, e->embed_out, e->x.p, d, m, true, std::sqrt((float)d)));
+    RVB_TRY(tap_keep(e, "x0", e->x.p, (size_t)m * d, false));
     void* eo = (char*)e->enc_out.p + (size_t)row0 * d * es;
     const bool f8 = e->fp8 && e->f8_state == 2;
     RVB_TRY(run_norm(e, e->x.as<float>(), e->enc[0].n_ffm, e->xn.p, false, m, d, NORM_LN, 0, nullptr, nullptr, nullptr,
                      (f8 && (e->f8_groups[0] & 1u)) ? e->f8[0].in_ffm1 : 0.f, 0.f, false, e->d_f8sat.as<unsigned>()));
+    RVB_TRY(tap_keep(e, "xn0", e->xn.p, (size_t)m * d, t16));
+    e->tap_live = false;
     for (size_t li = 0; li < e->enc.size(); ++li) {
       const bool last = li + 1 == e->enc.size();
       RVB_TRY(encoder_layer(e, e->enc[li], (int)li, m, nb, T2, last ? e->enc_after : e->enc[li + 1].n_ffm, last ? eo : e->xn.p,
@@ -411,6 +466,7 @@ int stream_chunk_impl(rvb_engine* e, const float* feats, int T0, int required_ca
   auto& st = e->stream_st;
   if (!st.active) { set_error("rvb_stream_chunk before rvb_stream_begin"); return E_STATE; }
   if (T0 < 7) { set_error("rvb_stream_chunk: a chunk needs at least 7 input frames (Conv2dSubsampling4)"); return E_ARG; }
+  if (e->tap_block >= 0) { set_error("rvb_stream_chunk: rvb_set_encoder_tap is on (the taps are the offline encoder's)"); return E_UNSUPPORTED; }
   RVB_HIP_CHECK(hipSetDevice(e->device));
   const int d = c.d_model, F0 = c.input_dim;
   const int T1 = (T0 - 3) / 2 + 1, F1 = (F0 - 3) / 2 + 1, T2 = (T1 - 3) / 2 + 1, F2 = (F1 - 3) / 2 + 1;

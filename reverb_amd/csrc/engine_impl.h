@@ -39,6 +39,11 @@ int run_gemm8(rvb_engine* e, const void* A8, int lda, const Linear& L, void* C, 
               float out_scale = 1.f, float alpha = 1.f, int act = ACT_NONE, const float* res = nullptr, int ldres = 0,
               unsigned* sat = nullptr);
 
+// encoder taps (rvb_set_encoder_tap): both do nothing unless rvb_encode is inside the tapped position (e->tap_live)
+int tap_keep(rvb_engine* e, const char* name, const void* src, size_t elems, bool is_bf16);     // device-to-device copy on the engine's stream
+void tap_note_gemm(rvb_engine* e);       // after a gemm() call: appends which kernel file it chose (gemm_last_path)
+int gemm_last_path();                    // gemm.hip: 2 = gemm2.hip, 1 = gemm.hip -- what gemm() dispatched to last on this thread
+
 // ---- engine_weights.hip
 int make_fbank_tables(rvb_engine* e);
 int finalize_impl(rvb_engine* e, const float* cat, int ncat);

@@ -187,6 +187,11 @@ static int launch(hipStream_t s, const GemmArgs& p) {
 
 int g_gemm_variant = 0;
 
+// the kernel file gemm() chose last on this thread (2 = gemm2.hip, 1 = gemm.hip, 0 = none yet): set where it dispatches, so that what
+// reports the choice (the encoder's `forms` tap, engine.hip tap_note_gemm) cannot drift from it
+static thread_local int t_last_path = 0;
+int gemm_last_path() { return t_last_path; }
+
 int gemm(hipStream_t s, int dtype, const GemmArgs& p) {
   const int ve = dtype == DT_BF16 ? 8 : 4;
   if (p.M < 0 || p.N <= 0 || p.K <= 0 || (p.K % ve) || (p.lda % ve) || (p.ldw % ve) ||
@@ -201,16 +206,21 @@ int gemm(hipStream_t s, int dtype, const GemmArgs& p) {
   }
   if (p.act == ACT_GLU) {     // pairs of columns gated in the epilogue: gemm2's phase-interleaved bf16 kernel only
     if (g_gemm_variant == 1 || !gemm_glu_supported(dtype, p)) { set_error("gemm: ACT_GLU needs the bf16 LDS-DMA kernel (see gemm_glu_supported)"); return E_UNSUPPORTED; }
+    t_last_path = 2;
     return gemm2(s, dtype, p);
   }
   if (p.in_fp8) {       // fp8 operands exist only on the LDS-DMA kernel
     if (!gemm2_applicable(dtype, p)) { set_error("gemm: fp8 operands need the bf16 engine, K % 128 == 0 and per-channel weight scales"); return E_ARG; }
+    t_last_path = 2;
     return gemm2(s, dtype, p);
   }
   // auto: the 256x256 LDS-DMA kernel for bf16 (1.5-2x); f32 stays on the 128x128 kernel, which already
   // runs at ~70 % of the 157 TFLOP/s f32 MFMA peak (profiles/r01_gemm_microbench.md)
-  if (g_gemm_variant != 1 && (dtype == DT_BF16 || g_gemm_variant == 2) && gemm2_applicable(dtype, p))
+  if (g_gemm_variant != 1 && (dtype == DT_BF16 || g_gemm_variant == 2) && gemm2_applicable(dtype, p)) {
+    t_last_path = 2;
     return gemm2(s, dtype, p);
+  }
+  t_last_path = 1;
   if (dtype == DT_BF16) {
     if (p.out_f32) return p.conv ? launch<bf16_t, float, true>(s, p) : launch<bf16_t, float, false>(s, p);
     return p.conv ? launch<bf16_t, bf16_t, true>(s, p) : launch<bf16_t, bf16_t, false>(s, p);

@@ -442,6 +442,7 @@ class Engine:
         t = C.c_int32(0)
         check(self.lib.rvb_encoder_frames(self.handle, C.byref(t)))
         self.batch, self.enc_frames, self.beam, self.topk = B, int(t.value), int(beam), k
+        self._last_T0 = int(T0)
         # joint_decode's tie retry encodes the batch again; only an encode that asked for joint decoding's pre-beam (topk) and
         # so may be followed by joint_decode keeps its arguments, and joint_decode drops them when it is done (every encode pinned
         # hundreds of MB of features for the engine's lifetime)
@@ -508,6 +509,32 @@ class Engine:
     def encoder_out(self) -> np.ndarray:
         out = np.empty((self.batch, self.enc_frames, self.cfg.d_model), np.float32)
         check(self.lib.rvb_get_encoder_out(self.handle, fptr(out)))
+        return out
+
+    def set_encoder_tap(self, block: int = -1):
+        """Parity taps of one position of the offline encoder (include/rvb.h rvb_set_encoder_tap): block 0 .. blocks - 1, `blocks`
+        for the front end before block 0, -1 for off.  The following encode() calls keep that position's stored tensors."""
+        check(self.lib.rvb_set_encoder_tap(self.handle, int(block)), "rvb_set_encoder_tap")
+
+    def encoder_tap(self, name: str) -> np.ndarray:
+        """One tensor the last tapped encode() kept, as float32 (bf16 widened bit for bit): [B * T, width] for a block's tensors,
+        X1 [B, T1, F1, d], X2 [B, T, F2, d], pos_keys [T, d], pos_bias [heads, T], forms: a list of ints (see rvb_get_encoder_tap)."""
+        c, B, T = self.cfg, self.batch, self.enc_frames
+        d, ff = c.d_model, c.ffn_dim
+        if name == "forms":
+            out = np.zeros(32, np.float32)
+            check(self.lib.rvb_get_encoder_tap(self.handle, b"forms", fptr(out), out.size), "rvb_get_encoder_tap")
+            return [int(v) for v in out[1:1 + int(out[0])]]
+        T0 = self._last_T0
+        T1, F1 = (T0 - 3) // 2 + 1, (c.input_dim - 3) // 2 + 1
+        F2 = (F1 - 3) // 2 + 1
+        if name == "glu":
+            shape = (B * T, d if self.encoder_tap("forms")[1] else 2 * d)
+        else:
+            shape = {"X1": (B, T1, F1, d), "X2": (B, T, F2, d), "pos_keys": (T, d), "pos_bias": (c.heads, T), "h_ffm": (B * T, ff),
+                     "h_ff": (B * T, ff), "qkv": (B * T, 3 * d)}.get(name, (B * T, d))
+        out = np.empty(shape, np.float32)
+        check(self.lib.rvb_get_encoder_tap(self.handle, name.encode(), fptr(out), out.size), "rvb_get_encoder_tap")
         return out
 
     def ctc_logprobs(self, chunk: int) -> np.ndarray:

@@ -31,6 +31,9 @@ MODEL_DIMS = {
     # the Reverb vocabulary size on small bodies: `joint_decoding` hard-codes sos = 10000 (search.py:479)
     "tiny_v10k":  dict(d=32,  h=2, ff=64,  blocks=4, dff=64,  dblocks=3, K=15, vocab=10001),
     "small_v10k": dict(d=128, h=4, ff=256, blocks=4, dff=256, dblocks=3, K=15, vocab=10001),
+    # a small chain through the code paths of r640's bf16 encoder (dk = 64: the pre-folded key; d % 128 == 0: GLU in the GEMM's
+    # epilogue; M >= 128 rows: gemm2), first and last block language-specific, the middle one plain (tests/test_asr_bf16_gpu.py)
+    "forms64": dict(d=256, h=4,  ff=512,  blocks=3,  dff=256,  dblocks=3, K=31, vocab=500),
     "r268":  dict(d=640,  h=8,  ff=2560, blocks=18, dff=2048, dblocks=3, K=31, vocab=10001),
     "r640":  dict(d=1024, h=16, ff=4096, blocks=18, dff=4096, dblocks=3, K=31, vocab=10001),
 }

@@ -130,6 +130,11 @@ def _parts(case):
     pre = A @ W.T + b
     S = np.abs(A) @ np.abs(W).T + np.abs(b)
     r = case["res"][:, :case["N"]].astype(np.float64) if case["res"] is not None else np.zeros((case["M"], case["N"]))
+    ra = case.get("rowadd")
+    if ra is not None:        # GemmArgs::rowadd: C[m][col0 + j] += add[m % rows][j], in fp32 after alpha and the residual, before the
+        add = np.asarray(ra["add"], np.float64)     # one rounding -- for the bound it is a second residual (one more fp32 addition)
+        r = r.copy()
+        r[:, ra["col0"]:ra["col0"] + add.shape[1]] += add[np.arange(case["M"]) % add.shape[0]]
     return pre, S, r
 
 
@@ -172,9 +177,10 @@ def bound(case):
         return 0.07 * np.abs(ref) + case["out_scale"] * 2.0 ** -9 * 1.01
     e = 1.1 * (2 * case["K"] + 8) * U32 * S
     if case["act"] == ACT_SILU:
-        from test_attention_kernels_gpu import EXP_MEASURED
+        from attention_ref import EXP_MEASURED
         e = e + (4.0 * EXP_MEASURED[case["dtype"]] + (np.abs(pre) + 4.0) * U32) * np.abs(act)
-    b = al * e + 3 * U32 * (al * np.abs(act) + np.abs(r))
+    # (with a row-periodic addend -- the engine builds it without a residual, so r is the addend alone -- one more addition: 4 u32)
+    b = al * e + (4 if case.get("rowadd") is not None else 3) * U32 * (al * np.abs(act) + np.abs(r))
     if case["out"] == "bf16":
         b = b + bf16_half_ulp(np.abs(ref) + b)
     elif case["out"] == "fp8":
