@@ -48,8 +48,8 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
 #include "kernels.h"
+#include "wave_asm.h"      // hidden stores, LDS-DMA pieces, uniform_ptr, counted waits, pixel_swz: each explained there, once
 
 namespace rvb {
 
@@ -60,40 +60,6 @@ constexpr int CB_ROW = CB_PT * 64;                      // one patch / mid row: 
 constexpr int CBB_R = 3, CBB_RING = 8;                  // output rows per step; rows per ring
 constexpr int CBB_OFF_MID = CBB_RING * CB_ROW + 128;    // 128 B: the two pixels the last strip reads past a ring's last row
 constexpr int CBB_LDS = CBB_OFF_MID + CBB_RING * CB_ROW + 128;
-
-typedef unsigned cb_u32x4 __attribute__((ext_vector_type(4)));
-
-// D[channel][pixel] += W[channel][k] . X[pixel][k]: the WEIGHTS are the A operand (see the file header)
-__device__ inline void cb_mma(const uint4& w, const uint4& x, f32x4_t& c) {
-  union U { uint4 u; bf16x8_t v; };
-  U uw, ux;
-  uw.u = w; ux.u = x;
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(uw.v, ux.v, c, 0, 0, 0);
-}
-
-// byte offset of (pixel g, 16-byte chunk c) in a [pixel][64 B] image whose chunks are swizzled with bit 2 of the pixel index
-__device__ inline unsigned cb_swz(unsigned g, unsigned c) { return g * 64u + ((c ^ (((g >> 2) & 1u) << 1)) << 4); }
-
-__device__ inline void cb_wait_all() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
-__device__ inline void cb_wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ inline const char* cb_uniform(const char* q) {
-  const unsigned long long v = (unsigned long long)q;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (const char*)(((unsigned long long)hi << 32) | lo);
-}
-
-__device__ inline void cb_dma1(unsigned off, const void* sbase, unsigned lds0) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(off), "s"(sbase), "s"(lds0)
-      : "memory");
-}
 
 // One convolution for NR consecutive output rows of this wave's column strip, sliding down NR + 2 input rows of a ring (input row i
 // of the slide is ring row row0 + i).  The fragment of input row i at column shift kw is the operand of tap (kh, kw) of output row
@@ -125,7 +91,7 @@ __device__ inline void cb_slide(const uint4 (&w)[9][2], const char* ring, const 
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           if (kh == 0 && kw == 0) acc[r][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-          cb_mma(w[kh * 3 + kw][j], xf[cur][kw], acc[r][j]);
+          Mma16<bf16_t>::run(w[kh * 3 + kw][j], xf[cur][kw], acc[r][j]);      // the WEIGHTS are the A operand (see the file header)
         }
       }
     __builtin_amdgcn_sched_barrier(0);
@@ -149,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void conv_block32_kernel(ConvBlockArgs p) {
   const int band = lin % bands;
   const int b = lin / bands;
   const int t0 = band * CB_OT;
-  const char* in_b = cb_uniform((const char*)p.in + (size_t)b * FP * TP * CB_NT * 2);
+  const char* in_b = uniform_ptr((const char*)p.in + (size_t)b * FP * TP * CB_NT * 2);
   char* out_b = (char*)p.out + (size_t)b * FP * TP * CB_NT * 2;
   const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)cb_smem;
 
@@ -168,7 +134,7 @@ __global__ __launch_bounds__(256, 2) void conv_block32_kernel(ConvBlockArgs p) {
     for (int i = 0; i < 3; ++i) {
       const int q = wave * 3 + i, pb = CBB_R * k + 3 + (q >> 2);
       const unsigned rowterm = (unsigned)(min(pb, FP - 1) * TP) * (CB_NT * 2);
-      cb_dma1(colterm[i] + rowterm, in_b, __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(pb & (CBB_RING - 1)) * CB_ROW + (unsigned)(q & 3) * 1024));
+      lds_dma1(colterm[i] + rowterm, in_b, __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(pb & (CBB_RING - 1)) * CB_ROW + (unsigned)(q & 3) * 1024));
     }
   };
   issue(-1);
@@ -192,9 +158,9 @@ __global__ __launch_bounds__(256, 2) void conv_block32_kernel(ConvBlockArgs p) {
   }
   unsigned soff[3];
 #pragma unroll
-  for (int kw = 0; kw < 3; ++kw) soff[kw] = cb_swz((unsigned)(wave * 16 + li + kw), lg);
-  const unsigned moff = cb_swz((unsigned)(wave * 16 + li), lg);
-  const unsigned roff = cb_swz((unsigned)(wave * 16 + li + 2), lg);
+  for (int kw = 0; kw < 3; ++kw) soff[kw] = pixel_swz((unsigned)(wave * 16 + li + kw), lg);
+  const unsigned moff = pixel_swz((unsigned)(wave * 16 + li), lg);
+  const unsigned roff = pixel_swz((unsigned)(wave * 16 + li + 2), lg);
   const char* patch = cb_smem;
   char* mid = cb_smem + CBB_OFF_MID;
   const int o = wave * 16 + li;
@@ -203,7 +169,7 @@ __global__ __launch_bounds__(256, 2) void conv_block32_kernel(ConvBlockArgs p) {
   const int t = t0 + o;
   const bool t_ok = o < CB_OT && t < p.T;
   const int K = (p.F + CBB_R - 1) / CBB_R;
-  cb_wait_all();
+  wait_vm_lds<0>();
   __syncthreads();
 
   for (int k = -1; k < K; ++k) {
@@ -219,12 +185,12 @@ __global__ __launch_bounds__(256, 2) void conv_block32_kernel(ConvBlockArgs p) {
           make_uint4(pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3]), pack2_bf16(v[4], v[5]), pack2_bf16(v[6], v[7]));
     });
     const int ob0 = CBB_R * k + 1;                          // first output row (bordered) of the step
-    cb_u32x4 rp[CBB_R];
+    u32x4_t rp[CBB_R];
     if (k >= 0) {
 #pragma unroll
-      for (int q = 0; q < CBB_R; ++q) rp[q] = *(const cb_u32x4*)(patch + (roff + (unsigned)((ob0 + q) & (CBB_RING - 1)) * CB_ROW));
+      for (int q = 0; q < CBB_R; ++q) rp[q] = *(const u32x4_t*)(patch + (roff + (unsigned)((ob0 + q) & (CBB_RING - 1)) * CB_ROW));
     }
-    cb_wait_all();                                     // mid written, residuals read, this wave's pieces of the next rows landed
+    wait_vm_lds<0>();                                     // mid written, residuals read, this wave's pieces of the next rows landed
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     if (k < 0) continue;

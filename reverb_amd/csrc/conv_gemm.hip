@@ -30,8 +30,8 @@
 // RVD_CONV_IGEMM=0); tests/test_diar_gpu.py compares it with resnet.hip's direct kernel.  Tried and not kept: the
 // row-contiguous read-back + up-front residual prefetch that helped gemm2's fp32 epilogue (no change here: bf16 output and
 // residual are a quarter of those bytes, the tile is bound by its K loop).
-#include "common.h"
 #include "kernels.h"
+#include "wave_asm.h"      // hidden stores, LDS-DMA pieces, uniform_ptr, counted waits, pixel_swz: each explained there, once
 
 #include <cstdlib>
 #include <type_traits>
@@ -40,39 +40,8 @@ namespace rvb {
 
 namespace {
 
-__device__ inline void cg_mma(const uint4& a, const uint4& b, f32x4_t& c) {
-  union U { uint4 u; bf16x8_t v; };
-  U ua, ub;
-  ua.u = a; ub.u = b;
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ua.v, ub.v, c, 0, 0, 0);
-}
-
-// one 1-KiB LDS-DMA piece (64 lanes x 16 bytes, lane order); inline asm so that hipcc's waitcnt pass does not see it
-// (it would drain vmcnt(0) before every ds_read); ordered by the explicit s_waitcnt in the loop.  M0 is saved/restored.
-__device__ inline void cg_dma(const void* g, unsigned lds) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %2\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, off\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(g), "s"(lds)
-      : "memory");
-}
-
-// one 16-byte store the compiler's waitcnt pass does not see (see the epilogue); s_nop 1: the TWO wait states gfx950 wants
-// between a store of more than 8 bytes and a VALU write of its data registers (gemm2.hip: store16_hidden)
-__device__ inline void cg_store16(void* q, const uint4& v) {
-  typedef unsigned cg_u32x4 __attribute__((ext_vector_type(4)));
-  const cg_u32x4 d = {v.x, v.y, v.z, v.w};
-  asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(q), "v"(d) : "memory");
-}
-
 __device__ inline void cg_pin(uint4& a, uint4& b) {
-  typedef unsigned cg_u32x4 __attribute__((ext_vector_type(4)));
-  cg_u32x4 x = {a.x, a.y, a.z, a.w}, y = {b.x, b.y, b.z, b.w};
+  u32x4_t x = {a.x, a.y, a.z, a.w}, y = {b.x, b.y, b.z, b.w};
   asm volatile("" : "+v"(x), "+v"(y)::"memory");
   a = make_uint4(x[0], x[1], x[2], x[3]); b = make_uint4(y[0], y[1], y[2], y[3]);
 }
@@ -148,11 +117,11 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(ConvArgs p) {
         const int b = m / (F * T), rem = m - b * (F * T);
         const int fo = rem / T, to = rem - fo * T;
         const bf16_t* src = in2 + ((size_t)(b * FP2 + s2 * fo + 1) * TP2 + s2 * to + 1) * C2 + j * BKE + (lc ^ ((row >> 1) & 7)) * 8;
-        cg_dma(src, dst + (wave * AR + i * 8) * BKB);
+        lds_dma1(src, dst + (wave * AR + i * 8) * BKB);
       }
       const size_t woff2 = (size_t)9 * Cin + (size_t)j * BKE;
 #pragma unroll
-      for (int i = 0; i < WP; ++i) cg_dma(w_src[i] + woff2, dst + BM * BKB + (wave * (WP * 8) + i * 8) * BKB);
+      for (int i = 0; i < WP; ++i) lds_dma1(w_src[i] + woff2, dst + BM * BKB + (wave * (WP * 8) + i * 8) * BKB);
       return;
     }
     const int tap = kt / cpt, c0 = (kt - tap * cpt) * BKE;
@@ -160,9 +129,9 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(ConvArgs p) {
     const size_t aoff = (size_t)(kh * TPi + kw) * Cin + c0;
     const size_t woff = (size_t)tap * Cin + c0;
 #pragma unroll
-    for (int i = 0; i < AP; ++i) cg_dma(a_src[i] + aoff, dst + (wave * AR + i * 8) * BKB);
+    for (int i = 0; i < AP; ++i) lds_dma1(a_src[i] + aoff, dst + (wave * AR + i * 8) * BKB);
 #pragma unroll
-    for (int i = 0; i < WP; ++i) cg_dma(w_src[i] + woff, dst + BM * BKB + (wave * (WP * 8) + i * 8) * BKB);
+    for (int i = 0; i < WP; ++i) lds_dma1(w_src[i] + woff, dst + BM * BKB + (wave * (WP * 8) + i * 8) * BKB);
   };
 
   f32x4_t acc[FI][FJ];
@@ -192,7 +161,7 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(ConvArgs p) {
 #pragma unroll
     for (int i = 0; i < FI; ++i)
 #pragma unroll
-      for (int j = 0; j < FJ; ++j) cg_mma(fa[buf][i], fb[buf][j], acc[i][j]);
+      for (int j = 0; j < FJ; ++j) Mma16<bf16_t>::run(fa[buf][i], fb[buf][j], acc[i][j]);
   };
   auto block = [&](auto mbufc, int q) __attribute__((always_inline)) {     // multiply buffer mbuf, read slice q into the other
     constexpr int mb = decltype(mbufc)::value;
@@ -207,7 +176,7 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(ConvArgs p) {
     if constexpr (NM - PER * NR > 0) __builtin_amdgcn_sched_group_barrier(0x008, NM - PER * NR, 0);
   };
   auto enter_stage = [&](int kt) __attribute__((always_inline)) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     __syncthreads();
     if (kt + 1 < nk) issue(kt + 1);
   };
@@ -215,7 +184,7 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(ConvArgs p) {
   std::integral_constant<int, 1> b1;
   issue(0);
   issue(1);
-  asm volatile("s_waitcnt vmcnt(%0)" ::"n"(AP + WP) : "memory");    // stage 0 = the older group of AP + WP pieces
+  wait_vm<AP + WP>();    // stage 0 = the older group of AP + WP pieces
   __syncthreads();
   read_slice(b0, 0);
   block(b0, 1);
@@ -254,7 +223,7 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(ConvArgs p) {
   asm volatile("" : "+v"(bias_r[0]), "+v"(bias_r[1]), "+v"(bias_r[2]), "+v"(bias_r[3]), "+v"(bias_r[4]), "+v"(bias_r[5]), "+v"(bias_r[6]), "+v"(bias_r[7]),
                "+v"(bias_r[8]), "+v"(bias_r[9]), "+v"(bias_r[10]), "+v"(bias_r[11]), "+v"(bias_r[12]), "+v"(bias_r[13]), "+v"(bias_r[14]), "+v"(bias_r[15]));
   // Round 4: the residual vectors of ALL slabs are requested before the first slab is transposed, and the stores are inline
-  // asm (cg_store16).  vmcnt counts loads and stores in one in-order queue: with the residual loaded inside the slab loop,
+  // asm (store16_hidden).  vmcnt counts loads and stores in one in-order queue: with the residual loaded inside the slab loop,
   // the wait for slab i's residual was also a wait for every store of slab i - 1 (s_waitcnt vmcnt(0) between any two stores
   // of the round-3 code object).  Now the compiler's waitcnt pass sees loads only -- all older than the first store -- and
   // the stores of a tile stream out behind each other.
@@ -318,7 +287,7 @@ __global__ __launch_bounds__(512) void conv_igemm_kernel(ConvArgs p) {
         bf16_t o[8];
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = f32_to_bf16(v[q * 8 + e]);
-        cg_store16(op + q * 8, *(const uint4*)o);
+        store16_hidden(op + q * 8, *(const uint4*)o);
       }
     }
     if constexpr (HR) {
@@ -393,9 +362,9 @@ __global__ __launch_bounds__(512) void conv_igemm8_kernel(ConvArgs p) {
     const size_t woff = (size_t)tap * Cin + c0;
     const unsigned dst = lds_base + (kt & 1) * STAGE;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) cg_dma(a_src[i] + aoff, dst + (wave * 32 + i * 8) * BKB);
+    for (int i = 0; i < 4; ++i) lds_dma1(a_src[i] + aoff, dst + (wave * 32 + i * 8) * BKB);
 #pragma unroll
-    for (int i = 0; i < WP; ++i) cg_dma(w_src[i] + woff, dst + 256 * BKB + (wave * (WP * 8) + i * 8) * BKB);
+    for (int i = 0; i < WP; ++i) lds_dma1(w_src[i] + woff, dst + 256 * BKB + (wave * (WP * 8) + i * 8) * BKB);
   };
 
   cg_f32x16 acc[MB][2];
@@ -416,7 +385,7 @@ __global__ __launch_bounds__(512) void conv_igemm8_kernel(ConvArgs p) {
 
   issue(0);
   for (int kt = 0; kt < nk; ++kt) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's pieces of stage kt
+    wait_vm<0>();       // this wave's pieces of stage kt
     __syncthreads();                                       // ... everybody's; nobody reads stage kt - 1 any more
     if (kt + 1 < nk) issue(kt + 1);
     const char* st = cg_smem + (kt & 1) * STAGE;

@@ -36,41 +36,14 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
 #include "kernels.h"
+#include "wave_asm.h"      // hidden stores, LDS-DMA pieces, uniform_ptr, counted waits, pixel_swz: each explained there, once
 
 namespace rvb {
 
 namespace {
 
 constexpr int CR_PF = 6, CR_OF = 4, CR_NT = 64;
-
-typedef unsigned cr_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ inline void cr_mma(const uint4& w, const uint4& x, f32x4_t& c) {
-  union U { uint4 u; bf16x8_t v; };
-  U uw, ux;
-  uw.u = w; ux.u = x;
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(uw.v, ux.v, c, 0, 0, 0);
-}
-__device__ inline unsigned cr_swz(unsigned g, unsigned c) { return g * 64u + ((c ^ (((g >> 2) & 1u) << 1)) << 4); }
-
-// one 16-byte store the compiler's waitcnt pass does not see: it waits for a store (vmcnt is one queue for loads and stores)
-// before the next m-tile's epilogue touches the registers the store read, i.e. it would drain every store one by one.  s_nop 1:
-// the TWO wait states gfx950 wants between a store of more than 8 bytes and a VALU write of its data registers
-// (scripts/micro/store_hazard.hip).  Sound with the compiler's counting of the residual loads: hidden stores are OLDER than the
-// loads it waits for, so they only make such a wait cover more than it thinks.
-__device__ inline void cr_store16(void* q, const uint4& v) {
-  const cr_u32x4 d = {v.x, v.y, v.z, v.w};
-  asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(q), "v"(d) : "memory");
-}
-__device__ inline void cr_wait_all() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); }
-__device__ inline void cr_wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ inline const char* cr_uniform(const char* q) {
-  const unsigned long long v = (unsigned long long)q;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (const char*)(((unsigned long long)hi << 32) | lo);
-}
 
 // RES / RELU are template parameters: with `if (p.res)` blocks in the body the compiler re-waits for the residual loads inside each
 // of them, and each such wait (counted against ITS loads only) also drains the hidden stores issued in between
@@ -79,23 +52,6 @@ constexpr int CN_ROW = CN_PT * 64;                  // 2 048 B
 constexpr int CN_PLANE = CR_PF * CN_ROW;            // 12 288 B
 constexpr int CN_BUF = 2 * CN_PLANE + 128;          // both chunk planes of a tile + the spill pad
 constexpr int CN_LDS = 2 * CN_BUF;
-
-// two 1-KiB LDS-DMA pieces: one patch row of one chunk plane (2 KiB), 16 pixels per piece
-__device__ inline void cr_dma2(const unsigned (&off)[2], const void* sbase, unsigned lds0) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %4\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %3\n\t"
-      "s_add_u32 m0, m0, 0x400\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %2, %3\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(off[0]), "v"(off[1]), "s"(sbase), "s"(lds0)
-      : "memory", "scc");
-}
 
 template <bool RES, bool RELU>
 __global__ __launch_bounds__(256, 2) void conv_row64_kernel(ConvArgs p) {
@@ -114,7 +70,7 @@ __global__ __launch_bounds__(256, 2) void conv_row64_kernel(ConvArgs p) {
   const int tf = lin % tiles_f;
   const int b = lin / tiles_f;
   const int f0 = tf * CR_OF;
-  const char* in_b = cr_uniform((const char*)p.in + (size_t)b * FP * TP * CR_NT * 2);
+  const char* in_b = uniform_ptr((const char*)p.in + (size_t)b * FP * TP * CR_NT * 2);
   const char* res_b = (const char*)p.res + (size_t)b * FP * TP * CR_NT * 2;
   char* out_b = (char*)p.out + (size_t)b * FP * TP * CR_NT * 2;
   const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)cr_smem;
@@ -138,7 +94,7 @@ __global__ __launch_bounds__(256, 2) void conv_row64_kernel(ConvArgs p) {
       unsigned off[2];
 #pragma unroll
       for (int g = 0; g < 2; ++g) off[g] = lineoff[i] + px[g];
-      cr_dma2(off, in_b, __builtin_amdgcn_readfirstlane(lds_base + (tt & 1) * CN_BUF + (q & 1) * CN_PLANE + (q >> 1) * CN_ROW));
+      lds_dma2(off[0], off[1], in_b, __builtin_amdgcn_readfirstlane(lds_base + (tt & 1) * CN_BUF + (q & 1) * CN_PLANE + (q >> 1) * CN_ROW));
     }
   };
   issue(0);
@@ -163,13 +119,13 @@ __global__ __launch_bounds__(256, 2) void conv_row64_kernel(ConvArgs p) {
   }
   unsigned aoff[3];
 #pragma unroll
-  for (int kw = 0; kw < 3; ++kw) aoff[kw] = cr_swz((unsigned)(col * 16 + li + kw), lg);
-  cr_wait_all();
+  for (int kw = 0; kw < 3; ++kw) aoff[kw] = pixel_swz((unsigned)(col * 16 + li + kw), lg);
+  wait_vm_lds<0>();
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap)
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
-      cr_u32x4 x = {w[tap][c][0].x, w[tap][c][0].y, w[tap][c][0].z, w[tap][c][0].w}, y = {w[tap][c][1].x, w[tap][c][1].y, w[tap][c][1].z, w[tap][c][1].w};
+      u32x4_t x = {w[tap][c][0].x, w[tap][c][0].y, w[tap][c][0].z, w[tap][c][0].w}, y = {w[tap][c][1].x, w[tap][c][1].y, w[tap][c][1].z, w[tap][c][1].w};
       asm volatile("" : "+v"(x), "+v"(y));
       w[tap][c][0] = make_uint4(x[0], x[1], x[2], x[3]); w[tap][c][1] = make_uint4(y[0], y[1], y[2], y[3]);
     }
@@ -181,11 +137,11 @@ __global__ __launch_bounds__(256, 2) void conv_row64_kernel(ConvArgs p) {
     if (tt + 1 < tiles_t) issue(tt + 1);       // into the other buffer: its readers (tile tt - 1) are behind the last barrier
     const int t = t0 + o;
     const unsigned tcl = (unsigned)min(t, p.To - 1) + 1;
-    cr_u32x4 rp[4];
+    u32x4_t rp[4];
     if constexpr (RES) {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
-        rp[q] = *(const cr_u32x4*)(res_b + ((size_t)((unsigned)(min(f0 + q, p.Fo - 1) + 1) * TP + tcl) * CR_NT + half * 32 + lg * 8) * 2);
+        rp[q] = *(const u32x4_t*)(res_b + ((size_t)((unsigned)(min(f0 + q, p.Fo - 1) + 1) * TP + tcl) * CR_NT + half * 32 + lg * 8) * 2);
     }
     const bool t_ok = o < CN_OT && t < p.To;
     f32x4_t acc[4][2];
@@ -211,7 +167,7 @@ __global__ __launch_bounds__(256, 2) void conv_row64_kernel(ConvArgs p) {
 #pragma unroll
           for (int j = 0; j < 2; ++j) {
             if (c == 0 && kh == 0 && kw == 0) acc[r][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-            cr_mma(w[kh * 3 + kw][c][j], xf[cur][kw], acc[r][j]);
+            Mma16<bf16_t>::run(w[kh * 3 + kw][c][j], xf[cur][kw], acc[r][j]);
           }
         }
       __builtin_amdgcn_sched_barrier(0);
@@ -220,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void conv_row64_kernel(ConvArgs p) {
         if (q == 0) {
           // this wave's pieces of the next patch (requested most of a tile of MFMAs ago) and the residual vectors have landed; the
           // stores below are younger than this wait, so nothing ever waits for them
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+          wait_vm<0>();
           if constexpr (RES) {
 #pragma unroll
             for (int m = 0; m < 4; ++m) asm volatile("" : "+v"(rp[m]));
@@ -242,11 +198,11 @@ __global__ __launch_bounds__(256, 2) void conv_row64_kernel(ConvArgs p) {
         }
         const int fo = f0 + q;
         if (t_ok && fo < p.Fo)
-          cr_store16(out_b + ((size_t)((unsigned)(fo + 1) * TP + t + 1) * CR_NT + half * 32 + lg * 8) * 2,
-                     make_uint4(pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3]), pack2_bf16(v[4], v[5]), pack2_bf16(v[6], v[7])));
+          store16_hidden(out_b + ((size_t)((unsigned)(fo + 1) * TP + t + 1) * CR_NT + half * 32 + lg * 8) * 2,
+                         make_uint4(pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3]), pack2_bf16(v[4], v[5]), pack2_bf16(v[6], v[7])));
       }
     }
-    cr_wait_lds();
+    wait_lds();
     __builtin_amdgcn_s_barrier();              // every wave's pieces of the next patch are in; this tile's buffer is free
     asm volatile("" ::: "memory");
   }

@@ -22,8 +22,8 @@
 #include <algorithm>
 #include <cstdlib>
 
-#include "common.h"
 #include "kernels.h"
+#include "wave_asm.h"      // hidden stores, LDS-DMA pieces, uniform_ptr, counted waits, pixel_swz: each explained there, once
 
 namespace rvb {
 
@@ -34,38 +34,6 @@ constexpr int CS_PLANE = CS_PP * 64;                // 2 048 B
 constexpr int CS_ROW = 2 * CS_PLANE;                // 4 096 B
 constexpr int CS_BUF = CS_PR * CS_ROW + 128;
 constexpr int CS_LDS = 2 * CS_BUF;
-
-typedef unsigned cs_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ inline void cs_mma(const uint4& w, const uint4& x, f32x4_t& c) {
-  union U { uint4 u; bf16x8_t v; };
-  U uw, ux;
-  uw.u = w; ux.u = x;
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(uw.v, ux.v, c, 0, 0, 0);
-}
-__device__ inline unsigned cs_swz(unsigned g, unsigned c) { return g * 64u + ((c ^ (((g >> 2) & 1u) << 1)) << 4); }
-// (conv_row64.hip: cr_store16)
-__device__ inline void cs_store16(void* q, const uint4& v) {
-  const cs_u32x4 d = {v.x, v.y, v.z, v.w};
-  asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(q), "v"(d) : "memory");
-}
-__device__ inline void cs_dma1(unsigned off, const void* sbase, unsigned lds0) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(off), "s"(sbase), "s"(lds0)
-      : "memory");
-}
-__device__ inline const char* cs_uniform(const char* q) {
-  const unsigned long long v = (unsigned long long)q;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (const char*)(((unsigned long long)hi << 32) | lo);
-}
 
 __global__ __launch_bounds__(256, 2) void conv_s2sc_kernel(ConvS2Args p) {
   extern __shared__ __attribute__((aligned(16))) char cs_smem[];
@@ -83,7 +51,7 @@ __global__ __launch_bounds__(256, 2) void conv_s2sc_kernel(ConvS2Args p) {
   const int tf = lin % tiles_f;
   const int b = lin / tiles_f;
   const int f0 = tf * CS_OF;
-  const char* in_b = cs_uniform((const char*)p.in + (size_t)b * FPi * TPi * 64);
+  const char* in_b = uniform_ptr((const char*)p.in + (size_t)b * FPi * TPi * 64);
   char* out_b = (char*)p.out + (size_t)b * FPo * TPo * 128;
   char* sc_b = (char*)p.sc + (size_t)b * FPo * TPo * 128;
   const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)cs_smem;
@@ -99,7 +67,7 @@ __global__ __launch_bounds__(256, 2) void conv_s2sc_kernel(ConvS2Args p) {
       const int q = wave * 9 + i, row = q >> 2, par = (q >> 1) & 1, g = q & 1;
       const unsigned rowterm = (unsigned)(min(2 * f0 + row, FPi - 1) * TPi) * 64u;
       const unsigned colterm = (unsigned)min(2 * (t0 + g * 16 + ppx) + par, TPi - 1) * 64u + piece_b;
-      cs_dma1(rowterm + colterm, in_b,
+      lds_dma1(rowterm + colterm, in_b,
               __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(tt & 1) * CS_BUF + (unsigned)row * CS_ROW + (unsigned)par * CS_PLANE + (unsigned)g * 1024));
     }
   };
@@ -124,20 +92,20 @@ __global__ __launch_bounds__(256, 2) void conv_s2sc_kernel(ConvS2Args p) {
   }
   // tap column 0 = E[o], 1 = O[o], 2 = E[o + 1]
   unsigned aoff[3];
-  aoff[0] = cs_swz((unsigned)(col * 16 + li), lg);
+  aoff[0] = pixel_swz((unsigned)(col * 16 + li), lg);
   aoff[1] = aoff[0] + CS_PLANE;
-  aoff[2] = cs_swz((unsigned)(col * 16 + li + 1), lg);
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+  aoff[2] = pixel_swz((unsigned)(col * 16 + li + 1), lg);
+  wait_vm_lds<0>();
   // (the weights are "used" here, so that the compiler carries no pending load of its own into the loop: its waits for one would
   // also wait for the LDS-DMA pieces and the stores it cannot see)
 #pragma unroll
   for (int tap = 0; tap < 9; ++tap) {
-    cs_u32x4 x = {w[tap][0].x, w[tap][0].y, w[tap][0].z, w[tap][0].w}, y = {w[tap][1].x, w[tap][1].y, w[tap][1].z, w[tap][1].w};
+    u32x4_t x = {w[tap][0].x, w[tap][0].y, w[tap][0].z, w[tap][0].w}, y = {w[tap][1].x, w[tap][1].y, w[tap][1].z, w[tap][1].w};
     asm volatile("" : "+v"(x), "+v"(y));
     w[tap][0] = make_uint4(x[0], x[1], x[2], x[3]); w[tap][1] = make_uint4(y[0], y[1], y[2], y[3]);
   }
   {
-    cs_u32x4 x = {wsc[0].x, wsc[0].y, wsc[0].z, wsc[0].w}, y = {wsc[1].x, wsc[1].y, wsc[1].z, wsc[1].w};
+    u32x4_t x = {wsc[0].x, wsc[0].y, wsc[0].z, wsc[0].w}, y = {wsc[1].x, wsc[1].y, wsc[1].z, wsc[1].w};
     asm volatile("" : "+v"(x), "+v"(y));
     wsc[0] = make_uint4(x[0], x[1], x[2], x[3]); wsc[1] = make_uint4(y[0], y[1], y[2], y[3]);
   }
@@ -168,13 +136,13 @@ __global__ __launch_bounds__(256, 2) void conv_s2sc_kernel(ConvS2Args p) {
         for (int kw = 0; kw < 3; ++kw) {
           if (r >= 1) {
 #pragma unroll
-            for (int j = 0; j < 2; ++j) cs_mma(w[6 + kw][j], xf[cur][kw], acc[r - 1][j]);
+            for (int j = 0; j < 2; ++j) Mma16<bf16_t>::run(w[6 + kw][j], xf[cur][kw], acc[r - 1][j]);
           }
           if (r < CS_OF) {
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
               if (kw == 0) acc[r][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-              cs_mma(w[kw][j], xf[cur][kw], acc[r][j]);
+              Mma16<bf16_t>::run(w[kw][j], xf[cur][kw], acc[r][j]);
             }
           }
         }
@@ -183,18 +151,18 @@ __global__ __launch_bounds__(256, 2) void conv_s2sc_kernel(ConvS2Args p) {
 #pragma unroll
         for (int kw = 0; kw < 3; ++kw)
 #pragma unroll
-          for (int j = 0; j < 2; ++j) cs_mma(w[3 + kw][j], xf[cur][kw], acc[r][j]);
+          for (int j = 0; j < 2; ++j) Mma16<bf16_t>::run(w[3 + kw][j], xf[cur][kw], acc[r][j]);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
           accs[r][j] = (f32x4_t){0.f, 0.f, 0.f, 0.f};
-          cs_mma(wsc[j], xf[cur][1], accs[r][j]);
+          Mma16<bf16_t>::run(wsc[j], xf[cur][1], accs[r][j]);
         }
       }
       __builtin_amdgcn_sched_barrier(0);
     }
     // this wave's pieces of the next patch (requested a whole tile of MFMAs ago) have landed, and the stores of the previous tile
     // with them (older in the same queue); the stores below are younger than this wait: nothing ever waits for them
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    wait_vm<0>();
     const int t = t0 + o;
     const bool t_ok = o < CS_OT && t < p.To;
 #pragma unroll
@@ -208,8 +176,8 @@ __global__ __launch_bounds__(256, 2) void conv_s2sc_kernel(ConvS2Args p) {
       const int fo = f0 + r;
       if (t_ok && fo < p.Fo) {
         const size_t at = ((size_t)((unsigned)(fo + 1) * TPo + t + 1) * 64 + half * 32 + lg * 8) * 2;
-        cs_store16(out_b + at, make_uint4(pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3]), pack2_bf16(v[4], v[5]), pack2_bf16(v[6], v[7])));
-        cs_store16(sc_b + at, make_uint4(pack2_bf16(s[0], s[1]), pack2_bf16(s[2], s[3]), pack2_bf16(s[4], s[5]), pack2_bf16(s[6], s[7])));
+        store16_hidden(out_b + at, make_uint4(pack2_bf16(v[0], v[1]), pack2_bf16(v[2], v[3]), pack2_bf16(v[4], v[5]), pack2_bf16(v[6], v[7])));
+        store16_hidden(sc_b + at, make_uint4(pack2_bf16(s[0], s[1]), pack2_bf16(s[2], s[3]), pack2_bf16(s[4], s[5]), pack2_bf16(s[6], s[7])));
       }
     }
     __builtin_amdgcn_s_barrier();              // every wave's pieces of the next patch are in; this tile's buffer is free

@@ -36,8 +36,8 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.h"
 #include "kernels.h"
+#include "wave_asm.h"      // hidden stores, LDS-DMA pieces, uniform_ptr, counted waits, pixel_swz: each explained there, once
 
 namespace rvb {
 
@@ -48,16 +48,7 @@ constexpr int CS_PATCH = CS_PF * CS_PT * 64;      // 24 576 B
 constexpr int CS_SROW = 32 * 4 + 16;              // fp32 slab row of 32 channels, padded
 constexpr int CS_SLAB = 16 * CS_SROW;             // per wave
 
-typedef unsigned cs_u32x4 __attribute__((ext_vector_type(4)));
-
-__device__ inline void cs_mma(const uint4& a, const uint4& b, f32x4_t& c) {
-  union U { uint4 u; bf16x8_t v; };
-  U ua, ub;
-  ua.u = a; ub.u = b;
-  c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ua.v, ub.v, c, 0, 0, 0);
-}
-
-// six 1-KiB LDS-DMA pieces: patch rows 0..5 (4 KiB apart in LDS), per-lane 32-bit byte offsets from a scalar base
+// six 1-KiB LDS-DMA pieces: patch rows 0..5 (4 KiB apart in LDS), per-lane 32-bit byte offsets from a scalar base (as wave_asm.h's lds_dma2)
 __device__ inline void cs_dma6(const unsigned (&off)[6], const void* sbase, unsigned lds0) {
   unsigned keep;
   asm volatile(
@@ -85,36 +76,16 @@ __device__ inline void cs_dma6(const unsigned (&off)[6], const void* sbase, unsi
       : "v"(off[0]), "v"(off[1]), "v"(off[2]), "v"(off[3]), "v"(off[4]), "v"(off[5]), "s"(sbase), "s"(lds0)
       : "memory", "scc");
 }
-__device__ inline void cs_dma1(unsigned off, const void* sbase, unsigned lds) {
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %3\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %2\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(off), "s"(sbase), "s"(lds)
-      : "memory");
-}
-__device__ inline cs_u32x4 cs_load16(unsigned off, const void* sbase) {
-  cs_u32x4 r;
+__device__ inline u32x4_t cs_load16(unsigned off, const void* sbase) {
+  u32x4_t r;
   asm volatile("global_load_dwordx4 %0, %1, %2" : "=v"(r) : "v"(off), "s"(sbase) : "memory");
   return r;
-}
-// ... and every LDS read of this wave has returned (in front of a barrier behind which its buffer is requested again)
-template <int N> __device__ inline void cs_wait_vmlgkm() { asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(N) : "memory"); }
-template <int N> __device__ inline void cs_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-__device__ inline const char* cs_uniform(const char* q) {
-  const unsigned long long v = (unsigned long long)q;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (const char*)(((unsigned long long)hi << 32) | lo);
 }
 
 // The residual vectors are loaded by inline asm and become valid at the counted wait: this empty statement, placed right
 // behind that wait, makes every later use of them depend on it (one statement on the merged path -- with the registers as
 // operands of two alternative wait statements the allocator copied them in front of one of the two, i.e. read them in flight)
-template <int NH> __device__ inline void cs_touch_rp(cs_u32x4 (&rp)[4][NH]) {
+template <int NH> __device__ inline void cs_touch_rp(u32x4_t (&rp)[4][NH]) {
   if constexpr (NH == 1)
     asm volatile("" : "+v"(rp[0][0]), "+v"(rp[1][0]), "+v"(rp[2][0]), "+v"(rp[3][0])::"memory");
   else
@@ -162,8 +133,8 @@ __global__ __launch_bounds__(256, NT == 32 ? 2 : 1) void conv_stream_kernel(Conv
   const int n_items = (tt1 - tt0) * NCH;
   if (n_items <= 0) return;
 
-  const char* in_b = cs_uniform((const char*)p.in + (size_t)b * FP * TP * CIN * 2);
-  const char* res_b = p.res ? cs_uniform((const char*)p.res + (size_t)b * FP * TP * NT * 2) : nullptr;
+  const char* in_b = uniform_ptr((const char*)p.in + (size_t)b * FP * TP * CIN * 2);
+  const char* res_b = p.res ? uniform_ptr((const char*)p.res + (size_t)b * FP * TP * NT * 2) : nullptr;
   char* out_b = (char*)p.out + (size_t)b * FP * TP * NT * 2;
   const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)cs_smem;
 
@@ -171,7 +142,7 @@ __global__ __launch_bounds__(256, NT == 32 ? 2 : 1) void conv_stream_kernel(Conv
   // piece pc = 16 rows x 64 B (inside one (chunk, tap) block, NT % 16 == 0); wave w takes pieces w, w + 4, ...
   {
     constexpr int NPC = NCH * 9 * NT / 16;
-    const char* wg = cs_uniform((const char*)p.w);
+    const char* wg = uniform_ptr((const char*)p.w);
 #pragma unroll
     for (int i = 0; i < (NPC + 3) / 4; ++i) {
       const int pc = i * 4 + wave;
@@ -179,7 +150,7 @@ __global__ __launch_bounds__(256, NT == 32 ? 2 : 1) void conv_stream_kernel(Conv
         const int row0 = pc * 16, ct = row0 / NT, n = row0 - ct * NT + (lane >> 2);
         const int tap = ct % 9, c = ct / 9;
         const unsigned off = (unsigned)((((tap * NCH + c) * NT + n) * 4 + (lane & 3)) * 16);
-        cs_dma1(off, wg, __builtin_amdgcn_readfirstlane(lds_base + pc * 1024));
+        lds_dma1(off, wg, __builtin_amdgcn_readfirstlane(lds_base + pc * 1024));
       }
     }
   }
@@ -214,17 +185,17 @@ __global__ __launch_bounds__(256, NT == 32 ? 2 : 1) void conv_stream_kernel(Conv
   const unsigned frow_off = (unsigned)(min(f, p.Fo - 1) + 1) * TP;        // bordered row of this wave's outputs (clamped)
 
   f32x4_t acc[4][NJ];
-  cs_u32x4 rp[4][NH];
+  u32x4_t rp[4][NH];
 #pragma unroll
   for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-    for (int h = 0; h < NH; ++h) rp[mi][h] = (cs_u32x4){0u, 0u, 0u, 0u};
+    for (int h = 0; h < NH; ++h) rp[mi][h] = (u32x4_t){0u, 0u, 0u, 0u};
 
   // ---- prologue: the first PD items requested; weights visible; item 0 landed
 #pragma unroll
   for (int k = 0; k < PD; ++k)
     if (k < n_items) issue(k);
-  if (PD == 2 && n_items > 1) cs_wait_vm<6>(); else cs_wait_vm<0>();
+  if (PD == 2 && n_items > 1) wait_vm<6>(); else wait_vm<0>();
   __syncthreads();
 
   auto item = [&](auto cc, int k) __attribute__((always_inline)) {
@@ -274,12 +245,12 @@ __global__ __launch_bounds__(256, NT == 32 ? 2 : 1) void conv_stream_kernel(Conv
 #pragma unroll
         for (int mi = 0; mi < 4; ++mi)
 #pragma unroll
-          for (int j = 0; j < NJ; ++j) cs_mma(af[cur][mi], bf[cur][j], acc[mi][j]);
+          for (int j = 0; j < NJ; ++j) Mma16<bf16_t>::run(af[cur][mi], bf[cur][j], acc[mi][j]);
         __builtin_amdgcn_sched_barrier(0);
       }
     }
     // everything older than the DMA just issued has landed (this wave's pieces of item k + 1, the residual vectors)
-    if (PD == 2 && more) cs_wait_vmlgkm<6>(); else cs_wait_vmlgkm<0>();
+    if (PD == 2 && more) wait_vm_lds<6>(); else wait_vm_lds<0>();
     if constexpr (last) cs_touch_rp<NH>(rp);
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -303,7 +274,7 @@ __global__ __launch_bounds__(256, NT == 32 ? 2 : 1) void conv_stream_kernel(Conv
 #pragma unroll
           for (int e = 0; e < 8; ++e) v[e] += bias_r[h][e];
           if (res_b) {
-            const cs_u32x4 raw = rp[mi][h];
+            const u32x4_t raw = rp[mi][h];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
               v[2 * e] += __uint_as_float(raw[e] << 16);
@@ -326,7 +297,7 @@ __global__ __launch_bounds__(256, NT == 32 ? 2 : 1) void conv_stream_kernel(Conv
     item(std::integral_constant<int, 0>(), k);
     if constexpr (NCH == 2) item(std::integral_constant<int, 1>(), k + 1);
   }
-  cs_wait_vm<0>();
+  wait_vm<0>();
 }
 
 template <int NT, int NCH, int NBUF>

@@ -39,16 +39,6 @@ namespace rvb {
 
 namespace {
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 // log(exp(x0) + exp(x1) + exp(x2)); -inf when all three are
 __device__ __forceinline__ float lse3(float x0, float x1, float x2) {
   const float m = fmaxf(fmaxf(x0, x1), x2);

@@ -38,8 +38,6 @@ namespace rvb {
 
 namespace {
 
-constexpr unsigned ARC_SLOT = 0x3fffu, ARC_T = 0x8000u;   // an arc word: LDS slot of the predecessor (0 = start) | its T may enter
-
 template <int NPT>
 __global__ __launch_bounds__(1024) void ctc_graph_forward_kernel(const GraphSeq* __restrict__ seqs, const float* __restrict__ lp, int ld,
                                                                  int r0, const int* __restrict__ rows, const int* __restrict__ node_tok,
@@ -209,8 +207,6 @@ __global__ void ctc_graph_backtrace_kernel(const GraphSeq* __restrict__ seqs, co
   out[0] = st;
 }
 
-int npt_for(int N) { return N <= 1024 ? 1 : N <= 2048 ? 2 : N <= 4096 ? 4 : 8; }
-
 constexpr int GRAPH_LDS_MAX = 2 * (CTC_GRAPH_MAX_NODES + 1) * (int)sizeof(float2);   // what an instantiation may be launched with
 
 template <int NPT>
@@ -233,7 +229,7 @@ int ctc_graph_forward(hipStream_t s, const GraphSeq* seqs, int n_seq, int max_N,
                       const float* wmax, float bias) {
   if (n_seq <= 0) return OK;
   if (max_N < 1 || max_N > CTC_GRAPH_MAX_NODES) { set_error("ctc_graph_forward: nodes out of range"); return E_ARG; }
-  const int npt = npt_for(max_N);
+  const int npt = ctc_graph_npt_for(max_N);
   const int threads = ctc_threads(max_N, npt);
   const int slots = max_N + 1;
   const size_t lds = (size_t)2 * slots * sizeof(float2);

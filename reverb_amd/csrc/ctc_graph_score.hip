@@ -43,14 +43,8 @@ namespace rvb {
 
 namespace {
 
-constexpr unsigned ARC_SLOT = 0x3fffu, ARC_T = 0x8000u;   // an arc word of ctc_graph.hip: LDS slot | the neighbour's T may pass
 constexpr unsigned REM_NEVER = 0xffffu;                   // frames to the end of a state that reaches no final node
 
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-}
 // The states are CARRIED in fp64 (registers, LDS, HBM between slabs): the state that carries the posterior may lie hundreds of nats
 // below the row maximum the normaliser follows, and an fp32 cell would round it at that magnitude once per frame in each sweep, an
 // error common to a row that only a division by the row's summed posterior could remove.  The transcendental part stays fp32: the
@@ -430,8 +424,6 @@ __global__ __launch_bounds__(1024) void ctc_graph_sum_backward_kernel(const Grap
   }
 }
 
-int npt_for(int N) { return N <= 1024 ? 1 : N <= 2048 ? 2 : N <= 4096 ? 4 : 8; }
-
 constexpr int SUM_LDS_MAX = 160 * 1024 - 1024;   // what an instantiation may be launched with: a workgroup's LDS less the static part
 static_assert((CTC_GRAPH_MAX_NODES + 1) * (int)sizeof(double2) <= SUM_LDS_MAX, "one row of {T, B} in fp64 fits the LDS");
 static_assert(2 * CTC_GRAPH_MAX_NODES * (int)sizeof(double) <= SUM_LDS_MAX, "two rows of beta(T) in fp64 fit the LDS");
@@ -466,7 +458,7 @@ int ctc_graph_sum_forward(hipStream_t s, const GraphSeq* seqs, int n_seq, int ma
                           double* csum, float* coff, float* arows) {
   if (n_seq <= 0) return OK;
   if (max_N < 1 || max_N > CTC_GRAPH_MAX_NODES) { set_error("ctc_graph_sum_forward: nodes out of range"); return E_ARG; }
-  const int npt = npt_for(max_N);
+  const int npt = ctc_graph_npt_for(max_N);
   const int threads = ctc_threads(max_N, npt);
   const int slots = max_N + 1;
   const int single = (size_t)2 * slots * sizeof(double2) > (size_t)SUM_LDS_MAX;      // above 5087 nodes: one buffer, two barriers per frame
@@ -495,7 +487,7 @@ int ctc_graph_sum_backward(hipStream_t s, const GraphSeq* seqs, int n_seq, int m
                            float* visit) {
   if (n_seq <= 0) return OK;
   if (max_N < 1 || max_N > CTC_GRAPH_MAX_NODES) { set_error("ctc_graph_sum_backward: nodes out of range"); return E_ARG; }
-  const int npt = npt_for(max_N);
+  const int npt = ctc_graph_npt_for(max_N);
   const int threads = ctc_threads(max_N, npt);
   const int slots = max_N;
   const size_t lds = (size_t)2 * slots * sizeof(double);

@@ -14,8 +14,8 @@
 // ds_read_b128 touch 16 distinct 16-byte slots of the 256-byte bank row.
 // Out-of-range rows are clamped (their results are never stored); K tails are not supported here
 // (gemm.hip handles them).
-#include "common.h"
 #include "kernels.h"
+#include "wave_asm.h"      // hidden stores, LDS-DMA pieces, uniform_ptr, counted waits, pixel_swz: each explained there, once
 
 #include <cstdlib>
 #include <type_traits>
@@ -54,24 +54,6 @@ typedef __attribute__((ext_vector_type(16))) float f32x16_t;
 // C = act(a_scale * w_scale[n] * sum_k A8[m][k] W8[n][k] + bias[n]) ...; OutT = fp8_t divides by out_scale and saturates.
 typedef __attribute__((ext_vector_type(8))) int i32x8_t;
 
-// One 16-byte global store the compiler's waitcnt bookkeeping does not see (gemm2p_kernel's full-tile epilogue explains why).
-// s_nop 1: gfx950 wants TWO wait states between a store of more than 8 bytes and a VALU write of its data registers -- hipcc
-// places them for the stores it knows (one unrelated VALU instruction + s_nop 0 in its own code), its hazard recognizer does
-// not look into inline asm, and with one (s_nop 0) 0.11 % of the stored words carried the NEXT value of the register on a
-// busy chip (scripts/micro/store_hazard.hip, profiles/r04_store_hazard.txt; in the first form of this epilogue: 16-128
-// wrong elements per million in one kernel whose register allocation put a v_add / v_mad right behind a store).  An LDS
-// read into the same registers right behind the store is safe (0 of 2.7e8 words).
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-__device__ inline void store16_hidden(void* q, unsigned a, unsigned b, unsigned c, unsigned d) {
-  const u32x4_t v = {a, b, c, d};
-  asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(q), "v"(v) : "memory");
-}
-// ... and its 8-byte sibling (ACT_GLU: a lane's eight columns are four gated values)
-__device__ inline void store8_hidden(void* q, unsigned a, unsigned b) {
-  typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-  const u32x2_t v = {a, b};
-  asm volatile("global_store_dwordx2 %0, %1, off\n\ts_nop 1" ::"v"(q), "v"(v) : "memory");
-}
 // a * sigmoid(b) as glu_dw_kernel's bf16 staging computes it
 __device__ inline float glu_gate(float a, float b) { return a * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * b)); }
 
@@ -154,10 +136,8 @@ __global__ __launch_bounds__(512) void gemm2_kernel(GemmArgs p) {
       const int kh = kk / 3, kw = kk - kh * 3;
       koff = ((size_t)kh * p.cF1 + kw) * p.cC + cin;
     }
-    // eight 1-KiB LDS-DMA pieces (4 of A, 4 of W) in ONE asm statement: hipcc's waitcnt pass does not
-    // see them (it would otherwise drain vmcnt(0) before every ds_read that follows a DMA issue), so
-    // the explicit `s_waitcnt vmcnt(0)` at the top of the K loop is what orders them.  M0 carries the
-    // wave-uniform LDS destination; it is saved and restored because the compiler owns it.
+    // eight 1-KiB LDS-DMA pieces (4 of A, 4 of W) in ONE asm statement (wave_asm.h: why inline asm, and M0); the explicit
+    // wait_vm<0>() at the top of the K loop is what orders them
     const unsigned ldsA = lds_base + (unsigned)(buf * STAGE2 + (wave * 32) * ROW2);
     const T* pa0 = a_src[0] + koff; const T* pa1 = a_src[1] + koff; const T* pa2 = a_src[2] + koff; const T* pa3 = a_src[3] + koff;
     const size_t wk = (size_t)kt * BKE;
@@ -251,7 +231,7 @@ __global__ __launch_bounds__(512) void gemm2_kernel(GemmArgs p) {
     issue(0, 0);
     for (int kt = 0; kt < nk; ++kt) {
       const int cur = kt & 1;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces of stage kt have landed
+      wait_vm<0>();   // this wave's DMA pieces of stage kt have landed
       __syncthreads();                                   // ... and so have everybody else's
       if (kt + 1 < nk) issue(kt + 1, cur ^ 1);
       const char* st = smem + cur * STAGE2;
@@ -347,7 +327,7 @@ __global__ __launch_bounds__(512) void gemm2_kernel(GemmArgs p) {
       }
     };
     auto enter_stage = [&](int kt) __attribute__((always_inline)) {          // kt >= 1
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces of stage kt have landed
+      wait_vm<0>();   // this wave's DMA pieces of stage kt have landed
       __syncthreads();                                   // ... everybody's have; nobody reads stage kt-1 any more
       if (kt + 1 < nk) issue(kt + 1, (kt + 1) & 1);      // into the buffer stage kt-1 just left
     };
@@ -386,7 +366,7 @@ __global__ __launch_bounds__(512) void gemm2_kernel(GemmArgs p) {
             for (int r = 0; r < 4; ++r) acc[i][j][r] = *(const float*)(tb + (lr * 4 + r) * TROW + (j * 16 + (lane & 15)) * 4) * inv_alpha;
           __builtin_amdgcn_wave_barrier();
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // stage 0's DMA pieces
+        wait_vm<0>();      // stage 0's DMA pieces
       }
     }
     if (!res_acc) {
@@ -394,9 +374,9 @@ __global__ __launch_bounds__(512) void gemm2_kernel(GemmArgs p) {
       if (nk > 1) {
         issue(1, 1);
         stage1_issued = true;
-        asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // stage 0 (the older group of 8 pieces)
+        wait_vm<8>();   // stage 0 (the older group of 8 pieces)
       } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        wait_vm<0>();
       }
     }
     __syncthreads();
@@ -422,7 +402,7 @@ __global__ __launch_bounds__(512) void gemm2_kernel(GemmArgs p) {
     issue(0, 0);
     for (int kt = 0; kt < nk; ++kt) {
       const int cur = kt & 1;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's DMA pieces of tile kt have landed
+      wait_vm<0>();   // this wave's DMA pieces of tile kt have landed
       __syncthreads();                                   // ... and so have everybody else's
       const char* sA = smem + cur * STAGE2 + (wr * 128 + frow) * ROW2;
       const char* sB = smem + cur * STAGE2 + B2M * ROW2 + (wc * 64 + frow) * ROW2;
@@ -676,7 +656,7 @@ __global__ __launch_bounds__(512) void gemm2_kernel(GemmArgs p) {
     } else {
       run([](float x) { return x; });
     }
-    if (p.dbg && tid == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); p.dbg[blockIdx.x * 6 + 3] = wall_clock64(); }
+    if (p.dbg && tid == 0) { wait_vm<0>(); p.dbg[blockIdx.x * 6 + 3] = wall_clock64(); }
     return;
   }
   // unaligned output / residual rows: element-wise stores
@@ -783,32 +763,6 @@ extern int g_gemm2_flags;
 static constexpr int P_NSLOT = 7, P_HT = 128 * ROW2, P_LEAD = P_NSLOT - 2, P_DEPTH = P_LEAD - 2;
 static constexpr int P_SROW = 64 * 4 + 16;                        // padded fp32 slab row (bytes)
 static constexpr int GEMM2P_LDS = P_NSLOT * P_HT + 8 * 16 * P_SROW;
-
-__device__ inline void dma2(unsigned off0, unsigned off1, const void* sbase, unsigned lds0) {
-  // two 1-KiB LDS-DMA pieces (8 rows x 128 B each, consecutive in LDS) from scalar base + per-lane 32-bit offsets.
-  // Inline asm on purpose (see issue() above); M0 belongs to the compiler: saved and restored.
-  unsigned keep;
-  asm volatile(
-      "s_mov_b32 %0, m0\n\t"
-      "s_mov_b32 m0, %4\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %1, %3\n\t"
-      "s_add_u32 m0, m0, 0x400\n\t"
-      "s_nop 0\n\t"
-      "global_load_lds_dwordx4 %2, %3\n\t"
-      "s_mov_b32 m0, %0"
-      : "=&s"(keep)
-      : "v"(off0), "v"(off1), "s"(sbase), "s"(lds0)
-      : "memory", "scc");
-}
-template <int N> __device__ inline void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
-// a wave-uniform pointer, provably so for the "s" operand of dma2 (uniform values that went through a VALU division live
-// in VGPRs otherwise); folds away when the value already sits in SGPRs
-__device__ inline const char* uniform_ptr(const char* q) {
-  const unsigned long long v = (unsigned long long)q;
-  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-  return (const char*)(((unsigned long long)hi << 32) | lo);
-}
 
 // T = bf16_t: 16x16x32 MFMAs on 16x16 accumulator fragments.  T = fp8_t (OCP e4m3, RVB_FP8 mode): the same ring and phases
 // with twice the K per 128-byte row and v_mfma_scale_f32_32x32x64_f8f6f4 at unit block scales on 32x32 accumulator blocks
@@ -974,19 +928,19 @@ __global__ __launch_bounds__(512) void gemm2p_kernel(GemmArgs p) {
       if (k_rev) { t = nk - 1 - t; ak = (size_t)t * ROW2; }      // this tile walks K downwards (see k_rev)
     }
     const unsigned dst = __builtin_amdgcn_readfirstlane(lds_wave + slot * P_HT);
-    if constexpr (ty == 0) dma2(offA[0][0], offA[0][1], uniform_ptr(a_base + ak), dst);
-    else if constexpr (ty == 1) dma2(offW[0][0], offW[0][1], uniform_ptr(w_base + (size_t)t * ROW2), dst);
-    else if constexpr (ty == 2) dma2(offW[1][0], offW[1][1], uniform_ptr(w_base + (size_t)t * ROW2), dst);
-    else dma2(offA[1][0], offA[1][1], uniform_ptr(a_base + ak), dst);
+    if constexpr (ty == 0) lds_dma2(offA[0][0], offA[0][1], uniform_ptr(a_base + ak), dst);
+    else if constexpr (ty == 1) lds_dma2(offW[0][0], offW[0][1], uniform_ptr(w_base + (size_t)t * ROW2), dst);
+    else if constexpr (ty == 2) lds_dma2(offW[1][0], offW[1][1], uniform_ptr(w_base + (size_t)t * ROW2), dst);
+    else lds_dma2(offA[1][0], offA[1][1], uniform_ptr(a_base + ak), dst);
   };
   // the same for K step t2 (0 or 1) of the NEXT tile (PERSIST; no convolution: K step t2 sits at byte t2 * 128 of a row)
   auto stage_next = [&](auto tyc, int t2, int slot) __attribute__((always_inline)) {
     constexpr int ty = decltype(tyc)::value;
     const unsigned dst = __builtin_amdgcn_readfirstlane(lds_wave + slot * P_HT);
-    if constexpr (ty == 0) dma2(offA[0][0], offA[0][1], uniform_ptr(a_next + (size_t)t2 * ROW2), dst);
-    else if constexpr (ty == 1) dma2(offW[0][0], offW[0][1], uniform_ptr(w_next + (size_t)t2 * ROW2), dst);
-    else if constexpr (ty == 2) dma2(offW[1][0], offW[1][1], uniform_ptr(w_next + (size_t)t2 * ROW2), dst);
-    else dma2(offA[1][0], offA[1][1], uniform_ptr(a_next + (size_t)t2 * ROW2), dst);
+    if constexpr (ty == 0) lds_dma2(offA[0][0], offA[0][1], uniform_ptr(a_next + (size_t)t2 * ROW2), dst);
+    else if constexpr (ty == 1) lds_dma2(offW[0][0], offW[0][1], uniform_ptr(w_next + (size_t)t2 * ROW2), dst);
+    else if constexpr (ty == 2) lds_dma2(offW[1][0], offW[1][1], uniform_ptr(w_next + (size_t)t2 * ROW2), dst);
+    else lds_dma2(offA[1][0], offA[1][1], uniform_ptr(a_next + (size_t)t2 * ROW2), dst);
   };
   auto stage = [&](int h, int slot) __attribute__((always_inline)) {       // prologue only: K steps 0 and 1
     const int t = h >> 2, ty = h & 3;
@@ -1603,7 +1557,7 @@ __global__ __launch_bounds__(512) void gemm2p_kernel(GemmArgs p) {
     if (p.act == ACT_SILU) run([](float x) { return x * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * x)); });
     else if (p.act == ACT_RELU) run([](float x) { return fmaxf(x, 0.0f); });
     else run([](float x) { return x; });
-    if (p.dbg && tid == 0) { if (!has_next) asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); p.dbg[dbg_i * 6 + 3] = wall_clock64(); }
+    if (p.dbg && tid == 0) { if (!has_next) wait_vm<0>(); p.dbg[dbg_i * 6 + 3] = wall_clock64(); }
     return;
   }
   // unaligned output / residual rows: element-wise stores

@@ -189,6 +189,7 @@ enum { CTC_ALIGN_MAX_TOKENS = 16383,             // per lattice: 2 L + 1 = 32 76
 // launch shape of the one-workgroup-per-lattice kernels (Viterbi, forward, backward, graph): the states a thread owns for the largest
 // lattice of the batch, and the threads that cover n states (or nodes) at per_thread each: whole waves, 1024 at the most
 inline int ctc_spt_for(int S) { return S <= 4096 ? 4 : S <= 16384 ? 16 : 32; }
+inline int ctc_graph_npt_for(int N) { return N <= 1024 ? 1 : N <= 2048 ? 2 : N <= 4096 ? 4 : 8; }     // the graph kernels: nodes per thread
 inline int ctc_threads(int n, int per_thread) { const int t = ((n + per_thread - 1) / per_thread + 63) / 64 * 64; return t < 1024 ? t : 1024; }
 struct VitSeq {            // one lattice of a batch, as the kernels read it
   int L, S, T;             // tokens, states 2 L + 1, frames
@@ -226,6 +227,8 @@ struct GraphSeq {          // one lattice of a batch, as the kernels read it
   long long bp_off;        // bytes into bp
   long long bp_stride;     // bytes per frame: 1 byte per node, nodes padded to a multiple of 64
 };
+// an arc word (ctc_graph.hip, ctc_graph_score.hip; forward or transposed): LDS slot of the neighbour (0 = start) | its T may pass
+constexpr unsigned ARC_SLOT = 0x3fffu, ARC_T = 0x8000u;
 // advances every lattice over its frames [f0, f1), as ctc_viterbi_forward does; an arc word is (predecessor + 1) | 0x8000 when the
 // predecessor is a node of another label (its token state may enter).  max_N selects the instantiation and sizes the LDS.
 int ctc_graph_forward(hipStream_t s, const GraphSeq* seqs, int n_seq, int max_N, const float* lp, int ld, int r0, const int* rows,

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "kernels.h"
+#include "wave_asm.h"      // wait_vm, u32x4_t
 
 namespace rvb {
 
@@ -529,10 +530,8 @@ __device__ inline void mb_st64(void* p, unsigned long long v) {
 }
 __device__ inline double mb_ldf(const double* p) { return __longlong_as_double((long long)mb_ld64(p)); }
 __device__ inline void mb_stf(double* p, double v) { mb_st64(p, (unsigned long long)__double_as_longlong(v)); }
-__device__ inline void mb_stores_done() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 // 16-byte sc1 (agent-scope, past the L1) accesses: __hip_atomic_* stops at 8 bytes
-typedef unsigned mb_u32x4 __attribute__((ext_vector_type(4)));
-__device__ inline void mb_st128x4(void* p, mb_u32x4 a, mb_u32x4 b, mb_u32x4 c, mb_u32x4 d) {
+__device__ inline void mb_st128x4(void* p, u32x4_t a, u32x4_t b, u32x4_t c, u32x4_t d) {
   asm volatile(
       "global_store_dwordx4 %0, %1, off sc1\n\t"
       "global_store_dwordx4 %0, %2, off offset:16 sc1\n\t"
@@ -541,7 +540,7 @@ __device__ inline void mb_st128x4(void* p, mb_u32x4 a, mb_u32x4 b, mb_u32x4 c, m
       "s_nop 1"
       :: "v"(p), "v"(a), "v"(b), "v"(c), "v"(d) : "memory");
 }
-__device__ inline void mb_ld128x4(const void* p, mb_u32x4& a, mb_u32x4& b, mb_u32x4& c, mb_u32x4& d) {
+__device__ inline void mb_ld128x4(const void* p, u32x4_t& a, u32x4_t& b, u32x4_t& c, u32x4_t& d) {
   asm volatile(
       "global_load_dwordx4 %0, %4, off sc1\n\t"
       "global_load_dwordx4 %1, %4, off offset:16 sc1\n\t"
@@ -703,7 +702,7 @@ __global__ __launch_bounds__(MB_NT) void linkage_mb_kernel(double* __restrict__ 
         // this round, loads the data words, reduces and hands the result to the other waves through LDS: one L2 round trip less
         // than {arrive at a counter, poll the counter, every wave loads the entries} (the all-waves polling variant lost to its
         // 256 pollers; this one has as many pollers as the counter has).
-        mb_stores_done();
+        wait_vm<0>();
         ++gen;
         __syncthreads();
         if (tid < 64 && xchg16) {
@@ -714,12 +713,12 @@ __global__ __launch_bounds__(MB_NT) void linkage_mb_kernel(double* __restrict__ 
             const int nbx = lv.v < INFINITY ? s_nb[li_of(lv.i)] : -1;
             const unsigned long long v0 = (unsigned long long)__double_as_longlong(lv.v), v2 = (unsigned long long)__double_as_longlong(ls.v),
                                      v3 = (unsigned long long)__double_as_longlong(part.v);
-            mb_st128x4(&ctl->ent16[gen & 1][b], (mb_u32x4){(unsigned)v0, (unsigned)(v0 >> 32), (unsigned)lv.i, gen},
-                       (mb_u32x4){(unsigned)nbx, (unsigned)ls.i, (unsigned)part.i, gen}, (mb_u32x4){(unsigned)v2, (unsigned)(v2 >> 32), 0u, gen},
-                       (mb_u32x4){(unsigned)v3, (unsigned)(v3 >> 32), 0u, gen});
+            mb_st128x4(&ctl->ent16[gen & 1][b], (u32x4_t){(unsigned)v0, (unsigned)(v0 >> 32), (unsigned)lv.i, gen},
+                       (u32x4_t){(unsigned)nbx, (unsigned)ls.i, (unsigned)part.i, gen}, (u32x4_t){(unsigned)v2, (unsigned)(v2 >> 32), 0u, gen},
+                       (u32x4_t){(unsigned)v3, (unsigned)(v3 >> 32), 0u, gen});
           }
           const LkEntry16* e = &ctl->ent16[gen & 1][lane & (G - 1)];
-          mb_u32x4 p0, p1, p2, p3;
+          u32x4_t p0, p1, p2, p3;
           unsigned spins = 0;
           for (;;) {
             mb_ld128x4(e, p0, p1, p2, p3);
@@ -751,7 +750,7 @@ __global__ __launch_bounds__(MB_NT) void linkage_mb_kernel(double* __restrict__ 
             mb_stf(&e->st_v, ls.v);
             mb_stf(&e->part_v, part.v);
             mb_st64(&e->part_z, (unsigned long long)(unsigned)part.i);
-            mb_stores_done();
+            wait_vm<0>();
             mb_st64(&e->st_z, (unsigned long long)(unsigned)ls.i | ((unsigned long long)gen << 32));
           }
           const LkEntry* e = &ctl->ent[gen & 1][lane & (G - 1)];
@@ -799,7 +798,7 @@ __global__ __launch_bounds__(MB_NT) void linkage_mb_kernel(double* __restrict__ 
         mb_stf(&e->part_v, part.v);
         mb_st64(&e->part_z, (unsigned long long)(unsigned)part.i);
       }
-      mb_stores_done();                                     // the merge pass's stores to D and the entry: acknowledged by the L2
+      wait_vm<0>();                                     // the merge pass's stores to D and the entry: acknowledged by the L2
       ++gen;
       if (!mb_grid_barrier(ctl, gen, G, &s_flag)) {
         if (b == 0 && tid == 0) g_min_dist[n - 1] = -2.0;
@@ -902,7 +901,7 @@ __global__ __launch_bounds__(MB_NT) void linkage_mb_kernel(double* __restrict__ 
         best = min_pair(best, MinPair{nd, z});
       }
     }
-    if constexpr (MB_EAGER > 0) mb_stores_done();           // the rescans below read what this pass wrote (own rows)
+    if constexpr (MB_EAGER > 0) wait_vm<0>();           // the rescans below read what this pass wrote (own rows)
     if constexpr (MB_EAGER > 0) part = block_argmin_alt(best, red, rphase);             // (barrier inside: the list is complete)
     else part = best;                                       // reduced together with the next round's local minima (block_argmin3_alt)
     if constexpr (MB_EAGER > 0) {
