@@ -329,6 +329,34 @@ int rvb_ctc_align_wild(rvb_engine* e, const int32_t* tokens, const int32_t* tok_
                        const int32_t* n_chunks, float wildcard_bias, int32_t* labels, int32_t* begin, int32_t* end, int32_t* peak,
                        float* confidence, float* score);
 
+/* LONG-FORM alignment: ONE transcript of any number of tokens over a recording that is encoded in several batches (a WINDOWED
+ * Viterbi, csrc/ctc_viterbi_window.hip).  At every frame only W consecutive states of the lattice are alive, the window; it follows
+ * the best partial path, moves only between kernel launches and never back.  With W >= 2 n_tokens + 1 it never moves and every
+ * output is rvb_ctc_align_wild's, bit for bit; otherwise the result is the best path among those that stay inside the windows, and
+ * min_margin tells how close that path came to a window edge (in states; an edge that is the lattice's own does not count; W when
+ * none counts).  A margin of 0 says the true path may have been cut off: align again with a wider window.
+ *   begin   tokens may hold RVB_CTC_WILDCARD (wildcard_bias finite and <= 0, as for rvb_ctc_align_wild).  total_frames = the valid
+ *           encoder frames of ALL batches to come (<= RVB_CTC_ALIGN_MAX_FRAMES, RVB_E_UNSUPPORTED above).  window_states: 0 (the
+ *           default, 32 768 = 16 384 tokens) or a multiple of 256 in [256, 32768]; reduced to the lattice rounded up to 32 states.
+ *           Refusals in rvb_ctc_align's words, all before any device work; no token cap beyond n_tokens + repeats <= total_frames.
+ *           Back-pointers take total_frames x W / 4 bytes (RVB_E_NOMEM naming them).  begin while a lattice is open replaces it.
+ *   feed    after rvb_encode: every valid frame of every chunk of the encoded batch, in order, continues the lattice (the log-probs
+ *           are recomputed in the slabs rvb_encode used, as rvb_ctc_align does).  RVB_E_STATE before begin, before rvb_encode, or
+ *           when the batch holds more frames than the lattice has left.  rvb_ctc_align*, _score and _find stay usable in between.
+ *   finish  RVB_E_STATE unless exactly total_frames were fed.  labels [total_frames], begin / end [n_tokens] as rvb_ctc_align
+ *           defines them over the whole lattice, score, min_margin (each nullable).  RVB_E_ARG "infeasible: no path inside the
+ *           window ..." when the score is -inf; outputs are then untouched.
+ *   emissions  lp[t][labels[t]] of the valid frames of the encoded batch (n_frames of them; a RVB_CTC_WILDCARD frame: the row
+ *           maximum), for peaks and confidences: encode the batches a second time and pass each its part of finish's labels.
+ *   end     releases the buffers. */
+int rvb_ctc_align_long_limits(int32_t* max_frames, int32_t* max_window_states, int32_t* default_window_states);
+int rvb_ctc_align_long_begin(rvb_engine* e, const int32_t* tokens, int n_tokens, int64_t total_frames, int window_states,
+                             float wildcard_bias);
+int rvb_ctc_align_long_feed(rvb_engine* e);
+int rvb_ctc_align_long_finish(rvb_engine* e, int32_t* labels, int32_t* begin, int32_t* end, float* score, int32_t* min_margin);
+int rvb_ctc_align_long_emissions(rvb_engine* e, const int32_t* labels, int n_frames, float* emit_out);
+int rvb_ctc_align_long_end(rvb_engine* e);
+
 /* rvb_ctc_align_wild for a transcript with ALTERNATIVES and OPTIONAL words: each sequence is a left-to-right token GRAPH, and one
  * Viterbi pass (csrc/ctc_graph.hip) picks the reading that was spoken and aligns it.  Sequence i has n_nodes[i] >= 1 nodes in
  * topological order (node_tokens, is_final: concatenated over the sequences).  Node j has a label (a vocab id other than the blank,
@@ -568,7 +596,7 @@ int rvb_comm_destroy(rvb_engine* e);
 /* Stage timing (HIP events on the engine stream).  level 1: every kernel family is bracketed;
  * names: "fbank","subsample","gemm","attention","rownorm","glu_dwconv","ctc_topk","embed",
  * "lse_gather" (the row kernel after the decoders' output layer: rescoring and rvb_attention_score),"search_host","ctc_align_lp" (rvb_ctc_align: CTC head + log-softmax),"ctc_viterbi" (its
- * forward pass + back-trace),"ctc_forward" / "ctc_backward" (rvb_ctc_score: the two sweeps),"ctc_graph_forward" / "ctc_graph_backward" (rvb_ctc_score_graph: the two sweeps),"ctc_find" (rvb_ctc_find: the search kernel),"ctc_graph" (rvb_ctc_align_graph:
+ * forward pass + back-trace),"ctc_viterbi_window" (rvb_ctc_align_long_feed / _finish: the windowed launches with their readbacks + back-trace),"ctc_forward" / "ctc_backward" (rvb_ctc_score: the two sweeps),"ctc_graph_forward" / "ctc_graph_backward" (rvb_ctc_score_graph: the two sweeps),"ctc_find" (rvb_ctc_find: the search kernel),"ctc_graph" (rvb_ctc_align_graph:
  * forward pass + back-trace).  level 2: only the GEMM launches (the dominant kernel; half the
  * events, ~1 % less perturbation of the step).  level 0: off.
  * flops: algorithmic FLOPs launched (gemm/attention only). */

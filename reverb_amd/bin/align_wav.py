@@ -6,7 +6,9 @@ attention decoders' loss_att and acc_att and the combined loss.  --wildcard TOKE
 transcribed: the aligner gives each marker the frames the rest of the transcript does not explain (at least one), and the marker
 shows up in the result as a word / label / token of its own.  --alternatives reads choices and optional words in the transcript,
 `it is {twenty|two zero} [um] goodbye`, and aligns the reading that was spoken; with --graph_score, `<audio>.score.json` holds the
-full-sum log-likelihood over ALL readings and the probability of every word run of the transcript.  Praat .lab / TextGrid output (--gen_praat there) is not written."""
+full-sum log-likelihood over ALL readings and the probability of every word run of the transcript.  A file of more than --max_chunks
+chunks, or a transcript of more than 16 383 tokens, is aligned over several device batches with a windowed lattice (--long_form forces
+it, --window_tokens N sets the window; ReverbASR.align).  Praat .lab / TextGrid output (--gen_praat there) is not written."""
 from __future__ import annotations
 
 import argparse
@@ -47,7 +49,17 @@ def get_args(argv=None):
                    help="with --alternatives (no --wildcard): also write <audio>.score.json, the full-sum score over all readings and "
                         "the probability, occupancy and mean_time of every word run")
     p.add_argument("--reverse_weight", type=float, default=None, help="weight of the right-to-left decoder in loss_att (default: the config's)")
+    p.add_argument("--long_form", action="store_true",
+                   help="align over several device batches with a windowed lattice (taken by itself when the file has more than "
+                        "--max_chunks chunks or more than 16383 tokens)")
+    p.add_argument("--window_tokens", type=int, default=None, metavar="N",
+                   help="long form: tokens of the transcript alive at a frame (default and most: 16384); the json result carries "
+                        "window_margin, how close the path came to the window's edge")
     args = p.parse_args(argv)
+    if (args.long_form or args.window_tokens is not None) and (args.score or args.posteriors or args.alternatives):
+        p.error("--long_form / --window_tokens: --score, --posteriors and --alternatives stay within one device batch")
+    if args.window_tokens is not None and args.window_tokens < 1:
+        p.error("--window_tokens must be at least 1")
     if args.wildcard is not None and (args.score or args.posteriors):
         p.error("--wildcard: the full-sum score (--score, --posteriors) is not defined for a transcript with gaps")
     if args.alternatives and (args.score or args.posteriors):
@@ -79,7 +91,8 @@ def main(argv=None):
     out = reverb.align(args.audio_file, transcript=transcript, format=args.format, verbatimicity=args.verbatimicity,
                        chunk_size=args.chunk_size, timings_adjustment=args.timings_adjustment,
                        posteriors=args.posteriors and args.format == "json", wildcard=args.wildcard,
-                       wildcard_bias=args.wildcard_bias, alternatives=args.alternatives)
+                       wildcard_bias=args.wildcard_bias, alternatives=args.alternatives, window_tokens=args.window_tokens,
+                       long_form=True if args.long_form or args.window_tokens is not None else None)
     if args.format == "json":
         out = json.dumps(out, ensure_ascii=False, indent=1)
     os.makedirs(args.result_dir, exist_ok=True)

@@ -249,6 +249,35 @@ struct CtcFinder {
   void release();
 };
 
+// ---- long-form alignment (ctc_viterbi_window.hip): ONE lattice of any number of tokens whose frames arrive over several encoded
+// batches, shared by rvb_ctc_align_long_* and the lab hook.  Only W consecutive states are alive at a frame (the window); the
+// window moves between launches, placed by ctc_window_next_lo from the best state the launch before reported.
+// plan() validates in CtcAligner::plan's words (no token cap beyond L <= frames; no device work), begin() allocates (E_NOMEM naming
+// the back-pointer bytes) and sets alpha to -inf, batch() takes the log-prob rows of the next frames (one encoded batch), advance()
+// runs the kernel over the frames of the batch whose rows lie in the slab (slabs in row order; launches of at most W / 4 frames),
+// finish() back-traces: states, score and the path's smallest distance to a window edge that is not the lattice's own.
+enum { CTC_WINDOW_MAX_STATES = 32768, CTC_WINDOW_DEFAULT_STATES = 32768 };
+// the window of the launch over frames [f0, f1), given the window before and the first-maximum state of the last frame (-1: none)
+int ctc_window_next_lo(int S, int T, int W, int f0, int f1, int lo_prev, int best_prev);
+struct CtcWindowAligner {
+  int L = 0, S = 0, S_pad = 0, T = 0, W = 0, blank = 0;
+  bool has_wild = false, open = false;
+  float bias = 0.f;
+  std::vector<int32_t> h_tokens, h_rows;           // h_rows: the rows of the batch being fed, its first frame is lattice frame fbase
+  int fed = 0, fbase = 0;                          // lattice frames advanced so far
+  int lo = 0, best = -1;                           // the last launch's window and the best state it reported
+  size_t bp_bytes = 0;
+  DevBuf d_tokens, d_rows, d_alpha, d_bp, d_lo, d_best, d_states, d_end;
+  int plan(const char* who, const int32_t* tokens, int n_tokens, int64_t total_frames, int window_states, int V, int blank_id,
+           bool allow_wild, float wildcard_bias);
+  int begin(hipStream_t s);
+  int batch(hipStream_t s, const std::vector<int32_t>& rows);
+  bool touches(int r0, int nrows) const;
+  int advance(hipStream_t s, const float* lp, int ld, int r0, int nrows, const float* wmax = nullptr);
+  int finish(hipStream_t s, int32_t* states /* [T] */, float* score, int32_t* min_margin, int32_t* lo_out = nullptr /* [T] */);
+  void release();
+};
+
 }  // namespace rvb
 
 struct rvb_engine {
@@ -366,6 +395,7 @@ struct rvb_engine {
   rvb::CtcFinder finder;           // rvb_ctc_find
   rvb::CtcGraphAligner graph_aligner;   // rvb_ctc_align_graph
   rvb::CtcGraphScorer graph_scorer;     // rvb_ctc_score_graph
+  rvb::CtcWindowAligner long_aligner;   // rvb_ctc_align_long_*: its own member, so the calls above stay usable between begin and finish
   rvb::DevBuf align_lp, align_tv, align_ti, align_row, align_col, align_out;   // fp32 [LOGIT_SLAB][V] log-softmax slab; gather scratch
 
   // ---- RCCL communicator of the C-ABI collectives (comm.hip; optional) ----

@@ -216,6 +216,108 @@ int rvb_ctc_align_wild(rvb_engine* e, const int32_t* tokens, const int32_t* tok_
                         end, peak, confidence, score);
 }
 
+// Long-form alignment (ctc_viterbi_window.hip): one lattice over several encoded batches.  feed sweeps the slabs of the encoded batch
+// exactly as align_sweep does (align_slabs, then align_slab per slab: the log-prob bits the searches saw) and hands each to the
+// windowed driver, which is a member of its own: the calls above and below stay usable between begin and finish.
+static void long_batch_rows(const rvb_engine* e, std::vector<int32_t>* rows) {
+  rows->clear();
+  for (int c = 0; c < e->B; ++c)
+    for (int t = 0; t < e->enc_lens[c]; ++t) rows->push_back(c * e->T2 + t);
+}
+
+int rvb_ctc_align_long_limits(int32_t* max_frames, int32_t* max_window_states, int32_t* default_window_states) {
+  if (max_frames) *max_frames = CTC_ALIGN_MAX_FRAMES;
+  if (max_window_states) *max_window_states = CTC_WINDOW_MAX_STATES;
+  if (default_window_states) *default_window_states = CTC_WINDOW_DEFAULT_STATES;
+  return OK;
+}
+
+int rvb_ctc_align_long_begin(rvb_engine* e, const int32_t* tokens, int n_tokens, int64_t total_frames, int window_states,
+                             float wildcard_bias) {
+  const char* who = "rvb_ctc_align_long_begin";
+  if (!e) { set_error("rvb_ctc_align_long_begin: null engine"); return E_ARG; }
+  CtcWindowAligner& al = e->long_aligner;
+  al.open = false;                                 // begin while a lattice is open replaces it, also when this one is refused
+  RVB_TRY(al.plan(who, tokens, n_tokens, total_frames, window_states, e->cfg.vocab, e->cfg.blank_id, true, wildcard_bias));
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  return al.begin(e->stream);
+}
+
+int rvb_ctc_align_long_feed(rvb_engine* e) {
+  if (!e) { set_error("rvb_ctc_align_long_feed: null engine"); return E_ARG; }
+  CtcWindowAligner& al = e->long_aligner;
+  if (!al.open) { set_error("rvb_ctc_align_long_feed before rvb_ctc_align_long_begin"); return E_STATE; }
+  if (e->B <= 0) { set_error("rvb_ctc_align_long_feed before rvb_encode"); return E_STATE; }
+  std::vector<int32_t> rows;
+  long_batch_rows(e, &rows);
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(al.batch(e->stream, rows));              // E_STATE when the batch holds more frames than the lattice has left
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
+  return sweep_slabs(e, slabs, false, "ctc_viterbi_window", al, [&](int r0, int nrows) {
+    return al.advance(e->stream, e->align_lp.as<float>(), e->cfg.vocab, r0, nrows, e->align_tv.as<float>());
+  });
+}
+
+int rvb_ctc_align_long_finish(rvb_engine* e, int32_t* labels, int32_t* begin, int32_t* end, float* score, int32_t* min_margin) {
+  if (!e) { set_error("rvb_ctc_align_long_finish: null engine"); return E_ARG; }
+  CtcWindowAligner& al = e->long_aligner;
+  if (!al.open) { set_error("rvb_ctc_align_long_finish before rvb_ctc_align_long_begin"); return E_STATE; }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  std::vector<int32_t> states((size_t)al.T);
+  {
+    Scope sc(e, "ctc_viterbi_window");
+    RVB_TRY(al.finish(e->stream, states.data(), score, min_margin));
+  }
+  if (labels)
+    for (int t = 0; t < al.T; ++t) labels[t] = (states[t] & 1) ? al.h_tokens[states[t] >> 1] : e->cfg.blank_id;
+  if (begin || end) {
+    const std::vector<float> no_emit;
+    run_outputs(states, no_emit, 0, al.T, [](int st) { return (st & 1) ? (st >> 1) : -1; }, begin, end, nullptr, nullptr);
+  }
+  return OK;
+}
+
+int rvb_ctc_align_long_emissions(rvb_engine* e, const int32_t* labels, int n_frames, float* emit_out) {
+  const char* who = "rvb_ctc_align_long_emissions";
+  if (!e) { set_error("rvb_ctc_align_long_emissions: null engine"); return E_ARG; }
+  if (!labels || !emit_out) { set_error("rvb_ctc_align_long_emissions: null argument"); return E_ARG; }
+  if (e->B <= 0) { set_error("rvb_ctc_align_long_emissions before rvb_encode"); return E_STATE; }
+  std::vector<int32_t> rows;
+  long_batch_rows(e, &rows);
+  if (n_frames != (int)rows.size()) {
+    set_error(std::string(who) + ": n_frames " + std::to_string(n_frames) + " is not the " + std::to_string(rows.size()) +
+              " valid frames of the encoded batch");
+    return E_ARG;
+  }
+  bool has_wild = false;
+  for (int t = 0; t < n_frames; ++t) {
+    if (labels[t] == RVB_CTC_WILDCARD) { has_wild = true; continue; }
+    if (labels[t] < 0 || labels[t] >= e->cfg.vocab) {
+      set_error(std::string(who) + ": label " + std::to_string(labels[t]) + " of frame " + std::to_string(t) + " outside [0, " +
+                std::to_string(e->cfg.vocab) + ")");
+      return E_ARG;
+    }
+  }
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
+  VitSeq q{};
+  q.T = n_frames;
+  const std::vector<VitSeq> seq(1, q);
+  const std::vector<int32_t> lab(labels, labels + n_frames);
+  std::vector<float> emit;
+  RVB_TRY(align_emissions(e, slabs, seq, rows, lab, has_wild, &emit));
+  memcpy(emit_out, emit.data(), (size_t)n_frames * 4);
+  return OK;
+}
+
+int rvb_ctc_align_long_end(rvb_engine* e) {
+  if (!e) { set_error("rvb_ctc_align_long_end: null engine"); return E_ARG; }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  e->long_aligner.release();
+  return OK;
+}
+
 // Alignment over token graphs (ctc_graph.hip): the slabs, the wildcard's emission and the second sweep for the confidences are those
 // of ctc_align_impl; what differs is the lattice and that the per-token outputs follow the chosen path.
 int rvb_ctc_align_graph_limits(int32_t* max_nodes, int32_t* max_in_degree, int32_t* max_arcs, int32_t* max_frames) {

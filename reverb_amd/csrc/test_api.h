@@ -188,6 +188,17 @@ int rvb_test_ctc_viterbi(const float* lp, int T, int V, const int32_t* tokens, i
  * rvb_test_ctc_viterbi refuses, and a bias that is positive or not finite, before any device work; outputs untouched. */
 int rvb_test_ctc_viterbi_wild(const float* lp, int T, int V, const float* w, float bias, const int32_t* tokens, int L, int blank,
                               int slab_rows, int32_t* labels_out, float* score_out);
+/* ctc_viterbi_window.hip: the windowed kernels and the driver rvb_ctc_align_long_* runs, over host log-probs fed slab_rows frames at
+ * a time (each slab cut into launches of at most W / 4 frames).  w == NULL: no wildcard (the plain kernels; RVB_CTC_WILDCARD is then
+ * an id outside the vocabulary); w given: the WILD kernels, whether or not a token is a wildcard.  window_states: 0 or a multiple of 256 in [256, 32768], reduced to S rounded up to 32.  lo_out[T]:
+ * the first state of each frame's window; min_margin_out: the path's smallest distance to a window edge that is not the lattice's
+ * own (W when no frame counts).  Refuses before any device work, outputs untouched, what rvb_test_ctc_viterbi_wild refuses (no token
+ * cap) and a bad window_states; a path that does not exist inside the windows is refused after the pass. */
+int rvb_test_ctc_viterbi_window(const float* lp, int T, int V, const float* w, float bias, const int32_t* tokens, int L, int blank,
+                                int slab_rows, int window_states, int32_t* labels_out, float* score_out, int32_t* lo_out,
+                                int32_t* min_margin_out);
+/* the host-only window policy (engine.h ctc_window_next_lo) */
+int rvb_test_ctc_window_next_lo(int S, int T, int W, int f0, int f1, int lo_prev, int best_prev);
 /* ctc_graph.hip: alignment of n_seq token graphs (arguments as rvb_ctc_align_graph) over host log-probs with the kernels
  * rvb_ctc_align_graph runs: lp is the lattices' frames concatenated ([sum T][V]), w [sum T] the wildcard's emission less the bias
  * (nullable when no node is a wildcard), slab_rows frames per launch (a slab may end inside a lattice or span several).

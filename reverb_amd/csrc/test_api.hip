@@ -646,6 +646,46 @@ int rvb_test_ctc_viterbi_wild(const float* lp, int T, int V, const float* w, flo
   return ctc_viterbi_lab("rvb_test_ctc_viterbi_wild", true, lp, T, V, w, bias, tokens, L, blank, slab_rows, labels_out, score_out);
 }
 
+int rvb_test_ctc_viterbi_window(const float* lp, int T, int V, const float* w, float bias, const int32_t* tokens, int L, int blank,
+                                int slab_rows, int window_states, int32_t* labels_out, float* score_out, int32_t* lo_out,
+                                int32_t* min_margin_out) {
+  const char* who = "rvb_test_ctc_viterbi_window";
+  const std::string me(who);
+  if (!lp || !tokens || !labels_out || !score_out || !lo_out || !min_margin_out) { set_error(me + ": null argument"); return E_ARG; }
+  if (T < 1 || slab_rows < 1) { set_error(me + ": need T >= 1 and slab_rows >= 1"); return E_ARG; }
+  CtcWindowAligner al;
+  RVB_TRY(al.plan(who, tokens, L, T, window_states, V, blank, w != nullptr, bias));
+  al.has_wild = w != nullptr;                      // w selects the WILD kernels, whether or not a token is a wildcard
+  RVB_TRY(need_gpu());
+  Dev dlp, dw;
+  std::vector<int32_t> rows((size_t)T), states((size_t)T), los((size_t)T);
+  for (int t = 0; t < T; ++t) rows[t] = t;
+  float score = 0.f;
+  int32_t margin = 0;
+  int r = up_raw(dlp, lp, (size_t)T * V * 4);
+  if (r == OK) r = up_raw(dw, w, (size_t)T * 4);
+  if (r == OK) r = al.begin(nullptr);
+  if (r == OK) r = al.batch(nullptr, rows);
+  r = feed_slabs(r, T, slab_rows, false, [&](int r0, int n) {
+    return al.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, n, w ? (const float*)dw.p + r0 : nullptr);
+  });
+  if (r == OK) r = al.finish(nullptr, states.data(), &score, &margin, los.data());
+  if (r != OK) (void)hipDeviceSynchronize();
+  al.release();
+  RVB_TRY(r);
+  *score_out = score;
+  *min_margin_out = margin;
+  for (int t = 0; t < T; ++t) {
+    labels_out[t] = (states[t] & 1) ? tokens[states[t] >> 1] : blank;
+    lo_out[t] = los[t];
+  }
+  return OK;
+}
+
+int rvb_test_ctc_window_next_lo(int S, int T, int W, int f0, int f1, int lo_prev, int best_prev) {
+  return ctc_window_next_lo(S, T, W, f0, f1, lo_prev, best_prev);
+}
+
 int rvb_test_ctc_viterbi_graph(const float* lp, const int32_t* T, int n_seq, int V, const float* w, float bias, const int32_t* node_tokens,
                                const int32_t* n_nodes, const int32_t* pred_off, const int32_t* preds, const uint8_t* is_final, int blank,
                                int slab_rows, int32_t* labels_out, int32_t* frame_node_out, float* score_out) {

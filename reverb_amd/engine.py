@@ -621,6 +621,44 @@ class Engine:
             t0 += n; f0 += frames[i]
         return out
 
+    # ---- long-form alignment (rvb_ctc_align_long_*, csrc/ctc_viterbi_window.hip): one transcript over several encoded batches
+    def align_long_begin(self, tokens, total_frames, window_states=0, wildcard_bias=0.0):
+        """Open ONE lattice of `tokens` (ids; ctc_align.WILDCARD allowed) over total_frames valid encoder frames, which the encoded
+        batches to come deliver through align_long_feed().  window_states: 0 (the default, 32 768) or a multiple of 256 in
+        [256, 32768]: the states alive at a frame.  -> the window in use (reduced to the lattice rounded up to 32 states)."""
+        tok = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+        self._long_tokens = tok.tolist()
+        self._long_frames = int(total_frames)
+        check(self.lib.rvb_ctc_align_long_begin(self.handle, iptr(tok if tok.size else np.zeros(1, np.int32)), int(tok.size),
+                                                int(total_frames), int(window_states), float(wildcard_bias)), "rvb_ctc_align_long_begin")
+        return min(int(window_states) or 32768, (2 * tok.size + 1 + 31) // 32 * 32)
+
+    def align_long_feed(self):
+        """After encode(): every valid frame of the encoded batch, in chunk order, continues the lattice."""
+        check(self.lib.rvb_ctc_align_long_feed(self.handle), "rvb_ctc_align_long_feed")
+
+    def align_long_finish(self):
+        """-> (labels [total_frames], begin [tokens], end [tokens], score, min_margin) once every frame was fed; min_margin is the
+        path's smallest distance, in states, to a window edge that is not the lattice's own (the window when no frame counts)."""
+        n = getattr(self, "_long_frames", 0)
+        nt = len(getattr(self, "_long_tokens", []))
+        labels = np.empty(max(n, 1), np.int32)
+        begin, end = np.empty(max(nt, 1), np.int32), np.empty(max(nt, 1), np.int32)
+        score, margin = np.empty(1, np.float32), np.empty(1, np.int32)
+        check(self.lib.rvb_ctc_align_long_finish(self.handle, iptr(labels), iptr(begin), iptr(end), fptr(score), iptr(margin)),
+              "rvb_ctc_align_long_finish")
+        return labels[:n], begin[:nt], end[:nt], float(score[0]), int(margin[0])
+
+    def align_long_emissions(self, labels):
+        """lp[t][labels[t]] of the valid frames of the encoded batch (a WILDCARD frame: the row maximum) -> fp32 [frames]"""
+        lab = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        out = np.empty(max(lab.size, 1), np.float32)
+        check(self.lib.rvb_ctc_align_long_emissions(self.handle, iptr(lab), int(lab.size), fptr(out)), "rvb_ctc_align_long_emissions")
+        return out[:lab.size]
+
+    def align_long_end(self):
+        check(self.lib.rvb_ctc_align_long_end(self.handle), "rvb_ctc_align_long_end")
+
     def align_graph(self, graphs, chunk_ranges=None, wildcard_bias=0.0):
         """align_wild() for transcripts with alternatives and optional words (rvb_ctc_align_graph, csrc/ctc_graph.hip): each sequence
         is a token_graph.TokenGraph, and one Viterbi pass picks the reading that was spoken and aligns it.  -> List[AlignResult]

@@ -28,6 +28,7 @@ from .search import DecodeResult
 from .tokenizer import RevBpeTokenizer
 from . import audio
 
+ALIGN_MAX_TOKENS = 16383          # RVB_CTC_ALIGN_MAX_TOKENS: what one workgroup's lattice holds; above it align() takes the long path
 _FRAME_DOWNSAMPLING_FACTOR = {"linear": 1, "conv2d": 4, "conv2d6": 6, "conv2d8": 8}
 CACHED_MODELS_DIR = Path.home() / ".cache/reverb"
 _MODELS = {"reverb_asr_v1": "https://huggingface.co/Revai/reverb-asr"}
@@ -283,7 +284,8 @@ class ReverbASR:
 
     def align(self, audio_file, transcript: Optional[str] = None, tokens=None, format: str = "ctm", verbatimicity: float = 1.0,
               chunk_size: int = 2051, timings_adjustment: float = 230, posteriors: bool = False, wildcard: Optional[str] = None,
-              wildcard_bias: float = 0.0, alternatives: bool = False):
+              wildcard_bias: float = 0.0, alternatives: bool = False, window_tokens: Optional[int] = None,
+              long_form: Optional[bool] = None):
         """Forced alignment of a KNOWN transcript (the reference's bin/alignment.py -> force_align, utils/ctc_utils.py:105-161): exactly
         one of `transcript` (text, tokenised with the model's tokenizer) or `tokens` (ids).  The whole file is encoded as
         transcribe_modes does and the transcript aligned as ONE sequence over all chunks.  format: "ctm" / "txt" (through get_output,
@@ -301,7 +303,16 @@ class ReverbASR:
         shows the chosen reading; json adds "text" (that reading) and "node" (the graph node) per token.  tokens= is refused: a
         graph is written as text.  With posteriors=True (json, no wildcard in the text: the full-sum score has none) each token of the
         chosen path also carries its node's probability (Engine.score_graph's visit: the posterior of the readings through that
-        node), occupancy, mean_time and peak_posterior of the full sum over ALL readings."""
+        node), occupancy, mean_time and peak_posterior of the full sum over ALL readings.
+        Recordings of any length.  A file of at most max_chunks chunks and 16 383 tokens is aligned as one encoded batch, exactly.
+        A longer one (long_form=None), or any file with long_form=True, takes the LONG path: the file is encoded batch by batch and
+        ONE lattice continues over the batches (Engine.align_long_*), in which only a window of 2 window_tokens states (rounded up to
+        256; default and most: 16 384 tokens = 32 768 states) is alive and follows the best partial path.  A window that holds
+        the whole transcript gives the exact alignment; otherwise the result is the best path inside the windows, json carries
+        "window_states" and "window_margin" (the path's smallest distance to a window edge, in states), and a margin below 64 logs
+        a warning: align again with a larger window_tokens.  ctm and json encode the file a second time for the confidences.
+        wildcard= works on the long path; alternatives=True and posteriors=True stay one-batch (ValueError on a file that needs
+        the long path).  long_form=False insists on the one-batch path."""
         from .ctc_align import WILDCARD, DecodeLike, align_to_ali, align_to_json, posteriors_to_json, split_by_chunk, split_transcript
         if (transcript is None) == (tokens is None):
             raise ValueError("align: give exactly one of transcript= (text) or tokens= (ids)")
@@ -326,7 +337,29 @@ class ReverbASR:
                 raise ValueError("align: posteriors come from the full-sum score, which has no wildcards")
             if tokens is None:
                 tokens = split_transcript(transcript, wildcard, lambda text: self.tokenizer.tokenize(text)[1])
-        eng, ids, n_chunks = self._encode_for_align("align", audio_file, transcript, tokens, verbatimicity, chunk_size)
+        if window_tokens is not None and int(window_tokens) < 1:
+            raise ValueError("align: window_tokens must be at least 1")
+        eng, ids, n_frames, n_chunks = self._prepare_for_align(audio_file, transcript, tokens, verbatimicity, chunk_size)
+        fits = n_chunks <= eng.cfg.max_chunks and len(ids) <= ALIGN_MAX_TOKENS
+        if long_form or (long_form is None and not fits):
+            if alternatives or posteriors:
+                raise ValueError("align: alternatives=True and posteriors=True stay one-batch (graphs and full-sum scores do not span "
+                                 f"encoded batches): the file has {n_chunks} chunks of {chunk_size} frames and {len(ids)} tokens, one "
+                                 f"batch holds {eng.cfg.max_chunks} chunks and {ALIGN_MAX_TOKENS} tokens"
+                                 + (" -- or drop long_form=True" if fits else " -- load the model with a larger max_chunks"))
+            res, window, margin = self._align_long(eng, ids, n_frames, n_chunks, chunk_size, window_tokens,
+                                                   wildcard_bias if wildcard is not None else 0.0, format in ("ctm", "json"))
+            name = Path(audio_file).name
+            if format == "ali":
+                return align_to_ali(name, res, wildcard)
+            if format == "json":
+                out = align_to_json(res, self.tokenizer, chunk_size, self.input_frame_length, self.output_frame_length, wildcard)
+                out["window_states"], out["window_margin"] = window, margin
+                return out
+            hyps = [DecodeLike(t, fr, cf, ends=en) for t, fr, cf, en in split_by_chunk(res, ends=True)]
+            return get_output(format, self.tokenizer, name, hyps, timings_adjustment, chunk_size, self.input_frame_length,
+                              self.output_frame_length, wildcard=wildcard)
+        n_chunks = self._encode_prepared("align", eng, n_frames, n_chunks, chunk_size)
         if graph is not None:
             res = eng.align_graph([graph], [(0, n_chunks)], wildcard_bias)[0]
         elif wildcard is None:
@@ -356,22 +389,73 @@ class ReverbASR:
         return get_output(format, self.tokenizer, name, hyps, timings_adjustment, chunk_size, self.input_frame_length,
                           self.output_frame_length, wildcard=wildcard)
 
-    def _encode_for_align(self, who: str, audio_file, transcript, tokens, verbatimicity: float, chunk_size: int):
-        """Tokenise and encode the whole file as ONE batch, as align() and score() need it -> (engine, ids, n_chunks)."""
+    def _align_long(self, eng: Engine, ids, n_frames: int, n_chunks: int, chunk_size: int, window_tokens, wildcard_bias: float,
+                    need_emissions: bool):
+        """The long path of align(): ONE lattice over the whole file, encoded batch by batch as find() does (Engine.align_long_*: a
+        windowed Viterbi, csrc/ctc_viterbi_window.hip) -> (AlignResult over all chunks, window states, window margin).  Peaks and
+        confidences need the log-prob of the chosen label at every frame, known only after the back-trace: the batches are then
+        encoded a second time (need_emissions); without them peak = begin and confidence = 0."""
+        from .ctc_align import AlignResult
+        mc = eng.cfg.max_chunks
+        lens_all = np.full(n_chunks, chunk_size, np.int32)
+        lens_all[-1] = n_frames - (n_chunks - 1) * chunk_size
+        enc_all = np.where(lens_all > 6, (lens_all - 7) // 4 + 1, 0).astype(np.int32)      # Conv2dSubsampling4: frames 6 + 4j < len
+        window = 0 if window_tokens is None else min(32768, -(-2 * int(window_tokens) // 256) * 256)
+        used = eng.align_long_begin(ids, int(enc_all.sum()), window, wildcard_bias)
+
+        def batches():
+            for c0 in range(0, n_chunks, mc):
+                eng.encode(None, lens_all[c0:c0 + mc], 1, 0.0, first_chunk=c0, T0=chunk_size)
+                assert eng.encoder_lens().tolist() == enc_all[c0:c0 + mc].tolist(), "encoder frames differ from the subsampling arithmetic"
+                yield int(enc_all[c0:c0 + mc].sum())
+
+        try:
+            for _ in batches():
+                eng.align_long_feed()
+            labels, begin, end, score, margin = eng.align_long_finish()
+            peak, conf = begin.copy(), np.zeros(len(begin), np.float32)
+            if need_emissions:
+                f0, parts = 0, []
+                for n in batches():
+                    parts.append(eng.align_long_emissions(labels[f0:f0 + n]))
+                    f0 += n
+                emit = np.concatenate(parts)
+                for k, (b, e) in enumerate(zip(begin, end)):                             # per run, as rvb_ctc_align does: first maximum
+                    peak[k] = b + int(np.argmax(emit[b:e + 1]))
+                    conf[k] = np.exp(emit[peak[k]])
+        finally:
+            eng.align_long_end()
+        if margin < 64 and margin < used:
+            logging.getLogger(__name__).warning(
+                "align: the path came within %d states of the edge of its window of %d states; a better path may lie outside: "
+                "align again with a larger window_tokens (now %d)", margin, used, used // 2)
+        res = AlignResult([int(t) for t in ids], labels.tolist(), begin.tolist(), end.tolist(), peak.tolist(), conf.tolist(), score, 0,
+                          enc_all.tolist())
+        return res, used, margin
+
+    def _prepare_for_align(self, audio_file, transcript, tokens, verbatimicity: float, chunk_size: int):
+        """Tokenise, upload and run the fbank -> (engine, ids, n_frames, n_chunks)."""
         ids = list(self.tokenizer.tokenize(transcript)[1]) if tokens is None else [int(t) for t in tokens]
         eng = self._engine_for_chunk(chunk_size)
         eng.upload_pcm(*self._load_pcm(audio_file, 16000))
         eng.set_cat_embs([verbatimicity, 1.0 - verbatimicity])
         eng.apply_decoding_chunk(-1, -1)
         n_frames = eng.fbank()
-        n_chunks = -(-n_frames // chunk_size)
+        return eng, ids, n_frames, -(-n_frames // chunk_size)
+
+    def _encode_for_align(self, who: str, audio_file, transcript, tokens, verbatimicity: float, chunk_size: int):
+        """Tokenise and encode the whole file as ONE batch, as align() and score() need it -> (engine, ids, n_chunks)."""
+        eng, ids, n_frames, n_chunks = self._prepare_for_align(audio_file, transcript, tokens, verbatimicity, chunk_size)
+        return eng, ids, self._encode_prepared(who, eng, n_frames, n_chunks, chunk_size)
+
+    def _encode_prepared(self, who: str, eng: Engine, n_frames: int, n_chunks: int, chunk_size: int) -> int:
         if n_chunks > eng.cfg.max_chunks:
             raise ValueError(f"{who}: the file has {n_chunks} chunks of {chunk_size} frames, the engine batches {eng.cfg.max_chunks}: "
                              "one lattice spans one encoded batch -- load the model with max_chunks >= the file's chunks")
         lens = np.full(n_chunks, chunk_size, np.int32)
         lens[-1] = n_frames - (n_chunks - 1) * chunk_size
         eng.encode(None, lens, 1, 0.0, first_chunk=0, T0=chunk_size)
-        return eng, ids, n_chunks
+        return n_chunks
 
     def score(self, audio_file, transcript: Optional[str] = None, tokens=None, verbatimicity: float = 1.0, chunk_size: int = 2051,
               posteriors: bool = False, attention: bool = False, reverse_weight: Optional[float] = None, alternatives: bool = False):
