@@ -123,6 +123,31 @@ int rvd_get_tap(rvd_engine* e, const char* name, float* out);
 int rvd_embed(rvd_engine* e, const int64_t* win, const float* mask, int n, float* emb_out);
 /* debug: the 80-bin log-mel features of one window as fed to the ResNet, [frames][80]; returns frames in *n */
 int rvd_get_emb_fbank(rvd_engine* e, int64_t window, float* out, int32_t* n_frames);
+/* Parity taps of the embedding pass (read-only; for the tests' stage-by-stage check of the ResNet34 trunk, whose three rotating
+ * buffers per stage keep nothing of a block).  rvd_set_emb_tap(e, 1) makes every later TRUNK PASS of rvd_embed copy its stored
+ * tensors, device to device on the engine's stream, into buffers the engine owns; the taps hold the LAST pass (rvd_embed runs one
+ * pass per rvd_emb_windows_per_pass() distinct windows).  Off (0, the default) releases them, and rvd_embed enqueues exactly what it
+ * enqueues without this entry point.  rvd_get_emb_tap copies one tensor out: bf16 widened to fp32 bit for bit, fp32 as it is;
+ * `capacity` = floats `out` can take.  With B windows and n items in the pass, stage s = 1..4 of F_s x T_s pixels (80 x 998, 40 x 499,
+ * 20 x 250, 10 x 125 for 10 s windows) and C_s = 32, 64, 128, 256 channels, block b = 0.. of that stage:
+ *   "feats"    [B][T_1][80]    fp32   the fbank frames of the pass's windows, before mean subtraction
+ *   "mean"     [B][80]         fp32   their per-window means, as the stem reads them
+ *   "stem"     [B][F_1 + 2][T_1 + 2][C_1]     the stem's output; like every tensor below WITH its zero border of one pixel
+ *   "s<s>b<b>.x"    the block's input as it stood when the block read it ([B][F + 2][T + 2][C] of the stage it comes from)
+ *   "s<s>b<b>.tmp"  its first convolution's output -- not stored by a block that runs as one kernel (conv_block.hip)
+ *   "s<s>b<b>.sc"   its projection shortcut's output -- only where the shortcut is stored (not when it rides in the second convolution's K loop)
+ *   "s<s>b<b>.out"  its output
+ *   "trunk"    [B][F_4 + 2][T_4 + 2][C_4]     what the pooling reads
+ *   "stats"    [n][2 C_4 F_4]                 the pooled statistics, as seg_1 reads them
+ *   "windows"  [B]  "item_b" [n]              the pass's window list and every item's row in it (integers as floats)
+ *   "forms"    [3 + 3 x 16]    B, the first item of the pass, n, then per block (stage-major): the kernel of its first and of its second
+ *              convolution (1 direct, 2 implicit GEMM, 3 row64, 4 stream, 5 implicit GEMM on the wide tile, 6 the one-kernel block, 7 the
+ *              stride-2 opener) and where its shortcut went (0 identity, 1 a launch of its own, 2 the stride-2 opener, 3 the K loop)
+ * Refused by name, with nothing written: rvd_set_emb_tap(e, 1) on an fp8 engine or with RVD_EMB_FP8=1 (RVB_E_UNSUPPORTED); a pass of
+ * rvd_embed over more than 4 windows while the taps are on (RVB_E_UNSUPPORTED); rvd_get_emb_tap before any such pass, or for a name
+ * the last pass did not keep (RVB_E_STATE); a buffer that is too small (RVB_E_ARG). */
+int rvd_set_emb_tap(rvd_engine* e, int enabled);
+int rvd_get_emb_tap(rvd_engine* e, const char* name, float* out, int64_t capacity);
 
 /* clustering step of the pipeline: the dendrogram scipy.cluster.hierarchy.linkage(X, method="centroid",
  * metric="euclidean") returns for X host fp64 [n][d] -- Z host fp64 [n-1][4] (id_a, id_b, distance, size),

@@ -319,6 +319,8 @@ DIAR_SIGNATURES = {
     "rvd_get_tap": (C.c_int, [_eng, C.c_char_p, _f32p]),
     "rvd_embed": (C.c_int, [_eng, _i64p, _f32p, C.c_int, _f32p]),
     "rvd_get_emb_fbank": (C.c_int, [_eng, C.c_int64, _f32p, _i32p]),
+    "rvd_set_emb_tap": (C.c_int, [_eng, C.c_int]),
+    "rvd_get_emb_tap": (C.c_int, [_eng, C.c_char_p, _f32p, C.c_int64]),
     "rvd_centroid_linkage": (C.c_int, [_eng, _f64p, C.c_int, C.c_int, _f64p]),
     "rvd_centroid_linkage_many": (C.c_int, [_eng, _f64p, _i32p, C.c_int, C.c_int, _f64p]),
     "rvd_set_linkage_workgroups": (C.c_int, [_eng, C.c_int]),

@@ -24,6 +24,8 @@ constexpr int FB_WIN = 400, FB_SHIFT = 160, FB_MEL = 80;
 // windows per trunk pass; RVD_EMB_BATCH overrides (tuning).  768 since round 4: 1 h of audio 385-392 ms at 192, 381 at 384,
 // 373 at 768 (profiles/r04_call17_persistent_batch.txt) -- fewer, longer launches; 27 GB of activations out of 288
 static int emb_batch() {
+  // librvb_test.so only: read per engine, so that a test can ask for several trunk passes (the product's value is fixed per process)
+  if (const char* l = lab_env("RVD_EMB_BATCH")) { const int x = atoi(l); if (x > 0) return x; }
   static int v = [] { const char* e = getenv("RVD_EMB_BATCH"); const int x = e ? atoi(e) : 0; return x > 0 ? x : 768; }();
   return v;
 }
@@ -84,6 +86,15 @@ struct rvd_engine {
   std::vector<float> scale8;
   int act_cap = 0;
   DevBuf e_win, e_mean, e_item_b, e_mask, e_stats, e_out;
+  // ---- parity taps of the embedding pass (rvd_set_emb_tap / rvd_get_emb_tap: read-only, for the tests' stage-by-stage check).
+  // Off (the default): tap_keep returns at once and rvd_embed enqueues what it always did.  On: every stored tensor of the LAST trunk
+  // pass is copied, device to device on the engine's stream, into buffers of the engine's own.
+  struct EmbTap { DevBuf buf; size_t bytes = 0; bool f32 = false, live = false; };
+  bool emb_tap = false, emb_tap_pass = false;      // the switch; a pass has run with it on
+  std::map<std::string, EmbTap> emb_taps;
+  std::vector<float> emb_tap_forms;                // see rvd_get_emb_tap "forms"
+  std::vector<int64_t> emb_tap_windows;            // the window list of the last pass
+  std::vector<int32_t> emb_tap_item_b;             // its items' rows in that list
 
   // profiling
   bool profiling = false;
@@ -117,6 +128,21 @@ void drain(rvd_engine* e) {
     e->event_pool.push_back(p.a); e->event_pool.push_back(p.b);
   }
   e->pending.clear();
+}
+
+// parity taps of the embedding pass: with the switch off nothing is enqueued
+constexpr int EMB_TAP_MAX_WINDOWS = 4;             // windows per pass while the taps are on (5 MB per stage-1 tensor and window)
+enum { EK_DIRECT = 1, EK_IGEMM = 2, EK_ROW64 = 3, EK_STREAM = 4, EK_IGEMM_WIDE = 5, EK_BLOCK32 = 6, EK_S2SC = 7 };     // "forms": which kernel ran
+enum { ESC_IDENTITY = 0, ESC_OWN_LAUNCH = 1, ESC_IN_OPENER = 2, ESC_IN_K_LOOP = 3 };                                  // ... and where the shortcut went
+int tap_keep(rvd_engine* e, const std::string& name, const void* src, size_t bytes, bool f32 = false, size_t offset = 0, size_t total = 0) {
+  if (!e->emb_tap) return OK;
+  auto& t = e->emb_taps[name];
+  if (total == 0) total = bytes;
+  RVB_TRY(t.buf.ensure(total));
+  RVB_HIP_CHECK(hipMemcpyAsync((char*)t.buf.p + offset, src, bytes, hipMemcpyDeviceToDevice, e->stream));
+  e->prof["emb_tap_copy"].launches += 1;
+  t.bytes = total; t.f32 = f32; t.live = true;
+  return OK;
 }
 
 int up_f32(rvd_engine* e, DevBuf& dst, const float* src, size_t n) {
@@ -553,19 +579,23 @@ int ensure_emb_workspace(rvd_engine* e, int B) {
   return OK;
 }
 
-int run_conv(rvd_engine* e, const ConvW& c, const void* in, const StageDims& di, const void* res, void* out, const StageDims& dq, int B, int relu) {
+int run_conv(rvd_engine* e, const ConvW& c, const void* in, const StageDims& di, const void* res, void* out, const StageDims& dq, int B, int relu,
+             int* kind = nullptr) {
   ConvArgs a{};
   a.in = in; a.w = c.w.p; a.bias = c.b.as<float>(); a.res = res; a.out = out;
   a.B = B; a.Fi = di.F; a.Ti = di.T; a.Cin = c.cin; a.Fo = dq.F; a.To = dq.T; a.Cout = c.cout;
   a.stride = c.stride; a.taps = c.taps; a.relu = relu;
   a.w_ig = c.w_ig.p;
   const std::string nm = std::string(c.taps == 1 ? "emb_conv_sc" : (c.stride == 2 ? "emb_conv_s2_" : "emb_conv_")) + (c.taps == 1 ? "" : std::to_string(c.cout));
+  int k = EK_DIRECT;
   if (conv_igemm_applicable(e->dtype, a)) {
     e->prof["emb_conv_igemm"].launches += 1;                                             // how many went to conv_gemm.hip
-    if (conv_igemm_wide(a)) e->prof["emb_conv_igemm_wide"].launches += 1;
+    k = EK_IGEMM;
+    if (conv_igemm_wide(a)) { e->prof["emb_conv_igemm_wide"].launches += 1; k = EK_IGEMM_WIDE; }
   }
-  else if (conv_row64_applicable(e->dtype, a)) e->prof["emb_conv_row64"].launches += 1;        // ... to conv_row64.hip
-  else if (conv_stream_applicable(e->dtype, a)) e->prof["emb_conv_stream"].launches += 1;     // ... to conv_stream.hip
+  else if (conv_row64_applicable(e->dtype, a)) { e->prof["emb_conv_row64"].launches += 1; k = EK_ROW64; }       // ... to conv_row64.hip
+  else if (conv_stream_applicable(e->dtype, a)) { e->prof["emb_conv_stream"].launches += 1; k = EK_STREAM; }   // ... to conv_stream.hip
+  if (kind) *kind = k;
   DScope sc(e, nm.c_str(), 2.0 * (double)B * dq.F * dq.T * c.cout * c.cin * c.taps);
   return conv2d(e->stream, e->dtype, a);
 }
@@ -581,6 +611,13 @@ int run_trunk(rvd_engine* e, int B, const void** trunk_out) {
   const void* x = e->act[0][0].p;
   StageDims dx = d0;
   int xi = 0;                                   // index of x among the stage's rotating buffers
+  // taps (off: nothing happens): a padded tensor of B windows, and the forms record of block (li, bi)
+  const size_t ts = dt_size(e->dtype);
+  auto padded = [&](const StageDims& q) { return (size_t)B * (q.F + 2) * (q.T + 2) * q.C * ts; };
+  auto tname = [](int li, size_t bi, const char* what) { return "s" + std::to_string(li + 1) + "b" + std::to_string(bi) + "." + what; };
+  int blk = 0;
+  auto form = [&](int k1, int k2, int sc) { if (e->emb_tap) { float* f = &e->emb_tap_forms[3 + 3 * (size_t)blk]; f[0] = (float)k1; f[1] = (float)k2; f[2] = (float)sc; } };
+  RVB_TRY(tap_keep(e, "stem", x, padded(d0)));
   for (int li = 0; li < 4; ++li) {
     const StageDims d = stage_dims(e, li);
     for (size_t bi = 0; bi < e->stages[li].size(); ++bi) {
@@ -590,6 +627,8 @@ int run_trunk(rvd_engine* e, int B, const void** trunk_out) {
       const int oi = xi < 0 ? 1 : (xi + 2) % 3;
       void* tmp = e->act[li][ti].p;
       void* out = e->act[li][oi].p;
+      blk = (int)bi; for (int q = 0; q < li; ++q) blk += (int)e->stages[q].size();
+      RVB_TRY(tap_keep(e, tname(li, bi, "x"), x, padded(dx)));
       if (!Bk.has_sc && dx.F == d.F && dx.T == d.T &&
           conv_block32_applicable(e->dtype, Bk.c1.cin, Bk.c1.cout, Bk.c2.cout, Bk.c1.stride, Bk.c2.stride, Bk.c1.taps, Bk.c2.taps, d.F, d.T)) {
         // the whole residual block in one kernel (conv_block.hip): x read once, out written once, the intermediate tensor in LDS
@@ -599,6 +638,8 @@ int run_trunk(rvd_engine* e, int B, const void** trunk_out) {
         e->prof["emb_conv_block"].launches += 1;
         { DScope sc(e, "emb_conv_32", 2.0 * 2.0 * (double)B * d.F * d.T * 32 * 32 * 9);
           RVB_TRY(conv_block32(e->stream, a)); }
+        RVB_TRY(tap_keep(e, tname(li, bi, "out"), out, padded(d)));
+        form(EK_BLOCK32, EK_BLOCK32, ESC_IDENTITY);
         x = out; dx = d; xi = oi;
         continue;
       }
@@ -638,6 +679,7 @@ int run_trunk(rvd_engine* e, int B, const void** trunk_out) {
         continue;
       }
       bool sc_done = false;
+      int k1 = EK_S2SC, k2 = EK_IGEMM;
       if (Bk.has_sc && !Bk.c2.w_ig_sc.p &&
           conv_s2sc_applicable(e->dtype, Bk.c1.cin, Bk.c1.cout, Bk.c1.stride, Bk.c1.taps, Bk.sc.cin, Bk.sc.cout, Bk.sc.stride, Bk.sc.taps, dx.F, dx.T, d.F, d.T)) {
         // the stride-2 convolution and the projection shortcut of the block that opens the 64-channel stage: one pass over x (conv_s2.hip)
@@ -651,8 +693,9 @@ int run_trunk(rvd_engine* e, int B, const void** trunk_out) {
           RVB_TRY(conv_s2sc(e->stream, a)); }
         sc_done = true;
       } else {
-        RVB_TRY(run_conv(e, Bk.c1, x, dx, nullptr, tmp, d, B, 1));
+        RVB_TRY(run_conv(e, Bk.c1, x, dx, nullptr, tmp, d, B, 1, &k1));
       }
+      RVB_TRY(tap_keep(e, tname(li, bi, "tmp"), tmp, padded(d)));
       if (f8blk && e->emb_f8_state == 1)
         RVB_TRY(act_amax_bf16(e->stream, tmp, (size_t)B * (d.F + 2) * (d.T + 2) * d.C, e->d_amax8.as<unsigned>() + ((li - 2) * 8 + (int)bi) * 2));
       if (Bk.has_sc && Bk.c2.w_ig_sc.p) {        // the projection shortcut inside the second convolution's K loop (RVD_CONV_SC_FUSE=1)
@@ -668,6 +711,8 @@ int run_trunk(rvd_engine* e, int B, const void** trunk_out) {
         { DScope sc(e, ("emb_conv_" + std::to_string(Bk.c2.cout)).c_str(),
                     2.0 * (double)B * d.F * d.T * Bk.c2.cout * ((double)Bk.c2.cin * 9 + Bk.sc.cin));
           RVB_TRY(conv2d(e->stream, e->dtype, a)); }
+        RVB_TRY(tap_keep(e, tname(li, bi, "out"), out, padded(d)));
+        form(k1, EK_IGEMM, ESC_IN_K_LOOP);
         x = out; dx = d; xi = oi;
         continue;
       }
@@ -675,13 +720,17 @@ int run_trunk(rvd_engine* e, int B, const void** trunk_out) {
       if (Bk.has_sc) {
         if (!sc_done) RVB_TRY(run_conv(e, Bk.sc, x, dx, nullptr, e->act[li][3].p, d, B, 0));
         res = e->act[li][3].p;
+        RVB_TRY(tap_keep(e, tname(li, bi, "sc"), res, padded(d)));
       }
-      RVB_TRY(run_conv(e, Bk.c2, tmp, d, res, out, d, B, 1));
+      RVB_TRY(run_conv(e, Bk.c2, tmp, d, res, out, d, B, 1, &k2));
+      RVB_TRY(tap_keep(e, tname(li, bi, "out"), out, padded(d)));
+      form(k1, k2, !Bk.has_sc ? ESC_IDENTITY : sc_done ? ESC_IN_OPENER : ESC_OWN_LAUNCH);
       if (f8blk && e->emb_f8_state == 1)
         RVB_TRY(act_amax_bf16(e->stream, out, (size_t)B * (d.F + 2) * (d.T + 2) * d.C, e->d_amax8.as<unsigned>() + ((li - 2) * 8 + (int)bi) * 2 + 1));
       x = out; dx = d; xi = oi;
     }
   }
+  RVB_TRY(tap_keep(e, "trunk", x, padded(dx)));
   *trunk_out = x;
   return OK;
 }
@@ -711,6 +760,11 @@ int embed_impl(rvd_engine* e, const int64_t* win, const float* mask, int n, floa
       ++i1;
     }
     const int B = (int)uniq.size(), ni = i1 - i0;
+    if (e->emb_tap && B > EMB_TAP_MAX_WINDOWS) {
+      set_error("rvd_embed: rvd_set_emb_tap is on and this pass covers " + std::to_string(B) + " windows (the taps keep at most " +
+                std::to_string(EMB_TAP_MAX_WINDOWS) + ": embed fewer windows per call)");
+      return E_UNSUPPORTED;
+    }
     {
       const int rc = ensure_emb_workspace(e, B);
       if (rc == E_NOMEM && B > 1) {                 // the activations of B windows do not fit beside what else lives on this GPU:
@@ -733,6 +787,19 @@ int embed_impl(rvd_engine* e, const int64_t* win, const float* mask, int n, floa
     RVB_HIP_CHECK(hipMemcpyAsync(e->e_mask.p, mask + (size_t)i0 * frames, (size_t)ni * frames * 4, hipMemcpyHostToDevice, e->stream));
     RVB_HIP_CHECK(hipStreamSynchronize(e->stream));    // uniq / item_b are locals
     const void* trunk = nullptr;
+    if (e->emb_tap) {                                  // the taps hold one pass: forget the last one's, keep this pass's stem inputs
+      for (auto& kv : e->emb_taps) kv.second.live = false;
+      e->emb_tap_forms.assign(3 + 3 * 16, 0.f);
+      e->emb_tap_forms[0] = (float)B; e->emb_tap_forms[1] = (float)i0; e->emb_tap_forms[2] = (float)ni;
+      e->emb_tap_windows = uniq; e->emb_tap_item_b = item_b;
+      const int fps_ = c.step_samples / FB_SHIFT;
+      const size_t fb_w = (size_t)e->nfr * FB_MEL * 4, mu_w = (size_t)FB_MEL * 4;
+      for (int b = 0; b < B; ++b) {
+        RVB_TRY(tap_keep(e, "feats", e->emb_fb.as<float>() + (size_t)uniq[b] * fps_ * FB_MEL, fb_w, true, b * fb_w, B * fb_w));
+        RVB_TRY(tap_keep(e, "mean", e->e_mean.as<float>() + (size_t)uniq[b] * FB_MEL, mu_w, true, b * mu_w, B * mu_w));
+      }
+      e->emb_tap_pass = true;
+    }
     if (e->emb_fp8 && e->emb_f8_state == 0) {          // the first trunk pass of an fp8 engine runs in bf16 and records the ranges
       RVB_TRY(e->d_amax8.ensure(32 * 4));
       RVB_TRY(e->d_sat8.ensure(4));
@@ -752,6 +819,7 @@ int embed_impl(rvd_engine* e, const int64_t* win, const float* mask, int n, floa
     }
     { DScope sc(e, "emb_pool");
       RVB_TRY(tstp_pool(e->stream, e->dtype, trunk, e->e_item_b.as<int>(), e->e_mask.as<float>(), frames, ni, d3.F, d3.T, d3.C, e->e_stats.p)); }
+    RVB_TRY(tap_keep(e, "stats", e->e_stats.p, (size_t)ni * stats * dt_size(e->dtype)));
     { DScope sc(e, "emb_linear", 2.0 * (double)ni * stats * c.emb_dim);
       GemmArgs g{};
       g.A = e->e_stats.p; g.W = e->seg1.w.p; g.bias = e->seg1.b.as<float>(); g.C = e->e_out.p;
@@ -848,6 +916,7 @@ void rvd_destroy(rvd_engine* e) {
     for (auto& blk : st)
       for (ConvW* cw : {&blk.c1, &blk.c2, &blk.sc}) { cw->w.release(); cw->b.release(); cw->w_ig.release(); cw->w_ig_sc.release(); cw->b_sc.release(); cw->w8.release(); cw->w8s.release(); }
   for (auto& row : e->act) for (auto& b : row) b.release();
+  for (auto& kv : e->emb_taps) kv.second.buf.release();
   (void)hipStreamDestroy(e->stream);
   delete e;
 }
@@ -1077,6 +1146,55 @@ int rvd_get_emb_fbank(rvd_engine* e, int64_t window, float* out, int32_t* n_fram
   const int64_t f0 = window * (e->cfg.step_samples / FB_SHIFT);
   RVB_HIP_CHECK(hipMemcpy(out, e->emb_fb.as<float>() + f0 * FB_MEL, (size_t)e->nfr * FB_MEL * 4, hipMemcpyDeviceToHost));
   if (n_frames) *n_frames = e->nfr;
+  return OK;
+}
+
+int rvd_set_emb_tap(rvd_engine* e, int enabled) {
+  if (!e) { set_error("rvd_set_emb_tap: null engine"); return E_ARG; }
+  if (!e->finalized || !e->has_emb) { set_error("rvd_set_emb_tap: needs a finalized engine with an embedding model"); return E_STATE; }
+  if (enabled && e->emb_fp8) {
+    set_error("rvd_set_emb_tap: not available on an fp8 engine or with RVD_EMB_FP8=1 (its calibration and fp8 passes store other tensors)");
+    return E_UNSUPPORTED;
+  }
+  if (enabled && e->dtype != DT_BF16 && e->dtype != DT_F32) { set_error("rvd_set_emb_tap: unsupported dtype"); return E_UNSUPPORTED; }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
+  e->emb_tap = enabled != 0;
+  if (!e->emb_tap) {                                   // off: the copies go, and with them what they held
+    for (auto& kv : e->emb_taps) kv.second.buf.release();
+    e->emb_taps.clear(); e->emb_tap_forms.clear(); e->emb_tap_windows.clear(); e->emb_tap_item_b.clear();
+    e->emb_tap_pass = false;
+  }
+  return OK;
+}
+
+int rvd_get_emb_tap(rvd_engine* e, const char* name, float* out, int64_t capacity) {
+  if (!e || !name || !out) { set_error("rvd_get_emb_tap: null argument"); return E_ARG; }
+  if (!e->emb_tap_pass) { set_error("rvd_get_emb_tap: no rvd_embed pass has run with rvd_set_emb_tap on"); return E_STATE; }
+  auto host_list = [&](size_t n, auto get) -> int {
+    if (capacity < (int64_t)n) { set_error(std::string("rvd_get_emb_tap: ") + name + " holds " + std::to_string(n) + " values, the buffer " + std::to_string(capacity)); return E_ARG; }
+    for (size_t i = 0; i < n; ++i) out[i] = get(i);
+    return OK;
+  };
+  if (!strcmp(name, "forms")) return host_list(e->emb_tap_forms.size(), [&](size_t i) { return e->emb_tap_forms[i]; });
+  if (!strcmp(name, "windows")) return host_list(e->emb_tap_windows.size(), [&](size_t i) { return (float)e->emb_tap_windows[i]; });
+  if (!strcmp(name, "item_b")) return host_list(e->emb_tap_item_b.size(), [&](size_t i) { return (float)e->emb_tap_item_b[i]; });
+  auto it = e->emb_taps.find(name);
+  if (it == e->emb_taps.end() || !it->second.live) {
+    set_error(std::string("rvd_get_emb_tap: no tap named ") + name + " was kept by the last pass of rvd_embed (a fused block stores no tmp, an identity shortcut no sc)");
+    return E_STATE;
+  }
+  const auto& t = it->second;
+  const bool wide = t.f32 || e->dtype == DT_F32;
+  const size_t n = t.bytes / (wide ? 4 : 2);
+  if (capacity < (int64_t)n) { set_error(std::string("rvd_get_emb_tap: ") + name + " holds " + std::to_string(n) + " values, the buffer " + std::to_string(capacity)); return E_ARG; }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
+  if (wide) { RVB_HIP_CHECK(hipMemcpy(out, t.buf.p, t.bytes, hipMemcpyDeviceToHost)); return OK; }
+  std::vector<uint16_t> tmp(n);
+  RVB_HIP_CHECK(hipMemcpy(tmp.data(), t.buf.p, t.bytes, hipMemcpyDeviceToHost));
+  uint32_t* o = (uint32_t*)out;
+  for (size_t i = 0; i < n; ++i) o[i] = (uint32_t)tmp[i] << 16;      // bf16 widened to fp32 bit for bit
   return OK;
 }
 

@@ -235,6 +235,60 @@ class DiarEngine:
         _check(self.lib.rvd_get_emb_fbank(self._h, int(window), fptr(out), C.byref(n)), "rvd_get_emb_fbank")
         return out[:n.value].copy()
 
+    # ------------------------------------------------------------------ parity taps of the embedding pass
+    EMB_BLOCKS = (3, 4, 6, 3)
+
+    def set_emb_tap(self, on: bool = True):
+        """Parity taps of the embedding trunk (include/rvd.h rvd_set_emb_tap): while on, every trunk pass of embed() keeps its stored
+        tensors (at most 4 windows per pass); off releases them."""
+        _check(self.lib.rvd_set_emb_tap(self._h, 1 if on else 0), "rvd_set_emb_tap")
+
+    def emb_forms(self) -> dict:
+        """-> dict(B, first_item, items, blocks=[(stage, block, kernel of conv 1, kernel of conv 2, shortcut form), ...]) of the last pass"""
+        f = np.zeros(3 + 3 * 16, np.float32)
+        _check(self.lib.rvd_get_emb_tap(self._h, b"forms", fptr(f), f.size), "rvd_get_emb_tap")
+        f = f.astype(np.int64)
+        blocks, k = [], 3
+        for s, nb in enumerate(self.EMB_BLOCKS, start=1):
+            for b in range(nb):
+                blocks.append((s, b, int(f[k]), int(f[k + 1]), int(f[k + 2])))
+                k += 3
+        return dict(B=int(f[0]), first_item=int(f[1]), items=int(f[2]), blocks=blocks)
+
+    def emb_tap(self, name: str) -> np.ndarray:
+        """One stored tensor of the last trunk pass by name (rvd_get_emb_tap): padded tensors [B, F + 2, T + 2, C], "feats" [B, T, 80],
+        "mean" [B, 80], "stats" [items, 2 C F], "windows" [B] and "item_b" [items] as int64."""
+        fm = self.emb_forms()
+        B, ni = fm["B"], fm["items"]
+        nfr = (int(self.cfg["window_samples"]) - 400) // 160 + 1
+        m = int(self.cfg["emb_channels"])
+        dims = [(80, nfr, m)]
+        for _ in range(3):
+            F, T, Cc = dims[-1]
+            dims.append(((F - 1) // 2 + 1, (T - 1) // 2 + 1, Cc * 2))
+        pad = lambda s: (B, dims[s][0] + 2, dims[s][1] + 2, dims[s][2])
+        if name in ("windows", "item_b"):
+            out = np.zeros(B if name == "windows" else ni, np.float32)
+            _check(self.lib.rvd_get_emb_tap(self._h, name.encode(), fptr(out), out.size), "rvd_get_emb_tap")
+            return out.astype(np.int64)
+        if name == "feats":
+            shape = (B, nfr, 80)
+        elif name == "mean":
+            shape = (B, 80)
+        elif name == "stem":
+            shape = pad(0)
+        elif name == "trunk":
+            shape = pad(3)
+        elif name == "stats":
+            shape = (ni, 2 * dims[3][2] * dims[3][0])
+        else:
+            s, b = int(name[1]) - 1, int(name[3:name.index(".")])
+            what = name[name.index(".") + 1:]
+            shape = pad(s - 1 if (what == "x" and b == 0 and s > 0) else s)
+        out = np.empty(shape, np.float32)
+        _check(self.lib.rvd_get_emb_tap(self._h, name.encode(), fptr(out), out.size), "rvd_get_emb_tap")
+        return out
+
     def set_linkage_workgroups(self, workgroups: int = 0):
         """Workgroups the clustering's merge loop may take (0 default = 16, 1, 2, 4, 8, 16).  The dendrogram does not depend on the count
         from 2 up; 1 selects another loop, which gives the same dendrogram bit for bit on input without tied distances and an equally

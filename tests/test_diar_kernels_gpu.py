@@ -19,6 +19,9 @@ from util import bf16_round, rnd, f32, i32
 from diar_stage_ref import (U32, HB, LSTM_F32_MAX, LSTM_BF16_MAX, LSTM_BF16_MEAN, half_ulp as _half_ulp, check_within as _check_within,
                             pool_norm_ref as _pool_norm_ref, conv1d5_ref, lstm_ref as _lstm_ref, classifier_ref)
 
+# ... and the TSTP reference in tests/emb_conv_ref.py, shared with the bf16 embedding network's stage checks
+from emb_conv_ref import nearest_map as _nearest_map, tstp_ref as _tstp_ref
+
 pytestmark = pytest.mark.gpu
 F32, BF16 = 0, 1
 
@@ -314,11 +317,6 @@ def test_classifier_refuses_shapes_it_does_not_cover(lib):
 
 
 # ------------------------------------------------------------------------------------ TSTP statistics pooling
-def _nearest_map(mask_len, TT):
-    src = torch.arange(mask_len, dtype=torch.float32).reshape(1, 1, mask_len)
-    return torch.nn.functional.interpolate(src, size=TT, mode="nearest").reshape(TT).long().numpy()
-
-
 @pytest.mark.parametrize("dtype", [F32, BF16])
 @pytest.mark.parametrize("mask_len,TT", [(589, 125), (589, 256), (100, 256), (7, 3), (589, 1)])
 def test_tstp(lib, dtype, mask_len, TT):
@@ -354,17 +352,9 @@ def test_tstp(lib, dtype, mask_len, TT):
     for it in range(n_items):
         w = mask[it, idx].astype(np.float64)                          # [TT]
         xv = x[item_b[it]].astype(np.float64).transpose(2, 0, 1)      # [C][F][TT]
-        s1, s2 = w.sum(), (w * w).sum()
-        v1 = s1 + 1e-8
-        mean = (xv * w).sum(-1) / v1
-        den = v1 - s2 / v1 + 1e-8
-        std = np.sqrt((w * (xv - mean[..., None]) ** 2).sum(-1) / den)
+        s1 = w.sum()
+        mean, std, m_tol, s_tol = _tstp_ref(dtype, xv, w)
         got = stats[it].reshape(2, C, F)
-        m_tol = 8 * TT * U32 * (np.abs(xv) * w).sum(-1) / v1
-        m_tol = m_tol + _half_ulp(dtype, mean, m_tol) + 1e-30
-        dm = np.abs(mean) * (4 * TT * U32 + 2e-8 / max(s1, 1e-8)) + m_tol
-        s_tol = 8 * TT * U32 * std * (1 + (v1 + s2 / v1) / den) + np.sqrt(s1 / den) * dm
-        s_tol = s_tol + _half_ulp(dtype, std, s_tol) + 1e-30
         _check_within(got[0], mean, m_tol, "tstp mean, item %d" % it)
         _check_within(got[1], std, s_tol, "tstp std, item %d" % it)
         if s1 == 0:

@@ -17,20 +17,10 @@ from test_diar_gpu import _record
 from util import bf16_round, f32
 
 pytestmark = pytest.mark.gpu
-F32, BF16 = 0, 1
-U32 = 2.0 ** -24          # fp32 unit roundoff
-HB = 2.0 ** -8            # half a bf16 ulp, relative to the value: at most 2^-8 (8 significant bits)
+# the fp64 references and derived bounds live in tests/emb_conv_ref.py, shared with the bf16-storage restatement of the network
+from emb_conv_ref import (F32, BF16, U32, check_within as _check_within, conv_ref as _ref, conv_ref_pixels as _ref_pixels,
+                          conv_bound as _bound, stem_ref as _stem_ref)
 DIRECT, IGEMM, ROW64, STREAM = 1, 2, 3, 4
-
-
-def _check_within(got, ref, tol, what):
-    """every element within its bound; returns the worst error / bound ratio"""
-    err = np.abs(got.astype(np.float64) - ref)
-    bad = err > tol
-    assert not bad.any(), "%s: %d elements outside the bound, worst err %.3g at bound %.3g (max err %.3g)" % (
-        what, int(bad.sum()), float(err[bad].max()), float(np.asarray(tol * np.ones_like(err))[bad][np.argmax(err[bad])]),
-        float(err.max()))
-    return float((err / np.maximum(tol, 1e-300)).max())
 
 
 def _rnd(dtype, a):
@@ -67,68 +57,6 @@ def _conv(lib, dtype, path, op, relu):
                              k * k, int(relu), fptr(x2), fptr(op["w2"]), Fi2, Ti2, Cin2, op["stride2"], _lib.iptr(ran))
     _lib.check(rc, "rvb_test_conv2d(path %d)" % path)
     return out, (int(ran[0]), int(ran[1]))
-
-
-def _ref(op, relu, batches=None):
-    """fp64 convolution of the rounded operands (3x3 pad 1 or 1x1, stride s; + the 1x1 / stride2 shortcut) -> (ref, bound
-    (K + 2) u sum|terms|), for the windows `batches` (default all)"""
-    sel = slice(None) if batches is None else list(batches)
-    x, w, s = op["x"][sel].astype(np.float64), op["w"].astype(np.float64), op["stride"]
-    B, Fi, Ti, Cin = x.shape
-    Cout, k = w.shape[0], w.shape[2]
-    Fo, To = (Fi - 1) // s + 1, (Ti - 1) // s + 1
-    xp = np.pad(x, ((0, 0), (1, 1), (1, 1), (0, 0))) if k == 3 else x
-    acc = np.zeros((B * Fo * To, Cout))
-    mag = np.zeros_like(acc)
-    K = k * k * Cin
-
-    def add(sl, wt):
-        a = np.ascontiguousarray(sl).reshape(-1, sl.shape[-1])
-        acc[...] += a @ wt
-        mag[...] += np.abs(a) @ np.abs(wt)
-    for kh in range(k):
-        for kw in range(k):
-            add(xp[:, kh:kh + s * (Fo - 1) + 1:s, kw:kw + s * (To - 1) + 1:s, :], w[:, :, kh, kw].T)
-    if op["x2"] is not None:
-        s2 = op["stride2"]
-        x2 = op["x2"][sel].astype(np.float64)
-        add(x2[:, ::s2, ::s2][:, :Fo, :To], op["w2"].astype(np.float64).T)
-        K += x2.shape[-1]
-    acc += op["bias"]
-    mag += np.abs(op["bias"].astype(np.float64))
-    if op["res"] is not None:
-        r = op["res"][sel].astype(np.float64).reshape(-1, Cout)
-        acc += r
-        mag += np.abs(r)
-    ref = np.maximum(acc, 0.0) if relu else acc
-    return ref.reshape(B, Fo, To, Cout), ((K + 2) * U32 * mag).reshape(B, Fo, To, Cout)
-
-
-def _ref_pixels(op, relu, pix):
-    """the same reference for single output pixels pix [n][3] = (b, fo, to): 3x3 convolutions without a shortcut"""
-    x, w, s = op["x"], op["w"].astype(np.float64), op["stride"]
-    Fi, Ti = x.shape[1:3]
-    Cout, Cin = w.shape[:2]
-    acc = np.zeros((len(pix), Cout))
-    mag = np.zeros_like(acc)
-    for kh in range(3):
-        for kw in range(3):
-            f, t = s * pix[:, 1] + kh - 1, s * pix[:, 2] + kw - 1
-            inside = ((f >= 0) & (f < Fi) & (t >= 0) & (t < Ti))[:, None]
-            a = np.where(inside, x[pix[:, 0], np.clip(f, 0, Fi - 1), np.clip(t, 0, Ti - 1)], 0.0).astype(np.float64)
-            acc += a @ w[:, :, kh, kw].T
-            mag += np.abs(a) @ np.abs(w[:, :, kh, kw]).T
-    acc += op["bias"]
-    mag += np.abs(op["bias"].astype(np.float64))
-    if op["res"] is not None:
-        r = op["res"][pix[:, 0], pix[:, 1], pix[:, 2]].astype(np.float64)
-        acc += r
-        mag += np.abs(r)
-    return (np.maximum(acc, 0.0) if relu else acc), (9 * Cin + 2) * U32 * mag
-
-
-def _bound(dtype, ref, tol):
-    return tol + (HB * (np.abs(ref) + tol) if dtype == BF16 else 0.0) + 1e-30
 
 
 def _check_conv(dtype, got, op, relu, what):
@@ -427,18 +355,8 @@ def test_emb_stem_against_fp64(lib, dtype, C, nfr, F, fps, nwin, win, dc):
     r = 0.0
     for b, v in enumerate(wl):
         plane = (fb[v * fps:v * fps + nfr, :F] - mean[v, :F]).T.astype(np.float64)      # [F][nfr], fp32 subtraction as the kernel's
-        p = np.pad(plane, 1)
-        acc = np.zeros((F, nfr, C))
-        mag = np.zeros_like(acc)
-        for kh in range(3):
-            for kw in range(3):
-                sl = p[kh:kh + F, kw:kw + nfr][:, :, None]
-                acc += sl * w[:, 0, kh, kw].astype(np.float64)
-                mag += np.abs(sl) * np.abs(w[:, 0, kh, kw].astype(np.float64))
-        acc += bias
-        mag += np.abs(bias.astype(np.float64))
-        ref = np.maximum(acc, 0.0)
-        r = max(r, _check_within(out[b], ref, _bound(dtype, ref, 11 * U32 * mag), "stem window %d" % v))
+        ref, tol = _stem_ref(plane, w, bias)
+        r = max(r, _check_within(out[b], ref, _bound(dtype, ref, tol), "stem window %d" % v))
         if dc:
             assert np.abs(plane[7]).max() < 10.0         # the 100-sigma offset is gone: the bin is centred like the others
     _record(test="emb_conv_kernels", kernel="stem", dtype=dtype, shape=[B, F, nfr, C], ratio=r)
