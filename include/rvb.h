@@ -357,6 +357,36 @@ int rvb_ctc_align_long_finish(rvb_engine* e, int32_t* labels, int32_t* begin, in
 int rvb_ctc_align_long_emissions(rvb_engine* e, const int32_t* labels, int n_frames, float* emit_out);
 int rvb_ctc_align_long_end(rvb_engine* e);
 
+/* LONG-FORM full-sum score: rvb_ctc_score (loglik, and with posteriors the per-token occupancy, mean frame, peak posterior and its
+ * frame) of ONE transcript of any number of tokens over a recording that is encoded in several batches (a WINDOWED forward-backward,
+ * csrc/ctc_fb_window.hip).  The window, its policy and its limits (rvb_ctc_align_long_limits) are the long alignment's, except that the
+ * window follows the first maximum of the normalised forward row over the states that can still reach the end.
+ * Band semantics.  lo_of[t], the window of the launch that computes frame t, is a multiple of 32 and never decreases.  Cell (t, s) is
+ * alive iff lo_of[t] <= s < min(lo_of[t] + W, S).  A transition (t-1, s') -> (t, s) counts iff both cells are alive and
+ * s' >= lo_of[t].  loglik is the full sum over the paths made of counted transitions (<= the full sum of the whole lattice), and the
+ * posteriors are those of that sum: over the alive states of a frame they add up to 1.
+ * Bit-identity.  With W >= 2 n_tokens + 1 rounded up to 32 the window never moves: loglik and all four per-token outputs are then
+ * rvb_ctc_score's bit for bit, however the batches cut the recording.
+ *   begin      tokens as rvb_ctc_score's (RVB_CTC_WILDCARD is an id outside the vocabulary); total_frames, window_states and the
+ *              refusals as rvb_ctc_align_long_begin's, all before any device work.  posteriors != 0 keeps the forward rows,
+ *              total_frames x W x 4 bytes (RVB_E_NOMEM naming them).  begin while a lattice is open replaces it.
+ *   feed       after rvb_encode, batches in ASCENDING order: every valid frame of every chunk continues the forward sweep.
+ *              RVB_E_STATE before begin, before rvb_encode, or when the batch holds more frames than the lattice has left.
+ *   loglik     RVB_E_STATE unless exactly total_frames were fed.  RVB_E_ARG "infeasible: no path inside the window ..." when the
+ *              score is -inf; the output is then untouched.
+ *   feed_back  needs posteriors and loglik; after rvb_encode, the same batches in DESCENDING order: each must hold exactly the
+ *              frames the forward sweep saw at that position, else RVB_E_STATE names what was expected.
+ *   finish     RVB_E_STATE unless the backward sweep reached frame 0.  Per token [n_tokens], each nullable, as rvb_ctc_score.
+ *   end        releases the buffers.
+ * rvb_ctc_align_long_*, the one-batch calls and the search stay usable in between. */
+int rvb_ctc_score_long_begin(rvb_engine* e, const int32_t* tokens, int n_tokens, int64_t total_frames, int window_states,
+                             int posteriors);
+int rvb_ctc_score_long_feed(rvb_engine* e);
+int rvb_ctc_score_long_loglik(rvb_engine* e, double* loglik);
+int rvb_ctc_score_long_feed_back(rvb_engine* e);
+int rvb_ctc_score_long_finish(rvb_engine* e, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame);
+int rvb_ctc_score_long_end(rvb_engine* e);
+
 /* rvb_ctc_align_wild for a transcript with ALTERNATIVES and OPTIONAL words: each sequence is a left-to-right token GRAPH, and one
  * Viterbi pass (csrc/ctc_graph.hip) picks the reading that was spoken and aligns it.  Sequence i has n_nodes[i] >= 1 nodes in
  * topological order (node_tokens, is_final: concatenated over the sequences).  Node j has a label (a vocab id other than the blank,
@@ -596,7 +626,7 @@ int rvb_comm_destroy(rvb_engine* e);
 /* Stage timing (HIP events on the engine stream).  level 1: every kernel family is bracketed;
  * names: "fbank","subsample","gemm","attention","rownorm","glu_dwconv","ctc_topk","embed",
  * "lse_gather" (the row kernel after the decoders' output layer: rescoring and rvb_attention_score),"search_host","ctc_align_lp" (rvb_ctc_align: CTC head + log-softmax),"ctc_viterbi" (its
- * forward pass + back-trace),"ctc_viterbi_window" (rvb_ctc_align_long_feed / _finish: the windowed launches with their readbacks + back-trace),"ctc_forward" / "ctc_backward" (rvb_ctc_score: the two sweeps),"ctc_graph_forward" / "ctc_graph_backward" (rvb_ctc_score_graph: the two sweeps),"ctc_find" (rvb_ctc_find: the search kernel),"ctc_graph" (rvb_ctc_align_graph:
+ * forward pass + back-trace),"ctc_viterbi_window" (rvb_ctc_align_long_feed / _finish: the windowed launches with their readbacks + back-trace),"ctc_fb_window_forward" / "ctc_fb_window_backward" (rvb_ctc_score_long_*: the two windowed sweeps with their readbacks),"ctc_forward" / "ctc_backward" (rvb_ctc_score: the two sweeps),"ctc_graph_forward" / "ctc_graph_backward" (rvb_ctc_score_graph: the two sweeps),"ctc_find" (rvb_ctc_find: the search kernel),"ctc_graph" (rvb_ctc_align_graph:
  * forward pass + back-trace).  level 2: only the GEMM launches (the dominant kernel; half the
  * events, ~1 % less perturbation of the step).  level 0: off.
  * flops: algorithmic FLOPs launched (gemm/attention only). */

@@ -107,6 +107,12 @@ SIGNATURES = {
     "rvb_ctc_align_long_finish": (C.c_int, [_eng, _i32p, _i32p, _i32p, _f32p, _i32p]),
     "rvb_ctc_align_long_emissions": (C.c_int, [_eng, _i32p, C.c_int, _f32p]),
     "rvb_ctc_align_long_end": (C.c_int, [_eng]),
+    "rvb_ctc_score_long_begin": (C.c_int, [_eng, _i32p, C.c_int, C.c_int64, C.c_int, C.c_int]),
+    "rvb_ctc_score_long_feed": (C.c_int, [_eng]),
+    "rvb_ctc_score_long_loglik": (C.c_int, [_eng, _f64p]),
+    "rvb_ctc_score_long_feed_back": (C.c_int, [_eng]),
+    "rvb_ctc_score_long_finish": (C.c_int, [_eng, _f32p, _f32p, _f32p, _i32p]),
+    "rvb_ctc_score_long_end": (C.c_int, [_eng]),
     "rvb_ctc_align_graph": (C.c_int, [_eng, _i32p, _i32p, _i32p, _i32p, _u8p, C.c_int, _i32p, _i32p, C.c_float, _i32p, _i32p, _i32p, _i32p,
                                       _i32p, _i32p, _i32p, _f32p, _f32p]),
     "rvb_ctc_align_graph_limits": (C.c_int, [_i32p, _i32p, _i32p, _i32p]),
@@ -233,6 +239,8 @@ TEST_SIGNATURES = {
     "rvb_test_ctc_viterbi_graph": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, _f32p, C.c_float, _i32p, _i32p, _i32p, _i32p, _u8p, C.c_int,
                                              C.c_int, _i32p, _i32p, _f32p]),
     "rvb_test_ctc_score": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, _f64p, _f32p, _f32p, _f32p, _i32p]),
+    "rvb_test_ctc_score_window": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _f64p, _f32p, _f32p,
+                                            _f32p, _i32p, _i32p, _i32p]),
     "rvb_test_ctc_score_graph": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, _u8p, C.c_int, C.c_int, _f64p, _f32p,
                                            _f32p, _f32p, _f32p, _i32p]),
     "rvb_test_ctc_score_batch": (C.c_int, [_f32p, _i32p, C.c_int, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _f64p, _f32p, _f32p, _f32p,

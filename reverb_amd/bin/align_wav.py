@@ -8,7 +8,9 @@ shows up in the result as a word / label / token of its own.  --alternatives rea
 `it is {twenty|two zero} [um] goodbye`, and aligns the reading that was spoken; with --graph_score, `<audio>.score.json` holds the
 full-sum log-likelihood over ALL readings and the probability of every word run of the transcript.  A file of more than --max_chunks
 chunks, or a transcript of more than 16 383 tokens, is aligned over several device batches with a windowed lattice (--long_form forces
-it, --window_tokens N sets the window; ReverbASR.align).  Praat .lab / TextGrid output (--gen_praat there) is not written."""
+it, --window_tokens N sets the window; ReverbASR.align).  --score and --posteriors go with the long form too: the score file then
+holds the windowed full-sum score (ReverbASR.score's long path) with the per-token posteriors, and the alignment file is written
+without them; --alternatives, --graph_score and --attention stay within one device batch.  Praat .lab / TextGrid output (--gen_praat there) is not written."""
 from __future__ import annotations
 
 import argparse
@@ -18,7 +20,10 @@ import os
 from pathlib import Path
 
 
-def get_args(argv=None):
+def get_args(argv=None, long_score=False):
+    """long_score=False is the parser's contract for its callers since the long form exists: --long_form / --window_tokens go with
+    the alignment alone.  The tool itself (main) passes True: --score and --posteriors then go with them too (ReverbASR.score's long
+    path); --alternatives, --graph_score and --attention stay within one device batch either way."""
     p = argparse.ArgumentParser(description="align a transcript with your model")
     p.add_argument("--model", default=None, help="reverb model name or a directory with config.yaml and a .pt file")
     p.add_argument("--config", default=None, help="config file")
@@ -56,7 +61,9 @@ def get_args(argv=None):
                    help="long form: tokens of the transcript alive at a frame (default and most: 16384); the json result carries "
                         "window_margin, how close the path came to the window's edge")
     args = p.parse_args(argv)
-    if (args.long_form or args.window_tokens is not None) and (args.score or args.posteriors or args.alternatives):
+    if (args.long_form or args.window_tokens is not None) and (args.alternatives or args.graph_score or args.attention):
+        p.error("--long_form / --window_tokens: --alternatives, --graph_score and --attention stay within one device batch")
+    if (args.long_form or args.window_tokens is not None) and (args.score or args.posteriors) and not long_score:
         p.error("--long_form / --window_tokens: --score, --posteriors and --alternatives stay within one device batch")
     if args.window_tokens is not None and args.window_tokens < 1:
         p.error("--window_tokens must be at least 1")
@@ -76,7 +83,7 @@ def get_args(argv=None):
 
 
 def main(argv=None):
-    args = get_args(argv)
+    args = get_args(argv, long_score=True)
     logging.basicConfig(level=getattr(logging, str(args.log_level).upper(), logging.INFO),
                         format="%(asctime)s %(levelname)s %(message)s")
     from reverb_amd.reverb import ReverbASR, load_model
@@ -88,11 +95,12 @@ def main(argv=None):
         reverb = ReverbASR(args.config, args.checkpoint, gpu=args.gpu, dtype=args.dtype, max_chunks=args.max_chunks)
     with open(args.transcript_file, encoding="utf-8") as f:
         transcript = " ".join(f.read().split())
+    long_form = True if args.long_form or args.window_tokens is not None else None
     out = reverb.align(args.audio_file, transcript=transcript, format=args.format, verbatimicity=args.verbatimicity,
                        chunk_size=args.chunk_size, timings_adjustment=args.timings_adjustment,
-                       posteriors=args.posteriors and args.format == "json", wildcard=args.wildcard,
+                       posteriors=args.posteriors and args.format == "json" and not long_form, wildcard=args.wildcard,
                        wildcard_bias=args.wildcard_bias, alternatives=args.alternatives, window_tokens=args.window_tokens,
-                       long_form=True if args.long_form or args.window_tokens is not None else None)
+                       long_form=long_form)
     if args.format == "json":
         out = json.dumps(out, ensure_ascii=False, indent=1)
     os.makedirs(args.result_dir, exist_ok=True)
@@ -103,7 +111,7 @@ def main(argv=None):
     if args.score or args.graph_score:
         sc = reverb.score(args.audio_file, transcript=transcript, verbatimicity=args.verbatimicity, chunk_size=args.chunk_size,
                           posteriors=args.posteriors or args.graph_score, attention=args.attention, reverse_weight=args.reverse_weight,
-                          alternatives=args.graph_score)
+                          alternatives=args.graph_score, window_tokens=args.window_tokens, long_form=long_form)
         path = os.path.join(args.result_dir, Path(args.audio_file).with_suffix(".score.json").name)
         with open(path, "w", encoding="utf-8") as f:
             f.write(json.dumps(sc, ensure_ascii=False, indent=1))

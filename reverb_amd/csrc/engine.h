@@ -278,6 +278,41 @@ struct CtcWindowAligner {
   void release();
 };
 
+// ---- long-form full-sum scoring (ctc_fb_window.hip): CtcScorer's two sweeps inside CtcWindowAligner's moving window, shared by
+// rvb_ctc_score_long_* and the lab hook.  plan() is CtcWindowAligner::plan without wildcards (no device work), begin() allocates (with
+// posteriors: T x W x 4 bytes of alpha rows, or E_NOMEM naming them), batch() / advance() feed the encoded batches in ascending order
+// (launches cut as the aligner's; the host keeps every launch's frames, window and reported best state), finish_forward() returns
+// loglik; batch_backward() / advance_backward() take the same batches in DESCENDING order, slabs descending within a batch, and replay
+// the recorded launches in reverse; finish_backward() returns the per-token reductions.
+struct CtcWindowScorer {
+  struct Launch { int f0, f1, lo, best; };
+  int L = 0, S = 0, S_pad = 0, T = 0, W = 0, blank = 0;
+  bool open = false, post = false, forward_done = false;
+  std::vector<int32_t> h_tokens, h_rows;           // h_rows: the rows of the batch being fed, its first frame is lattice frame fbase
+  std::vector<Launch> launches;                    // the forward launches in order: they tile [0, fed)
+  std::vector<int> batches;                        // frames of every forward batch, in order
+  int fed = 0, fbase = 0;                          // forward: lattice frames advanced so far
+  int lo = 0, best = -1;                           // the last launch's window and the best state it reported
+  int back = 0, back_batch = 0, cursor = 0;        // backward: frames still to go, batches still to come, launches below the cursor
+  const int32_t* lo_force = nullptr;               // lab hook: the window of launch i, in place of the policy's answer
+  int n_force = 0;
+  size_t row_bytes = 0;
+  DevBuf d_tokens, d_rows, d_alpha, d_seq, d_csum, d_loglik, d_llhat, d_best, d_coff, d_arows, d_beta, d_z, d_acc;
+  int plan(const char* who, const int32_t* tokens, int n_tokens, int64_t total_frames, int window_states, int V, int blank_id);
+  int launch_count(int slab_rows) const;           // launches of a forward sweep fed slab_rows frames at a time (one batch)
+  int rows_fit() const;                            // the lab switch RVB_CTC_SCORE_FAKE_NOMEM_ABOVE against the alpha rows; no device work
+  int begin(hipStream_t s, bool posteriors);
+  int batch(hipStream_t s, const std::vector<int32_t>& rows);
+  bool touches(int r0, int nrows) const;
+  int advance(hipStream_t s, const float* lp, int ld, int r0, int nrows);
+  int finish_forward(hipStream_t s, double* loglik);
+  int batch_backward(hipStream_t s, const std::vector<int32_t>& rows);
+  int advance_backward(hipStream_t s, const float* lp, int ld, int r0, int nrows);
+  int finish_backward(hipStream_t s, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame /* per token, nullable */);
+  void lo_per_frame(int32_t* lo_out /* [fed] */) const;
+  void release();
+};
+
 }  // namespace rvb
 
 struct rvb_engine {
@@ -396,6 +431,7 @@ struct rvb_engine {
   rvb::CtcGraphAligner graph_aligner;   // rvb_ctc_align_graph
   rvb::CtcGraphScorer graph_scorer;     // rvb_ctc_score_graph
   rvb::CtcWindowAligner long_aligner;   // rvb_ctc_align_long_*: its own member, so the calls above stay usable between begin and finish
+  rvb::CtcWindowScorer long_scorer;     // rvb_ctc_score_long_*: likewise
   rvb::DevBuf align_lp, align_tv, align_ti, align_row, align_col, align_out;   // fp32 [LOGIT_SLAB][V] log-softmax slab; gather scratch
 
   // ---- RCCL communicator of the C-ABI collectives (comm.hip; optional) ----

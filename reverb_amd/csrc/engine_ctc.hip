@@ -318,6 +318,80 @@ int rvb_ctc_align_long_end(rvb_engine* e) {
   return OK;
 }
 
+// Long-form full-sum score (ctc_fb_window.hip): rvb_ctc_score's two sweeps inside the aligner's moving window, one lattice over
+// several encoded batches.  feed sweeps the slabs of the encoded batch in ascending order, feed_back the same slabs in descending
+// order (the CTC head is recomputed, as for rvb_ctc_score's backward sweep).  The driver is a member of its own: the long aligner,
+// the one-batch calls and the search stay usable between begin and finish.
+int rvb_ctc_score_long_begin(rvb_engine* e, const int32_t* tokens, int n_tokens, int64_t total_frames, int window_states, int posteriors) {
+  const char* who = "rvb_ctc_score_long_begin";
+  if (!e) { set_error("rvb_ctc_score_long_begin: null engine"); return E_ARG; }
+  CtcWindowScorer& sc = e->long_scorer;
+  sc.open = false;                                 // begin while a lattice is open replaces it, also when this one is refused
+  RVB_TRY(sc.plan(who, tokens, n_tokens, total_frames, window_states, e->cfg.vocab, e->cfg.blank_id));
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  return sc.begin(e->stream, posteriors != 0);
+}
+
+int rvb_ctc_score_long_feed(rvb_engine* e) {
+  if (!e) { set_error("rvb_ctc_score_long_feed: null engine"); return E_ARG; }
+  CtcWindowScorer& sc = e->long_scorer;
+  if (!sc.open) { set_error("rvb_ctc_score_long_feed before rvb_ctc_score_long_begin"); return E_STATE; }
+  if (e->B <= 0) { set_error("rvb_ctc_score_long_feed before rvb_encode"); return E_STATE; }
+  std::vector<int32_t> rows;
+  long_batch_rows(e, &rows);
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(sc.batch(e->stream, rows));              // E_STATE when the batch holds more frames than the lattice has left
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
+  return sweep_slabs(e, slabs, false, "ctc_fb_window_forward", sc, [&](int r0, int nrows) {
+    return sc.advance(e->stream, e->align_lp.as<float>(), e->cfg.vocab, r0, nrows);
+  });
+}
+
+int rvb_ctc_score_long_loglik(rvb_engine* e, double* loglik) {
+  if (!e) { set_error("rvb_ctc_score_long_loglik: null engine"); return E_ARG; }
+  if (!loglik) { set_error("rvb_ctc_score_long_loglik: null argument"); return E_ARG; }
+  CtcWindowScorer& sc = e->long_scorer;
+  if (!sc.open) { set_error("rvb_ctc_score_long_loglik before rvb_ctc_score_long_begin"); return E_STATE; }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  Scope t(e, "ctc_fb_window_forward");
+  return sc.finish_forward(e->stream, loglik);
+}
+
+int rvb_ctc_score_long_feed_back(rvb_engine* e) {
+  if (!e) { set_error("rvb_ctc_score_long_feed_back: null engine"); return E_ARG; }
+  CtcWindowScorer& sc = e->long_scorer;
+  if (!sc.open) { set_error("rvb_ctc_score_long_feed_back before rvb_ctc_score_long_begin"); return E_STATE; }
+  if (!sc.post) { set_error("rvb_ctc_score_long_feed_back: the lattice was begun without posteriors"); return E_STATE; }
+  if (!sc.forward_done) { set_error("rvb_ctc_score_long_feed_back before rvb_ctc_score_long_loglik"); return E_STATE; }
+  if (e->B <= 0) { set_error("rvb_ctc_score_long_feed_back before rvb_encode"); return E_STATE; }
+  std::vector<int32_t> rows;
+  long_batch_rows(e, &rows);
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(sc.batch_backward(e->stream, rows));     // E_STATE unless the batch is the one the forward sweep saw at this position
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
+  return sweep_slabs(e, slabs, true, "ctc_fb_window_backward", sc, [&](int r0, int nrows) {
+    return sc.advance_backward(e->stream, e->align_lp.as<float>(), e->cfg.vocab, r0, nrows);
+  });
+}
+
+int rvb_ctc_score_long_finish(rvb_engine* e, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame) {
+  if (!e) { set_error("rvb_ctc_score_long_finish: null engine"); return E_ARG; }
+  CtcWindowScorer& sc = e->long_scorer;
+  if (!sc.open) { set_error("rvb_ctc_score_long_finish before rvb_ctc_score_long_begin"); return E_STATE; }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  Scope t(e, "ctc_fb_window_backward");
+  return sc.finish_backward(e->stream, occupancy, mean_frame, peak_post, peak_frame);
+}
+
+int rvb_ctc_score_long_end(rvb_engine* e) {
+  if (!e) { set_error("rvb_ctc_score_long_end: null engine"); return E_ARG; }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  e->long_scorer.release();
+  return OK;
+}
+
 // Alignment over token graphs (ctc_graph.hip): the slabs, the wildcard's emission and the second sweep for the confidences are those
 // of ctc_align_impl; what differs is the lattice and that the per-token outputs follow the chosen path.
 int rvb_ctc_align_graph_limits(int32_t* max_nodes, int32_t* max_in_degree, int32_t* max_arcs, int32_t* max_frames) {

@@ -214,6 +214,17 @@ int rvb_test_ctc_viterbi_graph(const float* lp, const int32_t* T, int n_seq, int
  * allocation would: RVB_E_NOMEM naming the byte count, with nothing allocated. */
 int rvb_test_ctc_score(const float* lp, int T, int V, const int32_t* tokens, int L, int blank, int slab_rows, double* loglik_out,
                        float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame);
+/* ctc_fb_window.hip: the windowed forward-backward kernels and the driver rvb_ctc_score_long_* runs, over host log-probs fed
+ * slab_rows frames at a time (forward slabs ascending, backward slabs descending; each slab cut into launches as
+ * rvb_test_ctc_viterbi_window's).  window_states as there.  lo_force (nullable, one entry per launch) replaces the policy's answer
+ * launch by launch: refused unless every entry is a multiple of 32 in [0, S_pad - W], the entries do not decrease and entry 0 is 0.
+ * lo_out [T]: the first state of each frame's window; best_out (nullable, one entry per launch): the state each launch reported.
+ * The four per-token outputs are nullable, and with all four null only the forward sweep runs.  Refuses before any device work,
+ * outputs untouched, what rvb_test_ctc_viterbi_window refuses (no wildcards), a bad lo_force and alpha rows (T x W x 4 bytes) above
+ * RVB_CTC_SCORE_FAKE_NOMEM_ABOVE; a band that holds no path is refused after the forward pass. */
+int rvb_test_ctc_score_window(const float* lp, int T, int V, const int32_t* tokens, int L, int blank, int slab_rows, int window_states,
+                              const int32_t* lo_force, double* loglik_out, float* occupancy, float* mean_frame, float* peak_post,
+                              int32_t* peak_frame, int32_t* lo_out, int32_t* best_out);
 /* the same for n_seq lattices in ONE launch per slab: lp is the lattices' frames concatenated ([sum T][V]), tokens their tokens
  * concatenated; outputs are concatenated alike.  A slab of slab_rows rows may end inside a lattice or span several. */
 int rvb_test_ctc_score_batch(const float* lp, const int32_t* T, int V, const int32_t* tokens, const int32_t* L, int n_seq, int blank,

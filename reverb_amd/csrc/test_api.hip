@@ -759,6 +759,63 @@ int rvb_test_ctc_score_batch(const float* lp, const int32_t* T, int V, const int
                        peak_post, peak_frame);
 }
 
+int rvb_test_ctc_score_window(const float* lp, int T, int V, const int32_t* tokens, int L, int blank, int slab_rows, int window_states,
+                              const int32_t* lo_force, double* loglik_out, float* occupancy, float* mean_frame, float* peak_post,
+                              int32_t* peak_frame, int32_t* lo_out, int32_t* best_out) {
+  const char* who = "rvb_test_ctc_score_window";
+  const std::string me(who);
+  if (!lp || !tokens || !loglik_out || !lo_out) { set_error(me + ": null argument"); return E_ARG; }
+  if (T < 1 || slab_rows < 1) { set_error(me + ": need T >= 1 and slab_rows >= 1"); return E_ARG; }
+  CtcWindowScorer sc;
+  RVB_TRY(sc.plan(who, tokens, L, T, window_states, V, blank));
+  const int n_launch = sc.launch_count(slab_rows);
+  if (lo_force) {
+    for (int i = 0; i < n_launch; ++i) {
+      const int v = lo_force[i];
+      if (v % 32 != 0 || v < 0 || v > sc.S_pad - sc.W || (i == 0 ? v != 0 : v < lo_force[i - 1])) {
+        set_error(me + ": lo_force[" + std::to_string(i) + "] = " + std::to_string(v) + " must be a multiple of 32 in [0, " +
+                  std::to_string(sc.S_pad - sc.W) + "], not below the entry before it, and 0 for launch 0");
+        return E_ARG;
+      }
+    }
+    sc.lo_force = lo_force;
+    sc.n_force = n_launch;
+  }
+  const bool post = occupancy || mean_frame || peak_post || peak_frame;
+  if (post) RVB_TRY(sc.rows_fit());
+  RVB_TRY(need_gpu());
+  Dev dlp;
+  std::vector<int32_t> rows((size_t)T);
+  for (int t = 0; t < T; ++t) rows[t] = t;
+  double ll = 0.0;
+  int r = up_raw(dlp, lp, (size_t)T * V * 4);
+  if (r == OK) r = sc.begin(nullptr, post);
+  if (r == OK) r = sc.batch(nullptr, rows);
+  r = feed_slabs(r, T, slab_rows, false, [&](int r0, int n) { return sc.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, n); });
+  if (r == OK) r = sc.finish_forward(nullptr, &ll);
+  std::vector<float> occ((size_t)L), mean((size_t)L), peak((size_t)L);
+  std::vector<int32_t> pf((size_t)L);
+  if (r == OK && post) {
+    r = sc.batch_backward(nullptr, rows);
+    r = feed_slabs(r, T, slab_rows, true, [&](int r0, int n) { return sc.advance_backward(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, n); });
+    if (r == OK) r = sc.finish_backward(nullptr, occ.data(), mean.data(), peak.data(), pf.data());
+  }
+  if (r != OK) (void)hipDeviceSynchronize();
+  const std::vector<CtcWindowScorer::Launch> launches = sc.launches;
+  sc.release();
+  RVB_TRY(r);                                      // nothing was written so far: a refusal leaves every output untouched
+  *loglik_out = ll;
+  for (const auto& m : launches)
+    for (int t = m.f0; t < m.f1; ++t) lo_out[t] = m.lo;
+  if (best_out)
+    for (size_t i = 0; i < launches.size(); ++i) best_out[i] = launches[i].best;
+  if (occupancy) memcpy(occupancy, occ.data(), (size_t)L * 4);
+  if (mean_frame) memcpy(mean_frame, mean.data(), (size_t)L * 4);
+  if (peak_post) memcpy(peak_post, peak.data(), (size_t)L * 4);
+  if (peak_frame) memcpy(peak_frame, pf.data(), (size_t)L * 4);
+  return OK;
+}
+
 int rvb_test_ctc_score_graph(const float* lp, const int32_t* T, int n_seq, int V, const int32_t* node_tokens, const int32_t* n_nodes,
                              const int32_t* pred_off, const int32_t* preds, const uint8_t* is_final, int blank, int slab_rows,
                              double* loglik_out, float* visit, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame) {

@@ -659,6 +659,42 @@ class Engine:
     def align_long_end(self):
         check(self.lib.rvb_ctc_align_long_end(self.handle), "rvb_ctc_align_long_end")
 
+    # ---- long-form full-sum score (rvb_ctc_score_long_*, csrc/ctc_fb_window.hip): score() of one transcript over several batches
+    def score_long_begin(self, tokens, total_frames, window_states=0, posteriors=False):
+        """Open ONE full-sum lattice of `tokens` over total_frames valid encoder frames; window_states as align_long_begin's.
+        posteriors=True keeps the forward rows (total_frames x window x 4 bytes) for the backward sweep.  -> the window in use."""
+        tok = np.ascontiguousarray(tokens, np.int32).reshape(-1)
+        self._score_long_tokens = int(tok.size)
+        check(self.lib.rvb_ctc_score_long_begin(self.handle, iptr(tok if tok.size else np.zeros(1, np.int32)), int(tok.size),
+                                                int(total_frames), int(window_states), int(bool(posteriors))), "rvb_ctc_score_long_begin")
+        return min(int(window_states) or 32768, (2 * tok.size + 1 + 31) // 32 * 32)
+
+    def score_long_feed(self):
+        """After encode(), batches in ascending order: every valid frame of the encoded batch continues the forward sweep."""
+        check(self.lib.rvb_ctc_score_long_feed(self.handle), "rvb_ctc_score_long_feed")
+
+    def score_long_loglik(self):
+        """-> loglik (fp64) once every frame was fed."""
+        ll = np.empty(1, np.float64)
+        check(self.lib.rvb_ctc_score_long_loglik(self.handle, dptr(ll)), "rvb_ctc_score_long_loglik")
+        return float(ll[0])
+
+    def score_long_feed_back(self):
+        """After score_long_loglik() and encode(), the same batches in DESCENDING order: the backward sweep (needs posteriors)."""
+        check(self.lib.rvb_ctc_score_long_feed_back(self.handle), "rvb_ctc_score_long_feed_back")
+
+    def score_long_finish(self):
+        """-> dict of per-token occupancy, mean_frame, peak_posterior, peak_frame (frames within the lattice), as score()'s."""
+        n = getattr(self, "_score_long_tokens", 0)
+        occ, mean, peak = (np.empty(max(n, 1), np.float32) for _ in range(3))
+        pkf = np.empty(max(n, 1), np.int32)
+        check(self.lib.rvb_ctc_score_long_finish(self.handle, fptr(occ), fptr(mean), fptr(peak), iptr(pkf)), "rvb_ctc_score_long_finish")
+        return {"occupancy": occ[:n].tolist(), "mean_frame": mean[:n].tolist(), "peak_posterior": peak[:n].tolist(),
+                "peak_frame": pkf[:n].tolist()}
+
+    def score_long_end(self):
+        check(self.lib.rvb_ctc_score_long_end(self.handle), "rvb_ctc_score_long_end")
+
     def align_graph(self, graphs, chunk_ranges=None, wildcard_bias=0.0):
         """align_wild() for transcripts with alternatives and optional words (rvb_ctc_align_graph, csrc/ctc_graph.hip): each sequence
         is a token_graph.TokenGraph, and one Viterbi pass picks the reading that was spoken and aligns it.  -> List[AlignResult]

@@ -458,7 +458,8 @@ class ReverbASR:
         return n_chunks
 
     def score(self, audio_file, transcript: Optional[str] = None, tokens=None, verbatimicity: float = 1.0, chunk_size: int = 2051,
-              posteriors: bool = False, attention: bool = False, reverse_weight: Optional[float] = None, alternatives: bool = False):
+              posteriors: bool = False, attention: bool = False, reverse_weight: Optional[float] = None, alternatives: bool = False,
+              window_tokens: Optional[int] = None, long_form: Optional[bool] = None):
         """How likely a KNOWN transcript is under the model: the full-sum CTC log-likelihood, the negative of what the reference
         calls loss_ctc (CTC.forward, transformer/ctc.py:65-104; bin/get_loss.py), of the transcript as ONE sequence over the whole
         file, tokenised and encoded exactly as align() does.  -> dict: loglik, n_tokens, n_frames, loglik_per_token, viterbi_score
@@ -475,8 +476,17 @@ class ReverbASR:
         same tokens both count.  -> dict: loglik, n_frames, viterbi_score and text (the best reading, from align(alternatives=True))
         and, with posteriors=True, words: one entry per node that opens a run of text, with text, node, probability (the posterior of
         the readings through that node; the branches of a choice, plus the skip of an optional one, sum to 1), occupancy and
-        mean_time (None where the node holds no mass).  tokens= and attention=True are refused."""
+        mean_time (None where the node holds no mass).  tokens= and attention=True are refused.
+        A file of more chunks than the engine batches, or a transcript of more than 16 383 tokens, takes the LONG path (long_form=None:
+        only then; True: always; False: never, such a file is refused): the file is encoded batch by batch and ONE full-sum lattice
+        continues over the batches inside a window of 2 window_tokens states, as align()'s long path does (Engine.score_long_*,
+        csrc/ctc_fb_window.hip); with posteriors=True the batches are encoded a second time, in reverse order, for the backward
+        sweep.  The result then also holds window_states and window_margin (align's); loglik is the sum over the paths inside the
+        windows, and a loglik below viterbi_score logs a warning: score again with a larger window_tokens.  attention=True and
+        alternatives=True are refused there."""
         from .ctc_align import posteriors_to_json
+        if window_tokens is not None and int(window_tokens) < 1:
+            raise ValueError("score: window_tokens must be at least 1")
         if alternatives and (tokens is not None or attention):
             raise ValueError("score: alternatives=True takes transcript= (text) and has no attention loss")
         if (transcript is None) == (tokens is None):
@@ -488,6 +498,8 @@ class ReverbASR:
             raise ValueError("chunk_size must be at least 7 frames (Conv2dSubsampling4 needs 7 input frames, subsampling.py:201-226)")
         if alternatives:
             from .token_graph import parse_alternatives
+            if long_form:
+                raise ValueError("score: alternatives=True stays one-batch (token graphs do not span encoded batches): drop long_form=True")
             graph = parse_alternatives(transcript, lambda text: self.tokenizer.tokenize(text)[1], None)
             eng, _, n_chunks = self._encode_for_align("score", audio_file, transcript, [], verbatimicity, chunk_size)
             res = eng.align_graph([graph], [(0, n_chunks)])[0]
@@ -500,7 +512,17 @@ class ReverbASR:
                 out["words"] = [{"text": graph.words[j], "node": j, "probability": float(sg["visit"][j]), "occupancy": p["occupancy"],
                                  "mean_time": p["mean_time"] if p["occupancy"] > 0 else None} for j, p in zip(opens, per)]
             return out
-        eng, ids, n_chunks = self._encode_for_align("score", audio_file, transcript, tokens, verbatimicity, chunk_size)
+        eng, ids, n_frames, n_chunks = self._prepare_for_align(audio_file, transcript, tokens, verbatimicity, chunk_size)
+        fits = n_chunks <= eng.cfg.max_chunks and len(ids) <= ALIGN_MAX_TOKENS
+        if long_form or (long_form is None and not fits):
+            if attention:
+                raise ValueError("score: attention=True stays one-batch (the attention decoder's memory is one chunk): the long path "
+                                 f"scores {n_chunks} chunks of {chunk_size} frames batch by batch"
+                                 + (" -- drop long_form=True" if fits else ""))
+            return self._score_long(eng, ids, n_frames, n_chunks, chunk_size, window_tokens, posteriors)
+        if long_form is False and len(ids) > ALIGN_MAX_TOKENS:
+            raise ValueError(f"score: long_form=False, but the transcript has {len(ids)} tokens and one batch's lattice holds {ALIGN_MAX_TOKENS}")
+        n_chunks = self._encode_prepared("score", eng, n_frames, n_chunks, chunk_size)
         res = eng.align([ids], [(0, n_chunks)])[0]
         sc = eng.score([ids], [(0, n_chunks)], posteriors=posteriors)[0]
         out = {"loglik": sc["loglik"], "n_tokens": sc["n_tokens"], "n_frames": sc["n_frames"],
@@ -516,6 +538,54 @@ class ReverbASR:
             att = eng.score([ids], [(0, 1)], attention=True, reverse_weight=reverse_weight)[0]
             for key in ("loss_ctc", "loss_att", "acc_att", "loss", "att_logp"):
                 out[key] = att[key]
+        return out
+
+    def _score_long(self, eng: Engine, ids, n_frames: int, n_chunks: int, chunk_size: int, window_tokens, posteriors: bool):
+        """The long path of score(): pass 1 encodes the batches in order and feeds both the windowed Viterbi (viterbi_score and
+        window_margin) and the windowed forward sweep; pass 2 (posteriors only) encodes them in reverse order for the backward sweep."""
+        from .ctc_align import AlignResult, posteriors_to_json
+        mc = eng.cfg.max_chunks
+        lens_all = np.full(n_chunks, chunk_size, np.int32)
+        lens_all[-1] = n_frames - (n_chunks - 1) * chunk_size
+        enc_all = np.where(lens_all > 6, (lens_all - 7) // 4 + 1, 0).astype(np.int32)      # Conv2dSubsampling4: frames 6 + 4j < len
+        window = 0 if window_tokens is None else min(32768, -(-2 * int(window_tokens) // 256) * 256)
+        total = int(enc_all.sum())
+
+        def encode(c0):
+            eng.encode(None, lens_all[c0:c0 + mc], 1, 0.0, first_chunk=c0, T0=chunk_size)
+            assert eng.encoder_lens().tolist() == enc_all[c0:c0 + mc].tolist(), "encoder frames differ from the subsampling arithmetic"
+
+        starts = list(range(0, n_chunks, mc))
+        eng.align_long_begin(ids, total, window, 0.0)
+        try:
+            used = eng.score_long_begin(ids, total, window, posteriors)
+            for c0 in starts:
+                encode(c0)
+                eng.align_long_feed()
+                eng.score_long_feed()
+            labels, begin, end, vit, margin = eng.align_long_finish()
+            loglik = eng.score_long_loglik()
+            post = None
+            if posteriors:
+                for c0 in reversed(starts):
+                    encode(c0)
+                    eng.score_long_feed_back()
+                post = eng.score_long_finish()
+        finally:
+            eng.align_long_end()
+            eng.score_long_end()
+        if loglik < vit - 1e-5 * total:
+            logging.getLogger(__name__).warning(
+                "score: loglik %.3f lies below viterbi_score %.3f: the scoring window of %d states lost the best path; "
+                "score again with a larger window_tokens (now %d)", loglik, vit, used, used // 2)
+        out = {"loglik": loglik, "n_tokens": len(ids), "n_frames": total, "loglik_per_token": loglik / len(ids),
+               "viterbi_score": float(vit), "window_states": used, "window_margin": margin}
+        if post is not None:
+            res = AlignResult([int(t) for t in ids], labels.tolist(), begin.tolist(), end.tolist(), begin.tolist(),
+                              [0.0] * len(begin), vit, 0, enc_all.tolist())
+            per = posteriors_to_json(res, post, chunk_size, self.input_frame_length, self.output_frame_length)
+            for key in ("occupancy", "mean_time", "peak_posterior"):
+                out[key] = [p[key] for p in per]
         return out
 
     def find(self, audio_file, phrases: Optional[List[str]] = None, phrase_file: Optional[str] = None, min_score: float = -1.0,
