@@ -417,6 +417,48 @@ int rvb_ctc_align_graph(rvb_engine* e, const int32_t* node_tokens, const int32_t
                         int32_t* begin, int32_t* end, int32_t* peak, float* confidence, float* score);
 int rvb_ctc_align_graph_limits(int32_t* max_nodes, int32_t* max_in_degree, int32_t* max_arcs, int32_t* max_frames);
 
+/* LONG-FORM alignment of a transcript with alternatives: rvb_ctc_align_graph for ONE graph of any number of nodes and arcs over a
+ * recording that is encoded in several batches (a WINDOWED graph Viterbi, csrc/ctc_graph_window.hip), by the protocol of
+ * rvb_ctc_align_long_*.  Graph, labels, predecessor lists, finals, the states B_start, T_j, B_j, the candidate order and "first
+ * maximum wins" are rvb_ctc_align_graph's.  The band is new:
+ *   W nodes are alive at a frame: window_nodes, 0 (the default, 8192) or a multiple of 256 in [256, 8192], reduced to the node count
+ *   rounded up to 64 when the graph is smaller.  lo_of[t], the window of the launch that computes frame t, is a multiple of 64 and
+ *   never decreases; lo_of[0] = 0.  Node j is alive at t iff lo_of[t] <= j < min(lo_of[t] + W, n_nodes); B_start iff lo_of[t] == 0.
+ *   A predecessor candidate p -> T_j at frame t counts iff j is alive at t and p >= lo_of[t] (p = -1: iff lo_of[t] == 0); the stay
+ *   candidates of an alive node always count.  A node above every window so far holds -inf, one below lo is never read again, a
+ *   candidate that does not count is -inf and never wins (the comparison is strict).  The path ends in the best of B_f, T_f over
+ *   the final nodes alive at the last frame, ascending, first maximum.
+ * With W >= n_nodes rounded up to 64 the window never moves: labels, frame nodes, path and score are rvb_ctc_align_graph's bit for
+ * bit, however the batches cut the recording.  Otherwise the result is the best path inside the windows, with an exact fp32 score
+ * of its own, and min_margin is that path's smallest distance in nodes to a window edge that is not the graph's own (the lower edge
+ * counts where lo_of[t] > 0, the upper where lo_of[t] + W < n_nodes; blank frames count with their node, B_start frames do not; W
+ * when no frame counts).  The window follows the best partial path; because an arc may jump over many nodes (the alternatives that
+ * were not spoken), a launch lasts only for as long as that path cannot have left through the window's top.
+ *   begin   one graph as rvb_ctc_align_graph's (n_nodes + 1 offsets in pred_off); total_frames = the valid encoder frames of ALL
+ *           batches to come (<= RVB_CTC_ALIGN_MAX_FRAMES).  Refusals in rvb_ctc_align_graph's words by node, all before any device
+ *           work; no node or arc cap, the in-degree cap stays.  Also refused: a bad window_nodes (RVB_E_ARG), a graph whose
+ *           shortest reading needs more frames than total_frames (RVB_E_ARG "infeasible"), and, when the window does not hold the
+ *           whole graph, an arc whose span j - p exceeds W / 2 - 64, a start predecessor counting as j + 1 (RVB_E_UNSUPPORTED
+ *           naming the node and the span: ask for a wider window).  Back-pointers take total_frames x W bytes (RVB_E_NOMEM naming
+ *           them).  begin while a lattice is open replaces it.
+ *   feed    after rvb_encode, as rvb_ctc_align_long_feed.  RVB_E_STATE before begin, before rvb_encode, or when the batch holds
+ *           more frames than the lattice has left.
+ *   finish  RVB_E_STATE unless exactly total_frames were fed.  labels / frame_node [total_frames], path_len [1], path_nodes /
+ *           begin / end [n_nodes] per path position, score, min_margin (each nullable), as rvb_ctc_align_graph defines them.
+ *           RVB_E_ARG "infeasible: no path inside the window ..." when the score is -inf; outputs are then untouched.
+ *   end     releases the buffers.
+ * Peaks and confidences: encode the batches a second time and pass each its part of finish's labels to
+ * rvb_ctc_align_long_emissions, which needs no open lattice.  The one-batch calls, rvb_ctc_align_long_*, rvb_ctc_score_long_* and
+ * the search stay usable between begin and finish.  Not offered: a windowed full sum over graphs, per-node posteriors on this path,
+ * several graphs per call. */
+int rvb_ctc_align_graph_long_limits(int32_t* max_frames, int32_t* max_in_degree, int32_t* max_window_nodes, int32_t* default_window_nodes);
+int rvb_ctc_align_graph_long_begin(rvb_engine* e, const int32_t* node_tokens, int n_nodes, const int32_t* pred_off, const int32_t* preds,
+                                   const uint8_t* is_final, int64_t total_frames, int window_nodes, float wildcard_bias);
+int rvb_ctc_align_graph_long_feed(rvb_engine* e);
+int rvb_ctc_align_graph_long_finish(rvb_engine* e, int32_t* labels, int32_t* frame_node, int32_t* path_len, int32_t* path_nodes,
+                                    int32_t* begin, int32_t* end, float* score, int32_t* min_margin);
+int rvb_ctc_align_graph_long_end(rvb_engine* e);
+
 /* Full-sum CTC score of a KNOWN transcript: log p(tokens | frames) summed over every alignment, the quantity the reference calls
  * the CTC loss (CTC.forward, asr/wenet/transformer/ctc.py:65-104 = torch.nn.CTCLoss(reduction='sum') over
  * log_softmax(ctc_lo(encoder_out)), reported by bin/get_loss.py): loglik = -loss.  Valid after rvb_encode / rvb_stream_finish; the

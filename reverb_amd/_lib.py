@@ -116,6 +116,11 @@ SIGNATURES = {
     "rvb_ctc_align_graph": (C.c_int, [_eng, _i32p, _i32p, _i32p, _i32p, _u8p, C.c_int, _i32p, _i32p, C.c_float, _i32p, _i32p, _i32p, _i32p,
                                       _i32p, _i32p, _i32p, _f32p, _f32p]),
     "rvb_ctc_align_graph_limits": (C.c_int, [_i32p, _i32p, _i32p, _i32p]),
+    "rvb_ctc_align_graph_long_limits": (C.c_int, [_i32p, _i32p, _i32p, _i32p]),
+    "rvb_ctc_align_graph_long_begin": (C.c_int, [_eng, _i32p, C.c_int, _i32p, _i32p, _u8p, C.c_int64, C.c_int, C.c_float]),
+    "rvb_ctc_align_graph_long_feed": (C.c_int, [_eng]),
+    "rvb_ctc_align_graph_long_finish": (C.c_int, [_eng, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _f32p, _i32p]),
+    "rvb_ctc_align_graph_long_end": (C.c_int, [_eng]),
     "rvb_ctc_score": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, _i32p, _f64p, _f32p, _f32p, _f32p, _i32p]),
     "rvb_ctc_score_graph": (C.c_int, [_eng, _i32p, _i32p, _i32p, _i32p, _u8p, C.c_int, _i32p, _i32p, _f64p, _f32p, _f32p, _f32p, _f32p,
                                       _i32p]),
@@ -238,6 +243,10 @@ TEST_SIGNATURES = {
     "rvb_test_ctc_window_next_lo": (C.c_int, [C.c_int] * 7),
     "rvb_test_ctc_viterbi_graph": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, _f32p, C.c_float, _i32p, _i32p, _i32p, _i32p, _u8p, C.c_int,
                                              C.c_int, _i32p, _i32p, _f32p]),
+    "rvb_test_ctc_graph_window": (C.c_int, [_f32p, C.c_int, C.c_int, _f32p, C.c_float, _i32p, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int,
+                                            C.c_int, _i32p, _i32p, _i32p, _f32p, _i32p, _i32p, _i32p]),
+    "rvb_test_ctc_graph_window_next": (C.c_int, [_i32p, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p,
+                                                 _i32p, _i32p, _i32p]),
     "rvb_test_ctc_score": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, _f64p, _f32p, _f32p, _f32p, _i32p]),
     "rvb_test_ctc_score_window": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, C.c_int, C.c_int, C.c_int, C.c_int, _i32p, _f64p, _f32p, _f32p,
                                             _f32p, _i32p, _i32p, _i32p]),

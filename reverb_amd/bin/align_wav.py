@@ -10,7 +10,8 @@ full-sum log-likelihood over ALL readings and the probability of every word run 
 chunks, or a transcript of more than 16 383 tokens, is aligned over several device batches with a windowed lattice (--long_form forces
 it, --window_tokens N sets the window; ReverbASR.align).  --score and --posteriors go with the long form too: the score file then
 holds the windowed full-sum score (ReverbASR.score's long path) with the per-token posteriors, and the alignment file is written
-without them; --alternatives, --graph_score and --attention stay within one device batch.  Praat .lab / TextGrid output (--gen_praat there) is not written."""
+without them; --graph_score and --attention stay within one device batch, and so does --alternatives unless --long_graph asks for
+the windowed graph alignment (--window_nodes N sets its window; any number of chunks and graph nodes).  Praat .lab / TextGrid output (--gen_praat there) is not written."""
 from __future__ import annotations
 
 import argparse
@@ -60,9 +61,23 @@ def get_args(argv=None, long_score=False):
     p.add_argument("--window_tokens", type=int, default=None, metavar="N",
                    help="long form: tokens of the transcript alive at a frame (default and most: 16384); the json result carries "
                         "window_margin, how close the path came to the window's edge")
+    p.add_argument("--long_graph", action="store_true",
+                   help="with --alternatives: align over several device batches with a windowed graph lattice (never taken by itself)")
+    p.add_argument("--window_nodes", type=int, default=None, metavar="N",
+                   help="with --long_graph: graph nodes alive at a frame (default and most: 8192); the json result carries "
+                        "window_margin, how close the path came to the window's edge")
     args = p.parse_args(argv)
     if (args.long_form or args.window_tokens is not None) and (args.alternatives or args.graph_score or args.attention):
-        p.error("--long_form / --window_tokens: --alternatives, --graph_score and --attention stay within one device batch")
+        p.error("--long_form / --window_tokens: --alternatives, --graph_score and --attention stay within one device batch "
+                "(a transcript with alternatives is aligned over several batches by --long_graph)")
+    if args.long_graph and not args.alternatives:
+        p.error("--long_graph aligns a transcript with alternatives: it needs --alternatives")
+    if args.long_graph and (args.graph_score or args.score or args.posteriors or args.attention):
+        p.error("--long_graph: --graph_score, --score, --posteriors and --attention stay within one device batch")
+    if args.window_nodes is not None and not args.long_graph:
+        p.error("--window_nodes goes with --long_graph")
+    if args.window_nodes is not None and args.window_nodes < 1:
+        p.error("--window_nodes must be at least 1")
     if (args.long_form or args.window_tokens is not None) and (args.score or args.posteriors) and not long_score:
         p.error("--long_form / --window_tokens: --score, --posteriors and --alternatives stay within one device batch")
     if args.window_tokens is not None and args.window_tokens < 1:
@@ -95,12 +110,12 @@ def main(argv=None):
         reverb = ReverbASR(args.config, args.checkpoint, gpu=args.gpu, dtype=args.dtype, max_chunks=args.max_chunks)
     with open(args.transcript_file, encoding="utf-8") as f:
         transcript = " ".join(f.read().split())
-    long_form = True if args.long_form or args.window_tokens is not None else None
+    long_form = True if args.long_form or args.window_tokens is not None or args.long_graph else None
     out = reverb.align(args.audio_file, transcript=transcript, format=args.format, verbatimicity=args.verbatimicity,
                        chunk_size=args.chunk_size, timings_adjustment=args.timings_adjustment,
                        posteriors=args.posteriors and args.format == "json" and not long_form, wildcard=args.wildcard,
-                       wildcard_bias=args.wildcard_bias, alternatives=args.alternatives, window_tokens=args.window_tokens,
-                       long_form=long_form)
+                       wildcard_bias=args.wildcard_bias, alternatives=args.alternatives,
+                       window_tokens=args.window_nodes if args.long_graph else args.window_tokens, long_form=long_form)
     if args.format == "json":
         out = json.dumps(out, ensure_ascii=False, indent=1)
     os.makedirs(args.result_dir, exist_ok=True)

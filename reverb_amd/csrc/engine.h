@@ -313,6 +313,51 @@ struct CtcWindowScorer {
   void release();
 };
 
+// ---- long-form alignment over a token graph (ctc_graph_window.hip): ONE graph of any number of nodes whose frames arrive over
+// several encoded batches, shared by rvb_ctc_align_graph_long_* and the lab hook.  Only W consecutive nodes are alive at a frame; the
+// window moves between launches, and both the window and the launch's length come from ctc_graph_window_next: an arc of a graph can
+// climb many nodes at once, so a launch lasts for as long as the highest node the best partial path can have reached stays inside.
+// plan() makes CtcGraphAligner::plan's checks in its words (no node or arc cap; no device work), computes the policy's tables and
+// refuses a graph whose shortest reading needs more frames than there are and, when the window does not hold the graph, an arc whose
+// span exceeds W / 2 - 64; begin() allocates (E_NOMEM naming the back-pointer bytes) and sets alpha to -inf, batch() takes the
+// log-prob rows of the next frames (one encoded batch), advance() runs the kernel over the frames of the batch whose rows lie in the
+// slab (slabs in row order), finish() back-traces: states as CtcGraphAligner's, score, and the path's smallest distance in nodes to
+// a window edge that is not the graph's own.
+enum { CTC_GRAPH_WINDOW_MAX_NODES = 8192, CTC_GRAPH_WINDOW_DEFAULT_NODES = 8192 };
+struct CtcGraphWindowTables {
+  int N = 0, startmax = -1;                        // nodes; the highest node with a start predecessor
+  std::vector<int32_t> M;                          // [N]: the largest successor of any node <= j (j itself where there is none)
+  std::vector<int32_t> E;                          // E[r]: the lowest node from which a final one is at most r frames away (r beyond: E.back())
+};
+struct CtcGraphWindowStep { int lo, f1; };
+// the launch that starts at frame f0 of a slab that ends at fend: its window and its end, given the window before and the node of the
+// first-maximum state of the last frame (-1: none finite).  1. lo = 0 at frame 0, else centred on the best node, never back, never
+// past the graph's end; 2. f1 = the frame before which the climber (M applied once a frame) would leave through the window's top, at
+// least f0 + 1, at most fend; 3. lo raised until the window's last node is at least E[T - f1]
+CtcGraphWindowStep ctc_graph_window_next(const CtcGraphWindowTables& g, int T, int W, int f0, int fend, int lo_prev, int best_prev);
+struct CtcGraphWindowAligner {
+  int N = 0, T = 0, W = 0, blank = 0;
+  bool has_wild = false, open = false;
+  float bias = 0.f;
+  CtcGraphWindowTables tab;
+  std::vector<int32_t> h_tokens, h_arc_off, h_finals, h_rows;   // h_rows: the rows of the batch being fed, its first frame is lattice frame fbase
+  std::vector<uint32_t> h_arcs;                    // per arc: the span j - p (start: j + 1) | (first arc: the node has a start arc) << 29 | last of its list << 30 | allow-T << 31
+  int fed = 0, fbase = 0;                          // lattice frames advanced so far
+  int lo = 0, best = -1, launches = 0;             // the last launch's window and the best node it reported
+  const int32_t* lo_force = nullptr;               // lab hook: every slab is ONE launch, in the window lo_force[launch]
+  int n_force = 0;
+  size_t bp_bytes = 0;
+  DevBuf d_tokens, d_arc_off, d_arcs, d_finals, d_rows, d_alpha, d_bp, d_lo, d_best, d_states, d_end;
+  int plan(const char* who, const int32_t* node_tokens, int n_nodes, const int32_t* pred_off, const int32_t* preds, const uint8_t* is_final,
+           int64_t total_frames, int window_nodes, int V, int blank_id, float wildcard_bias);
+  int begin(hipStream_t s);
+  int batch(hipStream_t s, const std::vector<int32_t>& rows);
+  bool touches(int r0, int nrows) const;
+  int advance(hipStream_t s, const float* lp, int ld, int r0, int nrows, const float* wmax = nullptr);
+  int finish(hipStream_t s, int32_t* states /* [T]: 2 * slot + token bit */, float* score, int32_t* min_margin, int32_t* lo_out = nullptr /* [T] */);
+  void release();
+};
+
 }  // namespace rvb
 
 struct rvb_engine {
@@ -432,6 +477,7 @@ struct rvb_engine {
   rvb::CtcGraphScorer graph_scorer;     // rvb_ctc_score_graph
   rvb::CtcWindowAligner long_aligner;   // rvb_ctc_align_long_*: its own member, so the calls above stay usable between begin and finish
   rvb::CtcWindowScorer long_scorer;     // rvb_ctc_score_long_*: likewise
+  rvb::CtcGraphWindowAligner long_graph_aligner;   // rvb_ctc_align_graph_long_*: likewise
   rvb::DevBuf align_lp, align_tv, align_ti, align_row, align_col, align_out;   // fp32 [LOGIT_SLAB][V] log-softmax slab; gather scratch
 
   // ---- RCCL communicator of the C-ABI collectives (comm.hip; optional) ----

@@ -456,6 +456,84 @@ int rvb_ctc_align_graph(rvb_engine* e, const int32_t* node_tokens, const int32_t
   return OK;
 }
 
+// Long-form alignment over a token graph (ctc_graph_window.hip): rvb_ctc_align_long_*'s protocol for ONE graph of any number of
+// nodes.  feed sweeps the slabs of the encoded batch as rvb_ctc_align_long_feed does; peaks and confidences come from a second pass
+// of encodes through rvb_ctc_align_long_emissions, which needs no open lattice.  The driver is a member of its own: the one-batch
+// calls, the long chain calls and the search stay usable between begin and finish.
+int rvb_ctc_align_graph_long_limits(int32_t* max_frames, int32_t* max_in_degree, int32_t* max_window_nodes, int32_t* default_window_nodes) {
+  if (max_frames) *max_frames = CTC_ALIGN_MAX_FRAMES;
+  if (max_in_degree) *max_in_degree = CTC_GRAPH_MAX_IN_DEGREE;
+  if (max_window_nodes) *max_window_nodes = CTC_GRAPH_WINDOW_MAX_NODES;
+  if (default_window_nodes) *default_window_nodes = CTC_GRAPH_WINDOW_DEFAULT_NODES;
+  return OK;
+}
+
+int rvb_ctc_align_graph_long_begin(rvb_engine* e, const int32_t* node_tokens, int n_nodes, const int32_t* pred_off, const int32_t* preds,
+                                   const uint8_t* is_final, int64_t total_frames, int window_nodes, float wildcard_bias) {
+  const char* who = "rvb_ctc_align_graph_long_begin";
+  if (!e) { set_error("rvb_ctc_align_graph_long_begin: null engine"); return E_ARG; }
+  CtcGraphWindowAligner& al = e->long_graph_aligner;
+  al.open = false;                                 // begin while a lattice is open replaces it, also when this one is refused
+  RVB_TRY(al.plan(who, node_tokens, n_nodes, pred_off, preds, is_final, total_frames, window_nodes, e->cfg.vocab, e->cfg.blank_id,
+                  wildcard_bias));
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  return al.begin(e->stream);
+}
+
+int rvb_ctc_align_graph_long_feed(rvb_engine* e) {
+  if (!e) { set_error("rvb_ctc_align_graph_long_feed: null engine"); return E_ARG; }
+  CtcGraphWindowAligner& al = e->long_graph_aligner;
+  if (!al.open) { set_error("rvb_ctc_align_graph_long_feed before rvb_ctc_align_graph_long_begin"); return E_STATE; }
+  if (e->B <= 0) { set_error("rvb_ctc_align_graph_long_feed before rvb_encode"); return E_STATE; }
+  std::vector<int32_t> rows;
+  long_batch_rows(e, &rows);
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(al.batch(e->stream, rows));              // E_STATE when the batch holds more frames than the lattice has left
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
+  return sweep_slabs(e, slabs, false, "ctc_graph_window", al, [&](int r0, int nrows) {
+    return al.advance(e->stream, e->align_lp.as<float>(), e->cfg.vocab, r0, nrows, e->align_tv.as<float>());
+  });
+}
+
+int rvb_ctc_align_graph_long_finish(rvb_engine* e, int32_t* labels, int32_t* frame_node, int32_t* path_len, int32_t* path_nodes,
+                                    int32_t* begin, int32_t* end, float* score, int32_t* min_margin) {
+  if (!e) { set_error("rvb_ctc_align_graph_long_finish: null engine"); return E_ARG; }
+  CtcGraphWindowAligner& al = e->long_graph_aligner;
+  if (!al.open) { set_error("rvb_ctc_align_graph_long_finish before rvb_ctc_align_graph_long_begin"); return E_STATE; }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  std::vector<int32_t> states((size_t)al.T);
+  {
+    Scope sc(e, "ctc_graph_window");
+    RVB_TRY(al.finish(e->stream, states.data(), score, min_margin));   // a refusal leaves every output untouched
+  }
+  std::vector<int32_t> node((size_t)al.T);
+  for (int t = 0; t < al.T; ++t) {
+    const int st = states[t], j = (st >> 1) - 1;
+    node[t] = (st & 1) ? j : -1;
+    if (labels) labels[t] = (st & 1) ? al.h_tokens[j] : e->cfg.blank_id;
+  }
+  if (frame_node) memcpy(frame_node, node.data(), node.size() * 4);
+  const std::vector<float> no_emit;
+  int n_path = 0;
+  auto next_on_path = [&](int j) {                 // a run is a node; its outputs go to the next position of the chosen path
+    if (j < 0) return -1;
+    const int k = n_path++;
+    if (path_nodes) path_nodes[k] = j;
+    return k;
+  };
+  run_outputs(node, no_emit, 0, al.T, next_on_path, begin, end, nullptr, nullptr);
+  if (path_len) *path_len = n_path;
+  return OK;
+}
+
+int rvb_ctc_align_graph_long_end(rvb_engine* e) {
+  if (!e) { set_error("rvb_ctc_align_graph_long_end: null engine"); return E_ARG; }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  e->long_graph_aligner.release();
+  return OK;
+}
+
 // Full-sum score (CTC.forward, transformer/ctc.py:65-104) over the same slabs: a forward sweep, and for per-token outputs the slabs
 // once more in descending order for the backward sweep (the CTC head is recomputed, as for the alignment's confidences).
 int rvb_ctc_score(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,

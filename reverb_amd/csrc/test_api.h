@@ -207,6 +207,26 @@ int rvb_test_ctc_window_next_lo(int S, int T, int W, int f0, int f1, int lo_prev
 int rvb_test_ctc_viterbi_graph(const float* lp, const int32_t* T, int n_seq, int V, const float* w, float bias, const int32_t* node_tokens,
                                const int32_t* n_nodes, const int32_t* pred_off, const int32_t* preds, const uint8_t* is_final, int blank,
                                int slab_rows, int32_t* labels_out, int32_t* frame_node_out, float* score_out);
+/* ctc_graph_window.hip: the windowed graph kernels and the driver rvb_ctc_align_graph_long_* runs, for ONE graph (arguments as
+ * rvb_ctc_align_graph_long_begin's) over host log-probs lp [T][V] fed slab_rows frames at a time; w [T] the wildcard's emission less
+ * the bias (nullable when no node is a wildcard).  window_nodes: 0 or a multiple of 256 in [256, 8192], reduced to the nodes rounded
+ * up to 64.  Without lo_force every slab is cut into launches by the policy (ctc_graph_window_next).  lo_force (nullable) replaces
+ * the policy: every slab is then ONE launch, in the window lo_force[slab]; refused unless every entry is a multiple of 64 in
+ * [0, max(0, N rounded up to 64 - W)], the entries do not decrease and entry 0 is 0.  labels_out / frame_node_out [T] as
+ * rvb_test_ctc_viterbi_graph's; lo_out [T]: the first node of each frame's window; min_margin_out: the path's smallest distance to
+ * a window edge that is not the graph's own (W when no frame counts); launches_out: kernel launches of the forward pass.  Refuses
+ * what rvb_ctc_align_graph_long_begin refuses, in the same words, and a bad lo_force, before any device work; a band that holds no
+ * path is refused (RVB_E_ARG) after the pass.  Outputs untouched on every refusal. */
+int rvb_test_ctc_graph_window(const float* lp, int T, int V, const float* w, float bias, const int32_t* node_tokens, int n_nodes,
+                              const int32_t* pred_off, const int32_t* preds, const uint8_t* is_final, int blank, int slab_rows, int window_nodes,
+                              const int32_t* lo_force, int32_t* labels_out, int32_t* frame_node_out, float* score_out, int32_t* lo_out,
+                              int32_t* min_margin_out, int32_t* launches_out);
+/* the host-only window policy (engine.h ctc_graph_window_next) on a given graph (blank id 0): n_query launches, each described by its
+ * first frame f0, its slab's end fend, the window before and the node the launch before reported (-1: none) -> its window and its
+ * end.  Refuses what rvb_ctc_align_graph_long_begin refuses and a query outside the lattice.  No device work. */
+int rvb_test_ctc_graph_window_next(const int32_t* node_tokens, int n_nodes, const int32_t* pred_off, const int32_t* preds,
+                                   const uint8_t* is_final, int T, int V, int window_nodes, int n_query, const int32_t* f0,
+                                   const int32_t* fend, const int32_t* lo_prev, const int32_t* best_prev, int32_t* lo_out, int32_t* f1_out);
 /* ctc_forward_backward.hip: full-sum score of tokens[L] over host log-probs lp [T][V] with the kernels rvb_ctc_score runs, advancing
  * slab_rows frames per launch in both sweeps (forward ascending, backward descending from the last frame).  loglik_out is fp64; the
  * four per-token outputs [L] are nullable, and with all four null only the forward sweep runs.  Refuses what rvb_test_ctc_viterbi

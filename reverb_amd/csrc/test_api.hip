@@ -718,6 +718,83 @@ int rvb_test_ctc_viterbi_graph(const float* lp, const int32_t* T, int n_seq, int
   return OK;
 }
 
+int rvb_test_ctc_graph_window(const float* lp, int T, int V, const float* w, float bias, const int32_t* node_tokens, int n_nodes,
+                              const int32_t* pred_off, const int32_t* preds, const uint8_t* is_final, int blank, int slab_rows, int window_nodes,
+                              const int32_t* lo_force, int32_t* labels_out, int32_t* frame_node_out, float* score_out, int32_t* lo_out,
+                              int32_t* min_margin_out, int32_t* launches_out) {
+  const char* who = "rvb_test_ctc_graph_window";
+  const std::string me(who);
+  if (!lp || !node_tokens || !pred_off || !preds || !is_final || !labels_out || !frame_node_out || !score_out || !lo_out || !min_margin_out ||
+      !launches_out) { set_error(me + ": null argument"); return E_ARG; }
+  if (T < 1 || slab_rows < 1) { set_error(me + ": need T >= 1 and slab_rows >= 1"); return E_ARG; }
+  CtcGraphWindowAligner al;
+  RVB_TRY(al.plan(who, node_tokens, n_nodes, pred_off, preds, is_final, T, window_nodes, V, blank, bias));
+  if (al.has_wild && !w) { set_error(me + ": a graph with wildcards needs w"); return E_ARG; }
+  if (lo_force) {
+    const int n_launch = (T + slab_rows - 1) / slab_rows, top = std::max(0, (al.N + 63) / 64 * 64 - al.W);
+    for (int i = 0; i < n_launch; ++i) {
+      const int v = lo_force[i];
+      if (v % 64 != 0 || v < 0 || v > top || (i == 0 ? v != 0 : v < lo_force[i - 1])) {
+        set_error(me + ": lo_force[" + std::to_string(i) + "] = " + std::to_string(v) + " must be a multiple of 64 in [0, " +
+                  std::to_string(top) + "], not below the entry before it, and 0 for launch 0");
+        return E_ARG;
+      }
+    }
+    al.lo_force = lo_force;
+    al.n_force = n_launch;
+  }
+  RVB_TRY(need_gpu());
+  Dev dlp, dw;
+  std::vector<int32_t> rows((size_t)T), states((size_t)T), los((size_t)T);
+  for (int t = 0; t < T; ++t) rows[t] = t;
+  float score = 0.f;
+  int32_t margin = 0;
+  int r = up_raw(dlp, lp, (size_t)T * V * 4);
+  if (r == OK) r = up_raw(dw, w, (size_t)T * 4);
+  if (r == OK) r = al.begin(nullptr);
+  if (r == OK) r = al.batch(nullptr, rows);
+  r = feed_slabs(r, T, slab_rows, false, [&](int r0, int n) {
+    return al.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, n, w ? (const float*)dw.p + r0 : nullptr);
+  });
+  if (r == OK) r = al.finish(nullptr, states.data(), &score, &margin, los.data());
+  if (r != OK) (void)hipDeviceSynchronize();
+  const int launches = al.launches;
+  al.release();
+  RVB_TRY(r);                                      // nothing was written so far: a refusal leaves every output untouched
+  *score_out = score;
+  *min_margin_out = margin;
+  *launches_out = launches;
+  for (int t = 0; t < T; ++t) {
+    const int st = states[t], node = (st >> 1) - 1;
+    frame_node_out[t] = (st & 1) ? node : -1;
+    labels_out[t] = (st & 1) ? node_tokens[node] : blank;
+    lo_out[t] = los[t];
+  }
+  return OK;
+}
+
+int rvb_test_ctc_graph_window_next(const int32_t* node_tokens, int n_nodes, const int32_t* pred_off, const int32_t* preds,
+                                   const uint8_t* is_final, int T, int V, int window_nodes, int n_query, const int32_t* f0,
+                                   const int32_t* fend, const int32_t* lo_prev, const int32_t* best_prev, int32_t* lo_out, int32_t* f1_out) {
+  const char* who = "rvb_test_ctc_graph_window_next";
+  const std::string me(who);
+  if (!f0 || !fend || !lo_prev || !best_prev || !lo_out || !f1_out || n_query < 0) { set_error(me + ": null argument"); return E_ARG; }
+  CtcGraphWindowAligner al;
+  RVB_TRY(al.plan(who, node_tokens, n_nodes, pred_off, preds, is_final, T, window_nodes, V, 0, 0.f));
+  const int top = std::max(0, (al.N + 63) / 64 * 64 - al.W);
+  for (int i = 0; i < n_query; ++i)
+    if (f0[i] < 0 || f0[i] >= fend[i] || fend[i] > T || lo_prev[i] < 0 || lo_prev[i] > top || lo_prev[i] % 64 != 0 || best_prev[i] < -1 ||
+        best_prev[i] >= al.N) {
+      set_error(me + ": query " + std::to_string(i) + " is outside the lattice");
+      return E_ARG;
+    }
+  for (int i = 0; i < n_query; ++i) {
+    const CtcGraphWindowStep st = ctc_graph_window_next(al.tab, T, al.W, f0[i], fend[i], lo_prev[i], best_prev[i]);
+    lo_out[i] = st.lo; f1_out[i] = st.f1;
+  }
+  return OK;
+}
+
 static int ctc_score_lab(const char* who, const float* lp, const int32_t* T, int V, const int32_t* tokens, const int32_t* L, int n_seq,
                          int blank, int slab_rows, double* loglik_out, float* occupancy, float* mean_frame, float* peak_post,
                          int32_t* peak_frame) {

@@ -725,6 +725,41 @@ class Engine:
             t0 += len(g); f0 += frames[i]
         return out
 
+    # ---- long-form graph alignment (rvb_ctc_align_graph_long_*, csrc/ctc_graph_window.hip): one graph over several encoded batches
+    def align_graph_long_begin(self, graph, total_frames, window_nodes=0, wildcard_bias=0.0):
+        """Open ONE lattice of `graph` (a token_graph.TokenGraph of any number of nodes) over total_frames valid encoder frames, which
+        the encoded batches to come deliver through align_graph_long_feed().  window_nodes: 0 (the default, 8192) or a multiple of
+        256 in [256, 8192]: the nodes alive at a frame.  -> the window in use (reduced to the graph rounded up to 64 nodes)."""
+        from ._lib import u8ptr
+        tok, off, prd, fin = (np.ascontiguousarray(a) for a in graph.arrays())
+        self._long_graph = graph
+        self._long_graph_frames = int(total_frames)
+        check(self.lib.rvb_ctc_align_graph_long_begin(self.handle, iptr(tok), int(tok.size), iptr(off), iptr(prd), u8ptr(fin),
+                                                      int(total_frames), int(window_nodes), float(wildcard_bias)),
+              "rvb_ctc_align_graph_long_begin")
+        return min(int(window_nodes) or 8192, (len(graph) + 63) // 64 * 64)
+
+    def align_graph_long_feed(self):
+        """After encode(): every valid frame of the encoded batch, in chunk order, continues the lattice."""
+        check(self.lib.rvb_ctc_align_graph_long_feed(self.handle), "rvb_ctc_align_graph_long_feed")
+
+    def align_graph_long_finish(self):
+        """-> (labels [total_frames], frame_node [total_frames], path nodes, begin, end (per path position), score, min_margin) once
+        every frame was fed; min_margin is the path's smallest distance, in nodes, to a window edge that is not the graph's own."""
+        graph = getattr(self, "_long_graph", None)
+        n, nn = getattr(self, "_long_graph_frames", 0), len(graph) if graph is not None else 0
+        labels, fnode = np.empty(max(n, 1), np.int32), np.empty(max(n, 1), np.int32)
+        path, begin, end = (np.empty(max(nn, 1), np.int32) for _ in range(3))
+        plen, score, margin = np.zeros(1, np.int32), np.empty(1, np.float32), np.empty(1, np.int32)
+        check(self.lib.rvb_ctc_align_graph_long_finish(self.handle, iptr(labels), iptr(fnode), iptr(plen), iptr(path), iptr(begin),
+                                                       iptr(end), fptr(score), iptr(margin)), "rvb_ctc_align_graph_long_finish")
+        k = int(plen[0])
+        return labels[:n], fnode[:n], path[:k], begin[:k], end[:k], float(score[0]), int(margin[0])
+
+    def align_graph_long_end(self):
+        check(self.lib.rvb_ctc_align_graph_long_end(self.handle), "rvb_ctc_align_graph_long_end")
+        self._long_graph = None
+
     def find(self, phrases, chunk_ranges=None, min_score=-1.0, max_hits=64, max_candidates=None):
         """Phrase search (rvb_ctc_find, csrc/ctc_find.hip): EVERY occurrence of each token phrase (1 .. 32 ids, none the blank) in the
         chunks of the last encode().  Sequence i covers the chunks chunk_ranges[i] = (first, count); the default is ONE sequence

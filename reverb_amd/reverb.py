@@ -311,8 +311,14 @@ class ReverbASR:
         the whole transcript gives the exact alignment; otherwise the result is the best path inside the windows, json carries
         "window_states" and "window_margin" (the path's smallest distance to a window edge, in states), and a margin below 64 logs
         a warning: align again with a larger window_tokens.  ctm and json encode the file a second time for the confidences.
-        wildcard= works on the long path; alternatives=True and posteriors=True stay one-batch (ValueError on a file that needs
-        the long path).  long_form=False insists on the one-batch path."""
+        wildcard= works on the long path; posteriors=True stays one-batch (ValueError on a file that needs the long path).
+        long_form=False insists on the one-batch path.
+        alternatives=True with long_form=True takes the long GRAPH path (Engine.align_graph_long_*: a windowed graph Viterbi,
+        csrc/ctc_graph_window.hip): a graph of any number of nodes, of which a window of window_tokens NODES (rounded up to 256;
+        default and most: 8192) is alive.  json then carries "window_nodes", "window_margin" (in nodes) and "text".  It is never
+        chosen silently: with long_form=None a file or a graph that does not fit one batch raises ValueError, which names
+        long_form=True.  An arc that jumps over more than window / 2 - 64 nodes (a very long alternative) is refused by the engine:
+        ask for a wider window."""
         from .ctc_align import WILDCARD, DecodeLike, align_to_ali, align_to_json, posteriors_to_json, split_by_chunk, split_transcript
         if (transcript is None) == (tokens is None):
             raise ValueError("align: give exactly one of transcript= (text) or tokens= (ids)")
@@ -328,7 +334,12 @@ class ReverbASR:
             from .token_graph import parse_alternatives
             if tokens is not None:
                 raise ValueError("align: alternatives=True takes transcript= (text)")
-            graph = parse_alternatives(transcript, lambda text: self.tokenizer.tokenize(text)[1], wildcard)
+            try:
+                graph = parse_alternatives(transcript, lambda text: self.tokenizer.tokenize(text)[1], wildcard, long_form=bool(long_form))
+            except ValueError as e:
+                if long_form is None and ("MAX_NODES" in str(e) or "MAX_ARCS" in str(e)):
+                    raise ValueError(f"{e}: long_form=True aligns a graph of any size inside a moving window") from None
+                raise
             if posteriors and WILDCARD in graph.tokens:
                 raise ValueError("align: alternatives=True with a wildcard has no posteriors: the full-sum score has no wildcards")
             tokens = []                                       # nothing to tokenise below
@@ -342,11 +353,27 @@ class ReverbASR:
         eng, ids, n_frames, n_chunks = self._prepare_for_align(audio_file, transcript, tokens, verbatimicity, chunk_size)
         fits = n_chunks <= eng.cfg.max_chunks and len(ids) <= ALIGN_MAX_TOKENS
         if long_form or (long_form is None and not fits):
-            if alternatives or posteriors:
-                raise ValueError("align: alternatives=True and posteriors=True stay one-batch (graphs and full-sum scores do not span "
-                                 f"encoded batches): the file has {n_chunks} chunks of {chunk_size} frames and {len(ids)} tokens, one "
+            if posteriors or (alternatives and not long_form):
+                raise ValueError("align: posteriors=True stays one-batch (full-sum scores do not span encoded batches) and "
+                                 "alternatives=True takes the long path only when asked to: "
+                                 f"the file has {n_chunks} chunks of {chunk_size} frames and {len(ids)} tokens, one "
                                  f"batch holds {eng.cfg.max_chunks} chunks and {ALIGN_MAX_TOKENS} tokens"
-                                 + (" -- or drop long_form=True" if fits else " -- load the model with a larger max_chunks"))
+                                 + (" -- or drop long_form=True" if fits else " -- load the model with a larger max_chunks")
+                                 + ("" if posteriors else ", or pass long_form=True for the windowed graph alignment"))
+            if graph is not None:
+                res, window, margin = self._align_graph_long(eng, graph, n_frames, n_chunks, chunk_size, window_tokens, wildcard_bias,
+                                                             format in ("ctm", "json"))
+                name = Path(audio_file).name
+                if format == "ali":
+                    return align_to_ali(name, res, wildcard)
+                if format == "json":
+                    out = align_to_json(res, self.tokenizer, chunk_size, self.input_frame_length, self.output_frame_length, wildcard)
+                    out["text"] = graph.text_of(res.nodes)
+                    out["window_nodes"], out["window_margin"] = window, margin
+                    return out
+                hyps = [DecodeLike(t, fr, cf, ends=en) for t, fr, cf, en in split_by_chunk(res, ends=True)]
+                return get_output(format, self.tokenizer, name, hyps, timings_adjustment, chunk_size, self.input_frame_length,
+                                  self.output_frame_length, wildcard=wildcard)
             res, window, margin = self._align_long(eng, ids, n_frames, n_chunks, chunk_size, window_tokens,
                                                    wildcard_bias if wildcard is not None else 0.0, format in ("ctm", "json"))
             name = Path(audio_file).name
@@ -388,6 +415,49 @@ class ReverbASR:
         hyps = [DecodeLike(t, fr, cf, ends=en) for t, fr, cf, en in split_by_chunk(res, ends=True)]
         return get_output(format, self.tokenizer, name, hyps, timings_adjustment, chunk_size, self.input_frame_length,
                           self.output_frame_length, wildcard=wildcard)
+
+    def _align_graph_long(self, eng: Engine, graph, n_frames: int, n_chunks: int, chunk_size: int, window_tokens, wildcard_bias: float,
+                          need_emissions: bool):
+        """The long path of align(alternatives=True): _align_long() for a token graph (Engine.align_graph_long_*: a windowed graph
+        Viterbi, csrc/ctc_graph_window.hip) -> (AlignResult of the chosen reading over all chunks, window nodes, window margin)."""
+        from .ctc_align import AlignResult
+        mc = eng.cfg.max_chunks
+        lens_all = np.full(n_chunks, chunk_size, np.int32)
+        lens_all[-1] = n_frames - (n_chunks - 1) * chunk_size
+        enc_all = np.where(lens_all > 6, (lens_all - 7) // 4 + 1, 0).astype(np.int32)      # Conv2dSubsampling4: frames 6 + 4j < len
+        window = 0 if window_tokens is None else min(8192, -(-int(window_tokens) // 256) * 256)
+        used = eng.align_graph_long_begin(graph, int(enc_all.sum()), window, wildcard_bias)
+
+        def batches():
+            for c0 in range(0, n_chunks, mc):
+                eng.encode(None, lens_all[c0:c0 + mc], 1, 0.0, first_chunk=c0, T0=chunk_size)
+                assert eng.encoder_lens().tolist() == enc_all[c0:c0 + mc].tolist(), "encoder frames differ from the subsampling arithmetic"
+                yield int(enc_all[c0:c0 + mc].sum())
+
+        try:
+            for _ in batches():
+                eng.align_graph_long_feed()
+            labels, _, nodes, begin, end, score, margin = eng.align_graph_long_finish()
+            peak, conf = begin.copy(), np.zeros(len(begin), np.float32)
+            if need_emissions:
+                f0, parts = 0, []
+                for n in batches():
+                    parts.append(eng.align_long_emissions(labels[f0:f0 + n]))
+                    f0 += n
+                emit = np.concatenate(parts)
+                for k, (b, e) in enumerate(zip(begin, end)):                             # per run, as rvb_ctc_align_graph does: first maximum
+                    peak[k] = b + int(np.argmax(emit[b:e + 1]))
+                    conf[k] = np.exp(emit[peak[k]])
+        finally:
+            eng.align_graph_long_end()
+        if margin < 64 and margin < used:
+            logging.getLogger(__name__).warning(
+                "align: the path came within %d nodes of the edge of its window of %d nodes; a better path may lie outside: "
+                "align again with a larger window_tokens (now %d)", margin, used, used)
+        nodes = nodes.tolist()
+        res = AlignResult([graph.tokens[j] for j in nodes], labels.tolist(), begin.tolist(), end.tolist(), peak.tolist(), conf.tolist(),
+                          score, 0, enc_all.tolist(), nodes)
+        return res, used, margin
 
     def _align_long(self, eng: Engine, ids, n_frames: int, n_chunks: int, chunk_size: int, window_tokens, wildcard_bias: float,
                     need_emissions: bool):

@@ -13,6 +13,9 @@ predecessor to a final node.  parse_alternatives builds one from text:
 Every maximal run of plain text is tokenised on its own, so a group stands between words, never inside one.  Epsilons do not exist
 in the graph: build(expression, entry set) returns the exit set, and a node's predecessor list is the entry set it was created with,
 nearest node first and -1 last -- the order in which the aligner breaks ties.
+
+The node and arc caps are those of the one-batch calls; long_form=True lifts them (the in-degree cap stays) for the graphs that
+Engine.align_graph_long_* / rvb_ctc_align_graph_long_* align inside a moving window.
 """
 from __future__ import annotations
 
@@ -30,7 +33,7 @@ META = "{}[]|"
 
 class TokenGraph:
     def __init__(self, tokens: Sequence[int], preds: Sequence[Sequence[int]], finals: Sequence[bool],
-                 words: Optional[Sequence[str]] = None):
+                 words: Optional[Sequence[str]] = None, long_form: bool = False):
         self.tokens = [int(t) for t in tokens]
         self.preds = [[int(p) for p in ps] for ps in preds]
         self.finals = [bool(f) for f in finals]
@@ -40,7 +43,7 @@ class TokenGraph:
             raise ValueError("empty graph: no node")
         if not (len(self.preds) == len(self.finals) == len(self.words) == n):
             raise ValueError("tokens, preds, finals and words must have one entry per node")
-        if n > MAX_NODES:
+        if n > MAX_NODES and not long_form:
             raise ValueError("%d nodes exceed RVB_CTC_GRAPH_MAX_NODES = %d" % (n, MAX_NODES))
         for j, ps in enumerate(self.preds):
             if not ps:
@@ -51,7 +54,7 @@ class TokenGraph:
                 raise ValueError("node %d: duplicate predecessor" % j)
             if any(p < -1 or p >= j for p in ps):
                 raise ValueError("node %d: a predecessor must be -1 (start) or an earlier node" % j)
-        if sum(map(len, self.preds)) > MAX_ARCS:
+        if sum(map(len, self.preds)) > MAX_ARCS and not long_form:
             raise ValueError("%d arcs exceed RVB_CTC_GRAPH_MAX_ARCS = %d" % (sum(map(len, self.preds)), MAX_ARCS))
         if not any(self.finals):
             raise ValueError("no final node")
@@ -148,10 +151,11 @@ def _parse(lexed):
     return seq
 
 
-def parse_alternatives(text: str, tokenize: Callable[[str], Sequence[int]], wildcard: Optional[str] = None) -> TokenGraph:
+def parse_alternatives(text: str, tokenize: Callable[[str], Sequence[int]], wildcard: Optional[str] = None,
+                       long_form: bool = False) -> TokenGraph:
     """Text with alternatives -> TokenGraph.  `tokenize` maps a run of plain text to token ids; `wildcard` is the gap marker (a word
     of the text) that becomes a node labelled WILDCARD.  graph.words has one entry per node: the text of the run a node opens (the
-    marker for a wildcard), "" for the further tokens of a run."""
+    marker for a wildcard), "" for the further tokens of a run.  long_form: no node or arc cap (TokenGraph)."""
     if wildcard is not None and (not wildcard or any(c.isspace() for c in wildcard)):
         raise ValueError("the wildcard marker must be one word")
     lexed = _lex(text)
@@ -162,7 +166,7 @@ def parse_alternatives(text: str, tokenize: Callable[[str], Sequence[int]], wild
     words: List[str] = []
 
     def add(label: int, entry: List[int], word: str) -> List[int]:
-        if len(tokens) >= MAX_NODES:
+        if len(tokens) >= MAX_NODES and not long_form:
             raise ValueError("more than RVB_CTC_GRAPH_MAX_NODES = %d nodes" % MAX_NODES)
         if len(entry) > MAX_IN_DEGREE:
             raise ValueError("node %d (%r): in-degree %d exceeds RVB_CTC_GRAPH_MAX_IN_DEGREE = %d" % (len(tokens), word, len(entry), MAX_IN_DEGREE))
@@ -205,6 +209,6 @@ def parse_alternatives(text: str, tokenize: Callable[[str], Sequence[int]], wild
     exits = build(tree, [-1])
     if not tokens or all(x < 0 for x in exits):
         raise ValueError("every path through the text is empty: nothing to align")
-    if sum(map(len, preds)) > MAX_ARCS:
+    if sum(map(len, preds)) > MAX_ARCS and not long_form:
         raise ValueError("%d arcs exceed RVB_CTC_GRAPH_MAX_ARCS = %d" % (sum(map(len, preds)), MAX_ARCS))
-    return TokenGraph(tokens, preds, [j in exits for j in range(len(tokens))], words)
+    return TokenGraph(tokens, preds, [j in exits for j in range(len(tokens))], words, long_form)
