@@ -285,6 +285,28 @@ int rvb_get_ctc_topk(rvb_engine* e, float* vals, int32_t* idx /* [B,T,beam] each
  * without this switch; switching off or to another position frees the kept copies. */
 int rvb_set_encoder_tap(rvb_engine* e, int block);
 int rvb_get_encoder_tap(rvb_engine* e, const char* name, float* out, int64_t capacity);
+/* The same for ONE position of one rescoring decoder (tests only; read-only): side 0 = left, 1 = right decoder; position 0 ..
+ * layers - 1 = that decoder layer, `layers` = the head (final norm, output layer, log-softmax gather), -1 = off (the default).  With a
+ * position selected, every following pass of that decoder over a prefix trie -- rvb_attention_rescore and rvb_attention_score;
+ * rvb_attention_decode and rvb_joint_decode run other code and ignore the switch -- copies every stored tensor of the position,
+ * device to device on the engine's stream.  R = trie rows, M = B * T encoder frames, P = (hypothesis, position) pairs:
+ *   layer:  x_in x_self x_src x_ff [R][d] fp32 (the residual stream on entry and after self attention, cross attention and the feed
+ *           forward); xn1 xn2 xn3 [R][d], qkv [R][3d], ao_self ao_src q [R][d], y [R][d] (language-specific layers only), h [R][ff],
+ *           kvmem [M][2d] (the layer's memory keys | values, made by rvb_prepare_rescoring or by the call): the compute dtype;
+ *           layer 0 also x_emb [R][d] fp32, the embedding's output
+ *   head:   x_in [R][d] fp32, xn_after [R][d] (compute dtype), logits [R][(V + 3) & ~3] fp32 (kept only while R <= 8192, one logit
+ *           slab; refused by name beyond), logp [P] fp32 in slot order (tgt_ptr)
+ *   trie:   the batch as the host built it, int32 carried in floats: 13, the lengths of the 13 arrays, then the arrays tok pos path
+ *           hq_start hq_len hq_pos0 hkv_start hkv_len crow_start crow_len tgt_ptr tgt work (trie_dims: those first 14 values alone)
+ *   forms:  forms[0] = n, then n integers in launch order -- per GEMM of the position 2 (gemm2.hip) or 1 (gemm.hip), per attention the
+ *           eight of its kernel instantiation (element size, padded dk, positional keys, waves, fold, key pad, occupancy, fragments):
+ *           layer = qkv, self attention, self_out, src_q, cross attention, src_out, [language mix,] ff1, ff2; head = the output layer
+ *           once per logit slab.  (The memory K/V GEMM runs before the layers, or in rvb_prepare_rescoring: not listed.)
+ * Refused by name with nothing written and the kept copies untouched: a position on an fp8 engine (RVB_E_UNSUPPORTED), a side or
+ * position out of range (RVB_E_ARG), a name the last pass did not keep (RVB_E_STATE), a buffer too small (RVB_E_ARG).  Off, the decoder
+ * enqueues exactly what it does without this switch; switching off, to another position or side frees the kept copies. */
+int rvb_set_decoder_tap(rvb_engine* e, int side, int position);
+int rvb_get_decoder_tap(rvb_engine* e, const char* name, float* out, int64_t capacity);
 
 /* ctc_greedy_search (search.py:106-121): tokens [B,T] (first ntok[b] valid) and the frame of each
  * token's first emission. */

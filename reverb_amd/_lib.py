@@ -96,6 +96,8 @@ SIGNATURES = {
     "rvb_get_ctc_logprobs": (C.c_int, [_eng, C.c_int, _f32p]),
     "rvb_set_encoder_tap": (C.c_int, [_eng, C.c_int]),
     "rvb_get_encoder_tap": (C.c_int, [_eng, C.c_char_p, _f32p, C.c_int64]),
+    "rvb_set_decoder_tap": (C.c_int, [_eng, C.c_int, C.c_int]),
+    "rvb_get_decoder_tap": (C.c_int, [_eng, C.c_char_p, _f32p, C.c_int64]),
     "rvb_get_ctc_topk": (C.c_int, [_eng, _f32p, _i32p]),
     "rvb_ctc_greedy": (C.c_int, [_eng, _i32p, _i32p, _i32p]),
     "rvb_ctc_align": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p, _f32p, _f32p]),

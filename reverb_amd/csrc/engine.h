@@ -468,6 +468,12 @@ struct rvb_engine {
   struct Tap { rvb::DevBuf buf; size_t elems = 0; bool bf16 = false; };
   std::map<std::string, Tap> taps;  // what the last tapped rvb_encode kept, by name (device copies, made on the engine's stream)
   std::vector<float> tap_forms;     // the forms that ran there: see rvb_get_encoder_tap "forms"
+  // decoder taps (rvb_set_decoder_tap / rvb_get_decoder_tap): the same tap_keep() / tap_note_gemm(); a tapped decoder_forward swaps
+  // these in for `taps` / `tap_forms` while it runs, so the encoder's kept copies and the decoder's never mix
+  int dtap_side = 0, dtap_pos = -1; // side 0 left / 1 right; position -1 off, 0 .. layers - 1 a layer, layers the head
+  int dtap_rows = 0;                // trie rows of the last tapped run
+  std::map<std::string, Tap> dtaps;
+  std::vector<float> dtap_forms, dtap_trie;   // forms as above (+ attention_last_form's eight per attention); the trie's host arrays
 
   // ---- forced alignment (rvb_ctc_align) ----
   rvb::CtcAligner aligner;

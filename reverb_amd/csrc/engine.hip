@@ -108,6 +108,11 @@ int tap_keep(rvb_engine* e, const char* name, const void* src, size_t elems, boo
 void tap_note_gemm(rvb_engine* e) {
   if (e->tap_live) e->tap_forms.push_back((float)gemm_last_path());       // what gemm() itself reports of the call just made
 }
+void tap_note_attention(rvb_engine* e) {
+  if (!e->tap_live) return;
+  const AttnForm f = attention_last_form(false);
+  for (int v : {f.elem_size, f.dkp, f.has_pos, f.nw, f.fold, f.padk, f.occ, f.mf}) e->tap_forms.push_back((float)v);
+}
 // out8 / out2_8 > 0: that output is fp8 bytes of value / scale (the calibrated per-tensor scale of the GEMM that reads it)
 int run_norm(rvb_engine* e, const float* x, const LNorm& n, void* out, bool out_f32, int M, int d, int mode,
              int silu, const void* add, const LNorm* second, void* out2, float out8, float out2_8, bool x_bf16, unsigned* sat,
@@ -303,6 +308,7 @@ void rvb_destroy(rvb_engine* e) {
   if (e->pcm_free) (void)hipEventDestroy(e->pcm_free);
   e->pcm_next.release();
   for (auto& t : e->taps) t.second.buf.release();
+  for (auto& t : e->dtaps) t.second.buf.release();
   (void)hipStreamDestroy(e->stream);
   delete e;
 }

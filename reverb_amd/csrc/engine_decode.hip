@@ -120,11 +120,38 @@ int decoder_memory_kv(rvb_engine* e, Decoder& D, int M) {
 // xent (rvb_attention_score): the slabs go through row_xent instead of lse_gather_multi, which also returns lse, the sum of the
 // logits and the arg-max of every trie row; null (rescoring): the launches are exactly the ones they always were
 struct XentRows { std::vector<float> lse; std::vector<double> sum_x; std::vector<int32_t> top1; };
+// Decoder taps (rvb_set_decoder_tap): while a tapped decoder_forward runs, the decoder's map and forms stand in for the encoder's, so
+// tap_keep / tap_note_gemm / tap_note_attention write there; e->tap_live is raised inside the tapped position only.  Off: nothing.
+struct DecTapScope {
+  rvb_engine* e; bool on;
+  DecTapScope(rvb_engine* e_, bool on_) : e(e_), on(on_) {
+    if (!on) return;
+    std::swap(e->taps, e->dtaps); std::swap(e->tap_forms, e->dtap_forms);
+    e->tap_forms.clear(); e->dtap_trie.clear();
+  }
+  ~DecTapScope() {
+    if (!on) return;
+    e->tap_live = false;
+    std::swap(e->taps, e->dtaps); std::swap(e->tap_forms, e->dtap_forms);
+  }
+};
 static int decoder_forward(rvb_engine* e, Decoder& D, const TrieBatch& t, std::vector<float>* logp, XentRows* xent = nullptr) {
   const rvb_model_cfg& c = e->cfg;
   const int d = c.d_model, heads = c.dec_heads, dk = d / heads, ff = c.dec_ffn_dim, V = c.vocab;
   const int M = e->B * e->T2, R = t.R, nhyp = (int)t.hq_start.size();
   const size_t es = dt_size(e->dtype);
+  const int nlayers = (int)D.layers.size();
+  const int tap_pos = e->dtap_pos >= 0 && &D == (e->dtap_side ? &e->dec_r : &e->dec_l) ? e->dtap_pos : -1;
+  const bool t16 = e->dtype == DT_BF16;
+  DecTapScope taps(e, tap_pos >= 0);
+  if (tap_pos >= 0) {       // the batch as the host built it: [13, the 13 lengths, the arrays], int32 carried in floats
+    const std::vector<int32_t>* arr[13] = {&t.tok, &t.pos, &t.path, &t.hq_start, &t.hq_len, &t.hq_pos0, &t.hkv_start, &t.hkv_len,
+                                           &t.crow_start, &t.crow_len, &t.tgt_ptr, &t.tgt, &t.work};
+    e->dtap_trie.push_back(13.f);
+    for (auto* a : arr) e->dtap_trie.push_back((float)a->size());
+    for (auto* a : arr) for (int32_t v : *a) e->dtap_trie.push_back((float)v);
+    e->dtap_rows = R;
+  }
   RVB_TRY(upload_i32(e, e->d_tok, t.tok.data(), R));
   RVB_TRY(upload_i32(e, e->d_pos, t.pos.data(), R));
   RVB_TRY(upload_i32(e, e->d_tgt, t.tgt.data(), t.P));
@@ -156,11 +183,19 @@ static int decoder_forward(rvb_engine* e, Decoder& D, const TrieBatch& t, std::v
     RVB_TRY(embed_tokens(e->stream, D.embed.as<float>(), e->pe_f32.as<float>(), e->d_tok.as<int>(), e->d_pos.as<int>(),
                          x, R, d, std::sqrt((float)d)));
   }
-  for (auto& L : D.layers) {
+  const size_t Rd = (size_t)R * d;
+  for (int li = 0; li < nlayers; ++li) {
+    DecLayer& L = D.layers[li];
+    e->tap_live = li == tap_pos;
+    if (li == 0) RVB_TRY(tap_keep(e, "x_emb", x, Rd, false));
+    RVB_TRY(tap_keep(e, "x_in", x, Rd, false));
+    RVB_TRY(tap_keep(e, "kvmem", L.kvmem.p, (size_t)M * 2 * d, t16));
     // self attention (causal): a hypothesis' owned rows are the queries, the rows of its whole prefix path the keys
     // decoder_layer.py:91-110, decoder.py:150-156
     RVB_TRY(run_norm(e, x, L.n1, e->dxn.p, false, R, d));
+    RVB_TRY(tap_keep(e, "xn1", e->dxn.p, Rd, t16));
     RVB_TRY(run_gemm(e, e->dxn.p, d, L.self_qkv, e->dqkv.p, 3 * d, R, false));
+    RVB_TRY(tap_keep(e, "qkv", e->dqkv.p, 3 * Rd, t16));
     AttnArgs a;
     memset(&a, 0, sizeof(a));
     a.q = e->dqkv.p; a.k = (const char*)e->dqkv.p + (size_t)d * es; a.v = (const char*)e->dqkv.p + (size_t)2 * d * es;
@@ -172,12 +207,17 @@ static int decoder_forward(rvb_engine* e, Decoder& D, const TrieBatch& t, std::v
     {
       Scope sc(e, "attention");
       RVB_TRY(attention(e->stream, e->dtype, with_lab(a)));
+      tap_note_attention(e);
     }
+    RVB_TRY(tap_keep(e, "ao_self", e->dao.p, Rd, t16));
     RVB_TRY(run_gemm(e, e->dao.p, d, L.self_out, x, d, R, true, 1.f, ACT_NONE, x, d));
+    RVB_TRY(tap_keep(e, "x_self", x, Rd, false));
     // cross attention over the chunk's encoder frames (memory K/V computed once, not per hypothesis:
     // the reference repeats the memory N times, asr_model.py:895)       decoder_layer.py:112-119
     RVB_TRY(run_norm(e, x, L.n2, e->dxn.p, false, R, d));
+    RVB_TRY(tap_keep(e, "xn2", e->dxn.p, Rd, t16));
     RVB_TRY(run_gemm(e, e->dxn.p, d, L.src_q, e->dq.p, d, R, false));
+    RVB_TRY(tap_keep(e, "q", e->dq.p, Rd, t16));
     memset(&a, 0, sizeof(a));
     a.q = e->dq.p; a.k = L.kvmem.p; a.v = (const char*)L.kvmem.p + (size_t)d * es;
     a.q_stride = d; a.k_stride = a.v_stride = 2 * d; a.o_stride = d; a.out = e->dao.p;
@@ -189,23 +229,38 @@ static int decoder_forward(rvb_engine* e, Decoder& D, const TrieBatch& t, std::v
     {
       Scope sc(e, "attention");
       RVB_TRY(attention(e->stream, e->dtype, with_lab(a)));
+      tap_note_attention(e);
     }
+    RVB_TRY(tap_keep(e, "ao_src", e->dao.p, Rd, t16));
     RVB_TRY(run_gemm(e, e->dao.p, d, L.src_out, x, d, R, true, 1.f, ACT_NONE, x, d));
+    RVB_TRY(tap_keep(e, "x_src", x, Rd, false));
     // feed forward (ReLU) with the language-specific mix     decoder_layer.py:121-127 / :313-333
     RVB_TRY(run_norm(e, x, L.n3, e->dxn.p, false, R, d));
+    RVB_TRY(tap_keep(e, "xn3", e->dxn.p, Rd, t16));
     const void* ffin = e->dxn.p;
     if (L.is_lsl) {
       RVB_TRY(run_gemm(e, e->dxn.p, d, L.lsl, e->dy.p, d, R, false));
+      RVB_TRY(tap_keep(e, "y", e->dy.p, Rd, t16));
       ffin = e->dy.p;
     }
     RVB_TRY(run_gemm(e, ffin, d, L.ff1, e->dh.p, ff, R, false, 1.f, ACT_RELU));
+    RVB_TRY(tap_keep(e, "h", e->dh.p, (size_t)R * ff, t16));
     RVB_TRY(run_gemm(e, e->dh.p, ff, L.ff2, x, d, R, true, 1.f, ACT_NONE, x, d));
+    RVB_TRY(tap_keep(e, "x_ff", x, Rd, false));
   }
+  e->tap_live = tap_pos == nlayers;
+  RVB_TRY(tap_keep(e, "x_in", x, Rd, false));
   RVB_TRY(run_norm(e, x, D.after, e->dxn.p, false, R, d));
+  RVB_TRY(tap_keep(e, "xn_after", e->dxn.p, Rd, t16));
   const int Vld = (V + 3) & ~3;
+  if (e->tap_live && R > LOGIT_SLAB) {       // the logits exist one slab at a time: none is kept, and rvb_get_decoder_tap says so
+    auto it = e->taps.find("logits");
+    if (it != e->taps.end()) { it->second.buf.release(); e->taps.erase(it); }
+  }
   for (int r0 = 0; r0 < R; r0 += LOGIT_SLAB) {
     const int rows = std::min(LOGIT_SLAB, R - r0);
     RVB_TRY(run_gemm(e, (const char*)e->dxn.p + (size_t)r0 * d * es, d, D.out, e->logits.p, Vld, rows, true));
+    if (R <= LOGIT_SLAB) RVB_TRY(tap_keep(e, "logits", e->logits.p, (size_t)R * Vld, false));
     Scope sc(e, "lse_gather");
     if (xent)
       RVB_TRY(row_xent(e->stream, e->logits.as<float>(), rows, V, Vld, e->d_tgt_ptr.as<int>() + r0, e->d_tgt.as<int>(),
@@ -214,6 +269,8 @@ static int decoder_forward(rvb_engine* e, Decoder& D, const TrieBatch& t, std::v
       RVB_TRY(lse_gather_multi(e->stream, e->logits.as<float>(), rows, V, Vld, e->d_tgt_ptr.as<int>() + r0, e->d_tgt.as<int>(),
                                e->d_logp.as<float>()));
   }
+  RVB_TRY(tap_keep(e, "logp", e->d_logp.p, (size_t)t.P, false));
+  e->tap_live = false;
   logp->resize(t.P);
   RVB_HIP_CHECK(hipMemcpyAsync(logp->data(), e->d_logp.p, (size_t)t.P * 4, hipMemcpyDeviceToHost, e->stream));
   if (xent) {
@@ -900,6 +957,63 @@ int rvb_attention_score(rvb_engine* e, const int32_t* tokens, const int32_t* tok
     }
   }
   if (!use_r && loss_r) for (int i = 0; i < n_seq; ++i) loss_r[i] = 0.0;
+  return OK;
+}
+
+int rvb_set_decoder_tap(rvb_engine* e, int side, int position) {
+  const std::string w("rvb_set_decoder_tap");
+  if (!e) { set_error(w + ": null engine"); return E_ARG; }
+  if (!e->finalized) { set_error(w + " before rvb_finalize"); return E_STATE; }
+  if (side != 0 && side != 1) { set_error(w + ": side must be 0 (left decoder) or 1 (right decoder)"); return E_ARG; }
+  const Decoder& D = side ? e->dec_r : e->dec_l;
+  if (position >= 0 && !D.present) { set_error(w + ": the model has no such decoder"); return E_STATE; }
+  if (position < -1 || position > (int)D.layers.size()) {
+    set_error(w + ": position must be -1 (off), 0 .. layers - 1, or layers (the head)"); return E_ARG;
+  }
+  if (position >= 0 && e->fp8) { set_error(w + ": not available on an fp8 engine"); return E_UNSUPPORTED; }
+  if (position != e->dtap_pos || side != e->dtap_side) {       // another position, or off: what the taps held is given back
+    RVB_HIP_CHECK(hipSetDevice(e->device));
+    RVB_TRY(wait_slices(e, -1));
+    RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
+    for (auto& t : e->dtaps) t.second.buf.release();
+    e->dtaps.clear(); e->dtap_forms.clear(); e->dtap_trie.clear(); e->dtap_rows = 0;
+  }
+  e->dtap_side = side; e->dtap_pos = position;
+  return OK;
+}
+int rvb_get_decoder_tap(rvb_engine* e, const char* name, float* out, int64_t capacity) {
+  const std::string w("rvb_get_decoder_tap: ");
+  if (!e || !name || !out) { set_error(w + "null argument"); return E_ARG; }
+  const bool forms = !strcmp(name, "forms"), dims = !strcmp(name, "trie_dims"), trie = dims || !strcmp(name, "trie");
+  auto it = e->dtaps.find(name);
+  if ((trie && e->dtap_trie.empty()) || (!forms && !trie && it == e->dtaps.end())) {
+    if (!strcmp(name, "logits") && e->dtap_pos >= 0 && e->dtap_rows > LOGIT_SLAB)
+      set_error(w + "logits are not kept for " + std::to_string(e->dtap_rows) + " trie rows: they exist one slab of " +
+                std::to_string(LOGIT_SLAB) + " rows at a time");
+    else
+      set_error(w + "no tap named " + name + " was kept by the last decoder pass (see rvb_set_decoder_tap)");
+    return E_STATE;
+  }
+  const size_t n = forms ? e->dtap_forms.size() + 1 : dims ? 14 : trie ? e->dtap_trie.size() : it->second.elems;
+  if (capacity < (int64_t)n) {
+    set_error(w + name + " holds " + std::to_string(n) + " values, the buffer " + std::to_string(capacity));
+    return E_ARG;
+  }
+  if (forms) {
+    out[0] = (float)e->dtap_forms.size();
+    for (size_t i = 0; i < e->dtap_forms.size(); ++i) out[1 + i] = e->dtap_forms[i];
+    return OK;
+  }
+  if (trie) { memcpy(out, e->dtap_trie.data(), n * 4); return OK; }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_HIP_CHECK(hipStreamSynchronize(e->stream));
+  if (!it->second.bf16) {
+    RVB_HIP_CHECK(hipMemcpy(out, it->second.buf.p, n * 4, hipMemcpyDeviceToHost));
+  } else {       // widened bit for bit
+    std::vector<bf16_t> tmp(n);
+    RVB_HIP_CHECK(hipMemcpy(tmp.data(), it->second.buf.p, n * 2, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; ++i) out[i] = bf16_to_f32(tmp[i]);
+  }
   return OK;
 }
 

@@ -43,6 +43,7 @@ int run_gemm8(rvb_engine* e, const void* A8, int lda, const Linear& L, void* C, 
 int tap_keep(rvb_engine* e, const char* name, const void* src, size_t elems, bool is_bf16);     // device-to-device copy on the engine's stream
 void tap_note_gemm(rvb_engine* e);       // after a gemm() call: appends which kernel file it chose (gemm_last_path)
 int gemm_last_path();                    // gemm.hip: 2 = gemm2.hip, 1 = gemm.hip -- what gemm() dispatched to last on this thread
+void tap_note_attention(rvb_engine* e);  // after an attention() call: appends the eight integers of attention_last_form
 
 // ---- engine_weights.hip
 int make_fbank_tables(rvb_engine* e);

@@ -537,6 +537,41 @@ class Engine:
         check(self.lib.rvb_get_encoder_tap(self.handle, name.encode(), fptr(out), out.size), "rvb_get_encoder_tap")
         return out
 
+    TRIE_ARRAYS = ("tok", "pos", "path", "hq_start", "hq_len", "hq_pos0", "hkv_start", "hkv_len", "crow_start", "crow_len", "tgt_ptr",
+                   "tgt", "work")
+
+    def set_decoder_tap(self, side: int = 0, position: int = -1):
+        """Parity taps of one position of a rescoring decoder (include/rvb.h rvb_set_decoder_tap): side 0 left / 1 right; position
+        0 .. layers - 1 a decoder layer, `layers` the head, -1 off.  The following rescore() / attention_score() calls keep that
+        position's stored tensors."""
+        check(self.lib.rvb_set_decoder_tap(self.handle, int(side), int(position)), "rvb_set_decoder_tap")
+
+    def decoder_tap(self, name: str):
+        """One tensor the last tapped decoder pass kept, as float32 (bf16 widened bit for bit), [rows, width]; `forms`: a list of
+        ints; `trie`: dict of the int32 arrays TRIE_ARRAYS (see rvb_get_decoder_tap)."""
+        c = self.cfg
+        d = c.d_model
+        if name == "forms":
+            out = np.zeros(256, np.float32)
+            check(self.lib.rvb_get_decoder_tap(self.handle, b"forms", fptr(out), out.size), "rvb_get_decoder_tap")
+            return [int(v) for v in out[1:1 + int(out[0])]]
+        if name == "trie":
+            head = np.zeros(1 + len(self.TRIE_ARRAYS), np.float32)
+            check(self.lib.rvb_get_decoder_tap(self.handle, b"trie_dims", fptr(head), head.size), "rvb_get_decoder_tap")
+            out = np.zeros(head.size + int(head[1:].sum()), np.float32)
+            check(self.lib.rvb_get_decoder_tap(self.handle, b"trie", fptr(out), out.size), "rvb_get_decoder_tap")
+            n = out[1:1 + len(self.TRIE_ARRAYS)].astype(np.int64)
+            assert int(out[0]) == len(self.TRIE_ARRAYS) and out.size == 1 + len(n) + int(n.sum())
+            off = np.concatenate([[0], np.cumsum(n)]) + 1 + len(n)
+            return {k: out[off[i]:off[i + 1]].astype(np.int32) for i, k in enumerate(self.TRIE_ARRAYS)}
+        trie = self.decoder_tap("trie")
+        R, P = len(trie["tok"]), len(trie["tgt"])
+        shape = {"qkv": (R, 3 * d), "h": (R, c.dec_ffn_dim), "kvmem": (self.batch * self.enc_frames, 2 * d),
+                 "logits": (R, (c.vocab + 3) & ~3), "logp": (P,)}.get(name, (R, d))
+        out = np.empty(shape, np.float32)
+        check(self.lib.rvb_get_decoder_tap(self.handle, name.encode(), fptr(out), out.size), "rvb_get_decoder_tap")
+        return out
+
     def ctc_logprobs(self, chunk: int) -> np.ndarray:
         out = np.empty((self.enc_frames, self.cfg.vocab), np.float32)
         check(self.lib.rvb_get_ctc_logprobs(self.handle, int(chunk), fptr(out)))
