@@ -471,8 +471,8 @@ int rvb_ctc_align_graph_limits(int32_t* max_nodes, int32_t* max_in_degree, int32
  *   end     releases the buffers.
  * Peaks and confidences: encode the batches a second time and pass each its part of finish's labels to
  * rvb_ctc_align_long_emissions, which needs no open lattice.  The one-batch calls, rvb_ctc_align_long_*, rvb_ctc_score_long_* and
- * the search stay usable between begin and finish.  Not offered: a windowed full sum over graphs, per-node posteriors on this path,
- * several graphs per call. */
+ * the search stay usable between begin and finish.  The full sum and the per-node posteriors of such a graph come from
+ * rvb_ctc_score_graph_long_* (below), a lattice of its own.  Not offered: several graphs per call. */
 int rvb_ctc_align_graph_long_limits(int32_t* max_frames, int32_t* max_in_degree, int32_t* max_window_nodes, int32_t* default_window_nodes);
 int rvb_ctc_align_graph_long_begin(rvb_engine* e, const int32_t* node_tokens, int n_nodes, const int32_t* pred_off, const int32_t* preds,
                                    const uint8_t* is_final, int64_t total_frames, int window_nodes, float wildcard_bias);
@@ -521,6 +521,44 @@ int rvb_ctc_score(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens,
 int rvb_ctc_score_graph(rvb_engine* e, const int32_t* node_tokens, const int32_t* n_nodes, const int32_t* pred_off,
                         const int32_t* preds, const uint8_t* is_final, int n_seq, const int32_t* first_chunk, const int32_t* n_chunks,
                         double* loglik, float* visit, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame);
+
+/* LONG-FORM full-sum score of a transcript with alternatives: rvb_ctc_score_graph (loglik, and with posteriors the per-node visit,
+ * occupancy, mean frame, peak posterior and its frame) for ONE graph of any number of nodes and arcs over a recording that is encoded
+ * in several batches (a WINDOWED full sum over the graph, csrc/ctc_graph_fb_window.hip), by the protocol of rvb_ctc_score_long_*.
+ * Graph, states, recurrences and the definitions of loglik, the posteriors and visit are rvb_ctc_score_graph's; the states are carried
+ * in fp64 as there.  The band is rvb_ctc_align_graph_long_*'s with log-sum-exp in place of the maximum:
+ *   W nodes are alive at a frame: window_nodes, 0 (the default, 4096) or a multiple of 256 in [256, 4096] (the fp64 states halve the
+ *   aligner's cap), reduced to the node count rounded up to 64.  lo_of[t] is a multiple of 64 and never decreases; lo_of[0] = 0.
+ *   Node j is alive at t iff lo_of[t] <= j < min(lo_of[t] + W, n_nodes); B_start iff lo_of[t] == 0.  A transition into T_j at t from
+ *   predecessor p counts iff j is alive at t and p >= lo_of[t] (p = -1: iff lo_of[t] == 0); stay transitions of an alive node
+ *   always count; a node that was not alive before holds -inf.  loglik is the log-sum over the final nodes alive at the last frame
+ *   (<= the full sum of the whole graph), and the posteriors are those of that sum: over the alive states of a frame they add up
+ *   to 1, also across a window move.  The window follows the first maximum of the normalised forward row over the states that can
+ *   still reach a final end, placed and cut by the aligner's policy.
+ * With W >= n_nodes rounded up to 64 the window never moves: loglik and all five per-node outputs are then rvb_ctc_score_graph's bit
+ * for bit (for graphs of at most 4096 nodes), however the batches cut the recording.
+ *   begin      one graph as rvb_ctc_align_graph_long_begin's; refusals in its words and rvb_ctc_score_graph's (a wildcard; with
+ *              posteriors a node with more than 64 successors; the window; the span; the infeasible shortest reading), all before
+ *              any device work.  posteriors != 0 keeps the forward rows, total_frames x W x 4 bytes (RVB_E_NOMEM naming them).
+ *              begin while a lattice is open replaces it.
+ *   feed       after rvb_encode, batches in ASCENDING order.  RVB_E_STATE before begin, before rvb_encode, or when the batch holds
+ *              more frames than the lattice has left.
+ *   loglik     RVB_E_STATE unless exactly total_frames were fed.  RVB_E_ARG "infeasible: no path inside the window ..." when the
+ *              sum is -inf; the output is then untouched.
+ *   feed_back  needs posteriors and loglik; after rvb_encode, the same batches in DESCENDING order: each must hold exactly the
+ *              frames the forward sweep saw at that position, else RVB_E_STATE names what was expected.
+ *   finish     RVB_E_STATE unless the backward sweep reached frame 0.  Per node [n_nodes], each nullable, as rvb_ctc_score_graph.
+ *   end        releases the buffers.
+ * The one-batch calls, the other long lattices and the search stay usable in between.  Not offered: wildcards in the sum, several
+ * graphs per call. */
+int rvb_ctc_score_graph_long_limits(int32_t* max_frames, int32_t* max_in_degree, int32_t* max_window_nodes, int32_t* default_window_nodes);
+int rvb_ctc_score_graph_long_begin(rvb_engine* e, const int32_t* node_tokens, int n_nodes, const int32_t* pred_off, const int32_t* preds,
+                                   const uint8_t* is_final, int64_t total_frames, int window_nodes, int posteriors);
+int rvb_ctc_score_graph_long_feed(rvb_engine* e);
+int rvb_ctc_score_graph_long_loglik(rvb_engine* e, double* loglik);
+int rvb_ctc_score_graph_long_feed_back(rvb_engine* e);
+int rvb_ctc_score_graph_long_finish(rvb_engine* e, float* visit, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame);
+int rvb_ctc_score_graph_long_end(rvb_engine* e);
 
 /* Phrase search: EVERY occurrence of given short phrases (names, terms) in the audio of the last rvb_encode / rvb_stream_finish, on
  * the device (csrc/ctc_find.hip, one wave per phrase and sequence).  n_phrases phrases, concatenated in `tokens`, tok_lens[p] ids
@@ -690,7 +728,7 @@ int rvb_comm_destroy(rvb_engine* e);
 /* Stage timing (HIP events on the engine stream).  level 1: every kernel family is bracketed;
  * names: "fbank","subsample","gemm","attention","rownorm","glu_dwconv","ctc_topk","embed",
  * "lse_gather" (the row kernel after the decoders' output layer: rescoring and rvb_attention_score),"search_host","ctc_align_lp" (rvb_ctc_align: CTC head + log-softmax),"ctc_viterbi" (its
- * forward pass + back-trace),"ctc_viterbi_window" (rvb_ctc_align_long_feed / _finish: the windowed launches with their readbacks + back-trace),"ctc_fb_window_forward" / "ctc_fb_window_backward" (rvb_ctc_score_long_*: the two windowed sweeps with their readbacks),"ctc_forward" / "ctc_backward" (rvb_ctc_score: the two sweeps),"ctc_graph_forward" / "ctc_graph_backward" (rvb_ctc_score_graph: the two sweeps),"ctc_find" (rvb_ctc_find: the search kernel),"ctc_graph" (rvb_ctc_align_graph:
+ * forward pass + back-trace),"ctc_viterbi_window" (rvb_ctc_align_long_feed / _finish: the windowed launches with their readbacks + back-trace),"ctc_fb_window_forward" / "ctc_fb_window_backward" (rvb_ctc_score_long_*: the two windowed sweeps with their readbacks),"ctc_forward" / "ctc_backward" (rvb_ctc_score: the two sweeps),"ctc_graph_forward" / "ctc_graph_backward" (rvb_ctc_score_graph: the two sweeps),"ctc_graph_fb_window_forward" / "ctc_graph_fb_window_backward" (rvb_ctc_score_graph_long_*: the two windowed sweeps with their readbacks),"ctc_find" (rvb_ctc_find: the search kernel),"ctc_graph" (rvb_ctc_align_graph:
  * forward pass + back-trace).  level 2: only the GEMM launches (the dominant kernel; half the
  * events, ~1 % less perturbation of the step).  level 0: off.
  * flops: algorithmic FLOPs launched (gemm/attention only). */

@@ -126,7 +126,14 @@ SIGNATURES = {
     "rvb_ctc_score": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _i32p, _i32p, _f64p, _f32p, _f32p, _f32p, _i32p]),
     "rvb_ctc_score_graph": (C.c_int, [_eng, _i32p, _i32p, _i32p, _i32p, _u8p, C.c_int, _i32p, _i32p, _f64p, _f32p, _f32p, _f32p, _f32p,
                                       _i32p]),
-    "rvb_ctc_find": (C.c_int, [_eng, _i32p, _i32p, C.c_int, _f32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f32p,
+    "rvb_ctc_score_graph_long_limits": (C.c_int, [_i32p, _i32p, _i32p, _i32p]),
+    "rvb_ctc_score_graph_long_begin": (C.c_int, [_eng, _i32p, C.c_int, _i32p, _i32p, _u8p, C.c_int64, C.c_int, C.c_int]),
+    "rvb_ctc_score_graph_long_feed": (C.c_int, [_eng]),
+    "rvb_ctc_score_graph_long_loglik": (C.c_int, [_eng, _f64p]),
+    "rvb_ctc_score_graph_long_feed_back": (C.c_int, [_eng]),
+    "rvb_ctc_score_graph_long_finish": (C.c_int, [_eng, _f32p, _f32p, _f32p, _f32p, _i32p]),
+    "rvb_ctc_score_graph_long_end": (C.c_int, [_eng]),
+    "rvb_ctc_find":(C.c_int, [_eng, _i32p, _i32p, C.c_int, _f32p, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _f32p,
                                _i64p]),
     "rvb_ctc_prefix_beam": (C.c_int, [_eng, C.c_int]),
     "rvb_set_context_graph": (C.c_int, [_eng, _i32p, _i32p, C.c_int, C.c_double]),
@@ -254,7 +261,9 @@ TEST_SIGNATURES = {
                                             _f32p, _i32p, _i32p, _i32p]),
     "rvb_test_ctc_score_graph": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, _u8p, C.c_int, C.c_int, _f64p, _f32p,
                                            _f32p, _f32p, _f32p, _i32p]),
-    "rvb_test_ctc_score_batch": (C.c_int, [_f32p, _i32p, C.c_int, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _f64p, _f32p, _f32p, _f32p,
+    "rvb_test_ctc_score_graph_window": (C.c_int, [_f32p, C.c_int, C.c_int, _i32p, C.c_int, _i32p, _i32p, _u8p, C.c_int, C.c_int, C.c_int, _i32p,
+                                                  _f64p, _f32p, _f32p, _f32p, _f32p, _i32p, _i32p, _i32p, _i32p]),
+    "rvb_test_ctc_score_batch":(C.c_int, [_f32p, _i32p, C.c_int, _i32p, _i32p, C.c_int, C.c_int, C.c_int, _f64p, _f32p, _f32p, _f32p,
                                            _i32p]),
     "rvb_test_ctc_find": (C.c_int, [_f32p, _i32p, C.c_int, C.c_int, _f32p, _i32p, _i32p, C.c_int, _f32p, C.c_int, C.c_int, C.c_int, C.c_int,
                                     _i64p, _i32p, _i32p, _f32p, _i32p, _i32p, _i32p, _f32p]),

@@ -11,7 +11,8 @@ chunks, or a transcript of more than 16 383 tokens, is aligned over several devi
 it, --window_tokens N sets the window; ReverbASR.align).  --score and --posteriors go with the long form too: the score file then
 holds the windowed full-sum score (ReverbASR.score's long path) with the per-token posteriors, and the alignment file is written
 without them; --graph_score and --attention stay within one device batch, and so does --alternatives unless --long_graph asks for
-the windowed graph alignment (--window_nodes N sets its window; any number of chunks and graph nodes).  Praat .lab / TextGrid output (--gen_praat there) is not written."""
+the windowed graph alignment (--window_nodes N sets its window; any number of chunks and graph nodes); --long_graph_score does
+that and also writes the windowed full-sum score over all readings to `<audio>.score.json` (ReverbASR.score's long graph path).  Praat .lab / TextGrid output (--gen_praat there) is not written."""
 from __future__ import annotations
 
 import argparse
@@ -66,6 +67,10 @@ def get_args(argv=None, long_score=False):
     p.add_argument("--window_nodes", type=int, default=None, metavar="N",
                    help="with --long_graph: graph nodes alive at a frame (default and most: 8192); the json result carries "
                         "window_margin, how close the path came to the window's edge")
+    p.add_argument("--long_graph_score", action="store_true",
+                   help="with --alternatives (no --wildcard): the windowed graph alignment of --long_graph, and <audio>.score.json with "
+                        "the windowed full-sum score over all readings and the probability, occupancy and mean_time of every word run "
+                        "(--window_nodes: at most 4096 here; the file is encoded three times)")
     args = p.parse_args(argv)
     if (args.long_form or args.window_tokens is not None) and (args.alternatives or args.graph_score or args.attention):
         p.error("--long_form / --window_tokens: --alternatives, --graph_score and --attention stay within one device batch "
@@ -74,7 +79,12 @@ def get_args(argv=None, long_score=False):
         p.error("--long_graph aligns a transcript with alternatives: it needs --alternatives")
     if args.long_graph and (args.graph_score or args.score or args.posteriors or args.attention):
         p.error("--long_graph: --graph_score, --score, --posteriors and --attention stay within one device batch")
-    if args.window_nodes is not None and not args.long_graph:
+    if args.long_graph_score and not args.alternatives:
+        p.error("--long_graph_score scores a transcript with alternatives: it needs --alternatives")
+    if args.long_graph_score and (args.wildcard is not None or args.attention or args.score or args.graph_score):
+        p.error("--long_graph_score: the windowed full sum over a graph has no gaps (--wildcard) and no attention loss (--attention), "
+                "and is neither --score nor --graph_score")
+    if args.window_nodes is not None and not (args.long_graph or args.long_graph_score):
         p.error("--window_nodes goes with --long_graph")
     if args.window_nodes is not None and args.window_nodes < 1:
         p.error("--window_nodes must be at least 1")
@@ -110,12 +120,13 @@ def main(argv=None):
         reverb = ReverbASR(args.config, args.checkpoint, gpu=args.gpu, dtype=args.dtype, max_chunks=args.max_chunks)
     with open(args.transcript_file, encoding="utf-8") as f:
         transcript = " ".join(f.read().split())
-    long_form = True if args.long_form or args.window_tokens is not None or args.long_graph else None
+    long_graph = args.long_graph or args.long_graph_score
+    long_form = True if args.long_form or args.window_tokens is not None or long_graph else None
     out = reverb.align(args.audio_file, transcript=transcript, format=args.format, verbatimicity=args.verbatimicity,
                        chunk_size=args.chunk_size, timings_adjustment=args.timings_adjustment,
                        posteriors=args.posteriors and args.format == "json" and not long_form, wildcard=args.wildcard,
                        wildcard_bias=args.wildcard_bias, alternatives=args.alternatives,
-                       window_tokens=args.window_nodes if args.long_graph else args.window_tokens, long_form=long_form)
+                       window_tokens=args.window_nodes if long_graph else args.window_tokens, long_form=long_form)
     if args.format == "json":
         out = json.dumps(out, ensure_ascii=False, indent=1)
     os.makedirs(args.result_dir, exist_ok=True)
@@ -123,10 +134,12 @@ def main(argv=None):
     with open(path, "w", encoding="utf-8") as f:
         f.write(out)
     logging.info("wrote %s", path)
-    if args.score or args.graph_score:
+    if args.score or args.graph_score or args.long_graph_score:
+        graph_score = args.graph_score or args.long_graph_score
         sc = reverb.score(args.audio_file, transcript=transcript, verbatimicity=args.verbatimicity, chunk_size=args.chunk_size,
-                          posteriors=args.posteriors or args.graph_score, attention=args.attention, reverse_weight=args.reverse_weight,
-                          alternatives=args.graph_score, window_tokens=args.window_tokens, long_form=long_form)
+                          posteriors=args.posteriors or graph_score, attention=args.attention, reverse_weight=args.reverse_weight,
+                          alternatives=graph_score, window_tokens=args.window_nodes if args.long_graph_score else args.window_tokens,
+                          long_form=long_form)
         path = os.path.join(args.result_dir, Path(args.audio_file).with_suffix(".score.json").name)
         with open(path, "w", encoding="utf-8") as f:
             f.write(json.dumps(sc, ensure_ascii=False, indent=1))

@@ -19,7 +19,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "librvb.so")
 OUT_TEST = os.path.join(HERE, "librvb_test.so")
-SOURCES = ["gemm.hip", "gemm2.hip", "attention.hip", "elementwise.hip", "softmax_topk.hip", "ctc_viterbi.hip", "ctc_viterbi_window.hip", "ctc_graph.hip", "ctc_graph_window.hip", "ctc_graph_score.hip", "ctc_forward_backward.hip", "ctc_fb_window.hip", "ctc_find.hip", "fbank.hip", "engine.hip", "engine_weights.hip", "engine_encode.hip", "engine_decode.hip", "engine_ctc.hip", "engine_batch.hip", "pause_chunks.hip", "diar.hip", "resnet.hip", "conv_gemm.hip", "conv_stream.hip", "conv_block.hip", "conv_row64.hip", "conv_s2.hip", "linkage.hip", "diar_engine.hip", "comm.hip", "search.cpp", "audio.cpp", "mp3.cpp"]
+SOURCES = ["gemm.hip", "gemm2.hip", "attention.hip", "elementwise.hip", "softmax_topk.hip", "ctc_viterbi.hip", "ctc_viterbi_window.hip", "ctc_graph.hip", "ctc_graph_window.hip", "ctc_graph_score.hip", "ctc_graph_fb_window.hip", "ctc_forward_backward.hip", "ctc_fb_window.hip", "ctc_find.hip", "fbank.hip", "engine.hip", "engine_weights.hip", "engine_encode.hip", "engine_decode.hip", "engine_ctc.hip", "engine_batch.hip", "pause_chunks.hip", "diar.hip", "resnet.hip", "conv_gemm.hip", "conv_stream.hip", "conv_block.hip", "conv_row64.hip", "conv_s2.hip", "linkage.hip", "diar_engine.hip", "comm.hip", "search.cpp", "audio.cpp", "mp3.cpp"]
 PRODUCT_ONLY = ["lab_env_off.cpp"]
 TEST_SOURCES = ["test_api.hip"]
 LINK = {OUT: SOURCES + PRODUCT_ONLY, OUT_TEST: SOURCES + TEST_SOURCES}      # library -> the sources whose objects it is linked from

@@ -358,6 +358,49 @@ struct CtcGraphWindowAligner {
   void release();
 };
 
+// ---- long-form full-sum scoring over a token graph (ctc_graph_fb_window.hip): CtcGraphScorer's two sweeps inside
+// CtcGraphWindowAligner's moving window, shared by rvb_ctc_score_graph_long_* and the lab hook.  plan() makes
+// CtcGraphWindowAligner::plan's checks in its words with this lattice's window cap (the fp64 states halve it), refuses wildcards and,
+// with posteriors, an out-degree above the in-degree cap, and builds the live-set words and the transposed arcs (no device work);
+// begin() allocates (with posteriors: T x W x 4 bytes of alpha rows, or E_NOMEM naming them); batch() / advance() feed the encoded
+// batches in ascending order, the launches cut by ctc_graph_window_next from the best node each launch reports (the host keeps every
+// launch's frames, window and best node); loglik() ends the forward sweep; batch_back() / advance_back() take the same batches in
+// DESCENDING order, slabs descending within a batch, and replay the recorded launches in reverse; finish() returns the per-node
+// reductions.
+enum { CTC_GRAPH_SCORE_WINDOW_MAX_NODES = 4096, CTC_GRAPH_SCORE_WINDOW_DEFAULT_NODES = 4096 };
+struct CtcGraphWindowScorer {
+  struct Launch { int f0, f1, lo, best; };
+  int N = 0, T = 0, W = 0, blank = 0;
+  bool open = false, post = false, forward_done = false;
+  CtcGraphWindowTables tab;
+  std::vector<int32_t> h_tokens, h_arc_off, h_finals, h_rows, h_succ_off;   // h_rows: the rows of the batch being fed, its first frame is lattice frame fbase
+  std::vector<uint32_t> h_arcs;                    // CtcGraphWindowAligner's words
+  std::vector<uint32_t> h_succs;                   // per successor: the span j' - j | last of its list << 30 | T_j' may be entered from T_j << 31
+  std::vector<uint32_t> h_rem;                     // per node: the fewest frames from T_j, from B_j to a final end; then B_start's
+  std::vector<uint8_t> h_fin;
+  std::vector<Launch> launches;                    // the forward launches in order: they tile [0, fed)
+  std::vector<int> batches;                        // frames of every forward batch, in order
+  int fed = 0, fbase = 0;                          // forward: lattice frames advanced so far
+  int lo = 0, best = -1;                           // the last launch's window and the best node it reported
+  int back = 0, back_batch = 0, cursor = 0;        // backward: frames still to go, batches still to come, launches below the cursor
+  const int32_t* lo_force = nullptr;               // lab hook: every slab is ONE launch, in the window lo_force[launch]
+  int n_force = 0;
+  size_t row_bytes = 0;
+  DevBuf d_tokens, d_arc_off, d_arcs, d_finals, d_rows, d_rem, d_alpha, d_lo, d_csum, d_loglik, d_llhat, d_best, d_coff, d_arows, d_beta,
+      d_acc, d_succ_off, d_succs, d_fin;
+  int plan(const char* who, const int32_t* node_tokens, int n_nodes, const int32_t* pred_off, const int32_t* preds, const uint8_t* is_final,
+           int64_t total_frames, int window_nodes, int V, int blank_id, bool posteriors);
+  int begin(hipStream_t s);
+  int batch(hipStream_t s, const std::vector<int32_t>& rows);
+  bool touches(int r0, int nrows) const;
+  int advance(hipStream_t s, const float* lp, int ld, int r0, int nrows);
+  int loglik(hipStream_t s, double* loglik_out);
+  int batch_back(hipStream_t s, const std::vector<int32_t>& rows);
+  int advance_back(hipStream_t s, const float* lp, int ld, int r0, int nrows);
+  int finish(hipStream_t s, float* visit, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame /* per node, nullable */);
+  void release();
+};
+
 }  // namespace rvb
 
 struct rvb_engine {
@@ -484,6 +527,7 @@ struct rvb_engine {
   rvb::CtcWindowAligner long_aligner;   // rvb_ctc_align_long_*: its own member, so the calls above stay usable between begin and finish
   rvb::CtcWindowScorer long_scorer;     // rvb_ctc_score_long_*: likewise
   rvb::CtcGraphWindowAligner long_graph_aligner;   // rvb_ctc_align_graph_long_*: likewise
+  rvb::CtcGraphWindowScorer long_graph_scorer;     // rvb_ctc_score_graph_long_*: likewise
   rvb::DevBuf align_lp, align_tv, align_ti, align_row, align_col, align_out;   // fp32 [LOGIT_SLAB][V] log-softmax slab; gather scratch
 
   // ---- RCCL communicator of the C-ABI collectives (comm.hip; optional) ----

@@ -271,6 +271,7 @@ void rvb_destroy(rvb_engine* e) {
   e->long_aligner.release();
   e->long_scorer.release();
   e->long_graph_aligner.release();
+  e->long_graph_scorer.release();
   e->finder.release();
   e->scorer.release();
   for (DevBuf* b : {&e->align_lp, &e->align_tv, &e->align_ti, &e->align_row, &e->align_col, &e->align_out}) b->release();

@@ -534,6 +534,90 @@ int rvb_ctc_align_graph_long_end(rvb_engine* e) {
   return OK;
 }
 
+// Long-form full-sum score over a token graph (ctc_graph_fb_window.hip): rvb_ctc_score_long_*'s protocol for ONE graph of any number
+// of nodes.  feed sweeps the slabs of the encoded batch in ascending order, feed_back the same slabs in descending order (the CTC head
+// is recomputed).  The driver is a member of its own: the one-batch calls, the other long lattices and the search stay usable between
+// begin and end.
+int rvb_ctc_score_graph_long_limits(int32_t* max_frames, int32_t* max_in_degree, int32_t* max_window_nodes, int32_t* default_window_nodes) {
+  if (max_frames) *max_frames = CTC_ALIGN_MAX_FRAMES;
+  if (max_in_degree) *max_in_degree = CTC_GRAPH_MAX_IN_DEGREE;
+  if (max_window_nodes) *max_window_nodes = CTC_GRAPH_SCORE_WINDOW_MAX_NODES;
+  if (default_window_nodes) *default_window_nodes = CTC_GRAPH_SCORE_WINDOW_DEFAULT_NODES;
+  return OK;
+}
+
+int rvb_ctc_score_graph_long_begin(rvb_engine* e, const int32_t* node_tokens, int n_nodes, const int32_t* pred_off, const int32_t* preds,
+                                   const uint8_t* is_final, int64_t total_frames, int window_nodes, int posteriors) {
+  const char* who = "rvb_ctc_score_graph_long_begin";
+  if (!e) { set_error("rvb_ctc_score_graph_long_begin: null engine"); return E_ARG; }
+  CtcGraphWindowScorer& sc = e->long_graph_scorer;
+  sc.open = false;                                 // begin while a lattice is open replaces it, also when this one is refused
+  RVB_TRY(sc.plan(who, node_tokens, n_nodes, pred_off, preds, is_final, total_frames, window_nodes, e->cfg.vocab, e->cfg.blank_id,
+                  posteriors != 0));
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  return sc.begin(e->stream);
+}
+
+int rvb_ctc_score_graph_long_feed(rvb_engine* e) {
+  if (!e) { set_error("rvb_ctc_score_graph_long_feed: null engine"); return E_ARG; }
+  CtcGraphWindowScorer& sc = e->long_graph_scorer;
+  if (!sc.open) { set_error("rvb_ctc_score_graph_long_feed before rvb_ctc_score_graph_long_begin"); return E_STATE; }
+  if (e->B <= 0) { set_error("rvb_ctc_score_graph_long_feed before rvb_encode"); return E_STATE; }
+  std::vector<int32_t> rows;
+  long_batch_rows(e, &rows);
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(sc.batch(e->stream, rows));              // E_STATE when the batch holds more frames than the lattice has left
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
+  return sweep_slabs(e, slabs, false, "ctc_graph_fb_window_forward", sc, [&](int r0, int nrows) {
+    return sc.advance(e->stream, e->align_lp.as<float>(), e->cfg.vocab, r0, nrows);
+  });
+}
+
+int rvb_ctc_score_graph_long_loglik(rvb_engine* e, double* loglik) {
+  if (!e) { set_error("rvb_ctc_score_graph_long_loglik: null engine"); return E_ARG; }
+  if (!loglik) { set_error("rvb_ctc_score_graph_long_loglik: null argument"); return E_ARG; }
+  CtcGraphWindowScorer& sc = e->long_graph_scorer;
+  if (!sc.open) { set_error("rvb_ctc_score_graph_long_loglik before rvb_ctc_score_graph_long_begin"); return E_STATE; }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  Scope t(e, "ctc_graph_fb_window_forward");
+  return sc.loglik(e->stream, loglik);
+}
+
+int rvb_ctc_score_graph_long_feed_back(rvb_engine* e) {
+  if (!e) { set_error("rvb_ctc_score_graph_long_feed_back: null engine"); return E_ARG; }
+  CtcGraphWindowScorer& sc = e->long_graph_scorer;
+  if (!sc.open) { set_error("rvb_ctc_score_graph_long_feed_back before rvb_ctc_score_graph_long_begin"); return E_STATE; }
+  if (!sc.post) { set_error("rvb_ctc_score_graph_long_feed_back: the lattice was begun without posteriors"); return E_STATE; }
+  if (!sc.forward_done) { set_error("rvb_ctc_score_graph_long_feed_back before rvb_ctc_score_graph_long_loglik"); return E_STATE; }
+  if (e->B <= 0) { set_error("rvb_ctc_score_graph_long_feed_back before rvb_encode"); return E_STATE; }
+  std::vector<int32_t> rows;
+  long_batch_rows(e, &rows);
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  RVB_TRY(sc.batch_back(e->stream, rows));         // E_STATE unless the batch is the one the forward sweep saw at this position
+  std::vector<std::pair<int, int>> slabs;
+  RVB_TRY(align_workspace(e, &slabs));
+  return sweep_slabs(e, slabs, true, "ctc_graph_fb_window_backward", sc, [&](int r0, int nrows) {
+    return sc.advance_back(e->stream, e->align_lp.as<float>(), e->cfg.vocab, r0, nrows);
+  });
+}
+
+int rvb_ctc_score_graph_long_finish(rvb_engine* e, float* visit, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame) {
+  if (!e) { set_error("rvb_ctc_score_graph_long_finish: null engine"); return E_ARG; }
+  CtcGraphWindowScorer& sc = e->long_graph_scorer;
+  if (!sc.open) { set_error("rvb_ctc_score_graph_long_finish before rvb_ctc_score_graph_long_begin"); return E_STATE; }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  Scope t(e, "ctc_graph_fb_window_backward");
+  return sc.finish(e->stream, visit, occupancy, mean_frame, peak_post, peak_frame);
+}
+
+int rvb_ctc_score_graph_long_end(rvb_engine* e) {
+  if (!e) { set_error("rvb_ctc_score_graph_long_end: null engine"); return E_ARG; }
+  RVB_HIP_CHECK(hipSetDevice(e->device));
+  e->long_graph_scorer.release();
+  return OK;
+}
+
 // Full-sum score (CTC.forward, transformer/ctc.py:65-104) over the same slabs: a forward sweep, and for per-token outputs the slabs
 // once more in descending order for the backward sweep (the CTC head is recomputed, as for the alignment's confidences).
 int rvb_ctc_score(rvb_engine* e, const int32_t* tokens, const int32_t* tok_lens, int n_seq, const int32_t* first_chunk,

@@ -258,6 +258,21 @@ int rvb_test_ctc_score_batch(const float* lp, const int32_t* T, int V, const int
 int rvb_test_ctc_score_graph(const float* lp, const int32_t* T, int n_seq, int V, const int32_t* node_tokens, const int32_t* n_nodes,
                              const int32_t* pred_off, const int32_t* preds, const uint8_t* is_final, int blank, int slab_rows,
                              double* loglik_out, float* visit, float* occupancy, float* mean_frame, float* peak_post, int32_t* peak_frame);
+/* ctc_graph_fb_window.hip: the windowed graph full-sum kernels and the driver rvb_ctc_score_graph_long_* runs, for ONE graph (arguments
+ * as rvb_ctc_score_graph_long_begin's) over host log-probs lp [T][V] fed slab_rows frames at a time (forward slabs ascending, backward
+ * slabs descending).  window_nodes: 0 or a multiple of 256 in [256, 4096], reduced to the nodes rounded up to 64.  Without lo_force
+ * every slab is cut into launches by the policy (ctc_graph_window_next) from the best node each launch reports.  lo_force (nullable)
+ * replaces the policy as in rvb_test_ctc_graph_window: every slab is then ONE launch, in the window lo_force[slab]; refused unless
+ * every entry is a multiple of 64 in [0, max(0, N rounded up to 64 - W)], the entries do not decrease and entry 0 is 0.  loglik_out is
+ * fp64; the five per-node outputs [n_nodes] are nullable, and with all five null only the forward sweep runs.  lo_out [T]: the first
+ * node of each frame's window; best_out (nullable, one entry per launch, at most T): the node each forward launch reported;
+ * launches_out (nullable): forward launches.  Refuses before any device work what rvb_ctc_score_graph_long_begin refuses, in the same
+ * words, and a bad lo_force; a band that holds no path is refused (RVB_E_ARG) after the forward pass.  Outputs untouched on every
+ * refusal. */
+int rvb_test_ctc_score_graph_window(const float* lp, int T, int V, const int32_t* node_tokens, int n_nodes, const int32_t* pred_off,
+                                    const int32_t* preds, const uint8_t* is_final, int blank, int slab_rows, int window_nodes,
+                                    const int32_t* lo_force, double* loglik_out, float* visit, float* occupancy, float* mean_frame,
+                                    float* peak_post, int32_t* peak_frame, int32_t* lo_out, int32_t* best_out, int32_t* launches_out);
 /* ctc_find.hip: phrase search over host log-probs with exactly the kernel and the host code rvb_ctc_find runs.  lp holds the frames
  * of n_seq sequences concatenated ([sum T][V]; T[i] >= 0), w [sum T] each row's maximum (null: computed on the host from lp);
  * n_phrases phrases concatenated in `tokens`; threshold [n_phrases]; slab_rows rows per launch (h, st and the counts carried in HBM).

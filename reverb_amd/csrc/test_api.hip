@@ -924,6 +924,66 @@ int rvb_test_ctc_score_graph(const float* lp, const int32_t* T, int n_seq, int V
   return r;
 }
 
+int rvb_test_ctc_score_graph_window(const float* lp, int T, int V, const int32_t* node_tokens, int n_nodes, const int32_t* pred_off,
+                                    const int32_t* preds, const uint8_t* is_final, int blank, int slab_rows, int window_nodes,
+                                    const int32_t* lo_force, double* loglik_out, float* visit, float* occupancy, float* mean_frame,
+                                    float* peak_post, int32_t* peak_frame, int32_t* lo_out, int32_t* best_out, int32_t* launches_out) {
+  const char* who = "rvb_test_ctc_score_graph_window";
+  const std::string me(who);
+  if (!lp || !node_tokens || !pred_off || !preds || !is_final || !loglik_out || !lo_out) { set_error(me + ": null argument"); return E_ARG; }
+  if (T < 1 || slab_rows < 1) { set_error(me + ": need T >= 1 and slab_rows >= 1"); return E_ARG; }
+  const bool post = visit || occupancy || mean_frame || peak_post || peak_frame;
+  CtcGraphWindowScorer sc;
+  RVB_TRY(sc.plan(who, node_tokens, n_nodes, pred_off, preds, is_final, T, window_nodes, V, blank, post));
+  if (lo_force) {
+    const int n_launch = (T + slab_rows - 1) / slab_rows, top = std::max(0, (sc.N + 63) / 64 * 64 - sc.W);
+    for (int i = 0; i < n_launch; ++i) {
+      const int v = lo_force[i];
+      if (v % 64 != 0 || v < 0 || v > top || (i == 0 ? v != 0 : v < lo_force[i - 1])) {
+        set_error(me + ": lo_force[" + std::to_string(i) + "] = " + std::to_string(v) + " must be a multiple of 64 in [0, " +
+                  std::to_string(top) + "], not below the entry before it, and 0 for launch 0");
+        return E_ARG;
+      }
+    }
+    sc.lo_force = lo_force;
+    sc.n_force = n_launch;
+  }
+  RVB_TRY(need_gpu());
+  Dev dlp;
+  const size_t n = (size_t)sc.N;
+  std::vector<int32_t> rows((size_t)T);
+  for (int t = 0; t < T; ++t) rows[t] = t;
+  double ll = 0.0;
+  int r = up_raw(dlp, lp, (size_t)T * V * 4);
+  if (r == OK) r = sc.begin(nullptr);
+  if (r == OK) r = sc.batch(nullptr, rows);
+  r = feed_slabs(r, T, slab_rows, false, [&](int r0, int nr) { return sc.advance(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, nr); });
+  if (r == OK) r = sc.loglik(nullptr, &ll);
+  std::vector<float> vis(n), occ(n), mean(n), peak(n);
+  std::vector<int32_t> pf(n);
+  if (r == OK && post) {
+    r = sc.batch_back(nullptr, rows);
+    r = feed_slabs(r, T, slab_rows, true, [&](int r0, int nr) { return sc.advance_back(nullptr, (const float*)dlp.p + (size_t)r0 * V, V, r0, nr); });
+    if (r == OK) r = sc.finish(nullptr, vis.data(), occ.data(), mean.data(), peak.data(), pf.data());
+  }
+  if (r != OK) (void)hipDeviceSynchronize();
+  const std::vector<CtcGraphWindowScorer::Launch> launches = sc.launches;
+  sc.release();
+  RVB_TRY(r);                                      // nothing was written so far: a refusal leaves every output untouched
+  *loglik_out = ll;
+  for (const auto& m : launches)
+    for (int t = m.f0; t < m.f1; ++t) lo_out[t] = m.lo;
+  if (best_out)
+    for (size_t i = 0; i < launches.size(); ++i) best_out[i] = launches[i].best;
+  if (launches_out) *launches_out = (int32_t)launches.size();
+  if (visit) memcpy(visit, vis.data(), n * 4);
+  if (occupancy) memcpy(occupancy, occ.data(), n * 4);
+  if (mean_frame) memcpy(mean_frame, mean.data(), n * 4);
+  if (peak_post) memcpy(peak_post, peak.data(), n * 4);
+  if (peak_frame) memcpy(peak_frame, pf.data(), n * 4);
+  return OK;
+}
+
 int rvb_test_ctc_find(const float* lp, const int32_t* T, int n_seq, int V, const float* w, const int32_t* tokens, const int32_t* tok_lens,
                       int n_phrases, const float* threshold, int blank, int slab_rows, int max_candidates, int max_hits,
                       int64_t* raw_count, int32_t* raw_end, int32_t* raw_start, float* raw_score, int32_t* n_hits, int32_t* hit_start,

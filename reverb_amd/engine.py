@@ -795,6 +795,46 @@ class Engine:
         check(self.lib.rvb_ctc_align_graph_long_end(self.handle), "rvb_ctc_align_graph_long_end")
         self._long_graph = None
 
+    # ---- long-form graph full sum (rvb_ctc_score_graph_long_*, csrc/ctc_graph_fb_window.hip): one graph over several encoded batches
+    def score_graph_long_begin(self, graph, total_frames, window_nodes=0, posteriors=False):
+        """Open ONE full-sum lattice of `graph` (a token_graph.TokenGraph of any number of nodes, no wildcards) over total_frames valid
+        encoder frames.  window_nodes: 0 (the default, 4096) or a multiple of 256 in [256, 4096].  posteriors=True keeps the forward
+        rows (total_frames x window x 4 bytes) for the backward sweep.  -> the window in use (reduced to the graph rounded up to 64)."""
+        from ._lib import u8ptr
+        tok, off, prd, fin = (np.ascontiguousarray(a) for a in graph.arrays())
+        self._score_long_graph_nodes = len(graph)
+        check(self.lib.rvb_ctc_score_graph_long_begin(self.handle, iptr(tok), int(tok.size), iptr(off), iptr(prd), u8ptr(fin),
+                                                      int(total_frames), int(window_nodes), int(bool(posteriors))),
+              "rvb_ctc_score_graph_long_begin")
+        return min(int(window_nodes) or 4096, (len(graph) + 63) // 64 * 64)
+
+    def score_graph_long_feed(self):
+        """After encode(), batches in ascending order: every valid frame of the encoded batch continues the forward sweep."""
+        check(self.lib.rvb_ctc_score_graph_long_feed(self.handle), "rvb_ctc_score_graph_long_feed")
+
+    def score_graph_long_loglik(self):
+        """-> loglik (fp64) once every frame was fed."""
+        ll = np.empty(1, np.float64)
+        check(self.lib.rvb_ctc_score_graph_long_loglik(self.handle, dptr(ll)), "rvb_ctc_score_graph_long_loglik")
+        return float(ll[0])
+
+    def score_graph_long_feed_back(self):
+        """After score_graph_long_loglik() and encode(), the same batches in DESCENDING order: the backward sweep (needs posteriors)."""
+        check(self.lib.rvb_ctc_score_graph_long_feed_back(self.handle), "rvb_ctc_score_graph_long_feed_back")
+
+    def score_graph_long_finish(self):
+        """-> dict of per-node visit, occupancy, mean_frame, peak_posterior, peak_frame (frames within the lattice), as score_graph()'s."""
+        n = getattr(self, "_score_long_graph_nodes", 0)
+        vis, occ, mean, peak = (np.empty(max(n, 1), np.float32) for _ in range(4))
+        pkf = np.empty(max(n, 1), np.int32)
+        check(self.lib.rvb_ctc_score_graph_long_finish(self.handle, fptr(vis), fptr(occ), fptr(mean), fptr(peak), iptr(pkf)),
+              "rvb_ctc_score_graph_long_finish")
+        return {"visit": vis[:n].tolist(), "occupancy": occ[:n].tolist(), "mean_frame": mean[:n].tolist(),
+                "peak_posterior": peak[:n].tolist(), "peak_frame": pkf[:n].tolist()}
+
+    def score_graph_long_end(self):
+        check(self.lib.rvb_ctc_score_graph_long_end(self.handle), "rvb_ctc_score_graph_long_end")
+
     def find(self, phrases, chunk_ranges=None, min_score=-1.0, max_hits=64, max_candidates=None):
         """Phrase search (rvb_ctc_find, csrc/ctc_find.hip): EVERY occurrence of each token phrase (1 .. 32 ids, none the blank) in the
         chunks of the last encode().  Sequence i covers the chunks chunk_ranges[i] = (first, count); the default is ONE sequence

@@ -552,8 +552,14 @@ class ReverbASR:
         continues over the batches inside a window of 2 window_tokens states, as align()'s long path does (Engine.score_long_*,
         csrc/ctc_fb_window.hip); with posteriors=True the batches are encoded a second time, in reverse order, for the backward
         sweep.  The result then also holds window_states and window_margin (align's); loglik is the sum over the paths inside the
-        windows, and a loglik below viterbi_score logs a warning: score again with a larger window_tokens.  attention=True and
-        alternatives=True are refused there."""
+        windows, and a loglik below viterbi_score logs a warning: score again with a larger window_tokens.  attention=True is
+        refused there.
+        alternatives=True with long_form=True takes the long GRAPH path (Engine.score_graph_long_*: a windowed full sum over the
+        graph, csrc/ctc_graph_fb_window.hip): a graph of any number of nodes, of which a window of window_tokens NODES (rounded up to
+        256; default and most: 4096) is alive; pass 1 also runs the windowed graph Viterbi, and posteriors=True encodes the batches a
+        second time in reverse order.  -> loglik, n_frames, viterbi_score, text, window_nodes, window_margin and, with posteriors,
+        words as above.  It is never chosen silently: with long_form=None a file or a graph that does not fit one batch raises
+        ValueError, which names long_form=True."""
         from .ctc_align import posteriors_to_json
         if window_tokens is not None and int(window_tokens) < 1:
             raise ValueError("score: window_tokens must be at least 1")
@@ -568,10 +574,20 @@ class ReverbASR:
             raise ValueError("chunk_size must be at least 7 frames (Conv2dSubsampling4 needs 7 input frames, subsampling.py:201-226)")
         if alternatives:
             from .token_graph import parse_alternatives
+            try:
+                graph = parse_alternatives(transcript, lambda text: self.tokenizer.tokenize(text)[1], None, long_form=bool(long_form))
+            except ValueError as e:
+                if long_form is None and ("MAX_NODES" in str(e) or "MAX_ARCS" in str(e)):
+                    raise ValueError(f"{e}: long_form=True scores a graph of any size inside a moving window") from None
+                raise
+            eng, _, n_frames, n_chunks = self._prepare_for_align(audio_file, transcript, [], verbatimicity, chunk_size)
             if long_form:
-                raise ValueError("score: alternatives=True stays one-batch (token graphs do not span encoded batches): drop long_form=True")
-            graph = parse_alternatives(transcript, lambda text: self.tokenizer.tokenize(text)[1], None)
-            eng, _, n_chunks = self._encode_for_align("score", audio_file, transcript, [], verbatimicity, chunk_size)
+                return self._score_graph_long(eng, graph, n_frames, n_chunks, chunk_size, window_tokens, posteriors)
+            if long_form is None and n_chunks > eng.cfg.max_chunks:
+                raise ValueError(f"score: alternatives=True takes the long path only when asked to: the file has {n_chunks} chunks of "
+                                 f"{chunk_size} frames, one batch holds {eng.cfg.max_chunks} -- pass long_form=True for the windowed "
+                                 "full sum over the graph, or load the model with a larger max_chunks")
+            n_chunks = self._encode_prepared("score", eng, n_frames, n_chunks, chunk_size)
             res = eng.align_graph([graph], [(0, n_chunks)])[0]
             sg = eng.score_graph([graph], [(0, n_chunks)], posteriors=posteriors)[0]
             out = {"loglik": sg["loglik"], "n_frames": sg["n_frames"], "viterbi_score": float(res.score), "text": graph.text_of(res.nodes)}
@@ -608,6 +624,58 @@ class ReverbASR:
             att = eng.score([ids], [(0, 1)], attention=True, reverse_weight=reverse_weight)[0]
             for key in ("loss_ctc", "loss_att", "acc_att", "loss", "att_logp"):
                 out[key] = att[key]
+        return out
+
+    def _score_graph_long(self, eng: Engine, graph, n_frames: int, n_chunks: int, chunk_size: int, window_tokens, posteriors: bool):
+        """The long path of score(alternatives=True): pass 1 encodes the batches in order and feeds both the windowed graph Viterbi
+        (viterbi_score, text and window_margin) and the windowed forward sweep over the graph (Engine.score_graph_long_*,
+        csrc/ctc_graph_fb_window.hip); pass 2 (posteriors only) encodes them in reverse order for the backward sweep."""
+        from .ctc_align import AlignResult, posteriors_to_json
+        mc = eng.cfg.max_chunks
+        lens_all = np.full(n_chunks, chunk_size, np.int32)
+        lens_all[-1] = n_frames - (n_chunks - 1) * chunk_size
+        enc_all = np.where(lens_all > 6, (lens_all - 7) // 4 + 1, 0).astype(np.int32)      # Conv2dSubsampling4: frames 6 + 4j < len
+        window = 0 if window_tokens is None else min(4096, -(-int(window_tokens) // 256) * 256)
+        total = int(enc_all.sum())
+
+        def encode(c0):
+            eng.encode(None, lens_all[c0:c0 + mc], 1, 0.0, first_chunk=c0, T0=chunk_size)
+            assert eng.encoder_lens().tolist() == enc_all[c0:c0 + mc].tolist(), "encoder frames differ from the subsampling arithmetic"
+
+        starts = list(range(0, n_chunks, mc))
+        eng.align_graph_long_begin(graph, total, window or 4096, 0.0)      # the scorer's default window, not the aligner's own
+        try:
+            used = eng.score_graph_long_begin(graph, total, window, posteriors)
+            for c0 in starts:
+                encode(c0)
+                eng.align_graph_long_feed()
+                eng.score_graph_long_feed()
+            labels, _, nodes, begin, end, vit, margin = eng.align_graph_long_finish()
+            loglik = eng.score_graph_long_loglik()
+            sg = None
+            if posteriors:
+                for c0 in reversed(starts):
+                    encode(c0)
+                    eng.score_graph_long_feed_back()
+                sg = eng.score_graph_long_finish()
+        finally:
+            eng.align_graph_long_end()
+            eng.score_graph_long_end()
+        if loglik < vit - 1e-5 * total:
+            logging.getLogger(__name__).warning(
+                "score: loglik %.3f lies below viterbi_score %.3f: the scoring window of %d nodes lost the best path; "
+                "score again with a larger window_tokens (now %d)", loglik, vit, used, used)
+        nodes = nodes.tolist()
+        out = {"loglik": loglik, "n_frames": total, "viterbi_score": float(vit), "text": graph.text_of(nodes), "window_nodes": used,
+               "window_margin": margin}
+        if sg is not None:
+            res = AlignResult([graph.tokens[j] for j in nodes], labels.tolist(), begin.tolist(), end.tolist(), begin.tolist(),
+                              [0.0] * len(begin), vit, 0, enc_all.tolist(), nodes)
+            opens = [j for j in range(len(graph)) if graph.words[j] != ""]
+            picked = {key: [sg[key][j] for j in opens] for key in ("occupancy", "mean_frame", "peak_posterior")}
+            per = posteriors_to_json(res, picked, chunk_size, self.input_frame_length, self.output_frame_length)
+            out["words"] = [{"text": graph.words[j], "node": j, "probability": float(sg["visit"][j]), "occupancy": p["occupancy"],
+                             "mean_time": p["mean_time"] if p["occupancy"] > 0 else None} for j, p in zip(opens, per)]
         return out
 
     def _score_long(self, eng: Engine, ids, n_frames: int, n_chunks: int, chunk_size: int, window_tokens, posteriors: bool):
