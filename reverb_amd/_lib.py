@@ -234,6 +234,8 @@ TEST_SIGNATURES = {
     "rvb_test_joint_result": (C.c_int, [C.c_void_p, _i32p, _i32p, _i32p, _f64p, _i32p, _f64p]),
     "rvb_test_glu_dwconv": (C.c_int, [C.c_int, _f32p, _f32p, _f32p, _f32p, _i32p, _f32p, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_int, _f32p, C.c_int]),
+    "rvb_test_dwconv_ln": (C.c_int, [_f32p, _f32p, _f32p, _f32p, _i32p, _f32p, _f32p, C.c_float, _f32p, _f32p, _f32p, C.c_int, C.c_int,
+                                     C.c_int, C.c_int, C.c_int]),
     "rvb_test_attention": (C.c_int, [C.c_int, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int,
                                      C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p, _i32p, C.c_int, C.c_int]),
     "rvb_test_attention_trie": (C.c_int, [C.c_int, _f32p, _f32p, _f32p, _f32p, C.c_int, C.c_int, C.c_int, _i32p, _i32p, _i32p,

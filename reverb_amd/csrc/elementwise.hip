@@ -5,6 +5,7 @@
 //                     decoder_layer.py:56-58,241-243, decoder.py:90) and the conv-module norm
 //                     (+SiLU, convolution.py:133-137; BatchNorm1d folded to a per-channel affine)
 //   glu_dwconv        convolution.py:107-131 (mask -> [pw-conv1 by GEMM] -> GLU -> depthwise conv)
+//   dwconv_ln         the depthwise conv and the conv-module norm + SiLU of the two lines above in one launch (bf16, offline)
 //   embed_tokens      decoder.py:82-87,157 + embedding.py:73-76
 //   logsoftmax_topk   ctc.py:106-114, asr_model.py:318-329, search.py:111,155
 //   lse_gather        asr_model.py:969 + search.py:417-437 (only the needed log-probs)
@@ -12,6 +13,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "wave_asm.h"
 
 namespace rvb {
 
@@ -162,23 +164,55 @@ __device__ inline float sq4(float dx, float dy, float dz, float dw) {
   }
 }
 
+// The lane <-> column map of the row kernels: a lane owns NV/2 runs of 8 consecutive columns, vector i covers columns COL(i) .. COL(i)+3
+#define COL(i) ((((lane) + 64 * ((i) >> 1)) << 3) + (((i) & 1) << 2))
+
+// The row body that rownorm_kernel and dwconv_ln_kernel share, so that a row normalised inside the depthwise kernel carries the bits
+// the separate pass gives it.  Statistics of one row held as NV float4 per lane (zeros beyond d); DPP: the bf16 engine's LDS-free
+// reduction (its summation tree differs in the last bit from __shfl_xor's, which the f32 engine keeps so that its results do not move).
+template <int NV, bool DPP>
+__device__ __forceinline__ void row_ln_stats(const float4* v, int lane, int d, float eps, float& mean, float& rstd) {
+  auto wsum = [](float x) __attribute__((always_inline)) { if constexpr (DPP) return wave_sum_dpp(x); else return wave_sum(x); };
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) sum += v[i].x + v[i].y + v[i].z + v[i].w;
+  mean = wsum(sum) / (float)d;
+  float sq = 0.f;
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    if (COL(i) < d) {
+      sq += sq4<NV>(v[i].x - mean, v[i].y - mean, v[i].z - mean, v[i].w - mean);
+    }
+  }
+  rstd = rsqrtf(wsum(sq) / (float)d + eps);
+}
+// ... and the affine + SiLU of one vector.  NARROW (bf16 / fp8 output): hardware exp2 / rcp.
+template <bool NARROW>
+__device__ __forceinline__ void row_affine_act(const float4& v, float mean, float rstd, const float4& g, const float4& be, bool silu, float* o) {
+  o[0] = (v.x - mean) * rstd * g.x + be.x; o[1] = (v.y - mean) * rstd * g.y + be.y;
+  o[2] = (v.z - mean) * rstd * g.z + be.z; o[3] = (v.w - mean) * rstd * g.w + be.w;
+  if (silu) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if constexpr (NARROW) o[e] = o[e] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * o[e]));
+      else o[e] = o[e] / (1.0f + expf(-o[e]));
+    }
+  }
+}
+
 template <typename OutT, typename AddT, int NV, bool TWO, int SW>
 __global__ __launch_bounds__(256, (NV <= 4 ? 4 : 2)) void rownorm_kernel(NormArgs a) {
   constexpr bool CT = SW >= 0;
-  // the bf16 engine's statistics use the LDS-free reduction (its summation tree differs in the last bit from __shfl_xor's, which the
-  // f32 engine keeps so that its results do not move)
   auto wsum = [](float x) __attribute__((always_inline)) { if constexpr (sizeof(AddT) == 2) return wave_sum_dpp(x); else return wave_sum(x); };
   const bool sw_xb = CT ? (bool)(SW & 1) : (bool)a.x_bf16;
   const bool sw_ln = CT ? (bool)(SW & 2) : a.mode == NORM_LN;
   const bool sw_silu = CT ? (bool)(SW & 4) : (bool)a.silu;
   const bool sw_add = CT ? (bool)(SW & 8) : a.add != nullptr;
   const bool sw_o2f8 = CT ? (bool)(SW & 16) : (bool)a.out2_fp8;
-  // a lane owns NV/2 runs of 8 consecutive columns (two float4 loads, one 16-byte bf16 / 8-byte fp8 store per run):
-  // vector i covers columns COL(i) .. COL(i)+3
+  // a lane owns NV/2 runs of 8 consecutive columns (two float4 loads, one 16-byte bf16 / 8-byte fp8 store per run)
   const int lane = threadIdx.x & 63;
   const int d = a.d;
   const int wave0 = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
-#define COL(i) ((((lane) + 64 * ((i) >> 1)) << 3) + (((i) & 1) << 2))
   float4 g[NV], be[NV], g2[TWO ? NV : 1], be2[TWO ? NV : 1];
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
@@ -224,20 +258,7 @@ __global__ __launch_bounds__(256, (NV <= 4 ? 4 : 2)) void rownorm_kernel(NormArg
   for (int row = wave0; row < a.M; row += nwaves) {
     load_row(row + nwaves, nx);                 // next row of this wave: in flight under the reductions below
     float mean = 0.f, rstd = 1.f;
-    if (sw_ln) {
-      float sum = 0.f;
-#pragma unroll
-      for (int i = 0; i < NV; ++i) sum += v[i].x + v[i].y + v[i].z + v[i].w;
-      mean = wsum(sum) / (float)d;
-      float sq = 0.f;
-#pragma unroll
-      for (int i = 0; i < NV; ++i) {
-        if (COL(i) < d) {
-          sq += sq4<NV>(v[i].x - mean, v[i].y - mean, v[i].z - mean, v[i].w - mean);
-        }
-      }
-      rstd = rsqrtf(wsum(sq) / (float)d + a.eps);
-    }
+    if (sw_ln) row_ln_stats<NV, sizeof(AddT) == 2>(v, lane, d, a.eps, mean, rstd);
     // The next row's values are taken out of the memory pipe HERE, before this row's stores are issued: `vmcnt` counts loads and
     // stores in one in-order queue, so a wait for the prefetch placed behind the stores would also wait for their round trip.
     if constexpr (CT) {
@@ -252,15 +273,8 @@ __global__ __launch_bounds__(256, (NV <= 4 ? 4 : 2)) void rownorm_kernel(NormArg
     for (int i = 0; i < NV; ++i) {
       const int c = COL(i);
       if (c >= d) continue;
-      float o[4] = {(v[i].x - mean) * rstd * g[i].x + be[i].x, (v[i].y - mean) * rstd * g[i].y + be[i].y,
-                    (v[i].z - mean) * rstd * g[i].z + be[i].z, (v[i].w - mean) * rstd * g[i].w + be[i].w};
-      if (sw_silu) {
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          if constexpr (sizeof(OutT) <= 2) o[e] = o[e] * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.44269504f * o[e]));
-          else o[e] = o[e] / (1.0f + expf(-o[e]));
-        }
-      }
+      float o[4];
+      row_affine_act<sizeof(OutT) <= 2>(v[i], mean, rstd, g[i], be[i], sw_silu, o);
       if (add) {
         if constexpr (sizeof(AddT) == 2) {
           const uint2 u = *(const uint2*)(add + c);
@@ -332,7 +346,6 @@ __global__ __launch_bounds__(256, (NV <= 4 ? 4 : 2)) void rownorm_kernel(NormArg
   }
   if (nsat != 0 && a.sat) atomicAdd(a.sat, nsat);          // rare: only lanes that clipped something touch the counter
   if (nsat2 != 0 && a.sat2) atomicAdd(a.sat2, nsat2);
-#undef COL
 }
 
 template <typename OutT, typename AddT>
@@ -586,6 +599,218 @@ int glu_dwconv(hipStream_t s, int dtype, const GluDwArgs& a) {
   dim3 grid(cdiv(a.T, DW_TT), cdiv(a.d, DW_CT), a.B);
   if (dtype == DT_BF16) hipLaunchKernelGGL(glu_dw_kernel<bf16_t>, grid, dim3(DW_THREADS), 0, s, a);
   else hipLaunchKernelGGL(glu_dw_kernel<float>, grid, dim3(DW_THREADS), 0, s, a);
+  RVB_HIP_CHECK(hipGetLastError());
+  return OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Depthwise conv + LayerNorm + SiLU of the bf16 offline path in ONE persistent kernel (DwLnArgs): the [B*T, d] matrix of gated
+// rows is cut into gridDim.x contiguous row ranges, whatever chunks they cross, and a workgroup walks its range DL_R rows at a time.
+//   * 8 waves x 64 lanes x 2 channels = 1024 channels: a lane keeps its 31 tap pairs, and in glu_dw_kernel's order runs the same
+//     FMA chain on them (bias first, taps ascending, one v_pk_fma_f32 per tap and output, one rounding to bf16): the same bits.
+//     A wave whose 128 channels lie at or beyond d only takes part in the barriers and in the norm.
+//   * the input rows stream by LDS-DMA into a ring of 64 rows x 2 KiB (the 46 rows under a step + the 16 of the next one = 62):
+//     a row enters LDS once per workgroup, and the next step's rows are in flight under this step's FMAs.  The one wait for them
+//     stands BEHIND the FMAs (vmcnt(0): the DMA pieces and the previous step's stores, all a step old by then).
+//   * what the DMA cannot know is put right afterwards.  Rows at or past their chunk's length are overwritten with GLU of the
+//     pointwise bias (rare; a row-uniform branch).  A tap outside its own chunk must read zero although the ring holds the
+//     neighbouring chunk's row there: a step whose window lies inside one chunk runs unmasked, any other runs the chain once per
+//     chunk among its outputs with the other chunks' rows replaced by zero (fma(w, 0, acc), as the zero-filled tile gives).
+//   * the 16 x d results go to a 32-KiB LDS slab as bf16 (what glu_dw_kernel writes to memory and the norm reads back), and after
+//     one barrier each wave runs rownorm_kernel<bf16, bf16, 4, false, 2|4|1>'s row body on two of them, in that kernel's lane <->
+//     column map, and stores 16-byte vectors.
+// LDS: 128 KiB ring + 32 KiB slab = the whole CU: one workgroup per CU, two waves per SIMD.
+static constexpr int DL_R = 16;                          // rows per step = consecutive outputs per thread
+static constexpr int DL_WIN = DL_R + DW_KMAX - 1;        // input rows under a step
+static constexpr int DL_RING = 64, DL_ROWB = 2048, DL_THREADS = 512;
+static constexpr int DL_SLAB0 = DL_RING * DL_ROWB;
+static constexpr int DL_LDS = DL_SLAB0 + DL_R * DL_ROWB;
+static_assert(DL_WIN + DL_R <= DL_RING && DL_LDS <= 160 * 1024 && DL_R % (DL_THREADS / 64) == 0, "ring and slab fill the LDS of a CU");
+typedef float dl_f32x2 __attribute__((ext_vector_type(2)));
+
+// every LDS access of this wave has returned, then the barrier; nothing moves across it
+__device__ __forceinline__ void dl_barrier() { wait_lds(); __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); }
+
+// glu_dw_kernel's FMA chain on the DL_WIN ring rows from `base` on; MASK: window rows outside [rlo, rhi) read as zero
+template <bool MASK>
+__device__ __forceinline__ void dl_chain(const char* ring_ch, int base, const dl_f32x2* wk, dl_f32x2 bv, int rlo, int rhi, dl_f32x2* acc) {
+#pragma unroll
+  for (int i = 0; i < DL_R; ++i) acc[i] = bv;
+#pragma unroll
+  for (int r = 0; r < DL_WIN; ++r) {
+    const uint32_t p = *(const uint32_t*)(ring_ch + ((base + r) & (DL_RING - 1)) * DL_ROWB);
+    float gx, gy;
+    Gate<bf16_t>::get(p, gx, gy);
+    if constexpr (MASK) {
+      const bool in = r >= rlo && r < rhi;
+      gx = in ? gx : 0.f; gy = in ? gy : 0.f;
+    }
+    const dl_f32x2 g = {gx, gy};
+#pragma unroll
+    for (int i = 0; i < DL_R; ++i) {
+      const int k = r - i;                        // compile-time after unrolling
+      if (k >= 0 && k < DW_KMAX) acc[i] = __builtin_elementwise_fma(wk[k], g, acc[i]);
+    }
+  }
+}
+
+__global__ __launch_bounds__(DL_THREADS) void dwconv_ln_kernel(DwLnArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char dl_smem[];
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int d = a.d, T = a.T, K = a.K, pad = (K - 1) / 2;
+  const int rows = a.B * T;
+  const int r_begin = (int)((int64_t)blockIdx.x * rows / gridDim.x), r_end = (int)((int64_t)(blockIdx.x + 1) * rows / gridDim.x);
+  if (r_begin >= r_end) return;                   // more workgroups than rows: the whole workgroup leaves
+  const unsigned lds_base = (unsigned)(size_t)(__attribute__((address_space(3))) char*)dl_smem;
+
+  // row g of the input -> ring row g & 63, as two 1-KiB pieces of 512 channels; wave w issues pieces w, w + 8, ...  Unconditional:
+  // a row outside the matrix and the columns at or beyond d read a clamped address, and nothing reads what they bring
+  const unsigned src_col[2] = {(unsigned)lane * 16u, (unsigned)min(512 + lane * 8, d - 8) * 2u};
+  auto issue = [&](int g0, int n) __attribute__((always_inline)) {
+    for (int p = wave; p < 2 * n; p += DL_THREADS / 64) {
+      const int g = g0 + (p >> 1), h = p & 1;
+      const char* src = (const char*)a.G + (size_t)min(max(g, 0), rows - 1) * d * 2 + src_col[h];
+      lds_dma1(src, __builtin_amdgcn_readfirstlane(lds_base + (unsigned)(g & (DL_RING - 1)) * DL_ROWB + (unsigned)h * 1024u));
+    }
+  };
+  issue(r_begin - pad, DL_WIN);
+
+  const int ch = wave * 128 + 2 * lane;
+  const bool cok = wave * 128 < d;                // d % 128 == 0: a wave's channels are in range together
+  dl_f32x2 wk[DW_KMAX];
+#pragma unroll
+  for (int k = 0; k < DW_KMAX; ++k)
+    wk[k] = (k < K && cok) ? *(const dl_f32x2*)(a.dw_w + (size_t)k * d + ch) : (dl_f32x2){0.f, 0.f};
+  dl_f32x2 bv = {0.f, 0.f};
+  uint32_t fill = 0;                              // GLU of the pointwise bias, as glu_dw_kernel stages it for a frame past the length
+  if (cok) {
+    bv = (dl_f32x2){a.dw_b[ch], a.dw_b[ch + 1]};
+    const float f0 = a.pw1_bias[ch] / (1.0f + expf(-a.pw1_bias[d + ch])), f1 = a.pw1_bias[ch + 1] / (1.0f + expf(-a.pw1_bias[d + ch + 1]));
+    fill = (uint32_t)f32_to_bf16(f0) | ((uint32_t)f32_to_bf16(f1) << 16);
+  }
+  float4 gm[4], be[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const int c = COL(i);
+    const bool ok = c < d;
+    gm[i] = ok ? *(const float4*)(a.gamma + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+    be[i] = ok ? *(const float4*)(a.beta + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  // lane j: does row g0 + j (j < n <= 64) lie at or past its chunk's length?  One unconditional load of `lens` per call (the row
+  // clamped into the matrix), asked a phase before the answer is used ...
+  auto past_len = [&](int g0, int n) __attribute__((always_inline)) {
+    const int g = g0 + lane, gc = min(max(g, 0), rows - 1);
+    const int b = gc / T, t = gc - b * T;
+    const int len = a.lens[b];
+    return lane < n && g == gc && t >= len;
+  };
+  // ... once the rows have landed and every wave knows it: those rows get the fill value (rare)
+  auto fill_rows = [&](bool need, int g0) __attribute__((always_inline)) {
+    unsigned long long m = __builtin_amdgcn_ballot_w64(need);
+    while (m) {
+      const int j = __builtin_ctzll(m);
+      m &= m - 1;
+      if (cok) *(uint32_t*)(dl_smem + ((g0 + j) & (DL_RING - 1)) * DL_ROWB + ch * 2) = fill;
+    }
+  };
+  const bool need0 = past_len(r_begin - pad, DL_WIN);
+  wait_vm<0>();                                   // this wave's pieces of the first window (and its taps) are in
+  dl_barrier();                                   // ... and every wave's
+  // the launch's constants are tied to this point, behind the wait: the compiler then knows them loaded, and places no wait of its
+  // own for them inside the loop, where it would stand right behind the DMA issue and drain it
+#pragma unroll
+  for (int k = 0; k < DW_KMAX; ++k) asm volatile("" : "+v"(wk[k]));
+  asm volatile("" : "+v"(bv), "+v"(fill));
+#pragma unroll
+  for (int i = 0; i < 4; ++i)
+    asm volatile("" : "+v"(gm[i].x), "+v"(gm[i].y), "+v"(gm[i].z), "+v"(gm[i].w), "+v"(be[i].x), "+v"(be[i].y), "+v"(be[i].z), "+v"(be[i].w));
+  fill_rows(need0, r_begin - pad);
+
+  const char* ring_ch = dl_smem + ch * 2;
+  char* slab = dl_smem + DL_SLAB0;
+  bf16_t* out = (bf16_t*)a.out;
+  for (int r0 = r_begin; r0 < r_end; r0 += DL_R) {
+    dl_barrier();                                 // the window of this step is in and put right; the slab has been read
+    const bool more = r0 + DL_R < r_end;
+    if (more) issue(r0 - pad + DL_WIN, DL_R);     // the rows the next step adds, into the ring rows the last step left behind
+    const bool need = past_len(r0 - pad + DL_WIN, DL_R) && more;
+    if (cok) {
+      const int n = min(DL_R, r_end - r0);
+      const int b0 = r0 / T, t0 = r0 - b0 * T;
+      const int base = (r0 - pad) & (DL_RING - 1);
+      dl_f32x2 acc[DL_R];
+      if (t0 >= pad && t0 - pad + DL_WIN <= T) {  // the whole window lies inside one chunk
+        dl_chain<false>(ring_ch, base, wk, bv, 0, DL_WIN, acc);
+#pragma unroll
+        for (int i = 0; i < DL_R; ++i) *(uint32_t*)(slab + i * DL_ROWB + ch * 2) = pack2_bf16(acc[i].x, acc[i].y);
+      } else {
+        // once per chunk among the outputs, [i0, i1): that chunk's rows [rlo, rlo + T) of the window, zeros elsewhere
+        int i0 = 0, t = t0, rlo = pad - t0;
+        while (i0 < n) {
+          const int i1 = min(n, i0 + T - t);
+          dl_chain<true>(ring_ch, base, wk, bv, rlo, rlo + T, acc);
+#pragma unroll
+          for (int i = 0; i < DL_R; ++i)
+            if (i >= i0 && i < i1) *(uint32_t*)(slab + i * DL_ROWB + ch * 2) = pack2_bf16(acc[i].x, acc[i].y);
+          i0 = i1; t = 0; rlo += T;
+        }
+      }
+    }
+    wait_vm<0>();                                 // the next step's pieces, requested a step of FMAs ago (and the last step's stores)
+    dl_barrier();                                 // the slab is whole, the next step's rows are in
+    fill_rows(need, r0 - pad + DL_WIN);           // in front of the stores below: the answer's wait would wait for them as well
+#pragma unroll
+    for (int q = 0; q < DL_R / (DL_THREADS / 64); ++q) {
+      const int i = wave * (DL_R / (DL_THREADS / 64)) + q, row = r0 + i;
+      if (row >= r_end) break;
+      float4 v[4];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int c = COL(2 * j);
+        const uint4 u = *(const uint4*)(slab + i * DL_ROWB + c * 2);
+        const bool ok = c < d;
+        v[2 * j] = make_float4(ok ? bf16_to_f32((bf16_t)(u.x & 0xffffu)) : 0.f, ok ? bf16_to_f32((bf16_t)(u.x >> 16)) : 0.f,
+                               ok ? bf16_to_f32((bf16_t)(u.y & 0xffffu)) : 0.f, ok ? bf16_to_f32((bf16_t)(u.y >> 16)) : 0.f);
+        v[2 * j + 1] = make_float4(ok ? bf16_to_f32((bf16_t)(u.z & 0xffffu)) : 0.f, ok ? bf16_to_f32((bf16_t)(u.z >> 16)) : 0.f,
+                                   ok ? bf16_to_f32((bf16_t)(u.w & 0xffffu)) : 0.f, ok ? bf16_to_f32((bf16_t)(u.w >> 16)) : 0.f);
+      }
+      float mean, rstd;
+      row_ln_stats<4, true>(v, lane, d, a.eps, mean, rstd);
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int c = COL(2 * j);
+        if (c >= d) continue;
+        float o[8];
+        row_affine_act<true>(v[2 * j], mean, rstd, gm[2 * j], be[2 * j], true, o);
+        row_affine_act<true>(v[2 * j + 1], mean, rstd, gm[2 * j + 1], be[2 * j + 1], true, o + 4);
+        *(uint4*)(out + (size_t)row * d + c) = make_uint4(pack2_bf16(o[0], o[1]), pack2_bf16(o[2], o[3]), pack2_bf16(o[4], o[5]), pack2_bf16(o[6], o[7]));
+      }
+    }
+  }
+}
+#undef COL
+
+bool dwconv_ln_supported(int dtype, const DwLnArgs& a) {
+  return dtype == DT_BF16 && a.G && a.out && a.B > 0 && a.T > 0 && (int64_t)a.B * a.T < ((int64_t)1 << 30) && a.K >= 1 && a.K <= DW_KMAX &&
+         (a.K & 1) && a.d > 512 && a.d <= 1024 && a.d % 128 == 0 && a.grid >= 0;
+}
+
+int dwconv_ln(hipStream_t s, int dtype, const DwLnArgs& a) {
+  if (!dwconv_ln_supported(dtype, a)) { set_error("dwconv_ln: bf16, odd kernel <= 31, 512 < d <= 1024 in multiples of 128"); return E_ARG; }
+  static int cus[64] = {0};                       // per device: a workgroup holds the whole LDS of a CU, so one per CU is all that runs
+  int dev = 0;
+  RVB_HIP_CHECK(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) { set_error("dwconv_ln: device index"); return E_ARG; }
+  if (!cus[dev]) {
+    int n = 0;
+    RVB_HIP_CHECK(hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev));
+    RVB_HIP_CHECK(hipFuncSetAttribute((const void*)dwconv_ln_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, DL_LDS));
+    cus[dev] = std::max(n, 1);
+  }
+  const int rows = a.B * a.T;
+  const int grid = a.grid > 0 ? a.grid : std::min(cus[dev], cdiv(rows, DL_R));
+  hipLaunchKernelGGL(dwconv_ln_kernel, dim3(grid), dim3(DL_THREADS), DL_LDS, s, a);
   RVB_HIP_CHECK(hipGetLastError());
   return OK;
 }

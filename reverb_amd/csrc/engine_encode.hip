@@ -8,7 +8,8 @@
 
 namespace rvb {
 
-static constexpr int GLU_FUSE_DEFAULT = 1;      // pointwise_conv1 + GLU in the GEMM's epilogue (encoder_layer: lab switch RVB_GLU_FUSE)
+static constexpr int DW_FUSE_DEFAULT = 1;       // depthwise conv + LayerNorm + SiLU in one kernel (encoder_layer: lab switch RVB_DW_FUSE)
+static constexpr int GLU_FUSE_DEFAULT = 1;     // pointwise_conv1 + GLU in the GEMM's epilogue (encoder_layer: lab switch RVB_GLU_FUSE)
 
 // ------------------------------------------------------------------------------------ encoder
 // One conformer block.  On entry e->xn already holds norm_ff_macaron(x) (written by the previous block's fused final
@@ -168,7 +169,23 @@ static int encoder_layer(rvb_engine* e, EncLayer& L, int lidx, int M, int B, int
   if (e->tap_live) e->tap_forms[1] = glu_fused ? 1.f : 0.f;
   RVB_TRY(tap_keep(e, "xn_conv", e->xn.p, Md, t16));
   RVB_TRY(tap_keep(e, "glu", e->h.p, glu_fused ? Md : 2 * Md, t16));
-  {
+  // depthwise conv + LayerNorm + SiLU in one kernel where dwconv_ln() serves the shape: the same bits without the `dconv` tensor.
+  // Everything else -- f32, streaming, causal, BatchNorm, fp8 pointwise_conv2, an ungated input, and a tapped block, whose
+  // "dconv" tap is that tensor -- runs the two kernels below.
+  bool dw_fused = false;
+  if (glu_fused && !f8_pw2 && e->cfg.cnn_norm == 0 && !e->cfg.cnn_causal && !e->tap_live) {
+    const char* fe = lab_env("RVB_DW_FUSE");       // read per call: the A/B test flips it inside one process
+    DwLnArgs g;
+    g.G = e->h.p; g.pw1_bias = L.pw1.b.as<float>(); g.dw_w = L.dw_w.as<float>(); g.dw_b = L.dw_b.as<float>(); g.lens = e->cur_lens;
+    g.gamma = L.n_cnn.g.as<float>(); g.beta = L.n_cnn.b.as<float>(); g.eps = L.n_cnn.eps; g.out = e->xn.p;
+    g.B = B; g.T = T; g.d = d; g.K = e->cfg.cnn_kernel;
+    if ((fe ? atoi(fe) : DW_FUSE_DEFAULT) && dwconv_ln_supported(e->dtype, g)) {
+      Scope sc(e, "glu_dwconv");
+      RVB_TRY(dwconv_ln(e->stream, e->dtype, g));
+      dw_fused = true;
+    }
+  }
+  if (!dw_fused) {
     GluDwArgs g;
     g.gated = glu_fused ? 1 : 0;
     g.G = e->h.p; g.pw1_bias = L.pw1.b.as<float>(); g.dw_w = L.dw_w.as<float>(); g.dw_b = L.dw_b.as<float>();
@@ -206,7 +223,7 @@ static int encoder_layer(rvb_engine* e, EncLayer& L, int lidx, int M, int B, int
     RVB_TRY(run_norm(e, e->dconv.as<float>(), L.n_cnn, e->xn.p, false, M, d, cmode, 1, nullptr, nullptr, nullptr, sc8.in_pw2, 0.f, dw16, satp(4)));
     RVB_TRY(run_gemm8(e, e->xn.p, d, L.pw2, x, d, M, sc8.in_pw2, 1, 1.f, 1.f, ACT_NONE, x, d));
   } else {
-    RVB_TRY(run_norm(e, e->dconv.as<float>(), L.n_cnn, e->xn.p, false, M, d, cmode, 1, nullptr, nullptr, nullptr, 0.f, 0.f, dw16));
+    if (!dw_fused) RVB_TRY(run_norm(e, e->dconv.as<float>(), L.n_cnn, e->xn.p, false, M, d, cmode, 1, nullptr, nullptr, nullptr, 0.f, 0.f, dw16));
     RVB_TRY(note(4, e->xn.p, (size_t)M * d));
     RVB_TRY(tap_keep(e, "xn_cnn", e->xn.p, Md, t16));
     RVB_TRY(run_gemm(e, e->xn.p, d, L.pw2, x, d, M, true, 1.f, ACT_NONE, x, d));

@@ -147,6 +147,26 @@ struct GluDwArgs {
 };
 int glu_dwconv(hipStream_t s, int dtype, const GluDwArgs& a);
 
+// The bf16 offline convolution module's depthwise conv + LayerNorm + SiLU in one persistent kernel: what glu_dwconv (gated input,
+// not causal, bf16 output) followed by rownorm (NORM_LN, silu, x_bf16, bf16 output) gives, bit for bit, without the [B*T, d]
+// tensor between them.  dwconv_ln_supported() says whether a call can run (bf16, odd K <= 31, 512 < d <= 1024 with d % 128 == 0);
+// a caller that gets false runs the two kernels.
+struct DwLnArgs {
+  const void* G;          // bf16 [B*T, d], gated by the pointwise GEMM's epilogue
+  const float* pw1_bias;  // [2d]
+  const float* dw_w;      // [K][d]: tap-major
+  const float* dw_b;      // [d]
+  const int* lens;        // [B] valid rows per chunk
+  const float* gamma;     // [d] LayerNorm
+  const float* beta;      // [d]
+  float eps;
+  void* out;              // bf16 [B*T, d]
+  int B, T, d, K;
+  int grid = 0;           // 0: min(CUs, ceil(B*T / 16)) workgroups, each with a contiguous range of rows; > 0: that many (tests)
+};
+bool dwconv_ln_supported(int dtype, const DwLnArgs& a);
+int dwconv_ln(hipStream_t s, int dtype, const DwLnArgs& a);
+
 // x[row] = E[tok[row]] * scale + PE[pos[row]]   (fp32)
 int embed_tokens(hipStream_t s, const float* E, const float* pe, const int* tok, const int* pos, float* out,
                  int rows, int d, float scale);

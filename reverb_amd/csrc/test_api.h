@@ -40,6 +40,13 @@ int rvb_test_joint_result(void* h, int32_t* tokens, int32_t* times, int32_t* end
 int rvb_test_glu_dwconv(int dtype, const float* G, const float* pw1_bias, const float* dw_w, const float* dw_b,
                         const int32_t* lens, float* out, int B, int T, int d, int K, int causal,
                         const float* hist /* nullable [K-1][2d] */, int hist_rows);
+/* dwconv_ln() of the bf16 engine on host floats: G [B][T][d] gated, dw_w [d][K] as the reference stores it, xn [B][T][d] = SiLU(LayerNorm(
+ * depthwise conv)).  grid > 0 launches that many workgroups (short row ranges that begin and end anywhere), 0 the launcher's own
+ * choice.  xn_two / dconv_two (nullable): the same inputs through glu_dwconv (gated, bf16 output) and rownorm (LayerNorm + SiLU on
+ * the bf16 input), and the tensor between the two.  Every device output starts as all-ones bytes (NaN). */
+int rvb_test_dwconv_ln(const float* G, const float* pw1_bias, const float* dw_w, const float* dw_b, const int32_t* lens,
+                       const float* gamma, const float* beta, float eps, float* xn, float* xn_two, float* dconv_two, int B, int T,
+                       int d, int K, int grid);
 int rvb_test_attention(int dtype, const float* q, const float* k, const float* v, const float* p,
                        const float* bias_u, const float* bias_v, float* out, int q_rows, int kv_rows, int p_rows,
                        int heads, int dk, const int32_t* q_start, const int32_t* q_len, const int32_t* kv_start,

@@ -361,6 +361,52 @@ int rvb_test_glu_dwconv(int dtype, const float* G, const float* pw1_bias, const 
   return OK;
 }
 
+int rvb_test_dwconv_ln(const float* G, const float* pw1_bias, const float* dw_w, const float* dw_b, const int32_t* lens,
+                       const float* gamma, const float* beta, float eps, float* xn, float* xn_two, float* dconv_two, int B, int T,
+                       int d, int K, int grid) {
+  if (!G || !pw1_bias || !dw_w || !dw_b || !lens || !gamma || !beta || !xn || B < 1 || T < 1 || d < 1 || K < 1 || grid < 0) {
+    set_error("rvb_test_dwconv_ln: null argument or a size < 1"); return E_ARG;
+  }
+  RVB_TRY(need_gpu());
+  const size_t n = (size_t)B * T * d;
+  Dev dG, dpb, dw, db, dl, dg, dbe, dout, dconv, dout2;
+  RVB_TRY(up_T(dG, DT_BF16, G, n));
+  RVB_TRY(up_raw(dpb, pw1_bias, (size_t)2 * d * 4));
+  std::vector<float> wt((size_t)d * K);            // tap-major on the device, as the engine keeps it
+  for (int c = 0; c < d; ++c)
+    for (int k = 0; k < K; ++k) wt[(size_t)k * d + c] = dw_w[(size_t)c * K + k];
+  RVB_TRY(up_raw(dw, wt.data(), (size_t)d * K * 4));
+  RVB_TRY(up_raw(db, dw_b, (size_t)d * 4));
+  RVB_TRY(up_raw(dl, lens, (size_t)B * 4));
+  RVB_TRY(up_raw(dg, gamma, (size_t)d * 4));
+  RVB_TRY(up_raw(dbe, beta, (size_t)d * 4));
+  RVB_TRY(dout.alloc(n * 2));
+  RVB_HIP_CHECK(hipMemset(dout.p, 0xff, n * 2));
+  DwLnArgs a;
+  a.G = dG.p; a.pw1_bias = (const float*)dpb.p; a.dw_w = (const float*)dw.p; a.dw_b = (const float*)db.p; a.lens = (const int*)dl.p;
+  a.gamma = (const float*)dg.p; a.beta = (const float*)dbe.p; a.eps = eps; a.out = dout.p; a.B = B; a.T = T; a.d = d; a.K = K; a.grid = grid;
+  RVB_TRY(dwconv_ln(nullptr, DT_BF16, a));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  RVB_TRY(down_T(dout, DT_BF16, false, xn, n));
+  if (!xn_two && !dconv_two) return OK;
+  RVB_TRY(dconv.alloc(n * 2));
+  RVB_HIP_CHECK(hipMemset(dconv.p, 0xff, n * 2));
+  RVB_TRY(dout2.alloc(n * 2));
+  RVB_HIP_CHECK(hipMemset(dout2.p, 0xff, n * 2));
+  GluDwArgs g;
+  g.G = dG.p; g.pw1_bias = a.pw1_bias; g.dw_w = a.dw_w; g.dw_b = a.dw_b; g.lens = a.lens; g.out = (float*)dconv.p;
+  g.B = B; g.T = T; g.d = d; g.K = K; g.out_bf16 = 1; g.gated = 1;
+  RVB_TRY(glu_dwconv(nullptr, DT_BF16, g));
+  NormArgs nn;
+  nn.x = (const float*)dconv.p; nn.x_bf16 = 1; nn.gamma = a.gamma; nn.beta = a.beta; nn.eps = eps; nn.mode = NORM_LN; nn.silu = 1;
+  nn.add = nullptr; nn.out = dout2.p; nn.out_f32 = 0; nn.M = B * T; nn.d = d;
+  RVB_TRY(rownorm(nullptr, DT_BF16, nn));
+  RVB_HIP_CHECK(hipDeviceSynchronize());
+  if (dconv_two) RVB_TRY(down_T(dconv, DT_BF16, false, dconv_two, n));
+  if (xn_two) RVB_TRY(down_T(dout2, DT_BF16, false, xn_two, n));
+  return OK;
+}
+
 int rvb_test_attention(int dtype, const float* q, const float* k, const float* v, const float* p, const float* bias_u,
                        const float* bias_v, float* out, int q_rows, int kv_rows, int p_rows, int heads, int dk,
                        const int32_t* q_start, const int32_t* q_len, const int32_t* kv_start, const int32_t* kv_len,
